@@ -15,6 +15,9 @@ every rank holds all of src1, and every rank ends with the whole reference-layou
 all-gather + re-layout, or direct peer stores, whichever the run verified and measured faster).  `other_configs` then
 carries the weak-scaling run (M = 4096 per rank) and BASELINE config 5 (Q4_0 32000 x 4096 x 512, row-split), each with
 compute-only / exchange-only / whole-step times.
+--dump-outputs DIR: after the run, rank 0 writes the dst of the last timed step (a row sample drawn with a fixed seed, at most
+32 MiB) as DIR/dst_rows.npy and the rows' indices as DIR/dst_row_index.npy.  Weights and src1 come from fixed seeds, so two
+builds run with the same arguments can be compared output for output.
 """
 import argparse
 import json
@@ -221,6 +224,8 @@ def self_launch(args):
            str(args.warmup), "--backend", backend, "--exchange", args.exchange, "--preheat-s", str(args.preheat_s)]
     if args.no_side_configs:
         cmd.append("--no-side-configs")
+    if args.dump_outputs:
+        cmd += ["--dump-outputs", os.path.abspath(args.dump_outputs)]
     p = subprocess.run(cmd, env=env, stdout=subprocess.PIPE, text=True)
     line = None
     for ln in p.stdout.splitlines():
@@ -264,8 +269,9 @@ def preheat(fn, seconds=None, world=1):
     return chunk * (1 + n_chunks)
 
 
-def timed_steps(fn, warmup, steps, world):
-    """W untimed steps, then EXACTLY K steps between barrier + synchronize on both sides; MAX over ranks."""
+def timed_steps(fn, warmup, steps, world, last=None):
+    """W untimed steps, then EXACTLY K steps between barrier + synchronize on both sides; MAX over ranks.
+    `last` (a list): receives a device copy of what the last timed step returned, taken after the timed region."""
     def barrier():
         if world > 1:
             torch.distributed.barrier()
@@ -273,16 +279,33 @@ def timed_steps(fn, warmup, steps, world):
     for _ in range(warmup):
         fn()
     barrier()
+    r = None
     t0 = time.perf_counter()
     for _ in range(steps):
-        fn()
+        r = fn()
     barrier()
     dt = time.perf_counter() - t0
+    if last is not None:
+        last.append(r.clone())      # the step's buffers are reused by the next call
     if world > 1:
         t = torch.tensor([dt], dtype=torch.float64, device="cuda" if torch.distributed.get_backend() == "nccl" else "cpu")
         torch.distributed.all_reduce(t, op=torch.distributed.ReduceOp.MAX)
         dt = float(t.item())
     return dt * 1e3 / steps
+
+
+DUMP_BYTES = 32 << 20       # --dump-outputs: at most this many bytes of dst, as whole rows drawn by a fixed seed
+
+
+def dump_outputs(d, dst):
+    """dst [N][M] f32 (the reference's layout) -> d/dst_rows.npy: a seeded sample of whole rows (d/dst_row_index.npy: which)."""
+    N, M = dst.shape
+    n = min(N, max(1, DUMP_BYTES // (4 * M)))
+    rows = np.sort(np.random.default_rng(0).choice(N, size=n, replace=False))
+    os.makedirs(d, exist_ok=True)
+    np.save(os.path.join(d, "dst_rows.npy"), dst[torch.from_numpy(rows).to(dst.device)].float().cpu().numpy())
+    np.save(os.path.join(d, "dst_row_index.npy"), rows.astype(np.float64))
+    return {"dir": d, "dst_shape": [N, M], "rows": int(n), "seed": 0}
 
 
 def make_runner(device, gdist, M_total, K, N, world, rank, exchange, chunks, seed):
@@ -434,7 +457,10 @@ def main():
                     help="dst shard exchange for --gpus > 1: RCCL all-gather + re-layout, direct peer stores by a kernel behind the product (push), or "
                          "peer stores from the GEMM's own store phase (push_fused); auto: push_fused when verified bit for bit against the all-gather, else rccl")
     ap.add_argument("--preheat-s", type=float, default=PREHEAT_S, help="seconds of untimed steps of the same workload ahead of each timed region")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write what the last timed step computed (a seeded row sample of dst) as DIR/*.npy")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     PREHEAT_S = args.preheat_s
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
@@ -475,7 +501,8 @@ def main():
     # W + K steps behind PREHEAT_S seconds of the same step: the steady-state figure, which is `value`
     cold_ms_per_step = timed_steps(lambda: runner.step(x), args.warmup, args.steps, world)
     n_pre = preheat(lambda: runner.step(x), world=world)
-    ms_per_step = timed_steps(lambda: runner.step(x), args.warmup, args.steps, world)
+    last = [] if args.dump_outputs else None
+    ms_per_step = timed_steps(lambda: runner.step(x), args.warmup, args.steps, world, last=last)
     flops_step = 2.0 * M * K * N
     value = flops_step / (ms_per_step * 1e-3) / 1e9
 
@@ -608,6 +635,8 @@ def main():
         if not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(M, K, N)
     if rank == 0:
+        if last:
+            out["dump_outputs"] = dump_outputs(args.dump_outputs, last[0])
         emit(out)
     if world > 1:
         torch.distributed.destroy_process_group()
