@@ -162,19 +162,6 @@ __device__ __forceinline__ void split3(float a, uint32_t &p0, uint32_t &p1, uint
 }
 #endif
 
-// ---- developer A/B switches: compiled in only with -DGGML_HIP_DEV (tools/build_variant.sh); the product library reads
-// no environment variable, so kernel selection in a host process never depends on its environment ----
-#include <stdlib.h>
-#ifdef GGML_HIP_DEV
-static inline int dev_env_int(const char *name, int dflt) { const char *e = getenv(name); return e ? atoi(e) : dflt; }
-static inline bool dev_env_set(const char *name) { return getenv(name) != nullptr; }
-static inline const char *dev_env_str(const char *name) { return getenv(name); }
-#else
-static inline int dev_env_int(const char *, int dflt) { return dflt; }
-static inline bool dev_env_set(const char *) { return false; }
-static inline const char *dev_env_str(const char *) { return nullptr; }
-#endif
-
 // ---- once per kernel AND device: hipFuncAttributeMaxDynamicSharedMemorySize is a per-device property of a kernel, and one
 // process may drive several devices (ggml_hip_init_devices).  One object per kernel instantiation (function-local static).
 #ifdef __cplusplus

@@ -772,7 +772,6 @@ hipError_t launch_dense16(const ggml_hip_weight *w, const mm_plan &pl, const voi
     switch (pl.form) {
     case D16F_S_256x128:  return launch_cfg_s<4, 8, 4, 1>(w, a, N, Npad, dst, ldd, st);
     case D16F_S_128x128:  return launch_cfg_s<4, 4, 2, 2>(w, a, N, Npad, dst, ldd, st);
-    case D16F_256x128:    return launch_cfg<2, 4, 4, 1>(w, a, N, Npad, dst, ldd, st);
     case D16F_S4_H128:    return launch_cfg<1, 2, 4, 1, 4>(w, a, N, Npad, dst, ldd, st);
     case D16F_S4_H32:     return launch_cfg<1, 2, 1, 1, 4>(w, a, N, Npad, dst, ldd, st);
     case D16F_V2_128x128: return launch_cfg<2, 2, 2, 2, 1, 2>(w, a, N, Npad, dst, ldd, st);

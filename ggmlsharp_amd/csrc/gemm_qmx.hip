@@ -1259,7 +1259,6 @@ hipError_t launch_typed(const ggml_hip_weight *w, const mm_plan &pl, act_planes 
     if (pl.family != MMF_MX) return hipErrorInvalidValue;
     switch (pl.form) {
     case MXF_256x128:     if constexpr (Q40) return launch_cfg<TYPE, 2, 4, 4, 1, 4, 2>(w, p, N, dst, ldd, st); break;
-    case MXF_256x128_ALT: if constexpr (Q40) return launch_cfg<TYPE, 4, 2, 2, 2, 4, 1>(w, p, N, dst, ldd, st); break;
     case MXF_N32_H64:     return launch_cfg<TYPE, 1, 1, 2, 1, 4, 2, 4>(w, p, N, dst, ldd, st);
     case MXF_N32_H32:     return launch_cfg<TYPE, 1, 1, 1, 1, 4, 2, 4>(w, p, N, dst, ldd, st);
     case MXF_S4_H128:     if constexpr (Q40) return launch_cfg<TYPE, 1, 2, 4, 1, 4, MX_SMALL_FB, 4>(w, p, N, dst, ldd, st); break;

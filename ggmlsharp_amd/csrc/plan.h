@@ -39,8 +39,7 @@ enum { MM_FLAG_WIDE = 1, MM_FLAG_EPILOGUE_FUSED = 2, MM_FLAG_PERSISTENT = 4, MM_
 // forms of the staged MX family (gemm_qmx.hip launch_typed): <WMT, WNT, WGM, WGN, KB, FB, KSP, VS>
 enum mx_form {
     MXF_256x128 = 0,      // <2,4,4,1,4,2>       unsplit, 8 tiles per wave (the headline form)
-    MXF_256x128_ALT,      // <4,2,2,2,4,1>       developer A/B only
-    MXF_N32_H64,          // <1,1,2,1,4,2,4>     up to 32 rows, four-way, 64-row tiles
+    MXF_N32_H64 = 2,      // <1,1,2,1,4,2,4>     up to 32 rows, four-way, 64-row tiles  (1: retired; ggml_hip_mm_plan reports these numbers, so they stay)
     MXF_N32_H32,          // <1,1,1,1,4,2,4>
     MXF_S4_H128,          // <1,2,4,1,4,FB,4>    four-way, 128-row tiles (Q4_0)
     MXF_S4_H64,           // <1,2,2,1,4,FB,4>
@@ -57,7 +56,7 @@ enum f16_form { F16F_N32_H64 = 0, F16F_N32_H32, F16F_S4_H128, F16F_S4_H64, F16F_
 // staged int8 family (gemm_q.hip): <IT, JT>
 enum i8_form { I8F_64x64 = 0, I8F_128x128 };
 // dense16.hip F16 forms
-enum d16_form { D16F_S_256x128 = 0, D16F_S_128x128, D16F_256x128, D16F_S4_H128, D16F_S4_H32, D16F_V2_128x128, D16F_S2_128x128, D16F_S2_128x64, D16F_128x128 };
+enum d16_form { D16F_S_256x128 = 0, D16F_S_128x128, D16F_S4_H128 = 3 /* (2: retired) */, D16F_S4_H32, D16F_V2_128x128, D16F_S2_128x128, D16F_S2_128x64, D16F_128x128 };
 // dense.hip
 enum dense_form { DNF_TILE = 0, DNF_BIG = 1, DNF_KSPLIT = 2 /* F32, 5..256 rows (plan.cpp plan_dense): 32 x 32 tiles, K over the workgroup's eight waves */ };
 
@@ -92,6 +91,6 @@ mm_plan plan_mul_mat(int type, int ext_type, int64_t M, int64_t K, int64_t N, bo
 uint32_t plan_tree_id(const mm_plan &p);
 // the K1 image for (type, K, N) with no weight at hand (no M: the exception cannot apply)
 int plan_image_kind(int type, int64_t K, int64_t N);
-// thread-local developer / test switch (ggml_hip_debug_force_gemm): 0 auto, 1 int8, 2 f16, 3 MX
+// thread-local test switch (ggml_hip_debug_force_gemm): 0 auto, 1 int8, 2 f16, 3 MX
 int plan_force_gemm();
 void plan_set_force_gemm(int which);

@@ -109,7 +109,7 @@ int    ggml_hip_mm_plan(int type, int64_t M, int64_t K, int64_t N, ggml_hip_mm_p
  * N > 8 on THIS thread's calls -- 0 automatic (by type, N and K), 1 int8 MFMA
  * (gemm_q.hip), 2 f16 MFMA (gemm_q16.hip), 3 MX (gemm_qmx.hip; for Q5_0 / Q8_0 its two-digit form, which needs the
  * weight to have been uploaded while 3 was in force -- the digit planes are not built otherwise).  Same results within
- * the documented tolerance whichever runs; -DGGML_HIP_DEV builds read GGML_HIP_GEMM=i8|f16|mx as the initial value. */
+ * the documented tolerance whichever runs. */
 void   ggml_hip_debug_force_gemm(int which);
 /* Step 1 alone with an explicit layout: every src1 row -> Q8_0 (quantize_row_q8_0, Ggml.cs:733-762, the loop of
  * Ggml.cs:6641-6654) written as image `image_kind` (see above) into d_work.  image_kind + 16 (kinds 0..2, K % 256 == 0):

@@ -59,7 +59,7 @@ def test_library_exports_every_declared_symbol():
 
 
 def test_product_library_reads_no_environment_variable():
-    """Developer A/B switches exist only in -DGGML_HIP_DEV builds: the product library does not import getenv."""
+    """The kernel plan has no environment overrides: the product library does not import getenv."""
     import subprocess
     und = subprocess.run(["nm", "-D", "--undefined-only", _lib.LIB_PATH], capture_output=True, text=True, check=True).stdout
     assert "getenv" not in und

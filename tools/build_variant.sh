@@ -1,7 +1,7 @@
 #!/bin/bash
 # usage: tools/build_variant.sh NAME FILE.hip "-DFOO=1 ..."   -> ggmlsharp_amd/lib/dbg/libggml_hip_NAME.so
 # Developer A/B builds: the product objects with ONE source recompiled under -DGGML_HIP_DEV + extra flags (select the
-# library with GGML_HIP_LIB=...).  `make dev` builds libggml_hip_dev.so: every source with the developer switches.
+# library with GGML_HIP_LIB=...).
 set -e
 cd "$(dirname "$0")/../ggmlsharp_amd/csrc"
 NAME=$1; FILE=$2; EXTRA=$3
