@@ -428,7 +428,7 @@ static DeviceCtx *call_slot() {
 static int alloc_weight(DeviceCtx *c, int type, int64_t K, int64_t M, ggml_hip_weight **out, int kq_type = 0) {
     ggml_hip_weight *w = new ggml_hip_weight();
     memset(w, 0, sizeof *w);
-    const bool kq = kq_type != 0;                           // (a k-quant weight: Q5_K / Q4_K in the planar Q5_1 form, Q6_K in the planar Q4_2 form)
+    const bool kq = kq_type != 0;                           // (a k-quant weight: Q5_K / Q4_K in the planar Q5_1 form, Q6_K / Q3_K in the planar Q4_2 form)
     w->ext_type = kq_type;
     static std::atomic<uint64_t> next_uid{1};
     w->type = type; w->M = M; w->K = K; w->Mpad = pad_rows(M > 0 ? M : 1); w->device = c->device; w->uid = next_uid.fetch_add(1);
@@ -447,8 +447,8 @@ static int alloc_weight(DeviceCtx *c, int type, int64_t K, int64_t M, ggml_hip_w
     } else {
         w->nbk = K / QK;
         const int64_t nba = pad_kblocks(w->nbk) + K_LOOKAHEAD;   // allocated k-blocks (zero past the real end)
-        // (Q6_K lives in the planar Q4_2 form on its int8 planes alone -- no kernel it is planned onto reads the nibble plane: a stub)
-        const size_t qs_bytes = kq_type == GGML_HIP_TYPE_Q6_K ? 256 : (size_t)nba * w->Mpad * (type == GGML_TYPE_Q8_0 ? 32 : 16);
+        // (Q6_K / Q3_K live in the planar Q4_2 form on its int8 planes alone -- no kernel they are planned onto reads the nibble plane: a stub)
+        const size_t qs_bytes = kq && kquant_two_scale(kq_type) ? 256 : (size_t)nba * w->Mpad * (type == GGML_TYPE_Q8_0 ? 32 : 16);
         const size_t plane = (size_t)nba * w->Mpad * 4;
         off_qs = 0; total = qs_bytes;
         off_d = total; total += plane;
@@ -460,7 +460,7 @@ static int alloc_weight(DeviceCtx *c, int type, int64_t K, int64_t M, ggml_hip_w
         if (type == GGML_TYPE_Q5_0 || type == GGML_TYPE_Q5_1 || type == GGML_TYPE_Q4_1 || type == GGML_TYPE_Q4_2) { off_i8 = total; total += (size_t)nba * w->Mpad * 32; }   // int8 operand planes (gemm_qmp.hip), zero past the end of K
         // the min plane as three bf16 pieces (K3p-int8's min-term product): whole pairs of k-groups, zero past the end of K
         if (type == GGML_TYPE_Q5_1 || type == GGML_TYPE_Q4_1) { off_mp = total; total += (size_t)((w->nbk + 15) / 16 * 2 * 3) * w->Mpad * 16; }
-        if (kq) { off_kh = total; total += (size_t)(w->nbk / 8 + 1) * w->Mpad * (kq_type == GGML_HIP_TYPE_Q6_K ? 32 : 16); }   // super-block headers, for the byte-exact download
+        if (kq) { off_kh = total; total += (size_t)(w->nbk / 8 + 1) * w->Mpad * kquant_hdr_bytes(kq_type); }   // super-block headers, for the byte-exact download
         if (with6) {   // bf6 operand planes of the MX mat-mat kernel: 0.75 B / weight and digit (Q5_0, Q8_0: two digits)
             const size_t nf = q4 ? 1 : 2;
             off_6a = total; total += (size_t)nba * nf * w->Mpad * 16;
@@ -498,11 +498,12 @@ int make_weight(DeviceCtx *c, int type, const void *rows, bool rows_on_host, int
     if (!out) return fail(GGML_HIP_ERR_ARG, "out is null");
     *out = nullptr;
     // Q5_K (unpinned extra, kquants.hip): super-blocks of 256 are re-laid-out as eight k-blocks of the planar Q5_1 form
-    // (r4: Q4_K the same way -- its super-block is Q5_K's without the fifth-bit bytes; the fifth-bit plane stays zero)
+    // (r4: Q4_K the same way -- its super-block is Q5_K's without the fifth-bit bytes; the fifth-bit plane stays zero; Q6_K and Q3_K in the
+    // planar Q4_2 form on int8 planes, each by its own converter)
     const bool kq = is_kquant(type);
     if (kq) {
         if (!rows || ne00 <= 0 || ne01 < 0 || row_begin < 0 || row_end < row_begin || row_end > ne01) return fail(GGML_HIP_ERR_ARG, "bad weight arguments");
-        if (ne00 % 256 != 0) return fail(GGML_HIP_ERR_SHAPE, "Q5_K / Q4_K: ne00 %% 256 != 0 (QK_K)");
+        if (ne00 % 256 != 0) return fail(GGML_HIP_ERR_SHAPE, "k-quants: ne00 %% 256 != 0 (QK_K)");
         if (nb01 < (uint64_t)(ne00 / 256) * kquant_bytes(type)) return fail(GGML_HIP_ERR_SHAPE, "nb01 smaller than a row");
         int rc = c ? GGML_HIP_OK : ensure_init();
         if (rc) return rc;
@@ -512,7 +513,12 @@ int make_weight(DeviceCtx *c, int type, const void *rows, bool rows_on_host, int
         const int64_t rows_n = row_end - row_begin;
         const uint64_t rb = (uint64_t)(ne00 / 256) * kquant_bytes(type);
         ggml_hip_weight *w = nullptr;
-        const bool q6k = type == GGML_HIP_TYPE_Q6_K;           // (the planar Q4_2 form on int8 planes: kquants.hip)
+        const bool two_scale = kquant_two_scale(type);         // (the planar Q4_2 form on int8 planes: kquants.hip)
+        auto to_planar = [&](const uint8_t *src, uint64_t pitch, int64_t first) {
+            return type == GGML_HIP_TYPE_Q6_K ? launch_q6k_to_planar(src, pitch, first, rows_n, w, st)
+                   : type == GGML_HIP_TYPE_Q3_K ? launch_q3k_to_planar(src, pitch, first, rows_n, w, st)
+                                                : launch_q5k_to_planar(type, src, pitch, first, rows_n, w, st);
+        };
         rc = alloc_weight(c, kquant_resident_type(type), ne00, rows_n, &w, type);
         if (rc) return rc;
         hipError_t e = hipMemsetAsync(w->qs, 0, w->bytes, st);
@@ -521,12 +527,12 @@ int make_weight(DeviceCtx *c, int type, const void *rows, bool rows_on_host, int
             e = hipMalloc(&staging, (size_t)rows_n * rb);
             if (e == hipSuccess)
                 e = hipMemcpy2DAsync(staging, rb, (const uint8_t *)rows + (uint64_t)row_begin * nb01, nb01, rb, (size_t)rows_n, hipMemcpyHostToDevice, st);
-            if (e == hipSuccess) e = q6k ? launch_q6k_to_planar((const uint8_t *)staging, rb, 0, rows_n, w, st) : launch_q5k_to_planar(type, (const uint8_t *)staging, rb, 0, rows_n, w, st);
+            if (e == hipSuccess) e = to_planar((const uint8_t *)staging, rb, 0);
         } else if (e == hipSuccess) {
-            e = q6k ? launch_q6k_to_planar((const uint8_t *)rows, nb01, row_begin, rows_n, w, st) : launch_q5k_to_planar(type, (const uint8_t *)rows, nb01, row_begin, rows_n, w, st);
+            e = to_planar((const uint8_t *)rows, nb01, row_begin);
         }
-        if (e == hipSuccess && !q6k) e = launch_q5_to_i8(w, st);      // (the planar Q5_1 form's int8 operand planes: gemm_qmp.hip serves prompt-sized batches; Q6_K's converter writes them itself)
-        if (e == hipSuccess && !q6k) e = launch_min_pieces(w, st);
+        if (e == hipSuccess && !two_scale) e = launch_q5_to_i8(w, st);      // (the planar Q5_1 form's int8 operand planes: gemm_qmp.hip serves prompt-sized batches; Q6_K's / Q3_K's converters write them themselves)
+        if (e == hipSuccess && !two_scale) e = launch_min_pieces(w, st);
         if (e == hipSuccess) e = launch_gemv_side_image(w, st);
         if (e == hipSuccess) e = hipStreamSynchronize(st);
         if (staging) (void)hipFree(staging);
@@ -677,6 +683,7 @@ int ggml_hip_weight_download(const ggml_hip_weight *w, void *host_rows, void *st
     void *staging = nullptr;
     HIP_TRY(hipMalloc(&staging, total));
     hipError_t e = w->ext_type == GGML_HIP_TYPE_Q6_K ? launch_planar_to_q6k(w, (uint8_t *)staging, st)
+                   : w->ext_type == GGML_HIP_TYPE_Q3_K ? launch_planar_to_q3k(w, (uint8_t *)staging, st)
                    : w->ext_type != 0 ? launch_planar_to_q5k(w, (uint8_t *)staging, st) : launch_planar_to_aos(w, (uint8_t *)staging, st);
     if (e == hipSuccess) e = hipMemcpyAsync(host_rows, staging, total, hipMemcpyDeviceToHost, st);
     if (e == hipSuccess) e = hipStreamSynchronize(st);
@@ -1065,6 +1072,7 @@ int ggml_hip_quantize_rows_dev(int type, const float *d_x, int64_t nrows, int64_
         if (k % 256 != 0) return fail(GGML_HIP_ERR_SHAPE, "k-quants: k %% 256 != 0");
         if (((uintptr_t)d_x & 15) != 0) return fail(GGML_HIP_ERR_SHAPE, "k-quants: the rows must be 16-byte aligned");
         if (type == GGML_HIP_TYPE_Q6_K) HIP_TRY(launch_quantize_q6k(d_x, nrows, k, d_blocks, (hipStream_t)stream));
+        else if (type == GGML_HIP_TYPE_Q3_K) HIP_TRY(launch_quantize_q3k(d_x, nrows, k, d_blocks, (hipStream_t)stream));
         else HIP_TRY(launch_quantize_kq(type, d_x, nrows, k, d_blocks, (hipStream_t)stream));
         return GGML_HIP_OK;
     }
@@ -1081,6 +1089,7 @@ int ggml_hip_dequantize_rows_dev(int type, const void *d_blocks, int64_t nrows, 
     if (is_kquant(type)) {                                      // unpinned extra (kquants.hip)
         if (k % 256 != 0) return fail(GGML_HIP_ERR_SHAPE, "k-quants: k %% 256 != 0");
         if (type == GGML_HIP_TYPE_Q6_K) HIP_TRY(launch_dequantize_q6k(d_blocks, nrows, k, d_y, (hipStream_t)stream));
+        else if (type == GGML_HIP_TYPE_Q3_K) HIP_TRY(launch_dequantize_q3k(d_blocks, nrows, k, d_y, (hipStream_t)stream));
         else HIP_TRY(launch_dequantize_q5k(type, d_blocks, nrows, k, d_y, (hipStream_t)stream));
         return GGML_HIP_OK;
     }

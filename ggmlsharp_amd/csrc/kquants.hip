@@ -1,4 +1,4 @@
-// kquants.hip -- Q5_K (r4: and Q4_K) weights (and the Q8_K activation rule) as an UNPINNED EXTRA.
+// kquants.hip -- Q5_K (r4: and Q4_K, Q6_K; then Q3_K) weights (and the Q8_K activation rule) as an UNPINNED EXTRA.
 //
 // The reference has no k-quants (TypeDefinitions.cs:153-169 stops at Q8_1; `grep -i q5_K` over /root/reference finds
 // nothing -- SURVEY 8(a) row K), BASELINE.json's north_star and config 4 name them anyway.  What is built here follows the
@@ -21,6 +21,10 @@
 // The INIT phase quantizes the activations with the Q8_K rule (one scale per 256 elements, quantize.hip K1 with K8 =
 // true) into the same operand images.  The 16 header bytes of every super-block are kept beside the planes so that a
 // download returns the uploaded bytes.
+// Q6_K and Q3_K (sixteen sub-blocks of 16 with a signed scale each, no min) live in the planar Q4_2 form on int8 planes instead --
+// two scales per 32-element k-block -- and run the int8 kernels that take two scales per k-block; Q3_K's planes are exactly those of the
+// Q6_K super-block it transcodes to (see the two sections below).  Not built: Q2_K -- its sub-blocks of 16 each carry a min, and no
+// resident form has two mins per k-block (the min-term products of the Q5_1 form are built per 32 elements).
 #include "common.h"
 
 namespace {
@@ -424,6 +428,221 @@ __global__ void quantize_q6k_kernel(const float *__restrict__ x, int64_t nsb, ui
     }
 }
 
+// ---- Q3_K ----------------------------------------------------------------------------------------------------------------------------------
+//     block_q3_K = { u8 hmask[32]; u8 qs[64]; u8 scales[12]; half d }                  110 bytes per 256 weights
+//     element e = 128 n + 32 s + l: v = ((qs[32 n + l] >> 2 s) & 3) + 4 ((hmask[l] >> (4 n + s)) & 1) - 4, in -4..3;  w[e] = (d * sc_{e / 16}) * v,
+//     sc_j = code - 32, the 6-bit code's low nibble scales[j] & 15 (j < 8) / scales[j - 8] >> 4, its high two bits (scales[8 + j % 4] >> 2 (j / 4)) & 3
+//     dot against Q8_K per super-block: (d * dy) * sum_j sc_j * <v_j, a_j>
+// Resident form: Q6_K's, byte for byte.  A Q3_K super-block IS the Q6_K one with q6 = v + 32, scales[j] = sc_j and the same d, so k-block
+// b = 4 n + s (elements 32 b .. 32 b + 31: bit b of hmask[l], bits 2 s, 2 s + 1 of qs[32 n + l]) becomes the two int8 planes of v and the
+// scales d * sc_{2 b}, d * sc_{2 b + 1} (exact in f32: 11 + 6 significant bits); every kernel that serves Q6_K serves it unchanged.  The 14
+// header bytes (scales[12], d) of a super-block are kept in a 16-byte slot; hmask and qs are rebuilt from the planes by the download.
+__device__ __forceinline__ int q3k_scale(const uint8_t *scales, int j) {
+    const int lo = j < 8 ? (scales[j] & 15) : (scales[j - 8] >> 4);
+    return (lo | (((scales[8 + (j & 3)] >> (2 * (j >> 2))) & 3) << 4)) - 32;
+}
+
+// one thread per (row, k-block); rows fastest so the plane stores coalesce
+__global__ void q3k_to_planar_kernel(const uint8_t *__restrict__ aos, uint64_t nb01, int64_t row_begin, int64_t rows, int64_t Mpad,
+                                     uint8_t *__restrict__ i8p, float *__restrict__ d, float *__restrict__ mm, uint8_t *__restrict__ khdr) {
+    const int64_t m = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const int64_t b = blockIdx.y;
+    if (m >= rows) return;
+    const int64_t sb = b >> 3;
+    const int bq = (int)(b & 7), n = bq >> 2, s = bq & 3;
+    const uint8_t *blk = aos + (uint64_t)(row_begin + m) * nb01 + (uint64_t)sb * 110;
+    const uint8_t *hm = blk, *qs = blk + 32 + 32 * n;
+    const float dd = h2f((uint16_t)(blk[108] | ((uint16_t)blk[109] << 8)));
+    const int64_t pi = b * Mpad + m;
+    d[pi] = dd * (float)q3k_scale(blk + 96, 2 * bq);       // exact: 11 + 6 significant bits
+    mm[pi] = dd * (float)q3k_scale(blk + 96, 2 * bq + 1);
+    uint32_t ev[4] = {0, 0, 0, 0}, od[4] = {0, 0, 0, 0};
+#pragma unroll
+    for (int t = 0; t < 32; ++t) {
+        const int v = (int)((qs[t] >> (2 * s)) & 3u) + 4 * (int)((hm[t] >> bq) & 1u) - 4;
+        const uint32_t byte = (uint32_t)(uint8_t)(int8_t)v << (8 * ((t >> 1) & 3));
+        if (t & 1) od[t >> 3] |= byte; else ev[t >> 3] |= byte;      // plane h byte j = element 2 j + h
+    }
+    *(uint4 *)(i8p + ((b * 2 + 0) * Mpad + m) * 16) = make_uint4(ev[0], ev[1], ev[2], ev[3]);
+    *(uint4 *)(i8p + ((b * 2 + 1) * Mpad + m) * 16) = make_uint4(od[0], od[1], od[2], od[3]);
+    if (bq == 0) {
+        uint32_t h[4] = {0, 0, 0, 0};
+#pragma unroll
+        for (int i = 0; i < 14; ++i) h[i >> 2] |= (uint32_t)blk[96 + i] << (8 * (i & 3));
+        *(uint4 *)(khdr + (sb * Mpad + m) * 16) = make_uint4(h[0], h[1], h[2], h[3]);
+    }
+}
+
+// exact inverse: one thread per (row, super-block)
+__global__ void planar_to_q3k_kernel(uint8_t *__restrict__ aos, uint64_t nb01, int64_t rows, int64_t Mpad, const uint8_t *__restrict__ i8p,
+                                     const uint8_t *__restrict__ khdr) {
+    const int64_t m = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const int64_t sb = blockIdx.y;
+    if (m >= rows) return;
+    uint8_t *blk = aos + (uint64_t)m * nb01 + (uint64_t)sb * 110;
+    for (int i = 0; i < 96; ++i) blk[i] = 0;
+    for (int bq = 0; bq < 8; ++bq) {
+        const int n = bq >> 2, s = bq & 3;
+        uint8_t *hm = blk, *qs = blk + 32 + 32 * n;
+        const int64_t b = sb * 8 + bq;
+        for (int hsel = 0; hsel < 2; ++hsel) {
+            const uint4 w4 = *(const uint4 *)(i8p + ((b * 2 + hsel) * Mpad + m) * 16);
+            const uint32_t w[4] = {w4.x, w4.y, w4.z, w4.w};
+            for (int j = 0; j < 16; ++j) {
+                const int t = 2 * j + hsel;
+                const uint32_t q = (uint32_t)((int)(int8_t)((w[j >> 2] >> (8 * (j & 3))) & 0xFFu) + 4);   // 0..7
+                qs[t] |= (uint8_t)((q & 3u) << (2 * s));
+                hm[t] |= (uint8_t)((q >> 2) << bq);
+            }
+        }
+    }
+    const uint8_t *h = khdr + (sb * Mpad + m) * 16;
+    for (int i = 0; i < 14; ++i) blk[96 + i] = h[i];
+}
+
+// dequantize_row_q3_K of the published format: one thread per (row-major) k-block of 32 outputs
+__global__ void dequantize_q3k_kernel(const uint8_t *__restrict__ in, int64_t nkb, float *__restrict__ y) {
+    const int64_t k = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (k >= nkb) return;
+    const uint8_t *blk = in + (k >> 3) * 110;
+    const int bq = (int)(k & 7), n = bq >> 2, s = bq & 3;
+    const uint8_t *hm = blk, *qs = blk + 32 + 32 * n;
+    const float dd = h2f((uint16_t)(blk[108] | ((uint16_t)blk[109] << 8)));
+    const float d0 = dd * (float)q3k_scale(blk + 96, 2 * bq), d1 = dd * (float)q3k_scale(blk + 96, 2 * bq + 1);
+    float *o = y + k * 32;
+    for (int t = 0; t < 32; ++t) {
+        const int v = (int)((qs[t] >> (2 * s)) & 3u) + 4 * (int)((hm[t] >> bq) & 1u) - 4;
+        o[t] = (t < 16 ? d0 : d1) * (float)v;               // upstream: d_all * (sc - 32) first, then times the value
+    }
+}
+
+// quantize_row_q3_K_reference of the published format, restated (tests/np_q3k.py quantize_q3_K is the same steps): per sub-block of 16
+// make_q3_quants(16, 4, x, L, true) -- codes l = nearest(-4 / max * x) in -4..3, then up to five passes that move one code at a time to
+// nearest(x sl2 / slx) where that raises the x^2-weighted fit (slx^2 / sl2) -- its scale sumlx / suml2; the sixteen scales as 6-bit codes
+// against d = half(max scale / -32); the codes again under the ROUNDED scales, l = nearest(x / (d sc)) in -4..3.  Every float operation a
+// binary32 operation in the order written (-ffp-contract=off), nearest = round half to even.  Sixteen lanes per super-block, one sub-block
+// each; the super-block's largest scale and the bit transpositions by width-16 shuffles.
+__global__ void quantize_q3k_kernel(const float *__restrict__ x, int64_t nsb, uint8_t *__restrict__ out) {
+    const int64_t tid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const int64_t sb_raw = tid >> 4;
+    const bool active = sb_raw < nsb;
+    const int64_t sb = active ? sb_raw : nsb - 1;           // (idle lanes of the last group shadow the last super-block: the shuffles want every lane)
+    const int j = (int)(tid & 15);
+    const float *xs = x + sb * 256 + 16 * j;
+    float v[16];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        const float4 t = ((const float4 *)xs)[i];
+        v[4 * i] = t.x; v[4 * i + 1] = t.y; v[4 * i + 2] = t.z; v[4 * i + 3] = t.w;
+    }
+    // make_q3_quants(16, nmax = 4, x, L, do_rmse = true)
+    float amax = 0.0f, mx = 0.0f;
+#pragma unroll
+    for (int i = 0; i < 16; ++i) { const float ax = fabsf(v[i]); if (ax > amax) { amax = ax; mx = v[i]; } }
+    int L[16];
+    float scale = 0.0f;
+#pragma unroll
+    for (int i = 0; i < 16; ++i) L[i] = 0;                  // (an all-zero sub-block: codes 0, scale 0)
+    if (amax != 0.0f) {
+        const float iscale = -4.0f / mx;
+        float sumlx = 0.0f, suml2 = 0.0f;
+#pragma unroll
+        for (int i = 0; i < 16; ++i) {
+            const int l = (int)fminf(fmaxf(rintf(iscale * v[i]), -4.0f), 3.0f);
+            L[i] = l;
+            const float w = v[i] * v[i];
+            sumlx += (w * v[i]) * (float)l;
+            suml2 += (w * (float)l) * (float)l;
+        }
+        for (int itry = 0; itry < 5; ++itry) {
+            int changed = 0;
+#pragma unroll
+            for (int i = 0; i < 16; ++i) {
+                const float w = v[i] * v[i];
+                float slx = sumlx - (w * v[i]) * (float)L[i];
+                if (slx > 0.0f) {
+                    float sl2 = suml2 - (w * (float)L[i]) * (float)L[i];
+                    const int nl = (int)fminf(fmaxf(rintf((v[i] * sl2) / slx), -4.0f), 3.0f);   // (clamped before the conversion: slx may be tiny)
+                    if (nl != L[i]) {
+                        slx += (w * v[i]) * (float)nl;
+                        sl2 += (w * (float)nl) * (float)nl;
+                        if (sl2 > 0.0f && (slx * slx) * suml2 > (sumlx * sumlx) * sl2) { L[i] = nl; sumlx = slx; suml2 = sl2; ++changed; }
+                    }
+                }
+            }
+            if (!changed) break;
+        }
+#pragma unroll
+        for (int i = 0; i < 16; ++i) L[i] += 4;
+        scale = sumlx / suml2;
+    }
+    // the first sub-block scale of largest magnitude (upstream: `if (fabsf(scale) > amax)` from 0)
+    float best = fabsf(scale);
+    int bidx = j;
+#pragma unroll
+    for (int o = 1; o < 16; o <<= 1) {
+        const float ob = __shfl_xor(best, o, 16);
+        const int oi = __shfl_xor(bidx, o, 16);
+        if (ob > best || (ob == best && oi < bidx)) { best = ob; bidx = oi; }
+    }
+    const float max_scale = __shfl(scale, bidx, 16);
+    const bool zero = best == 0.0f;
+    const float isc = zero ? 0.0f : -32.0f / max_scale;
+    const _Float16 dh = zero ? (_Float16)0.0f : (_Float16)(1.0f / isc);
+    const int code = zero ? 0 : (int)fminf(fmaxf(rintf(isc * scale), -32.0f), 31.0f) + 32;
+    const float dd = (float)dh * (float)(code - 32);        // the scale as the stored bytes give it
+    if (dd != 0.0f) {
+#pragma unroll
+        for (int i = 0; i < 16; ++i) L[i] = (int)fminf(fmaxf(rintf(v[i] / dd), -4.0f), 3.0f) + 4;
+    }
+    uint8_t *blk = out + sb * 110;
+    // element 16 j + i = 128 n + 32 s + 16 h + i (j = 8 n + 2 s + h): its high bit is bit 4 n + s = j / 2 of hmask[16 h + i], its low two
+    // bits go to bits 2 s, 2 s + 1 of qs[32 n + 16 h + i]
+    const int n = j >> 3, s = (j >> 1) & 3, h = j & 1;
+    uint32_t lo[4] = {0, 0, 0, 0}, hb = 0;                  // sixteen bytes-to-be of low bit pairs, sixteen high bits
+#pragma unroll
+    for (int i = 0; i < 16; ++i) {
+        lo[i >> 2] |= (uint32_t)(L[i] & 3) << (8 * (i & 3));
+        hb |= (uint32_t)(L[i] >> 2) << i;
+    }
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const uint32_t l2 = __shfl_xor(lo[k], 2, 16), l4 = __shfl_xor(lo[k], 4, 16), l6 = __shfl_xor(lo[k], 6, 16);   // s ^ 1, s ^ 2, s ^ 3
+        if (active && s == 0) {
+            const uint32_t word = lo[k] | (l2 << 2) | (l4 << 4) | (l6 << 6);
+            uint8_t *q = blk + 32 + 32 * n + 16 * h + 4 * k;
+            q[0] = (uint8_t)word; q[1] = (uint8_t)(word >> 8); q[2] = (uint8_t)(word >> 16); q[3] = (uint8_t)(word >> 24);
+        }
+    }
+    uint32_t hw[4] = {0, 0, 0, 0};                          // hmask[16 h + i] bit q = the high bit of element i of sub-block 2 q + h
+#pragma unroll
+    for (int q = 0; q < 8; ++q) {
+        const uint32_t hq = __shfl(hb, 2 * q + h, 16);
+#pragma unroll
+        for (int i = 0; i < 16; ++i) hw[i >> 2] |= ((hq >> i) & 1u) << (8 * (i & 3) + q);
+    }
+    int codes[16];
+#pragma unroll
+    for (int q = 0; q < 16; ++q) codes[q] = __shfl(code, q, 16);
+    if (active && j < 2) {
+#pragma unroll
+        for (int i = 0; i < 16; ++i) blk[16 * h + i] = (uint8_t)(hw[i >> 2] >> (8 * (i & 3)));
+    }
+    if (active && j == 0) {
+        uint32_t sc[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+#pragma unroll
+        for (int q = 0; q < 16; ++q) {
+            if (q < 8) sc[q] |= (uint32_t)(codes[q] & 15);
+            else sc[q - 8] |= (uint32_t)(codes[q] & 15) << 4;
+            sc[8 + (q & 3)] |= (uint32_t)(codes[q] >> 4) << (2 * (q >> 2));
+        }
+#pragma unroll
+        for (int i = 0; i < 12; ++i) blk[96 + i] = (uint8_t)sc[i];
+        const uint16_t hbits = __builtin_bit_cast(uint16_t, dh);
+        blk[108] = (uint8_t)hbits; blk[109] = (uint8_t)(hbits >> 8);
+    }
+}
+
 }  // namespace
 
 hipError_t launch_q5k_to_planar(int kq_type, const uint8_t *aos, uint64_t nb01, int64_t row_begin, int64_t rows, ggml_hip_weight *w, hipStream_t st) {
@@ -484,5 +703,34 @@ hipError_t launch_quantize_q6k(const float *x, int64_t nrows, int64_t k, void *b
     const int64_t nsb = nrows * (k / 256);
     if (nsb <= 0) return hipSuccess;
     quantize_q6k_kernel<<<dim3((unsigned)((nsb * 16 + 127) / 128)), 128, 0, st>>>(x, nsb, (uint8_t *)blocks);
+    return hipGetLastError();
+}
+
+
+hipError_t launch_q3k_to_planar(const uint8_t *aos, uint64_t nb01, int64_t row_begin, int64_t rows, ggml_hip_weight *w, hipStream_t st) {
+    if (rows <= 0) return hipSuccess;
+    dim3 grid((unsigned)((rows + 127) / 128), (unsigned)w->nbk);
+    q3k_to_planar_kernel<<<grid, 128, 0, st>>>(aos, nb01, row_begin, rows, w->Mpad, w->i8p, w->d, w->m, w->khdr);
+    return hipGetLastError();
+}
+
+hipError_t launch_planar_to_q3k(const ggml_hip_weight *w, uint8_t *aos, hipStream_t st) {
+    if (w->M <= 0) return hipSuccess;
+    dim3 grid((unsigned)((w->M + 127) / 128), (unsigned)(w->nbk / 8));
+    planar_to_q3k_kernel<<<grid, 128, 0, st>>>(aos, (uint64_t)(w->nbk / 8) * 110, w->M, w->Mpad, w->i8p, w->khdr);
+    return hipGetLastError();
+}
+
+hipError_t launch_dequantize_q3k(const void *blocks, int64_t nrows, int64_t k, float *y, hipStream_t st) {
+    const int64_t nkb = nrows * (k / 32);
+    if (nkb <= 0) return hipSuccess;
+    dequantize_q3k_kernel<<<dim3((unsigned)((nkb + 127) / 128)), 128, 0, st>>>((const uint8_t *)blocks, nkb, y);
+    return hipGetLastError();
+}
+
+hipError_t launch_quantize_q3k(const float *x, int64_t nrows, int64_t k, void *blocks, hipStream_t st) {
+    const int64_t nsb = nrows * (k / 256);
+    if (nsb <= 0) return hipSuccess;
+    quantize_q3k_kernel<<<dim3((unsigned)((nsb * 16 + 127) / 128)), 128, 0, st>>>(x, nsb, (uint8_t *)blocks);
     return hipGetLastError();
 }

@@ -6,7 +6,7 @@
  *   - neighbours of the path and their fused forms                      (ggml_hip_compute_forward_{cpy,add,mul,scale,rms_norm,silu,...})
  *   - device-level fused / grouped products                             (ggml_hip_norm_mul_mat_dev, _mul_mat_multi_dev, _mul_mat_epilogue_dev, ...)
  *   - several devices in one process, one process per device           (ggml_hip_split_weight_*, _mul_mat_split_dev, _ipc_*, _push_columns_dev, ...)
- *   - the k-quant extension type                                        (GGML_HIP_TYPE_Q5_K)
+ *   - the k-quant extension types                                       (GGML_HIP_TYPE_Q5_K, _Q4_K, _Q6_K, _Q3_K)
  *   - TEST HOOKS (ggml_hip_debug_*): inert unless called; ggml_hip_debug_force_gemm acts on the CALLING THREAD only.
  */
 #ifndef GGML_HIP_EXT_H
@@ -39,6 +39,14 @@ extern "C" {
  * the staged int8 form: WHICH one serves a shape is ggml_hip_mm_plan's answer, the only authority -- no range is restated here).  ggml_hip_quantize_rows_dev: quantize_row_q6_K_reference WITHOUT the least-squares refinement of the
  * sub-block scales (make_qx_quants in its plain form) -- a valid encoder of the published structure.  Unpinned like the other two. */
 #define GGML_HIP_TYPE_Q6_K 114
+/* Q3_K of the same published format -- { u8 hmask[32]; u8 qs[64]; u8 scales[12]; half d }, 110 bytes per 256 weights: sixteen sub-blocks
+ * of 16 three-bit weights v = q2 + 4 hbit - 4 (element e: n = e / 128, s = (e % 128) / 32, l = e % 32; q2 = bits 2 s, 2 s + 1 of qs[32 n + l],
+ * hbit = bit 4 n + s of hmask[l]) with a 6-bit scale each (sc_j = code - 32: low nibble of scales[j] (j < 8) / high nibble of scales[j - 8],
+ * high two bits 2 (j / 4), 2 (j / 4) + 1 of scales[8 + j % 4]), no min; y = (d * sc_j) * v.  A Q3_K super-block IS a Q6_K one with q6 = v + 32
+ * and scales[j] = sc_j, so it lives in Q6_K's resident form byte for byte and runs the same kernels; its 14 header bytes are kept for the
+ * download.  ggml_hip_quantize_rows_dev: quantize_row_q3_K_reference of the published format (make_q3_quants with its weighted refinement,
+ * 6-bit scales against d = max scale / -32).  Accepted by the same entries as the other three; unpinned like them. */
+#define GGML_HIP_TYPE_Q3_K 111
 
 
 /* OPT-IN, and a deviation from the reference's contract (which leaves EVERY node's data in host memory, Ggml.cs:3539-3704):
