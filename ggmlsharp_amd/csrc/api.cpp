@@ -778,6 +778,24 @@ int ggml_hip_quantize_act_dev(const float *d_src1, int64_t N, int64_t K, int64_t
     return GGML_HIP_OK;
 }
 
+// the COMPUTE launch of an INIT-based plan: the family's launcher, with the store-phase epilogue (nullptr: none) where the plan fuses one
+static hipError_t launch_planned(const ggml_hip_weight *w, const mm_plan &pl, act_planes p, int64_t N, float *dst, int64_t ldd, hipStream_t st,
+                                 const mm_epilogue *ep) {
+    switch (pl.family) {
+    case MMF_K3S_I8:    return launch_gemm_q8_small(w, pl, p, N, dst, ldd, st, ep);
+    case MMF_K3P_I8:    return launch_gemm_q8_mid(w, pl, p, N, dst, ldd, st, ep);
+    case MMF_K3S_MX: case MMF_K3P_MX: case MMF_MX:
+                        return launch_gemm_qmx(w, pl, p, N, dst, ldd, st, ep);   // (its ld_add / ld2 bound covers every MX form, K3p-MX included)
+    }
+    if (ep) return hipErrorNotSupported;                    // (the other families have no fused epilogue: plan flags)
+    switch (pl.family) {
+    case MMF_GEMV_ROWS: return launch_gemv_q(w, p, N, dst, ldd, st);
+    case MMF_F16:       return launch_gemm_q16(w, pl, p, N, dst, ldd, st);
+    case MMF_I8:        return launch_gemm_q(w, pl, p, N, dst, ldd, st);
+    default:            return hipErrorInvalidValue;
+    }
+}
+
 int ggml_hip_mul_mat_compute_dev(const ggml_hip_weight *w, int64_t N, float *d_dst, int64_t ldd, const void *d_work,
                                  size_t work_bytes, void *stream) {
     if (!w || !d_dst) return fail(GGML_HIP_ERR_ARG, "null argument");
@@ -787,19 +805,8 @@ int ggml_hip_mul_mat_compute_dev(const ggml_hip_weight *w, int64_t N, float *d_d
     if (!d_work || work_bytes < ggml_hip_mul_mat_work_size(w->type, w->K, N)) return fail(GGML_HIP_ERR_ARG, "work buffer too small");
     int rc = weight_device_current(w);
     if (rc) return rc;
-    act_planes p = act_carve((void *)d_work, w->K, pad_act(N));
     const mm_plan pl = weight_plan(w, N, false);            // (the COMPUTE-only entry: INIT wrote this plan's image)
-    const mm_epilogue none{0, nullptr, 0, nullptr, 0, 1.0f};
-    switch (pl.family) {
-    case MMF_K3S_I8:    HIP_TRY(launch_gemm_q8_small(w, pl, p, N, d_dst, ldd, (hipStream_t)stream, nullptr)); break;
-    case MMF_K3P_I8:    HIP_TRY(launch_gemm_q8_mid(w, pl, p, N, d_dst, ldd, (hipStream_t)stream, none)); break;
-    case MMF_GEMV_ROWS: HIP_TRY(launch_gemv_q(w, p, N, d_dst, ldd, (hipStream_t)stream)); break;
-    case MMF_K3S_MX: case MMF_K3P_MX: case MMF_MX:
-                        HIP_TRY(launch_gemm_qmx(w, pl, p, N, d_dst, ldd, (hipStream_t)stream)); break;
-    case MMF_F16:       HIP_TRY(launch_gemm_q16(w, pl, p, N, d_dst, ldd, (hipStream_t)stream)); break;
-    case MMF_I8:        HIP_TRY(launch_gemm_q(w, pl, p, N, d_dst, ldd, (hipStream_t)stream)); break;
-    default:            return fail(GGML_HIP_ERR_RUNTIME, "no kernel family for this product (plan family %d)", pl.family);
-    }
+    HIP_TRY(launch_planned(w, pl, act_carve((void *)d_work, w->K, pad_act(N)), N, d_dst, ldd, (hipStream_t)stream, nullptr));
     return GGML_HIP_OK;
 }
 
@@ -875,10 +882,7 @@ int ggml_hip_mul_mat_epilogue_dev(const ggml_hip_weight *w, const float *d_src1,
         }
         rc = ggml_hip_mul_mat_init_dev(w, d_src1, N, ld1, d_work, work_bytes, stream);
         if (rc) return rc;
-        const act_planes pl = act_carve(d_work, w->K, pad_act(N));
-        const hipError_t e = plan.family == MMF_K3S_I8 ? launch_gemm_q8_small(w, plan, pl, N, d_dst, ldd, (hipStream_t)stream, &ep)
-                             : plan.family == MMF_K3P_I8 ? launch_gemm_q8_mid(w, plan, pl, N, d_dst, ldd, (hipStream_t)stream, ep)
-                                                         : launch_gemm_qmx(w, plan, pl, N, d_dst, ldd, (hipStream_t)stream, &ep);
+        const hipError_t e = launch_planned(w, plan, act_carve(d_work, w->K, pad_act(N)), N, d_dst, ldd, (hipStream_t)stream, &ep);
         if (e == hipSuccess) return GGML_HIP_OK;
         // not supported = operands of the EPILOGUE beyond the 32-bit offsets of these kernels (ld_add / ld2 past 4 GiB): the product itself
         // succeeds, so it does with an epilogue -- the unfused path below
@@ -926,10 +930,7 @@ int ggml_hip_mul_mat_push_dev(const ggml_hip_weight *w, const float *d_src1, int
         rc = ggml_hip_mul_mat_init_dev(w, d_src1, N, ld1, d_work, work_bytes, stream);
         if (rc) return rc;
         const mm_plan plan = weight_plan(w, N, true);
-        const act_planes pl = act_carve(d_work, w->K, pad_act(N));
-        const hipError_t e = plan.family == MMF_K3P_I8 ? launch_gemm_q8_mid(w, plan, pl, N, mine, ld_total, (hipStream_t)stream, ep)
-                             : plan.family == MMF_K3S_I8 ? launch_gemm_q8_small(w, plan, pl, N, mine, ld_total, (hipStream_t)stream, &ep)
-                                                         : launch_gemm_qmx(w, plan, pl, N, mine, ld_total, (hipStream_t)stream, &ep);
+        const hipError_t e = launch_planned(w, plan, act_carve(d_work, w->K, pad_act(N)), N, mine, ld_total, (hipStream_t)stream, &ep);
         if (e == hipSuccess) return GGML_HIP_OK;
         // not supported = ld_total beyond what the store phase addresses (a tile's rows past the 32-bit buffer offsets of the staged MX forms,
         // a row stride past K3p's int): the product itself still runs, as ggml_hip_mul_mat_epilogue_dev's unfused path does -- the plain
@@ -1011,8 +1012,8 @@ int ggml_hip_mul_mat_multi_dev(const ggml_hip_weight *const *w, int n_w, const f
 }
 
 /* the same for any N, with the work buffer a batch needs: src1 is quantized ONCE (the INIT phase, Ggml.cs:6641-6654, is the same for
- * every matrix of one type and K) and the matrices follow -- in one launch where gemm_qmx.hip has the form (5 <= N <= 64), else one
- * COMPUTE after the other behind the shared image.  Every row is bit for bit what ggml_hip_mul_mat_dev gives for that matrix. */
+ * every matrix of one type and K) and the matrices follow -- in one launch where plan.cpp plans the group (plan_mul_mat_group: K3s,
+ * 5 <= N <= 64), else one COMPUTE after the other behind the shared image.  Every row is bit for bit what ggml_hip_mul_mat_dev gives for that matrix. */
 int ggml_hip_mul_mat_multi_work_dev(const ggml_hip_weight *const *w, int n_w, const float *d_src1, int64_t ld1, int64_t N, float *const *d_dst,
                                     const int64_t *ldd, void *d_work, size_t work_bytes, void *stream) {
     if (!w || !d_src1 || !d_dst || !ldd) return fail(GGML_HIP_ERR_ARG, "null argument");
@@ -1039,15 +1040,14 @@ int ggml_hip_mul_mat_multi_work_dev(const ggml_hip_weight *const *w, int n_w, co
     }
     int rc = ggml_hip_mul_mat_init_dev(w[0], d_src1, N, ld1, d_work, work_bytes, stream);
     if (rc) return rc;
-    if (kind == 3 && n_w >= 2) {
+    int64_t M[4], Mpad[4];
+    for (int i = 0; i < n_w; ++i) { M[i] = w[i]->M; Mpad[i] = w[i]->Mpad; }
+    const mm_plan g = plan_mul_mat_group(w[0]->type, w[0]->ext_type, M, Mpad, n_w, w[0]->K, N);
+    if (g.family != MMF_NONE) {
         for (int i = 1; i < n_w; ++i) { rc = weight_device_current(w[i]); if (rc) return rc; }
-        const hipError_t e = launch_gemm_qmx_multi(w, n_w, act_carve(d_work, w[0]->K, pad_act(N)), N, d_dst, ldd, (hipStream_t)stream);
-        if (e == hipSuccess) return GGML_HIP_OK;
-        if (e != hipErrorNotSupported) { (void)hipGetLastError(); return fail(GGML_HIP_ERR_RUNTIME, "multi mul_mat: %s", hipGetErrorString(e)); }
-    }
-    if (kind == 0 && n_w >= 2 && pl0.family == MMF_K3S_I8) {
-        for (int i = 1; i < n_w; ++i) { rc = weight_device_current(w[i]); if (rc) return rc; }
-        const hipError_t e = launch_gemm_q8_small_multi(w, n_w, act_carve(d_work, w[0]->K, pad_act(N)), N, d_dst, ldd, (hipStream_t)stream);
+        const act_planes p = act_carve(d_work, w[0]->K, pad_act(N));
+        const hipError_t e = g.family == MMF_K3S_MX ? launch_gemm_qmx_multi(g, w, n_w, p, N, d_dst, ldd, (hipStream_t)stream)
+                                                    : launch_gemm_q8_small_multi(g, w, n_w, p, N, d_dst, ldd, (hipStream_t)stream);
         if (e == hipSuccess) return GGML_HIP_OK;
         if (e != hipErrorNotSupported) { (void)hipGetLastError(); return fail(GGML_HIP_ERR_RUNTIME, "multi mul_mat: %s", hipGetErrorString(e)); }
     }

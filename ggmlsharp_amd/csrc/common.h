@@ -180,6 +180,20 @@ struct PerDeviceOnce {
     }
 };
 #endif
+#ifdef __HIPCC__
+// Launch KERN with `lds` bytes of dynamic LDS after raising its attribute to `attr_lds` (once per instantiation and device); returns
+// the launch's error.  Grids, block sizes and LDS bytes are the caller's.  kfn<kernel<...>> names the instantiation.
+template <auto KERN> struct kfn_t {};
+template <auto KERN> constexpr kfn_t<KERN> kfn{};
+template <auto KERN, typename... A>
+hipError_t launch_lds(kfn_t<KERN>, dim3 grid, dim3 block, size_t lds, int attr_lds, hipStream_t st, A... args) {
+    static PerDeviceOnce once;
+    const hipError_t attr = once.max_dynamic_lds((const void *)KERN, attr_lds);
+    if (attr != hipSuccess) return attr;
+    KERN<<<grid, block, lds, st>>>(args...);
+    return hipGetLastError();
+}
+#endif
 
 // ---- epilogue applied to the accumulators of a mat-mul kernel as they are stored (the add / scale node
 // that follows a mul_mat node, fused into its store phase).  mode 0: none.  mode 1 (add, Ggml.cs:4622-4682): dst keeps the
@@ -198,6 +212,8 @@ struct mm_epilogue {
     int npush;
     float *push[MM_PUSH_MAX];
 };
+// launchers take `const mm_epilogue *`, nullptr meaning none; the kernels take the epilogue by value
+static inline mm_epilogue epilogue_or_none(const mm_epilogue *ep) { return ep ? *ep : mm_epilogue{0, nullptr, 0, nullptr, 0, 1.0f}; }
 
 // ---- prologue of the fused mat-vec (prologue side): the activation row the kernel quantizes is not read
 // but COMPUTED, y = (x * rms_scale(x)) * g -- the rms_norm -> mul pair in front of a mul_mat (Ggml.cs:5858-5920, 5007-5035) --
@@ -355,17 +371,20 @@ hipError_t launch_gemv_q_fused_pro(const ggml_hip_weight *w, const float *x, int
 hipError_t launch_gemm_q(const ggml_hip_weight *w, const mm_plan &pl, act_planes p, int64_t N, float *dst, int64_t ldd, hipStream_t st);
 // Q8_0, 5 <= N <= 64, K >= 2048: the stage-free batched-decode form on the int8 matrix cores (gemm_q8s.hip; image 0 of K1); ep: add / scale in the store phase
 hipError_t launch_gemm_q8_small(const ggml_hip_weight *w, const mm_plan &pl, act_planes p, int64_t N, float *dst, int64_t ldd, hipStream_t st, const mm_epilogue *ep);
-hipError_t launch_gemm_q8_small_multi(const ggml_hip_weight *const *w, int n_w, act_planes p, int64_t N, float *const *dst, const int64_t *ldd, hipStream_t st);
+hipError_t launch_gemm_q8_small_multi(const mm_plan &g, const ggml_hip_weight *const *w, int n_w, act_planes p, int64_t N, float *const *dst, const int64_t *ldd,
+                                      hipStream_t st);
 hipError_t launch_gemm_q16(const ggml_hip_weight *w, const mm_plan &pl, act_planes p, int64_t N, float *dst, int64_t ldd, hipStream_t st);
-// 2..4 matrices of one type and K behind one activation image in ONE launch (5 <= N <= 64, Q4_0 / Q4_1, K >= 2048: gemm_qmx.hip K3s);
-// hipErrorNotSupported otherwise -- the caller computes them one after the other
-hipError_t launch_gemm_qmx_multi(const ggml_hip_weight *const *w, int n_w, act_planes p, int64_t N, float *const *dst, const int64_t *ldd, hipStream_t st);
+// 2..4 matrices of one type and K behind one activation image in ONE launch of the group plan g (plan.h plan_mul_mat_group: K3s,
+// Q4_0 / Q4_1 here, Q8_0 in gemm_q8s.hip); hipErrorNotSupported where a plane or dst is beyond the kernel -- the caller then computes
+// them one after the other
+hipError_t launch_gemm_qmx_multi(const mm_plan &g, const ggml_hip_weight *const *w, int n_w, act_planes p, int64_t N, float *const *dst, const int64_t *ldd,
+                                 hipStream_t st);
 hipError_t launch_gemm_qmx(const ggml_hip_weight *w, const mm_plan &pl, act_planes p, int64_t N, float *dst, int64_t ldd, hipStream_t st,
-                           const mm_epilogue *ep = nullptr);
+                           const mm_epilogue *ep);
 // Q4_0, prompt-sized batches, K >= 2048 (gemm_qmp.hip K3p); hipErrorNotSupported where the form does not apply
-hipError_t launch_gemm_qmx_mid(const ggml_hip_weight *w, const mm_plan &pl, act_planes p, int64_t N, float *dst, int64_t ldd, hipStream_t st, const mm_epilogue &ep);
+hipError_t launch_gemm_qmx_mid(const ggml_hip_weight *w, const mm_plan &pl, act_planes p, int64_t N, float *dst, int64_t ldd, hipStream_t st, const mm_epilogue *ep);
 // the same form on the int8 matrix cores: Q8_0, image 0 (gemm_qmp.hip)
-hipError_t launch_gemm_q8_mid(const ggml_hip_weight *w, const mm_plan &pl, act_planes p, int64_t N, float *dst, int64_t ldd, hipStream_t st, const mm_epilogue &ep);
+hipError_t launch_gemm_q8_mid(const ggml_hip_weight *w, const mm_plan &pl, act_planes p, int64_t N, float *dst, int64_t ldd, hipStream_t st, const mm_epilogue *ep);
 hipError_t launch_dense(const ggml_hip_weight *w, const mm_plan &pl, const float *x, int64_t N, int64_t ld1, float *dst, int64_t ldd,
                         hipStream_t st);
 

@@ -355,15 +355,8 @@ hipError_t launch_dense(const ggml_hip_weight *w, const mm_plan &pl, const float
         const int kr = (int)(w->K / 8);
         const size_t lds = (size_t)8 * 2 * 32 * DLD * 4;
         (void)hipGetLastError();
-#define DKS_GO(V) do { \
-            auto kern = dense_f32_ksplit_kernel<V>; \
-            static PerDeviceOnce once; \
-            const hipError_t attr = once.max_dynamic_lds((const void *)kern, (int)lds); \
-            if (attr != hipSuccess) return attr; \
-            kern<<<g2, 512, lds, st>>>((const float *)w->dense, x, dst, w->M, N, w->K, ld1, ldd, kr); } while (0)
-        if (vec) DKS_GO(true); else DKS_GO(false);           // (a strided or misaligned src1: the same sums from scalar loads)
-#undef DKS_GO
-        return hipGetLastError();
+        auto go = [&](auto k) { return launch_lds(k, g2, 512, lds, (int)lds, st, (const float *)w->dense, x, dst, w->M, N, w->K, ld1, ldd, kr); };
+        return vec ? go(kfn<dense_f32_ksplit_kernel<true>>) : go(kfn<dense_f32_ksplit_kernel<false>>);   // (a strided or misaligned src1: the same sums from scalar loads)
     }
     {   // F32 weights, enough 128 x 128 tiles to fill the chip (plan.cpp): the big-tile kernel (bitwise the same result; it reads src1 in
         // 16-byte pieces -- a strided or misaligned src1 takes the 64 x 64 kernel, whose fma chain is the same)

@@ -508,37 +508,26 @@ void dense16s_kernel(const uint8_t *__restrict__ wpan, const uint8_t *__restrict
 template <int WMT, int WNT, int WGM, int WGN>
 hipError_t launch_cfg_s(const ggml_hip_weight *w, const uint8_t *apan, int64_t N, int64_t Npad, float *dst, int64_t ldd, hipStream_t st) {
     using C = CfgS<WMT, WNT, WGM, WGN>;
-    auto kern = dense16s_kernel<WMT, WNT, WGM, WGN>;
-    static PerDeviceOnce once;
-    const hipError_t attr = once.max_dynamic_lds((const void *)kern, C::TOTAL);
-    if (attr != hipSuccess) return attr;
     if (w->Mpad % C::TM != 0 || Npad % C::TN != 0) return hipErrorInvalidValue;
     const int64_t Kpad = dense16_kpad(w->K);
     const int tiles_m = (int)((w->M + C::TM - 1) / C::TM), tiles_n = (int)((N + C::TN - 1) / C::TN);
     const uint64_t w_bytes = (uint64_t)(Kpad / 8 + DENSE16_SPARE_PANELS) * w->Mpad * 16, a_bytes = (uint64_t)(Kpad / 8) * Npad * 16;
     if (w_bytes > 0xFFFFFFFFull || a_bytes > 0xFFFFFFFFull || (uint64_t)C::TN * ldd * 4 > 0xFFFFFFFFull) return hipErrorNotSupported;
-    kern<<<dim3((unsigned)(tiles_m * tiles_n)), C::NT, C::TOTAL, st>>>(w->p16, apan, dst, (int)w->M, (int)N, (int)w->Mpad, (int)Npad,
-                                                                       (int)(Kpad / (16 * KS)), (int)ldd, tiles_m, tiles_n, (uint32_t)w_bytes,
-                                                                       (uint32_t)a_bytes);
-    return hipGetLastError();
+    return launch_lds(kfn<dense16s_kernel<WMT, WNT, WGM, WGN>>, dim3((unsigned)(tiles_m * tiles_n)), C::NT, C::TOTAL, C::TOTAL, st, w->p16, apan, dst,
+                      (int)w->M, (int)N, (int)w->Mpad, (int)Npad, (int)(Kpad / (16 * KS)), (int)ldd, tiles_m, tiles_n, (uint32_t)w_bytes, (uint32_t)a_bytes);
 }
 
 template <int WMT, int WNT, int WGM, int WGN, int KSP = 1, int VS = 1>
 hipError_t launch_cfg(const ggml_hip_weight *w, const uint8_t *apan, int64_t N, int64_t Npad, float *dst, int64_t ldd, hipStream_t st) {
     using C = Cfg<WMT, WNT, WGM, WGN>;
-    auto kern = dense16_kernel<WMT, WNT, WGM, WGN, KSP, VS>;
-        static PerDeviceOnce once;   // per kernel instantiation; the attribute is set once per device
-    const hipError_t attr = once.max_dynamic_lds((const void *)kern, C::TOTAL * KSP);
-    if (attr != hipSuccess) return attr;
     if (w->Mpad % C::TM != 0 || Npad % C::TN != 0) return hipErrorInvalidValue;
     const int64_t Kpad = dense16_kpad(w->K);
     const int tiles_m = (int)((w->M + C::TM - 1) / C::TM), tiles_n = (int)((N + C::TN - 1) / C::TN);
     const uint64_t w_bytes = (uint64_t)(Kpad / 8 + DENSE16_SPARE_PANELS) * w->Mpad * 16, a_bytes = (uint64_t)(Kpad / 8) * Npad * 16;
     if (w_bytes > 0xFFFFFFFFull || a_bytes > 0xFFFFFFFFull || (uint64_t)C::TN * ldd * 4 > 0xFFFFFFFFull) return hipErrorNotSupported;
-    kern<<<dim3((unsigned)(tiles_m * tiles_n)), C::NT * KSP, C::TOTAL * KSP, st>>>(w->p16, apan, dst, (int)w->M, (int)N, (int)w->Mpad, (int)Npad,
-                                                                     (int)(Kpad / (16 * KS)), (int)ldd, tiles_m, tiles_n, (uint32_t)w_bytes,
-                                                                     (uint32_t)a_bytes);
-    return hipGetLastError();
+    return launch_lds(kfn<dense16_kernel<WMT, WNT, WGM, WGN, KSP, VS>>, dim3((unsigned)(tiles_m * tiles_n)), C::NT * KSP, C::TOTAL * KSP, C::TOTAL * KSP, st,
+                      w->p16, apan, dst, (int)w->M, (int)N, (int)w->Mpad, (int)Npad, (int)(Kpad / (16 * KS)), (int)ldd, tiles_m, tiles_n, (uint32_t)w_bytes,
+                      (uint32_t)a_bytes);
 }
 
 
@@ -804,14 +793,10 @@ hipError_t launch_dense32_init(const float *x, int64_t N, int64_t K, int64_t ld1
 hipError_t launch_dense32(const ggml_hip_weight *w, const void *work, int64_t N, float *dst, int64_t ldd, hipStream_t st) {
     const int64_t Npad = pad_act(N), Kpad = dense16_kpad(w->K);
     constexpr int LDS = 2 * 12 * 128 * 16;
-    static PerDeviceOnce once;
-    const hipError_t attr = once.max_dynamic_lds((const void *)dense32s_kernel, LDS);
-    if (attr != hipSuccess) return attr;
     if (w->Mpad % 128 != 0 || Npad % 128 != 0) return hipErrorInvalidValue;
     const int tiles_m = (int)((w->M + 127) / 128), tiles_n = (int)((N + 127) / 128);
     const uint64_t w_bytes = (uint64_t)(Kpad / 8 * 3 + DENSE32_SPARE_PANELS) * w->Mpad * 16, a_bytes = (uint64_t)(Kpad / 8 * 3) * Npad * 16;
     if (w_bytes > 0xFFFFFFFFull || a_bytes > 0xFFFFFFFFull || (uint64_t)128 * ldd * 4 > 0xFFFFFFFFull) return hipErrorNotSupported;
-    dense32s_kernel<<<dim3((unsigned)(tiles_m * tiles_n)), 256, LDS, st>>>(w->p32, (const uint8_t *)work, dst, (int)w->M, (int)N, (int)w->Mpad, (int)Npad,
-                                                                           (int)(Kpad / 32), (int)ldd, tiles_m, tiles_n, (uint32_t)w_bytes, (uint32_t)a_bytes);
-    return hipGetLastError();
+    return launch_lds(kfn<dense32s_kernel>, dim3((unsigned)(tiles_m * tiles_n)), 256, LDS, LDS, st, w->p32, (const uint8_t *)work, dst, (int)w->M, (int)N,
+                      (int)w->Mpad, (int)Npad, (int)(Kpad / 32), (int)ldd, tiles_m, tiles_n, (uint32_t)w_bytes, (uint32_t)a_bytes);
 }

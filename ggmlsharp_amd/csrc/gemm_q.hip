@@ -452,15 +452,9 @@ __global__ __launch_bounds__(256, 2) void gemm_q_kernel(const uint8_t *__restric
 template <int TYPE, int IT, int JT>
 hipError_t launch_cfg(const ggml_hip_weight *w, act_planes p, int64_t N, float *dst, int64_t ldd, hipStream_t st) {
     using T = Tile<TYPE, IT, JT>;
-    auto kern = gemm_q_kernel<TYPE, IT, JT>;
-        static PerDeviceOnce once;   // per kernel instantiation; the attribute is set once per device
-    const hipError_t attr = once.max_dynamic_lds((const void *)kern, T::LDS);
-    if (attr != hipSuccess) return attr;
     const int tiles_m = (int)((w->M + T::TM - 1) / T::TM), tiles_n = (int)((N + T::TN - 1) / T::TN);
-    dim3 grid((unsigned)(tiles_m * tiles_n));
-    kern<<<grid, 256, T::LDS, st>>>(TYPE == GQ_TYPE_I8X2 ? w->i8p : w->qs, w->qh, w->d, w->m, p.a8, p.ad, p.as, dst, w->M, N, w->Mpad, p.Npad, w->nbk, ldd,
-                                    tiles_m, tiles_n);
-    return hipGetLastError();
+    return launch_lds(kfn<gemm_q_kernel<TYPE, IT, JT>>, dim3((unsigned)(tiles_m * tiles_n)), 256, T::LDS, T::LDS, st, TYPE == GQ_TYPE_I8X2 ? w->i8p : w->qs,
+                      w->qh, w->d, w->m, p.a8, p.ad, p.as, dst, w->M, N, w->Mpad, p.Npad, w->nbk, ldd, tiles_m, tiles_n);
 }
 
 // 128 x 128 tiles when they already give >= 2 workgroups per CU, else 64 x 64 to fill the chip (plan.cpp plan_i8; one chain over K either way)

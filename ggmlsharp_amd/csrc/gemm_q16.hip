@@ -519,13 +519,8 @@ void gemm_q16_kernel(const uint8_t *__restrict__ wqs, const uint32_t *__restrict
 template <int TYPE, int WMT, int WNT, int WGM, int WGN, int KB, int KSP = 1>
 hipError_t launch_cfg(const ggml_hip_weight *w, act_planes p, int64_t N, float *dst, int64_t ldd, hipStream_t st) {
     using C = Cfg<TYPE, WMT, WNT, WGM, WGN, KB>;
-    auto kern = gemm_q16_kernel<TYPE, WMT, WNT, WGM, WGN, KB, KSP>;
-        static PerDeviceOnce once;   // per kernel instantiation; the attribute is set once per device
-    const hipError_t attr = once.max_dynamic_lds((const void *)kern, C::TOTAL * KSP);
-    if (attr != hipSuccess) return attr;
     if (w->Mpad % C::TM != 0 || p.Npad % C::TN != 0) return hipErrorInvalidValue;
     const int tiles_m = (int)((w->M + C::TM - 1) / C::TM), tiles_n = (int)((N + C::TN - 1) / C::TN);
-    dim3 grid((unsigned)(tiles_m * tiles_n));
     const int nstages = (int)((w->nbk + KB - 1) / KB);      // planes and image are zero-padded to whole stages (KB | K_STAGE_PAD)
     static_assert(K_STAGE_PAD % KB == 0, "stage padding");
     const uint64_t nba = (uint64_t)pad_kblocks(w->nbk);
@@ -534,10 +529,10 @@ hipError_t launch_cfg(const ggml_hip_weight *w, act_planes p, int64_t N, float *
     const uint64_t ad_bytes = nba * (uint64_t)p.Npad * 4, dst_bytes = ((uint64_t)(N - 1) * (uint64_t)ldd + (uint64_t)w->M) * 4;
     constexpr uint64_t LIM = 0xFFFFFFFFull;                  // 32-bit buffer offsets
     if (wq_bytes > LIM || a_bytes > LIM || (uint64_t)C::TN * (uint64_t)ldd * 4 > LIM) return hipErrorNotSupported;   // api.cpp routes such shapes to gemm_q.hip
-    kern<<<grid, C::NT * KSP, C::TOTAL * KSP, st>>>(w->qs, w->qh, w->d, w->m, (const uint8_t *)p.a8, p.ad, (const float *)p.as, dst, (int)w->M,
-                                        (int)N, (int)w->Mpad, (int)p.Npad, nstages, (int)ldd, tiles_m, tiles_n, (uint32_t)wq_bytes,
-                                        (uint32_t)wd_bytes, (uint32_t)a_bytes, (uint32_t)ad_bytes, (uint32_t)dst_bytes);
-    return hipGetLastError();
+    return launch_lds(kfn<gemm_q16_kernel<TYPE, WMT, WNT, WGM, WGN, KB, KSP>>, dim3((unsigned)(tiles_m * tiles_n)), C::NT * KSP, C::TOTAL * KSP,
+                      C::TOTAL * KSP, st, w->qs, w->qh, w->d, w->m, (const uint8_t *)p.a8, p.ad, (const float *)p.as, dst, (int)w->M, (int)N, (int)w->Mpad,
+                      (int)p.Npad, nstages, (int)ldd, tiles_m, tiles_n, (uint32_t)wq_bytes, (uint32_t)wd_bytes, (uint32_t)a_bytes, (uint32_t)ad_bytes,
+                      (uint32_t)dst_bytes);
 }
 
 // The form was chosen by plan.cpp (plan_f16: the K split by N and K, the tile height by the tile count).  The measurements behind it:

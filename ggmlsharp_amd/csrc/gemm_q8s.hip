@@ -518,58 +518,62 @@ void gemm_q8_small_multi_kernel(const q8s_set ws, const int8_t *__restrict__ a8,
 #undef Q8S
 }
 
-hipError_t launch_q8_small_multi(const ggml_hip_weight *const *w, int n_w, act_planes p, int64_t N, float *const *dst, const int64_t *ldd, hipStream_t st) {
+// the instantiation for a weight form (TY: gemm_q8_small_kernel's numbering) -- R16: the 16-row kernel, W its 16-column slices, else W tiles per workgroup
+template <int NB, bool ROT, int W, int TY, bool R16>
+constexpr auto q8s_kernel() {
+    if constexpr (R16) return gemm_q8_small16_kernel<8, NB, ROT, W, TY>;
+    else return gemm_q8_small_kernel<8, NB, ROT, W, TY>;
+}
+template <int NB, bool ROT, int W, bool R16, typename Go>
+hipError_t q8s_by_type(int ty, Go go) {
+    switch (ty) {
+    case 4: return go(kfn<q8s_kernel<NB, ROT, W, 4, R16>()>);
+    case 3: return go(kfn<q8s_kernel<NB, ROT, W, 3, R16>()>);
+    case 2: return go(kfn<q8s_kernel<NB, ROT, W, 2, R16>()>);
+    case 1: return go(kfn<q8s_kernel<NB, ROT, W, 1, R16>()>);
+    default: return go(kfn<q8s_kernel<NB, ROT, W, 0, R16>()>);
+    }
+}
+
+// Q8_0 matrices of one K behind one activation image, planned by plan.cpp (plan_mul_mat_group)
+hipError_t launch_q8_small_multi(const mm_plan &g, const ggml_hip_weight *const *w, int n_w, act_planes p, int64_t N, float *const *dst, const int64_t *ldd,
+                                 hipStream_t st) {
     constexpr int KS = 8;
     const int nbkp = (int)pad_kblocks(w[0]->nbk);
-    int nloc = (nbkp + KS - 1) / KS;
-    nloc += nloc & 1;                                       // (plan.cpp k3p_i8_nloc: the single-matrix form's ranges -- a group computes its members' bits)
+    const int nloc = g.nloc, wmt = g.wmt;
     const int ncol = (int)((N + 31) / 32);
-    if (nloc > 128 || p.Npad < 32 * ncol) return hipErrorNotSupported;
-    int64_t t32 = 0;
-    for (int i = 0; i < n_w; ++i) t32 += (w[i]->M + 31) / 32 * ncol;
-    // r5: three / four tiles per workgroup as well -- the fewest that keep the group inside one round of the chip (gate / up of a 7B model, 2 x 11008 rows: 230 workgroups of 96
-    // rows; it was 344 of 64, a second round a third full).  A 96-row tile may overhang the padded rows: it reads the neighbouring plane there and stores nothing.
-    auto groups = [&](int t) { int64_t g = 0; for (int i = 0; i < n_w; ++i) g += (w[i]->M + 32 * t - 1) / (32 * t) * ncol; return g; };
-    const int wmt = t32 <= 256 ? 1 : t32 <= 512 ? 2 : groups(3) <= 256 ? 3 : 4;
     const uint64_t aq_bytes = (uint64_t)nbkp * 2 * (uint64_t)p.Npad * 16;
-    if (aq_bytes > 0xFFFFFFFFull) return hipErrorNotSupported;
     q8s_set ws = {};
     ws.n = n_w;
     int wgs = 0;
     for (int i = 0; i < 4; ++i) {
         if (i < n_w) {
             const ggml_hip_weight *x = w[i];
+            if (!x->qs || !x->d) return hipErrorNotSupported;
             const uint64_t wq_bytes = (uint64_t)nbkp * 2 * (uint64_t)x->Mpad * 16;
-            if (x->type != GGML_TYPE_Q8_0 || !x->qs || !x->d || x->nbk != w[0]->nbk || x->Mpad % (wmt == 3 ? 32 : 32 * wmt) != 0 || wq_bytes > 0xFFFFFFFFull) return hipErrorNotSupported;
             wgs += (int)((x->M + 32 * wmt - 1) / (32 * wmt)) * ncol;
             ws.qs[i] = x->qs; ws.d[i] = x->d; ws.dst[i] = dst[i]; ws.M[i] = (int)x->M; ws.Mpad[i] = (int)x->Mpad; ws.ldd[i] = ldd[i]; ws.w_bytes[i] = (uint32_t)wq_bytes;
         }
         ws.wg_end[i] = wgs;
     }
-    const int nb = wmt >= 3 ? 4 : wmt == 2 || nloc <= 8 ? 8 : 16, rows = (nloc + nb - 1) / nb * nb;   // (table rows: whole rounds of the form's slots)
-    const int tab = KS * rows * 32 * 4, xch = KS * wmt * 16 * 64 * 4;
-    const int lds = tab > xch ? tab : xch;
-    dim3 grid((unsigned)wgs);
+    const k3s_slots s = plan_k3s_slots(g, GGML_TYPE_Q8_0);
     (void)hipGetLastError();
-#define Q8M_GO(NB, ROT, WMT) do { \
-        auto kern = gemm_q8_small_multi_kernel<KS, NB, ROT, WMT>; \
-        static PerDeviceOnce once; \
-        const hipError_t attr = once.max_dynamic_lds((const void *)kern, 160 * 1024); \
-        if (attr != hipSuccess) return attr; \
-        kern<<<grid, KS * 64, lds, st>>>(ws, p.a8, p.ad, (int)N, (int)p.Npad, (int)w[0]->nbk, nloc, (uint32_t)aq_bytes, ncol); } while (0)
-    if (wmt == 4) { if (nloc <= 4) Q8M_GO(4, false, 4); else Q8M_GO(4, true, 4); }
-    else if (wmt == 3) { if (nloc <= 4) Q8M_GO(4, false, 3); else Q8M_GO(4, true, 3); }
-    else if (wmt == 2) { if (nloc <= 8) Q8M_GO(8, false, 2); else Q8M_GO(8, true, 2); }
-    else if (nloc <= 8) Q8M_GO(8, false, 1);
-    else if (nloc <= 16) Q8M_GO(16, false, 1);
-    else Q8M_GO(16, true, 1);
-#undef Q8M_GO
-    return hipGetLastError();
+    auto go = [&](auto k) {
+        return launch_lds(k, dim3((unsigned)wgs), KS * 64, s.lds, 160 * 1024, st, ws, p.a8, p.ad, (int)N, (int)p.Npad, (int)w[0]->nbk, nloc, (uint32_t)aq_bytes, ncol);
+    };
+    switch (wmt) {
+    case 4: return s.rot ? go(kfn<gemm_q8_small_multi_kernel<KS, 4, true, 4>>) : go(kfn<gemm_q8_small_multi_kernel<KS, 4, false, 4>>);
+    case 3: return s.rot ? go(kfn<gemm_q8_small_multi_kernel<KS, 4, true, 3>>) : go(kfn<gemm_q8_small_multi_kernel<KS, 4, false, 3>>);
+    case 2: return s.rot ? go(kfn<gemm_q8_small_multi_kernel<KS, 8, true, 2>>) : go(kfn<gemm_q8_small_multi_kernel<KS, 8, false, 2>>);
+    default:
+        if (s.rot) return go(kfn<gemm_q8_small_multi_kernel<KS, 16, true, 1>>);
+        return s.slots == 8 ? go(kfn<gemm_q8_small_multi_kernel<KS, 8, false, 1>>) : go(kfn<gemm_q8_small_multi_kernel<KS, 16, false, 1>>);
+    }
 }
 
 hipError_t launch_q8_small(const ggml_hip_weight *w, const mm_plan &pl, act_planes p, int64_t N, float *dst, int64_t ldd, hipStream_t st, const mm_epilogue &ep) {
     constexpr int KS = 8;
-    // k-blocks per wave and tiles per workgroup (one up to 256 tile groups, two beyond: same bits) from plan.cpp (plan_k3s_i8)
+    // k-blocks per wave, tiles per workgroup (one up to 256 tile groups, two beyond: same bits) and the slots from plan.cpp (plan_k3s_i8, plan_k3s_slots)
     const int nbkp = (int)pad_kblocks(w->nbk);
     const int nloc = pl.nloc, wmt = pl.wmt;
     const int ncol = (int)((N + 31) / 32);
@@ -587,80 +591,53 @@ hipError_t launch_q8_small(const ggml_hip_weight *w, const mm_plan &pl, act_plan
     if (pl.family != MMF_K3S_I8 || !(q5 || q42 || w->type == GGML_TYPE_Q8_0) || !planes || !w->d || nloc > 128 || KS * nloc < nbkp || p.Npad < 32 * ncol) return hipErrorInvalidValue;
     if (q51 && (!w->mp3 || !p.sp3)) return hipErrorInvalidValue;
     const bool q5k = (q51 && w->ext_type != 0) || q41;      // (the Q5_K extension: activations by the Q8_K rule, three min pieces; Q4_1: three pieces too)
+    const int ty = q42 ? 4 : q5k ? 3 : q51 ? 2 : q5 ? 1 : 0;
     if (w->Mpad % (32 * wmt) != 0) return hipErrorInvalidValue;
     const uint64_t wq_bytes = (uint64_t)nbkp * 2 * (uint64_t)w->Mpad * 16, aq_bytes = (uint64_t)nbkp * 2 * (uint64_t)p.Npad * 16;
     if (wq_bytes > 0xFFFFFFFFull || aq_bytes > 0xFFFFFFFFull) return hipErrorInvalidValue;
+    const k3s_slots s = plan_k3s_slots(pl, w->type);
     if (pl.tile_m == 16) {
         // r5: 16-row tiles (plan_k3s_i8: Q8_0 / Q5_0 where the 32-row tiles leave CUs idle) -- the same tree, NCT 16-column slices per workgroup
-        if (!(w->type == GGML_TYPE_Q8_0 || q5 || q42)) return hipErrorInvalidValue;
         const int nct = pl.tile_n / 16;
         const int ncg = (int)((N + pl.tile_n - 1) / pl.tile_n);
         if (p.Npad < (int64_t)pl.tile_n * ncg || w->Mpad % 16 != 0) return hipErrorInvalidValue;
         const int ntw16 = (int)((w->M + 15) / 16);
         if (nct != 1 && nct != 2) return hipErrorInvalidValue;       // (four slices per workgroup were built and measured: slower than two 32-row workgroups, plan.cpp)
-        const int nb16 = nloc <= 8 ? 8 : 16, rows16 = (nloc + nb16 - 1) / nb16 * nb16;
-        const int tab16 = KS * rows16 * pl.tile_n * 4, xch16 = KS * nct * 4 * 64 * 4;
-        const int lds16 = tab16 > xch16 ? tab16 : xch16;
-        if (lds16 > 160 * 1024) return hipErrorInvalidValue;
-        dim3 grid16((unsigned)(ntw16 * ncg));
+        if (s.lds > 160 * 1024) return hipErrorInvalidValue;
         (void)hipGetLastError();
-#define Q8S16_GO1(NB, ROT, NCT, TY) do { \
-        auto kern = gemm_q8_small16_kernel<KS, NB, ROT, NCT, TY>; \
-        static PerDeviceOnce once; \
-        const hipError_t attr = once.max_dynamic_lds((const void *)kern, 160 * 1024); \
-        if (attr != hipSuccess) return attr; \
-        kern<<<grid16, KS * 64, lds16, st>>>(planes, w->d, p.a8, p.ad, dst, (int)w->M, (int)N, (int)w->Mpad, (int)p.Npad, (int)w->nbk, nloc, ldd, ep, ntw16, \
-                                          (uint32_t)wq_bytes, (uint32_t)aq_bytes, w->m, w->mp3, p.sp3); } while (0)
-#define Q8S16_GO(NB, ROT, NCT) do { if (q42) Q8S16_GO1(NB, ROT, NCT, 4); else if (q5k) Q8S16_GO1(NB, ROT, NCT, 3); else if (q51) Q8S16_GO1(NB, ROT, NCT, 2); \
-                                    else if (q5) Q8S16_GO1(NB, ROT, NCT, 1); else Q8S16_GO1(NB, ROT, NCT, 0); } while (0)
-        if (nct == 2) { if (nloc <= 8) Q8S16_GO(8, false, 2); else if (nloc <= 16) Q8S16_GO(16, false, 2); else Q8S16_GO(16, true, 2); }
-        else { if (nloc <= 8) Q8S16_GO(8, false, 1); else if (nloc <= 16) Q8S16_GO(16, false, 1); else Q8S16_GO(16, true, 1); }
-#undef Q8S16_GO
-#undef Q8S16_GO1
-        return hipGetLastError();
+        auto go = [&](auto k) {
+            return launch_lds(k, dim3((unsigned)(ntw16 * ncg)), KS * 64, s.lds, 160 * 1024, st, planes, w->d, p.a8, p.ad, dst, (int)w->M, (int)N, (int)w->Mpad,
+                              (int)p.Npad, (int)w->nbk, nloc, ldd, ep, ntw16, (uint32_t)wq_bytes, (uint32_t)aq_bytes, w->m, w->mp3, p.sp3);
+        };
+        if (nct == 2) return s.rot ? q8s_by_type<16, true, 2, true>(ty, go) : s.slots == 8 ? q8s_by_type<8, false, 2, true>(ty, go) : q8s_by_type<16, false, 2, true>(ty, go);
+        return s.rot ? q8s_by_type<16, true, 1, true>(ty, go) : s.slots == 8 ? q8s_by_type<8, false, 1, true>(ty, go) : q8s_by_type<16, false, 1, true>(ty, go);
     }
     const int ntw = (int)((w->M + 32 * wmt - 1) / (32 * wmt));
-    const int nb = wmt == 4 ? 4 : wmt == 2 || nloc <= 8 ? 8 : 16, rows = (nloc + nb - 1) / nb * nb;   // (table rows: whole rounds of the form's slots)
-    const int tab = KS * rows * 32 * 4, xch = KS * wmt * 16 * 64 * 4;
-    const int lds = tab > xch ? tab : xch;
-    dim3 grid((unsigned)(ntw * ncol));
     (void)hipGetLastError();                                // (the value returned below is this launch's, not an earlier call's)
-#define Q8S_GO1(NB, ROT, WMT, TY) do { \
-        auto kern = gemm_q8_small_kernel<KS, NB, ROT, WMT, TY>; \
-        static PerDeviceOnce once; \
-        const hipError_t attr = once.max_dynamic_lds((const void *)kern, 160 * 1024); \
-        if (attr != hipSuccess) return attr; \
-        kern<<<grid, KS * 64, lds, st>>>(planes, w->d, p.a8, p.ad, dst, (int)w->M, (int)N, (int)w->Mpad, (int)p.Npad, (int)w->nbk, nloc, ldd, ep, ntw, \
-                                      (uint32_t)wq_bytes, (uint32_t)aq_bytes, w->mp3, p.sp3, w->m); } while (0)
-#define Q8S_GO(NB, ROT, WMT) do { if (q42) Q8S_GO1(NB, ROT, WMT, 4); else if (q5k) Q8S_GO1(NB, ROT, WMT, 3); else if (q51) Q8S_GO1(NB, ROT, WMT, 2); else if (q5) Q8S_GO1(NB, ROT, WMT, 1); else Q8S_GO1(NB, ROT, WMT, 0); } while (0)
-    // one tile per workgroup: a wave's range in 8 / 16 slots, longer K in rounds of 16; two tiles (more than 256 tile groups): 8 slots,
-    // in rounds beyond K = 2048
-    if (wmt == 4) {                                         // (r5: four tiles per workgroup, more than 512 tile groups -- Q8_0 / Q5_0: four slots in turn)
-        if (q42 || q51) return hipErrorInvalidValue;
-        if (q5) { if (nloc <= 4) Q8S_GO1(4, false, 4, 1); else Q8S_GO1(4, true, 4, 1); }
-        else { if (nloc <= 4) Q8S_GO1(4, false, 4, 0); else Q8S_GO1(4, true, 4, 0); }
+    auto go = [&](auto k) {
+        return launch_lds(k, dim3((unsigned)(ntw * ncol)), KS * 64, s.lds, 160 * 1024, st, planes, w->d, p.a8, p.ad, dst, (int)w->M, (int)N, (int)w->Mpad,
+                          (int)p.Npad, (int)w->nbk, nloc, ldd, ep, ntw, (uint32_t)wq_bytes, (uint32_t)aq_bytes, w->mp3, p.sp3, w->m);
+    };
+    if (wmt == 4) {                                         // (r5: four tiles per workgroup, more than 512 tile groups -- Q8_0 / Q5_0 only)
+        if (ty == 1) return s.rot ? go(kfn<gemm_q8_small_kernel<KS, 4, true, 4, 1>>) : go(kfn<gemm_q8_small_kernel<KS, 4, false, 4, 1>>);
+        if (ty == 0) return s.rot ? go(kfn<gemm_q8_small_kernel<KS, 4, true, 4, 0>>) : go(kfn<gemm_q8_small_kernel<KS, 4, false, 4, 0>>);
+        return hipErrorInvalidValue;
     }
-    else if (wmt == 2) { if (nloc <= 8) Q8S_GO(8, false, 2); else Q8S_GO(8, true, 2); }
-    else if (nloc <= 8) Q8S_GO(8, false, 1);
-    else if (nloc <= 16) Q8S_GO(16, false, 1);
-    else Q8S_GO(16, true, 1);
-#undef Q8S_GO
-#undef Q8S_GO1
-    return hipGetLastError();
+    if (wmt == 2) return s.rot ? q8s_by_type<8, true, 2, false>(ty, go) : q8s_by_type<8, false, 2, false>(ty, go);
+    return s.rot ? q8s_by_type<16, true, 1, false>(ty, go) : s.slots == 8 ? q8s_by_type<8, false, 1, false>(ty, go) : q8s_by_type<16, false, 1, false>(ty, go);
 }
 
 }  // namespace
 
 hipError_t launch_gemm_q8_small(const ggml_hip_weight *w, const mm_plan &pl, act_planes p, int64_t N, float *dst, int64_t ldd, hipStream_t st, const mm_epilogue *ep) {
     if (N <= 0 || w->M <= 0) return hipSuccess;
-    const mm_epilogue none{0, nullptr, 0, nullptr, 0, 1.0f};
-    return launch_q8_small(w, pl, p, N, dst, ldd, st, ep ? *ep : none);
+    return launch_q8_small(w, pl, p, N, dst, ldd, st, epilogue_or_none(ep));
 }
 
-hipError_t launch_gemm_q8_small_multi(const ggml_hip_weight *const *w, int n_w, act_planes p, int64_t N, float *const *dst, const int64_t *ldd, hipStream_t st) {
-    if (n_w < 2 || n_w > 4 || N < 5 || N > 64) return hipErrorNotSupported;
+hipError_t launch_gemm_q8_small_multi(const mm_plan &g, const ggml_hip_weight *const *w, int n_w, act_planes p, int64_t N, float *const *dst, const int64_t *ldd,
+                                      hipStream_t st) {
+    if (g.family != MMF_K3S_I8) return hipErrorInvalidValue;
     for (int i = 0; i < n_w; ++i)
-        if (!w[i] || w[i]->type != GGML_TYPE_Q8_0 || w[i]->M <= 0) return hipErrorNotSupported;
-    return launch_q8_small_multi(w, n_w, p, N, dst, ldd, st);
+        if (!w[i] || w[i]->type != GGML_TYPE_Q8_0) return hipErrorNotSupported;
+    return launch_q8_small_multi(g, w, n_w, p, N, dst, ldd, st);
 }
-

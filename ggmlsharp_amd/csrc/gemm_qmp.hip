@@ -652,7 +652,13 @@ static unsigned persistent_grid(int tiles) {
     return (unsigned)(tiles < 4 * n ? tiles : n);
 }
 
-hipError_t launch_gemm_q8_mid(const ggml_hip_weight *w, const mm_plan &pl, act_planes p, int64_t N, float *dst, int64_t ldd, hipStream_t st, const mm_epilogue &ep) {
+template <int TYPE, bool M3, typename Go>
+static hipError_t q8_mid_go(bool sliced, int wmt, Go go) {
+    if (wmt == 2) return sliced ? go(kfn<gemm_q8_mid_kernel<TYPE, M3, true, 2>>) : go(kfn<gemm_q8_mid_kernel<TYPE, M3, false, 2>>);
+    return sliced ? go(kfn<gemm_q8_mid_kernel<TYPE, M3, true, 4>>) : go(kfn<gemm_q8_mid_kernel<TYPE, M3, false, 4>>);
+}
+
+hipError_t launch_gemm_q8_mid(const ggml_hip_weight *w, const mm_plan &pl, act_planes p, int64_t N, float *dst, int64_t ldd, hipStream_t st, const mm_epilogue *ep) {
     const bool with_min = w->type == GGML_TYPE_Q5_1 || w->type == GGML_TYPE_Q4_1;
     const bool two = w->type == GGML_TYPE_Q4_2;             // (and Q6_K in its planar form: int8 planes, the k-block's second scale in the m plane)
     const uint8_t *planes = w->type == GGML_TYPE_Q8_0 ? w->qs : (w->type == GGML_TYPE_Q5_0 || with_min || two) ? w->i8p : nullptr;
@@ -675,27 +681,23 @@ hipError_t launch_gemm_q8_mid(const ggml_hip_weight *w, const mm_plan &pl, act_p
     const size_t lds = tab > xch ? tab : xch;
     if (lds > 160 * 1024 || ch > nloc) return hipErrorInvalidValue;
     (void)hipGetLastError();
-#define Q8MID_GO(...) do { if (wmt == 2) { if (sliced) Q8MID_GO1(__VA_ARGS__, true, 2); else Q8MID_GO1(__VA_ARGS__, false, 2); } \
-                           else { if (sliced) Q8MID_GO1(__VA_ARGS__, true, 4); else Q8MID_GO1(__VA_ARGS__, false, 4); } } while (0)
-#define Q8MID_GO1(...) do { \
-        auto kern = gemm_q8_mid_kernel<__VA_ARGS__>; \
-        static PerDeviceOnce once; \
-        const hipError_t attr = once.max_dynamic_lds((const void *)kern, 160 * 1024); \
-        if (attr != hipSuccess) return attr; \
-        kern<<<dim3(persistent_grid(tiles_m * tiles_n)), KS * 64, lds, st>>>(planes, w->d, p.a8, p.ad, dst, (int)w->M, (int)N, (int)w->Mpad, (int)p.Npad, \
-                                                                        (int)w->nbk, nloc, (int)ldd, tiles_m, tiles_n, (uint32_t)wq_bytes, (uint32_t)aq_bytes, ep, two ? (const uint8_t *)w->m : w->mp3, p.sp3, ch); } while (0)
+    const mm_epilogue e = epilogue_or_none(ep);
+    auto go = [&](auto k) {
+        return launch_lds(k, dim3(persistent_grid(tiles_m * tiles_n)), KS * 64, lds, 160 * 1024, st, planes, w->d, p.a8, p.ad, dst, (int)w->M, (int)N, (int)w->Mpad,
+                          (int)p.Npad, (int)w->nbk, nloc, (int)ldd, tiles_m, tiles_n, (uint32_t)wq_bytes, (uint32_t)aq_bytes, e,
+                          two ? (const uint8_t *)w->m : w->mp3, p.sp3, ch);
+    };
     // (Q4_1: the kernel of Q5_1 -- unsigned values 0..15 on the int8 planes, the same min term)
-    if (w->type == GGML_TYPE_Q8_0) Q8MID_GO(GGML_TYPE_Q8_0, false); else if (w->type == GGML_TYPE_Q5_0) Q8MID_GO(GGML_TYPE_Q5_0, false);
-    else if (two) Q8MID_GO(GGML_TYPE_Q4_2, false);
+    if (w->type == GGML_TYPE_Q8_0) return q8_mid_go<GGML_TYPE_Q8_0, false>(sliced, wmt, go);
+    if (w->type == GGML_TYPE_Q5_0) return q8_mid_go<GGML_TYPE_Q5_0, false>(sliced, wmt, go);
+    if (two) return q8_mid_go<GGML_TYPE_Q4_2, false>(sliced, wmt, go);
     // (the min of a Q5_1 block is an f16 value: two bf16 pieces; Q4_1's is an f32, Q5_K's an f32 product: three)
-    else if (w->ext_type != 0 || w->type == GGML_TYPE_Q4_1) Q8MID_GO(GGML_TYPE_Q5_1, true); else Q8MID_GO(GGML_TYPE_Q5_1, false);
-#undef Q8MID_GO
-#undef Q8MID_GO1
-    return hipGetLastError();
+    if (w->ext_type != 0 || w->type == GGML_TYPE_Q4_1) return q8_mid_go<GGML_TYPE_Q5_1, true>(sliced, wmt, go);
+    return q8_mid_go<GGML_TYPE_Q5_1, false>(sliced, wmt, go);
 }
 
 // Q4_0 (plan.cpp plan_k3p_mx: at least 8 k-blocks per wave, tables within LDS, offsets within 32 bits)
-hipError_t launch_gemm_qmx_mid(const ggml_hip_weight *w, const mm_plan &pl, act_planes p, int64_t N, float *dst, int64_t ldd, hipStream_t st, const mm_epilogue &ep) {
+hipError_t launch_gemm_qmx_mid(const ggml_hip_weight *w, const mm_plan &pl, act_planes p, int64_t N, float *dst, int64_t ldd, hipStream_t st, const mm_epilogue *ep) {
     if (pl.family != MMF_K3P_MX || w->type != GGML_TYPE_Q4_0 || !w->q6a || !w->q6b) return hipErrorInvalidValue;
     if (ldd > 0x7FFFFFFF) return hipErrorNotSupported;     // (see launch_gemm_q8_mid)
     const int nbkp = (int)pad_kblocks(w->nbk);
@@ -714,13 +716,12 @@ hipError_t launch_gemm_qmx_mid(const ggml_hip_weight *w, const mm_plan &pl, act_
     const size_t tab = (size_t)KS * ch * (32 * WNT) * 4, xch = (size_t)KS * 4 * 16 * 64 * 4;
     const size_t lds = tab > xch ? tab : xch;
     if (lds > 160 * 1024) return hipErrorInvalidValue;
-    auto kern = wmt == 2 ? (sliced ? gemm_qmx_mid_kernel<true, 2> : gemm_qmx_mid_kernel<false, 2>) : (sliced ? gemm_qmx_mid_kernel<true, 4> : gemm_qmx_mid_kernel<false, 4>);
-    static PerDeviceOnce once[4];
-    const hipError_t attr = once[(wmt == 2 ? 2 : 0) + (sliced ? 1 : 0)].max_dynamic_lds((const void *)kern, 160 * 1024);
-    if (attr != hipSuccess) return attr;
     (void)hipGetLastError();
-    kern<<<dim3(persistent_grid(tiles_m * tiles_n)), KS * 64, lds, st>>>(w->q6a, w->q6b, w->d, (const uint8_t *)p.a8, p.ad, dst, (int)w->M, (int)N,
-                                                                                     (int)w->Mpad, (int)p.Npad, nbkp, nloc, (int)ldd, tiles_m, tiles_n,
-                                                                                     (uint32_t)wq_bytes, (uint32_t)wd_bytes, (uint32_t)a_bytes, ep, ch);
-    return hipGetLastError();
+    auto go = [&](auto k) {
+        return launch_lds(k, dim3(persistent_grid(tiles_m * tiles_n)), KS * 64, lds, 160 * 1024, st, w->q6a, w->q6b, w->d, (const uint8_t *)p.a8, p.ad, dst,
+                          (int)w->M, (int)N, (int)w->Mpad, (int)p.Npad, nbkp, nloc, (int)ldd, tiles_m, tiles_n, (uint32_t)wq_bytes, (uint32_t)wd_bytes, (uint32_t)a_bytes,
+                          epilogue_or_none(ep), ch);
+    };
+    if (wmt == 2) return sliced ? go(kfn<gemm_qmx_mid_kernel<true, 2>>) : go(kfn<gemm_qmx_mid_kernel<false, 2>>);
+    return sliced ? go(kfn<gemm_qmx_mid_kernel<true, 4>>) : go(kfn<gemm_qmx_mid_kernel<false, 4>>);
 }

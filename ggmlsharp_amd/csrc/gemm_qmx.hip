@@ -1072,20 +1072,11 @@ void gemm_qmx_small_multi_kernel(const mxs_set ws, const uint8_t *__restrict__ a
 #undef MXS
 }
 
-// the epilogue of the call in flight on this host thread (set by launch_gemm_qmx around launch_typed: the tile-form selection
-// below has a dozen call sites, the epilogue concerns none of them)
-thread_local mm_epilogue t_epilogue = {0, nullptr, 0, nullptr, 0, 1.0f};
-
 template <int TYPE, int WMT, int WNT, int WGM, int WGN, int KB, int FB, int KSP = 1, int VS = 1>
-hipError_t launch_cfg(const ggml_hip_weight *w, act_planes p, int64_t N, float *dst, int64_t ldd, hipStream_t st) {
+hipError_t launch_cfg(const ggml_hip_weight *w, act_planes p, int64_t N, float *dst, int64_t ldd, hipStream_t st, const mm_epilogue *ep) {
     using C = Cfg<TYPE, WMT, WNT, WGM, WGN, KB>;
-    auto kern = gemm_qmx_kernel<TYPE, WMT, WNT, WGM, WGN, KB, FB, KSP, VS>;
-        static PerDeviceOnce once;   // per kernel instantiation; the attribute is set once per device
-    const hipError_t attr = once.max_dynamic_lds((const void *)kern, C::TOTAL * KSP);
-    if (attr != hipSuccess) return attr;
     if (w->Mpad % C::TM != 0 || p.Npad % C::TN != 0 || !w->q6a || !w->q6b) return hipErrorInvalidValue;
     const int tiles_m = (int)((w->M + C::TM - 1) / C::TM), tiles_n = (int)((N + C::TN - 1) / C::TN);
-    dim3 grid((unsigned)(tiles_m * tiles_n));
     const int nstages = (int)((w->nbk + KB - 1) / KB);      // planes and image are zero-padded to whole stages (KB | K_STAGE_PAD)
     static_assert(K_STAGE_PAD % KB == 0, "stage padding");
     const uint64_t nba = (uint64_t)pad_kblocks(w->nbk);
@@ -1095,19 +1086,19 @@ hipError_t launch_cfg(const ggml_hip_weight *w, act_planes p, int64_t N, float *
     const uint64_t ad_bytes = nba * (uint64_t)p.Npad * 4, dst_bytes = ((uint64_t)(N - 1) * (uint64_t)ldd + (uint64_t)w->M) * 4;
     constexpr uint64_t LIM = 0xFFFFFFFFull;                  // 32-bit buffer offsets
     if (wq_bytes > LIM || a_bytes > LIM || (uint64_t)C::TN * (uint64_t)ldd * 4 > LIM) return hipErrorNotSupported;   // api.cpp routes such shapes to gemm_q.hip
-    kern<<<grid, C::NT * KSP, C::TOTAL * KSP, st>>>(w->q6a, w->q6b, w->d, w->m, (const uint8_t *)p.a8, p.ad, (const float *)p.as, dst, (int)w->M,
-                                        (int)N, (int)w->Mpad, (int)p.Npad, nstages, (int)ldd, tiles_m, tiles_n, (uint32_t)wq_bytes,
-                                        (uint32_t)wd_bytes, (uint32_t)a_bytes, (uint32_t)ad_bytes, (uint32_t)dst_bytes, t_epilogue);
-    return hipGetLastError();
+    return launch_lds(kfn<gemm_qmx_kernel<TYPE, WMT, WNT, WGM, WGN, KB, FB, KSP, VS>>, dim3((unsigned)(tiles_m * tiles_n)), C::NT * KSP, C::TOTAL * KSP,
+                      C::TOTAL * KSP, st, w->q6a, w->q6b, w->d, w->m, (const uint8_t *)p.a8, p.ad, (const float *)p.as, dst, (int)w->M, (int)N, (int)w->Mpad,
+                      (int)p.Npad, nstages, (int)ldd, tiles_m, tiles_n, (uint32_t)wq_bytes, (uint32_t)wd_bytes, (uint32_t)a_bytes, (uint32_t)ad_bytes,
+                      (uint32_t)dst_bytes, epilogue_or_none(ep));
 }
 
-// K3s launch: KS = 8 waves per 32-row tile, each a contiguous eighth of K in pairs of blocks; the slots hold a wave's whole range
-// for K <= 4096 (8 pairs) and K <= 2048 (4 pairs), longer K refills them in turn.  Chosen by N and K alone.
+// K3s launch: KS = 8 waves per 32-row tile, each a contiguous eighth of K in pairs of blocks.  Chosen by N and K alone.
 template <int TYPE>
-hipError_t launch_small(const ggml_hip_weight *w, const mm_plan &pl, act_planes p, int64_t N, float *dst, int64_t ldd, hipStream_t st) {
+hipError_t launch_small(const ggml_hip_weight *w, const mm_plan &pl, act_planes p, int64_t N, float *dst, int64_t ldd, hipStream_t st, const mm_epilogue *ep) {
     constexpr int KS = 8;
+    constexpr bool Q40 = TYPE == GGML_TYPE_Q4_0, Q41 = TYPE == GGML_TYPE_Q4_1;
     if (!w->q6a || !w->q6b) return hipErrorInvalidValue;
-    // geometry and applicability were decided by plan.cpp (plan_k3s_mx): k-blocks per wave, 32-row tiles per workgroup (more tiles than CUs:
+    // geometry, applicability and the slots were decided by plan.cpp (plan_k3s_mx, plan_k3s_slots): k-blocks per wave, 32-row tiles per workgroup (more tiles than CUs:
     // two of them per workgroup, four beyond 512 tiles -- every workgroup pulls the whole activation image through its CU's vector
     // memory path, and that path is what bounds the form; same blocks in the same order per element: the same bits)
     const int nbkp = (int)pad_kblocks(w->nbk);
@@ -1115,120 +1106,95 @@ hipError_t launch_small(const ggml_hip_weight *w, const mm_plan &pl, act_planes 
     const uint64_t nba = (uint64_t)nbkp;
     const uint64_t wq_bytes = (nba + K_LOOKAHEAD) * (uint64_t)w->Mpad * 16, wd_bytes = (nba + K_LOOKAHEAD) * (uint64_t)w->Mpad * 4;
     const uint64_t a_bytes = nba * 48 * (uint64_t)p.Npad, ad_bytes = nba * (uint64_t)p.Npad * 4;
-    if (nloc > 128 || wq_bytes > 0xFFFFFFFFull || a_bytes > 0xFFFFFFFFull) return hipErrorInvalidValue;    // (the plan never sends such a shape here)
+    const k3s_slots s = plan_k3s_slots(pl, TYPE);
+    if (nloc > 128 || wq_bytes > 0xFFFFFFFFull || a_bytes > 0xFFFFFFFFull || s.lds > 160 * 1024) return hipErrorInvalidValue;    // (the plan never sends such a shape here)
+    const mm_epilogue e = epilogue_or_none(ep);
     if (pl.tile_m == 16) {
         // r5: 16-row tiles (plan_k3s_mx: where the 32-row tiles leave CUs idle) -- the same tree, NCT 16-column slices per workgroup
-        {
-            constexpr bool Q41 = TYPE == GGML_TYPE_Q4_1;
-            const int nct = pl.tile_n / 16, ncg = (int)((N + pl.tile_n - 1) / pl.tile_n);
-            if (p.Npad < (int64_t)pl.tile_n * ncg || w->Mpad % 16 != 0 || (nloc & 1)) return hipErrorInvalidValue;
-            if (nct != 1 && nct != 2) return hipErrorInvalidValue;
-            if (Q41 && (!w->m || !p.as)) return hipErrorInvalidValue;
-            const int np16 = nloc <= 8 ? 4 : 8;                          // pairs in flight per wave (the slots; beyond 16 k-blocks per wave: in turn)
-            const bool rot16 = nloc > 2 * np16;
-            const int rows16 = rot16 ? nloc : 2 * np16;
-            const int tab16 = KS * rows16 * pl.tile_n * 4, xch16 = KS * nct * 4 * 64 * 4;
-            const int lds16 = tab16 > xch16 ? tab16 : xch16;
-            if (lds16 > 160 * 1024) return hipErrorInvalidValue;
-            const int ntw16 = (int)((w->M + 15) / 16);
-            dim3 grid16((unsigned)(ntw16 * ncg));
-#define K3S16_GO(NP, ROT, NCT) do { \
-            auto kern = gemm_qmx_small16_kernel<KS, NP, ROT, NCT, Q41>; \
-            static PerDeviceOnce once; \
-            const hipError_t attr = once.max_dynamic_lds((const void *)kern, 160 * 1024); \
-            if (attr != hipSuccess) return attr; \
-            kern<<<grid16, KS * 64, lds16, st>>>(w->q6a, w->q6b, w->d, w->m, (const uint8_t *)p.a8, p.ad, (const float *)p.as, dst, (int)w->M, (int)N, (int)w->Mpad, \
-                                              (int)p.Npad, nbkp, nloc, (int)ldd, (uint32_t)wq_bytes, (uint32_t)wd_bytes, (uint32_t)a_bytes, t_epilogue, ntw16); } while (0)
-            if (nct == 2) {
-                if (nloc <= 8) K3S16_GO(4, false, 2); else if (nloc <= 16) K3S16_GO(8, false, 2);
-                else if constexpr (Q41) K3S16_GO(6, true, 2);            // (Q4_1 carries the min and d1 * sum(a) per slot: eight slots of two slices spill)
-                else K3S16_GO(8, true, 2);
-            }
-            else { if (nloc <= 8) K3S16_GO(4, false, 1); else if (nloc <= 16) K3S16_GO(8, false, 1); else K3S16_GO(8, true, 1); }
-#undef K3S16_GO
-            return hipGetLastError();
+        const int nct = pl.tile_n / 16, ncg = (int)((N + pl.tile_n - 1) / pl.tile_n);
+        if (p.Npad < (int64_t)pl.tile_n * ncg || w->Mpad % 16 != 0 || (nloc & 1)) return hipErrorInvalidValue;
+        if (nct != 1 && nct != 2) return hipErrorInvalidValue;
+        if (Q41 && (!w->m || !p.as)) return hipErrorInvalidValue;
+        const int ntw16 = (int)((w->M + 15) / 16);
+        auto go = [&](auto k) {
+            return launch_lds(k, dim3((unsigned)(ntw16 * ncg)), KS * 64, s.lds, 160 * 1024, st, w->q6a, w->q6b, w->d, w->m, (const uint8_t *)p.a8, p.ad,
+                              (const float *)p.as, dst, (int)w->M, (int)N, (int)w->Mpad, (int)p.Npad, nbkp, nloc, (int)ldd, (uint32_t)wq_bytes, (uint32_t)wd_bytes,
+                              (uint32_t)a_bytes, e, ntw16);
+        };
+        if (nct == 2) {
+            if (!s.rot) return s.slots == 4 ? go(kfn<gemm_qmx_small16_kernel<KS, 4, false, 2, Q41>>) : go(kfn<gemm_qmx_small16_kernel<KS, 8, false, 2, Q41>>);
+            if constexpr (Q41) return go(kfn<gemm_qmx_small16_kernel<KS, 6, true, 2, Q41>>);
+            else return go(kfn<gemm_qmx_small16_kernel<KS, 8, true, 2, Q41>>);
         }
+        if (!s.rot) return s.slots == 4 ? go(kfn<gemm_qmx_small16_kernel<KS, 4, false, 1, Q41>>) : go(kfn<gemm_qmx_small16_kernel<KS, 8, false, 1, Q41>>);
+        return go(kfn<gemm_qmx_small16_kernel<KS, 8, true, 1, Q41>>);
     }
-    const int rows = nloc <= 8 ? 8 : nloc <= 16 ? 16 : nloc;
     const int ncol = (int)((N + 31) / 32);                  // 32-column slices of src1: one workgroup per tile group and slice
-    if (p.Npad < 32 * ncol) return hipErrorInvalidValue;
-    const bool two = wmt == 2;
-    const int tab = KS * rows * 32 * 4, xch = KS * wmt * 16 * 64 * 4;
-    const int lds = tab > xch ? tab : xch;
+    if (p.Npad < 32 * ncol || w->Mpad % (32 * wmt) != 0) return hipErrorInvalidValue;
     const int ntw = (int)((w->M + 32 * wmt - 1) / (32 * wmt));
-    dim3 grid((unsigned)(ntw * ncol));
-    if (w->Mpad % (32 * wmt) != 0) return hipErrorInvalidValue;
-#define K3S_GO(NP, ROT, WMT) do { \
-        auto kern = gemm_qmx_small_kernel<TYPE, KS, NP, ROT, WMT>; \
-        static PerDeviceOnce once; \
-        const hipError_t attr = once.max_dynamic_lds((const void *)kern, 160 * 1024); \
-        if (attr != hipSuccess) return attr; \
-        kern<<<grid, KS * 64, lds, st>>>(w->q6a, w->q6b, w->d, w->m, (const uint8_t *)p.a8, p.ad, (const float *)p.as, dst, (int)w->M, (int)N, \
-                                      (int)w->Mpad, (int)p.Npad, nbkp, nloc, (int)ldd, (uint32_t)wq_bytes, (uint32_t)wd_bytes, (uint32_t)a_bytes, \
-                                      (uint32_t)ad_bytes, t_epilogue, ntw); } while (0)
-    if (wmt == 4) { if constexpr (TYPE == GGML_TYPE_Q4_0) K3S_GO(2, true, 4); }
-    else if (two) { if (nloc <= 8) K3S_GO(4, false, 2); else if constexpr (TYPE == GGML_TYPE_Q4_1) K3S_GO(3, true, 2); else K3S_GO(4, true, 2); }
-    else if (nloc <= 8) K3S_GO(4, false, 1);
-    else if (nloc <= 16) K3S_GO(8, false, 1);
-    else { if constexpr (TYPE == GGML_TYPE_Q4_1) K3S_GO(4, true, 1); else K3S_GO(8, true, 1); }   // (Q4_1 carries three more registers per pair)
-#undef K3S_GO
-    return hipGetLastError();
+    auto go = [&](auto k) {
+        return launch_lds(k, dim3((unsigned)(ntw * ncol)), KS * 64, s.lds, 160 * 1024, st, w->q6a, w->q6b, w->d, w->m, (const uint8_t *)p.a8, p.ad,
+                          (const float *)p.as, dst, (int)w->M, (int)N, (int)w->Mpad, (int)p.Npad, nbkp, nloc, (int)ldd, (uint32_t)wq_bytes, (uint32_t)wd_bytes,
+                          (uint32_t)a_bytes, (uint32_t)ad_bytes, e, ntw);
+    };
+    // (the slots plan_k3s_slots gives each type: the instantiations below)
+    if (wmt == 4) {
+        if constexpr (Q40) return go(kfn<gemm_qmx_small_kernel<TYPE, KS, 2, true, 4>>);
+        return hipErrorInvalidValue;
+    }
+    if (wmt == 2) {
+        if (!s.rot) return go(kfn<gemm_qmx_small_kernel<TYPE, KS, 4, false, 2>>);
+        if constexpr (Q41) return go(kfn<gemm_qmx_small_kernel<TYPE, KS, 3, true, 2>>);
+        else return go(kfn<gemm_qmx_small_kernel<TYPE, KS, 4, true, 2>>);
+    }
+    if (!s.rot) return s.slots == 4 ? go(kfn<gemm_qmx_small_kernel<TYPE, KS, 4, false, 1>>) : go(kfn<gemm_qmx_small_kernel<TYPE, KS, 8, false, 1>>);
+    if constexpr (Q41) return go(kfn<gemm_qmx_small_kernel<TYPE, KS, 4, true, 1>>);
+    else return go(kfn<gemm_qmx_small_kernel<TYPE, KS, 8, true, 1>>);
 }
 
-// K3s for several matrices of one type and K behind one activation image: hipErrorNotSupported where the single-matrix form would
-// not run either (the caller then computes them one after the other).  Tiles per workgroup by the tiles of all of them together.
+// K3s for several matrices of one type and K behind one activation image, planned by plan.cpp (plan_mul_mat_group).  Tiles per workgroup by
+// the tiles of all of them together.
 template <int TYPE>
-hipError_t launch_small_multi(const ggml_hip_weight *const *w, int n_w, act_planes p, int64_t N, float *const *dst, const int64_t *ldd, hipStream_t st) {
+hipError_t launch_small_multi(const mm_plan &g, const ggml_hip_weight *const *w, int n_w, act_planes p, int64_t N, float *const *dst, const int64_t *ldd,
+                              hipStream_t st) {
     constexpr int KS = 8;
+    constexpr bool Q40 = TYPE == GGML_TYPE_Q4_0, Q41 = TYPE == GGML_TYPE_Q4_1;
     const int nbkp = (int)pad_kblocks(w[0]->nbk);
-    int nloc = (nbkp + KS - 1) / KS;
-    nloc += nloc & 1;
-    if (w[0]->nbk < 64 || nloc > 128) return hipErrorNotSupported;
+    const int nloc = g.nloc, wmt = g.wmt;
     const uint64_t nba = (uint64_t)nbkp;
     const uint64_t a_bytes = nba * 48 * (uint64_t)p.Npad, ad_bytes = nba * (uint64_t)p.Npad * 4;
-    if (a_bytes > 0xFFFFFFFFull) return hipErrorNotSupported;
     const int ncol = (int)((N + 31) / 32);
-    if (p.Npad < 32 * ncol) return hipErrorNotSupported;
-    int64_t t32 = 0;
-    for (int i = 0; i < n_w; ++i) t32 += (w[i]->M + 31) / 32 * ncol;
-    // r5: THREE tiles per workgroup where that is the fewest that keeps the group inside one round of the chip (gate / up of a 7B model: 2 x 11008 rows are 230 workgroups of 96 rows,
-    // 172 of 128): geometry on the form's tree, like the other tile counts.  A 96-row tile may overhang the padded rows: it reads the neighbouring plane's bytes there (inside the
-    // buffer, or zeros past it) and stores nothing.
-    auto groups = [&](int t) { int64_t g = 0; for (int i = 0; i < n_w; ++i) g += (w[i]->M + 32 * t - 1) / (32 * t) * ncol; return g; };
-    const int wmt = t32 <= 256 ? 1 : t32 <= 512 || TYPE == GGML_TYPE_Q4_1 ? 2 : groups(3) <= 256 ? 3 : 4;
     mxs_set ws = {};
     ws.n = n_w;
     int wgs = 0;
     for (int i = 0; i < 4; ++i) {
         if (i < n_w) {
             const ggml_hip_weight *x = w[i];
+            if (!x->q6a || !x->q6b) return hipErrorNotSupported;
             const uint64_t wq_bytes = (nba + K_LOOKAHEAD) * (uint64_t)x->Mpad * 16, wd_bytes = (nba + K_LOOKAHEAD) * (uint64_t)x->Mpad * 4;
-            if (!x->q6a || !x->q6b || x->nbk != w[0]->nbk || x->Mpad % (wmt == 3 ? 32 : 32 * wmt) != 0 || wq_bytes > 0xFFFFFFFFull) return hipErrorNotSupported;
             wgs += (int)((x->M + 32 * wmt - 1) / (32 * wmt)) * ncol;
             ws.a[i] = x->q6a; ws.b[i] = x->q6b; ws.d[i] = x->d; ws.m[i] = x->m; ws.dst[i] = dst[i];
             ws.M[i] = (int)x->M; ws.Mpad[i] = (int)x->Mpad; ws.ldd[i] = (int)ldd[i]; ws.wa_bytes[i] = (uint32_t)wq_bytes; ws.wd_bytes[i] = (uint32_t)wd_bytes;
         }
         ws.wg_end[i] = wgs;
     }
-    const int rows = nloc <= 8 ? 8 : nloc <= 16 ? 16 : nloc;
-    const int tab = KS * rows * 32 * 4, xch = KS * wmt * 16 * 64 * 4;
-    const int lds = tab > xch ? tab : xch;
-    dim3 grid((unsigned)wgs);
-#define K3M_GO(NP, ROT, WMT) do { \
-        auto kern = gemm_qmx_small_multi_kernel<TYPE, KS, NP, ROT, WMT>; \
-        static PerDeviceOnce once; \
-        const hipError_t attr = once.max_dynamic_lds((const void *)kern, 160 * 1024); \
-        if (attr != hipSuccess) return attr; \
-        kern<<<grid, KS * 64, lds, st>>>(ws, (const uint8_t *)p.a8, p.ad, (const float *)p.as, (int)N, (int)p.Npad, nbkp, nloc, (uint32_t)a_bytes, \
-                                      (uint32_t)ad_bytes, ncol); } while (0)
-    if (wmt == 4) { if constexpr (TYPE == GGML_TYPE_Q4_0) K3M_GO(2, true, 4); }
-    else if (wmt == 3) { if constexpr (TYPE == GGML_TYPE_Q4_0) K3M_GO(2, true, 3); }
-    else if (wmt == 2) { if (nloc <= 8) K3M_GO(4, false, 2); else if constexpr (TYPE == GGML_TYPE_Q4_1) K3M_GO(3, true, 2); else K3M_GO(4, true, 2); }
-    else if (nloc <= 8) K3M_GO(4, false, 1);
-    else if (nloc <= 16) K3M_GO(8, false, 1);
-    else { if constexpr (TYPE == GGML_TYPE_Q4_1) K3M_GO(4, true, 1); else K3M_GO(8, true, 1); }
-#undef K3M_GO
-    return hipGetLastError();
+    const k3s_slots s = plan_k3s_slots(g, TYPE);
+    auto go = [&](auto k) {
+        return launch_lds(k, dim3((unsigned)wgs), KS * 64, s.lds, 160 * 1024, st, ws, (const uint8_t *)p.a8, p.ad, (const float *)p.as, (int)N, (int)p.Npad,
+                          nbkp, nloc, (uint32_t)a_bytes, (uint32_t)ad_bytes, ncol);
+    };
+    if (wmt >= 3) {
+        if constexpr (Q40) return wmt == 4 ? go(kfn<gemm_qmx_small_multi_kernel<TYPE, KS, 2, true, 4>>) : go(kfn<gemm_qmx_small_multi_kernel<TYPE, KS, 2, true, 3>>);
+        return hipErrorInvalidValue;
+    }
+    if (wmt == 2) {
+        if (!s.rot) return go(kfn<gemm_qmx_small_multi_kernel<TYPE, KS, 4, false, 2>>);
+        if constexpr (Q41) return go(kfn<gemm_qmx_small_multi_kernel<TYPE, KS, 3, true, 2>>);
+        else return go(kfn<gemm_qmx_small_multi_kernel<TYPE, KS, 4, true, 2>>);
+    }
+    if (!s.rot) return s.slots == 4 ? go(kfn<gemm_qmx_small_multi_kernel<TYPE, KS, 4, false, 1>>) : go(kfn<gemm_qmx_small_multi_kernel<TYPE, KS, 8, false, 1>>);
+    if constexpr (Q41) return go(kfn<gemm_qmx_small_multi_kernel<TYPE, KS, 4, true, 1>>);
+    else return go(kfn<gemm_qmx_small_multi_kernel<TYPE, KS, 8, true, 1>>);
 }
 
 #ifndef MX_SMALL_FB
@@ -1249,27 +1215,27 @@ hipError_t launch_small_multi(const ggml_hip_weight *const *w, int n_w, act_plan
 //   * a short, wide product (a row shard): 64 x 64 tiles of four 1-tile waves wherever the 128 x 64 grid leaves CUs idle
 //     (1024 x 4096 x 768 37.0 -> 26.3 us, 512 x 4096 x 1024 36.8 -> 24.1, 512 x 11008 x 2048 94.5 -> 71.8).
 template <int TYPE>
-hipError_t launch_typed(const ggml_hip_weight *w, const mm_plan &pl, act_planes p, int64_t N, float *dst, int64_t ldd, hipStream_t st) {
+hipError_t launch_typed(const ggml_hip_weight *w, const mm_plan &pl, act_planes p, int64_t N, float *dst, int64_t ldd, hipStream_t st, const mm_epilogue *ep) {
     constexpr bool Q40 = TYPE == GGML_TYPE_Q4_0, Q4 = Q40 || TYPE == GGML_TYPE_Q4_1;
     if (pl.family == MMF_K3S_MX) {
-        if constexpr (Q4) return launch_small<TYPE>(w, pl, p, N, dst, ldd, st);
+        if constexpr (Q4) return launch_small<TYPE>(w, pl, p, N, dst, ldd, st, ep);
         return hipErrorInvalidValue;
     }
-    if (pl.family == MMF_K3P_MX) return launch_gemm_qmx_mid(w, pl, p, N, dst, ldd, st, t_epilogue);
+    if (pl.family == MMF_K3P_MX) return launch_gemm_qmx_mid(w, pl, p, N, dst, ldd, st, ep);
     if (pl.family != MMF_MX) return hipErrorInvalidValue;
     switch (pl.form) {
-    case MXF_256x128:     if constexpr (Q40) return launch_cfg<TYPE, 2, 4, 4, 1, 4, 2>(w, p, N, dst, ldd, st); break;
-    case MXF_N32_H64:     return launch_cfg<TYPE, 1, 1, 2, 1, 4, 2, 4>(w, p, N, dst, ldd, st);
-    case MXF_N32_H32:     return launch_cfg<TYPE, 1, 1, 1, 1, 4, 2, 4>(w, p, N, dst, ldd, st);
-    case MXF_S4_H128:     if constexpr (Q40) return launch_cfg<TYPE, 1, 2, 4, 1, 4, MX_SMALL_FB, 4>(w, p, N, dst, ldd, st); break;
-    case MXF_S4_H64:      return launch_cfg<TYPE, 1, 2, 2, 1, 4, MX_SMALL_FB, 4>(w, p, N, dst, ldd, st);
-    case MXF_S4_H32:      return launch_cfg<TYPE, 1, 2, 1, 1, 4, MX_SMALL_FB, 4>(w, p, N, dst, ldd, st);
-    case MXF_S2V2_H64:    if constexpr (Q40) return launch_cfg<TYPE, 1, 2, 2, 1, 4, 2, 2, 2>(w, p, N, dst, ldd, st); break;
-    case MXF_S2_H128:     return launch_cfg<TYPE, 1, 2, 4, 1, 4, 2, 2>(w, p, N, dst, ldd, st);
-    case MXF_S2_H64:      return launch_cfg<TYPE, 1, 2, 2, 1, 4, 2, 2>(w, p, N, dst, ldd, st);
-    case MXF_128x128:     return launch_cfg<TYPE, 2, 2, 2, 2, 4, 2>(w, p, N, dst, ldd, st);
-    case MXF_64x64:       if constexpr (Q40) return launch_cfg<TYPE, 1, 1, 2, 2, 4, 2>(w, p, N, dst, ldd, st); break;
-    case MXF_128x64:      return launch_cfg<TYPE, 1, 2, 4, 1, 4, 2>(w, p, N, dst, ldd, st);
+    case MXF_256x128:     if constexpr (Q40) return launch_cfg<TYPE, 2, 4, 4, 1, 4, 2>(w, p, N, dst, ldd, st, ep); break;
+    case MXF_N32_H64:     return launch_cfg<TYPE, 1, 1, 2, 1, 4, 2, 4>(w, p, N, dst, ldd, st, ep);
+    case MXF_N32_H32:     return launch_cfg<TYPE, 1, 1, 1, 1, 4, 2, 4>(w, p, N, dst, ldd, st, ep);
+    case MXF_S4_H128:     if constexpr (Q40) return launch_cfg<TYPE, 1, 2, 4, 1, 4, MX_SMALL_FB, 4>(w, p, N, dst, ldd, st, ep); break;
+    case MXF_S4_H64:      return launch_cfg<TYPE, 1, 2, 2, 1, 4, MX_SMALL_FB, 4>(w, p, N, dst, ldd, st, ep);
+    case MXF_S4_H32:      return launch_cfg<TYPE, 1, 2, 1, 1, 4, MX_SMALL_FB, 4>(w, p, N, dst, ldd, st, ep);
+    case MXF_S2V2_H64:    if constexpr (Q40) return launch_cfg<TYPE, 1, 2, 2, 1, 4, 2, 2, 2>(w, p, N, dst, ldd, st, ep); break;
+    case MXF_S2_H128:     return launch_cfg<TYPE, 1, 2, 4, 1, 4, 2, 2>(w, p, N, dst, ldd, st, ep);
+    case MXF_S2_H64:      return launch_cfg<TYPE, 1, 2, 2, 1, 4, 2, 2>(w, p, N, dst, ldd, st, ep);
+    case MXF_128x128:     return launch_cfg<TYPE, 2, 2, 2, 2, 4, 2>(w, p, N, dst, ldd, st, ep);
+    case MXF_64x64:       if constexpr (Q40) return launch_cfg<TYPE, 1, 1, 2, 2, 4, 2>(w, p, N, dst, ldd, st, ep); break;
+    case MXF_128x64:      return launch_cfg<TYPE, 1, 2, 4, 1, 4, 2>(w, p, N, dst, ldd, st, ep);
     default: break;
     }
     return hipErrorInvalidValue;                            // (a form the plan never gives this type)
@@ -1277,31 +1243,28 @@ hipError_t launch_typed(const ggml_hip_weight *w, const mm_plan &pl, act_planes 
 
 }  // namespace
 
-hipError_t launch_gemm_qmx_multi(const ggml_hip_weight *const *w, int n_w, act_planes p, int64_t N, float *const *dst, const int64_t *ldd, hipStream_t st) {
-    if (n_w < 2 || n_w > 4 || N < 5 || N > 64) return hipErrorNotSupported;
+hipError_t launch_gemm_qmx_multi(const mm_plan &g, const ggml_hip_weight *const *w, int n_w, act_planes p, int64_t N, float *const *dst, const int64_t *ldd,
+                                 hipStream_t st) {
+    if (g.family != MMF_K3S_MX) return hipErrorInvalidValue;
     for (int i = 0; i < n_w; ++i)
-        if (!w[i] || w[i]->type != w[0]->type || w[i]->M <= 0 || (uint64_t)32 * (uint64_t)ldd[i] * 4 > 0xFFFFFFFFull) return hipErrorNotSupported;
+        if (!w[i] || (uint64_t)32 * (uint64_t)ldd[i] * 4 > 0xFFFFFFFFull) return hipErrorNotSupported;   // (32-bit offsets inside a tile; the plan has no ldd)
     switch (w[0]->type) {
-    case GGML_TYPE_Q4_0: return launch_small_multi<GGML_TYPE_Q4_0>(w, n_w, p, N, dst, ldd, st);
-    case GGML_TYPE_Q4_1: return launch_small_multi<GGML_TYPE_Q4_1>(w, n_w, p, N, dst, ldd, st);
-    default: return hipErrorNotSupported;
+    case GGML_TYPE_Q4_0: return launch_small_multi<GGML_TYPE_Q4_0>(g, w, n_w, p, N, dst, ldd, st);
+    case GGML_TYPE_Q4_1: return launch_small_multi<GGML_TYPE_Q4_1>(g, w, n_w, p, N, dst, ldd, st);
+    default: return hipErrorInvalidValue;
     }
 }
 
 hipError_t launch_gemm_qmx(const ggml_hip_weight *w, const mm_plan &pl, act_planes p, int64_t N, float *dst, int64_t ldd, hipStream_t st,
                            const mm_epilogue *ep) {
     if (N <= 0 || w->M <= 0) return hipSuccess;
-    struct Scope {                                          // the epilogue lives for this launch only
-        explicit Scope(const mm_epilogue *e) { if (e) t_epilogue = *e; }
-        ~Scope() { t_epilogue = mm_epilogue{0, nullptr, 0, nullptr, 0, 1.0f}; }
-    } scope(ep);
     if (ep && ep->mode == 1 && ((uint64_t)64 * (uint64_t)ep->ld_add * 4 > 0xFFFFFFFFull || (uint64_t)256 * (uint64_t)ep->ld2 * 4 > 0xFFFFFFFFull))
         return hipErrorNotSupported;                        // (32-bit offsets inside a tile, as for dst)
     switch (w->type) {
-    case GGML_TYPE_Q4_0: return launch_typed<GGML_TYPE_Q4_0>(w, pl, p, N, dst, ldd, st);
-    case GGML_TYPE_Q4_1: return launch_typed<GGML_TYPE_Q4_1>(w, pl, p, N, dst, ldd, st);
-    case GGML_TYPE_Q5_0: return launch_typed<GGML_TYPE_Q5_0>(w, pl, p, N, dst, ldd, st);
-    case GGML_TYPE_Q8_0: return launch_typed<GGML_TYPE_Q8_0>(w, pl, p, N, dst, ldd, st);
+    case GGML_TYPE_Q4_0: return launch_typed<GGML_TYPE_Q4_0>(w, pl, p, N, dst, ldd, st, ep);
+    case GGML_TYPE_Q4_1: return launch_typed<GGML_TYPE_Q4_1>(w, pl, p, N, dst, ldd, st, ep);
+    case GGML_TYPE_Q5_0: return launch_typed<GGML_TYPE_Q5_0>(w, pl, p, N, dst, ldd, st, ep);
+    case GGML_TYPE_Q8_0: return launch_typed<GGML_TYPE_Q8_0>(w, pl, p, N, dst, ldd, st, ep);
     default: return hipErrorInvalidValue;
     }
 }

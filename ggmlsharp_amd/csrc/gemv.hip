@@ -689,13 +689,10 @@ __global__ __launch_bounds__(GV_THREADS, (NC <= 2 && !PRO ? 4 : 2)) void gemv_fu
     gemv_fused_body<TYPE, NC, GV_ROWS, SC, PRO, true>(ws, x, ld1, nbk, N, ntiles, ep, pro);
 }
 
-// the prologue of the call in flight on this host thread (launch_gemv_q_fused_pro sets it around the type dispatch)
-thread_local const mm_prologue *t_prologue = nullptr;
-
 template <int TYPE, bool FUSED, int ROWS>
 hipError_t launch_rows(const ggml_hip_weight *w, const float *x, int64_t ld1, act_planes p, int64_t N, float *dst,
-                       int64_t ldd, hipStream_t st, const mm_epilogue *epp) {
-    const mm_epilogue ep = epp ? *epp : mm_epilogue{0, nullptr, 0, nullptr, 0, 1.0f};
+                       int64_t ldd, hipStream_t st, const mm_epilogue *epp, const mm_prologue *pro) {
+    const mm_epilogue ep = epilogue_or_none(epp);
     const int ntiles = (int)((w->M + ROWS - 1) / ROWS);
     dim3 grid((unsigned)(ntiles < GV_MAX_WGS ? ntiles : GV_MAX_WGS));
     if constexpr (FUSED && !GV_OLD_FUSED) {
@@ -707,14 +704,14 @@ hipError_t launch_rows(const ggml_hip_weight *w, const float *x, int64_t ld1, ac
 #define GVF_LAUNCH(NC) do { \
         if (w->ext_type != 0) {                 /* a k-quant weight (planar Q5_1 form): activations by the Q8_K rule */ \
             if constexpr (TYPE == GGML_TYPE_Q5_1 || TYPE == GV_TYPE_I8X2) { \
-                if (t_prologue || ep.mode != 0 || w->nbk % 8 != 0 || w->nbk / 8 > GV_K8_SB || (TYPE == GV_TYPE_I8X2 && !w->i8p)) return hipErrorNotSupported; \
+                if (pro || ep.mode != 0 || w->nbk % 8 != 0 || w->nbk / 8 > GV_K8_SB || (TYPE == GV_TYPE_I8X2 && !w->i8p)) return hipErrorNotSupported; \
                 if (w->nbk <= GV_CHUNK) gemv_fused_kernel<TYPE, NC, ROWS, true, false, true><<<grid, GV_THREADS, 0, st>>>(GVF_ARGS, mm_prologue{nullptr, 0, nullptr, nullptr}); \
                 else gemv_fused_kernel<TYPE, NC, ROWS, false, false, true><<<grid, GV_THREADS, 0, st>>>(GVF_ARGS, mm_prologue{nullptr, 0, nullptr, nullptr}); \
             } else return hipErrorNotSupported; \
         } else if constexpr (TYPE == GV_TYPE_I8X2) return hipErrorNotSupported;   /* (the form exists for the k-quant extension only) */ \
-        else if (t_prologue) { \
-            if (w->nbk <= GV_CHUNK) gemv_fused_kernel<TYPE, NC, ROWS, true, true><<<grid, GV_THREADS, 0, st>>>(GVF_ARGS, *t_prologue); \
-            else gemv_fused_kernel<TYPE, NC, ROWS, false, true><<<grid, GV_THREADS, 0, st>>>(GVF_ARGS, *t_prologue); \
+        else if (pro) { \
+            if (w->nbk <= GV_CHUNK) gemv_fused_kernel<TYPE, NC, ROWS, true, true><<<grid, GV_THREADS, 0, st>>>(GVF_ARGS, *pro); \
+            else gemv_fused_kernel<TYPE, NC, ROWS, false, true><<<grid, GV_THREADS, 0, st>>>(GVF_ARGS, *pro); \
         } else if (w->nbk <= GV_CHUNK) gemv_fused_kernel<TYPE, NC, ROWS, true><<<grid, GV_THREADS, 0, st>>>(GVF_ARGS, mm_prologue{nullptr, 0, nullptr, nullptr}); \
         else gemv_fused_kernel<TYPE, NC, ROWS, false><<<grid, GV_THREADS, 0, st>>>(GVF_ARGS, mm_prologue{nullptr, 0, nullptr, nullptr}); } while (0)
             if (N <= 1) GVF_LAUNCH(1);
@@ -725,7 +722,7 @@ hipError_t launch_rows(const ggml_hip_weight *w, const float *x, int64_t ld1, ac
             return hipGetLastError();
         }
     }
-    if (ep.mode != 0 || t_prologue) return hipErrorNotSupported;          // (callers ask gemv_fused_has_epilogue first)
+    if (ep.mode != 0 || pro) return hipErrorNotSupported;          // (callers ask gemv_fused_has_epilogue first)
     if (FUSED && w->ext_type != 0) return hipErrorNotSupported;           // (the block-staged fused form quantizes by the Q8_0 rule: plan.cpp keeps k-quants off it)
 #define GV_LAUNCH(NC) gemv_q_kernel<TYPE, NC, FUSED, ROWS><<<grid, GV_THREADS, 0, st>>>((TYPE == GV_TYPE_I8X2 ? w->i8p : w->qs), w->gs, x, ld1, p.a8, p.ad, p.as, dst, w->M, w->Mpad, p.Npad, w->nbk, ldd, (int)N, ntiles)
     if (N <= 1) GV_LAUNCH(1);
@@ -739,27 +736,27 @@ hipError_t launch_rows(const ggml_hip_weight *w, const float *x, int64_t ld1, ac
 
 template <int TYPE, bool FUSED>
 hipError_t launch_typed(const ggml_hip_weight *w, const float *x, int64_t ld1, act_planes p, int64_t N, float *dst,
-                        int64_t ldd, hipStream_t st, const mm_epilogue *ep) {
+                        int64_t ldd, hipStream_t st, const mm_epilogue *ep, const mm_prologue *pro) {
     // 32 rows per workgroup measured 5 % faster at M = 32000 (4.46 vs 4.24 TB/s) and 13 % slower at M = 4096; a choice by
     // M would change the summation tree between a row shard and the unsplit matrix, and the multi-GPU path promises
     // bit-identical results for any split -- so one shape for every M.
-    return launch_rows<TYPE, FUSED, 16>(w, x, ld1, p, N, dst, ldd, st, ep);
+    return launch_rows<TYPE, FUSED, 16>(w, x, ld1, p, N, dst, ldd, st, ep, pro);
 }
 
 template <bool FUSED>
 hipError_t launch_any(const ggml_hip_weight *w, const float *x, int64_t ld1, act_planes p, int64_t N, float *dst,
-                      int64_t ldd, hipStream_t st, const mm_epilogue *ep = nullptr) {
+                      int64_t ldd, hipStream_t st, const mm_epilogue *ep, const mm_prologue *pro) {
     if (N <= 0 || w->M <= 0) return hipSuccess;
     if (N > (FUSED ? GEMV_MAX_N : GEMV_WIDE_MAX_N)) return hipErrorInvalidValue;
     switch (w->type) {
-    case GGML_TYPE_Q4_0: return launch_typed<GGML_TYPE_Q4_0, FUSED>(w, x, ld1, p, N, dst, ldd, st, ep);
-    case GGML_TYPE_Q4_1: return launch_typed<GGML_TYPE_Q4_1, FUSED>(w, x, ld1, p, N, dst, ldd, st, ep);
-    case GGML_TYPE_Q5_0: return launch_typed<GGML_TYPE_Q5_0, FUSED>(w, x, ld1, p, N, dst, ldd, st, ep);
+    case GGML_TYPE_Q4_0: return launch_typed<GGML_TYPE_Q4_0, FUSED>(w, x, ld1, p, N, dst, ldd, st, ep, pro);
+    case GGML_TYPE_Q4_1: return launch_typed<GGML_TYPE_Q4_1, FUSED>(w, x, ld1, p, N, dst, ldd, st, ep, pro);
+    case GGML_TYPE_Q5_0: return launch_typed<GGML_TYPE_Q5_0, FUSED>(w, x, ld1, p, N, dst, ldd, st, ep, pro);
     case GGML_TYPE_Q4_2:
-        if (w->ext_type != 0) return w->i8p ? launch_typed<GV_TYPE_I8X2, FUSED>(w, x, ld1, p, N, dst, ldd, st, ep) : hipErrorInvalidValue;   // (Q6_K: int8 planes)
-        return launch_typed<GGML_TYPE_Q4_2, FUSED>(w, x, ld1, p, N, dst, ldd, st, ep);
-    case GGML_TYPE_Q5_1: return launch_typed<GGML_TYPE_Q5_1, FUSED>(w, x, ld1, p, N, dst, ldd, st, ep);
-    case GGML_TYPE_Q8_0: return launch_typed<GGML_TYPE_Q8_0, FUSED>(w, x, ld1, p, N, dst, ldd, st, ep);
+        if (w->ext_type != 0) return w->i8p ? launch_typed<GV_TYPE_I8X2, FUSED>(w, x, ld1, p, N, dst, ldd, st, ep, pro) : hipErrorInvalidValue;   // (Q6_K: int8 planes)
+        return launch_typed<GGML_TYPE_Q4_2, FUSED>(w, x, ld1, p, N, dst, ldd, st, ep, pro);
+    case GGML_TYPE_Q5_1: return launch_typed<GGML_TYPE_Q5_1, FUSED>(w, x, ld1, p, N, dst, ldd, st, ep, pro);
+    case GGML_TYPE_Q8_0: return launch_typed<GGML_TYPE_Q8_0, FUSED>(w, x, ld1, p, N, dst, ldd, st, ep, pro);
     default: return hipErrorInvalidValue;
     }
 }
@@ -767,13 +764,13 @@ hipError_t launch_any(const ggml_hip_weight *w, const float *x, int64_t ld1, act
 }  // namespace
 
 hipError_t launch_gemv_q(const ggml_hip_weight *w, act_planes p, int64_t N, float *dst, int64_t ldd, hipStream_t st) {
-    return launch_any<false>(w, nullptr, 0, p, N, dst, ldd, st);
+    return launch_any<false>(w, nullptr, 0, p, N, dst, ldd, st, nullptr, nullptr);
 }
 
 hipError_t launch_gemv_q_fused(const ggml_hip_weight *w, const float *x, int64_t ld1, int64_t N, float *dst, int64_t ldd,
                                hipStream_t st, const mm_epilogue *ep) {
     act_planes none = {nullptr, nullptr, nullptr, 0};
-    return launch_any<true>(w, x, ld1, none, N, dst, ldd, st, ep);
+    return launch_any<true>(w, x, ld1, none, N, dst, ldd, st, ep, nullptr);
 }
 
 namespace {
@@ -827,10 +824,6 @@ bool gemv_fused_has_epilogue(int64_t N) { return N >= 1 && N <= 4 && !GV_OLD_FUS
 hipError_t launch_gemv_q_fused_pro(const ggml_hip_weight *w, const float *x, int64_t ld1, const mm_prologue &pro, int64_t N, float *dst,
                                    int64_t ldd, hipStream_t st, const mm_epilogue *ep) {
     if (!gemv_fused_has_epilogue(N)) return hipErrorNotSupported;
-    struct Scope {
-        explicit Scope(const mm_prologue *p) { t_prologue = p; }
-        ~Scope() { t_prologue = nullptr; }
-    } scope(&pro);
     act_planes none = {nullptr, nullptr, nullptr, 0};
-    return launch_any<true>(w, x, ld1, none, N, dst, ldd, st, ep);
+    return launch_any<true>(w, x, ld1, none, N, dst, ldd, st, ep, &pro);
 }

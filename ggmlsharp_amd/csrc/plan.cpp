@@ -145,18 +145,19 @@ void plan_gemv(mm_plan &p, int type, int64_t M, int64_t K, int64_t N, bool fused
 // workgroups per weight tile (Q8_0 4096 x 4096 x 64 11.3 | 13.1, 4096 x 11008 x 64 25.9 | 30.5).  And beyond 64 rows wherever the 16-row workgroups still fit
 // one round (1024 rows at 128 src1 rows, 512 at 256): Q4_0 1024 x 4096 x 128 7.7 -> 6.7, 512 x 4096 x 128 7.8 -> 5.2, 1024 x 11008 x 128 16.0 -> 13.9,
 // Q5_1 1024 x 4096 x 128 9.0 -> 7.9: the workgroup count decides, the row count does not.
-// rows16: the k-block slots of a wave in the caller's launcher.
+// The LDS the launch needs follows from the plan (plan_k3s_slots).
 constexpr int64_t K3S_16_NMAX = 512, K3S_16_WGS = 256;
-void k3s_tile16(mm_plan &p, int64_t M, int64_t N, int rows16) {
+void k3s_tile16(mm_plan &p, int type, int64_t M, int64_t N) {
     if (N > K3S_16_NMAX) return;
     // (17..32 rows on a SHORT matrix: one 16-column slice per workgroup and two workgroups per weight tile while those fit one round -- 2048 rows are 256 workgroups that way,
     // 128 with both slices in one: Q4_0 2048 x 4096 x 32 7.5 -> 5.9 us, 1024 x 4096 x 32 6.7 -> 5.2, 2048 x 8192 x 32 12.6 -> 9.9, Q8_0 2048 x 4096 x 32 8.6 -> 6.6, Q5_1 8.3 -> 6.8.
     // Geometry, like the tile height.)
     const int tn16 = N <= 16 || cdiv(M, 16) * cdiv(N, 16) <= K3S_16_WGS ? 16 : 32;
-    const int64_t wg16 = cdiv(M, 16) * cdiv(N, tn16);
-    if ((int64_t)KS8 * rows16 * tn16 * 4 > 160 * 1024 || wg16 > K3S_16_WGS) return;   // (the LDS of a CU; one round)
-    p.form = 5 + (tn16 == 16 ? 0 : 1);
-    p.wmt = 1; p.tile_m = 16; p.tile_n = tn16; p.tiles_per_wave = tn16 / 16; p.wgs = wg16;
+    mm_plan q = p;
+    q.form = 5 + (tn16 == 16 ? 0 : 1);
+    q.wmt = 1; q.tile_m = 16; q.tile_n = tn16; q.tiles_per_wave = tn16 / 16; q.wgs = cdiv(M, 16) * cdiv(N, tn16);
+    if (plan_k3s_slots(q, type).lds > 160 * 1024 || q.wgs > K3S_16_WGS) return;   // (the LDS of a CU; one round)
+    p = q;
 }
 
 bool plan_k3s_i8(mm_plan &p, int type, int64_t M, int64_t Mpad, int64_t K, int64_t N) {
@@ -186,10 +187,7 @@ bool plan_k3s_i8(mm_plan &p, int type, int64_t M, int64_t Mpad, int64_t K, int64
     // half of the weight operand's lanes -- and its result is handed to the 16 x 16 tiles' lanes once per wave, so the bits are the 32-row form's.  32-row | 16-row tiles:
     // Q5_1 4096 x 4096 x 9 / 16 / 32 12.8 | 8.0, 12.9 | 8.0, 12.9 | 10.2 us, 4096 x 11008 x 16 / 32 27.7 | 16.2, 27.7 | 21.4, 2048 x 8192 x 32 16.7 | 13.1, 4096 x 28672 x 16 62.5 | 34.8,
     // Q5_K 4096 x 4096 x 16 13.0 | 8.1, Q4_K x 32 13.2 | 10.4, 4096 x 11008 x 16 28.4 | 16.4)
-    if (type == GGML_TYPE_Q8_0 || type == GGML_TYPE_Q5_0 || type == GGML_TYPE_Q4_2 || type == GGML_TYPE_Q5_1) {
-        const int nb16 = nloc <= 8 ? 8 : 16;
-        k3s_tile16(p, M, N, (int)cdiv(nloc, nb16) * nb16);   // (the launcher's slots: gemm_q8s.hip)
-    }
+    if (type == GGML_TYPE_Q8_0 || type == GGML_TYPE_Q5_0 || type == GGML_TYPE_Q4_2 || type == GGML_TYPE_Q5_1) k3s_tile16(p, type, M, N);
     return true;
 }
 
@@ -240,8 +238,7 @@ bool plan_k3p_mx(mm_plan &p, int64_t M, int64_t Mpad, int64_t K, int64_t N) {
 // K3s (gemm_qmx.hip launch_small), Q4_0 / Q4_1: KS = 8 waves per 32-row tile, each a contiguous eighth of K in pairs of blocks
 bool plan_k3s_mx(mm_plan &p, int type, int64_t M, int64_t Mpad, int64_t K, int64_t N) {
     const int nbkp = (int)pad_kblocks(K / QK);
-    int nloc = (int)cdiv(nbkp, KS8);
-    nloc += nloc & 1;                                       // pairs of blocks stay inside one wave
+    const int nloc = k3p_mx_nloc(K);                        // pairs of blocks stay inside one wave
     if (nloc > 128) return false;                           // (the table pieces a lane holds, two rounds of eight: K <= 32768; r4 -- it was K <= 16384)
     if (((uint64_t)nbkp + K_LOOKAHEAD) * (uint64_t)Mpad * 16 > LIM32 || (uint64_t)nbkp * 48 * (uint64_t)pad_act(N) > LIM32) return false;
     const int ncol = (int)cdiv(N, 32);
@@ -257,8 +254,7 @@ bool plan_k3s_mx(mm_plan &p, int type, int64_t M, int64_t Mpad, int64_t K, int64
     // 16-row tiles (k3s_tile16): Q4_0 4096 x 4096 x 32 10.6 | 8.6 us per COMPUTE launch (32-row | 16-row tiles, replayed graphs, 32 weight copies in turn),
     // x 16 and x 5 10.6 | 7.1, 4096 x 11008 x 32 22.6 | 19.0, 2048 x 8192 x 32 19.1 | 16.5; the whole call at 16 rows 13.8 | 10.3.
     // (Q4_1 too: its min term as k = 0 / 2 of one v_mfma_f32_16x16x4_f32 per pair -- the 32-row form's two fmaf in the same order)
-    const int np16 = nloc <= 8 ? 4 : 8;
-    k3s_tile16(p, M, N, nloc > 2 * np16 ? nloc : 2 * np16);   // (the launcher's slots: gemm_qmx.hip launch_small)
+    k3s_tile16(p, type, M, N);
     return true;
 }
 
@@ -507,4 +503,70 @@ uint32_t plan_tree_id(const mm_plan &p) {
     const int parts[] = {p.arith, p.ksplit, p.kstyle, p.kunit, p.flags & MM_FLAG_Q8K};
     for (int v : parts) { h ^= (uint32_t)v; h *= 16777619u; }
     return h;
+}
+
+// The slots of a K3s launch (gemm_qmx.hip launch_small, gemm_q8s.hip launch_q8_small and the grouped launches); the launchers map them to an instantiation.
+k3s_slots plan_k3s_slots(const mm_plan &p, int type) {
+    const int nloc = p.nloc, wmt = p.wmt;
+    const bool q41 = type == GGML_TYPE_Q4_1;
+    k3s_slots s;
+    if (p.family == MMF_K3S_MX && p.tile_m == 16) {
+        // pairs in flight per wave; beyond 16 k-blocks per wave: in turn (Q4_1 carries the min and d1 * sum(a) per slot: eight slots of two slices spill)
+        const int np = nloc <= 8 ? 4 : 8;
+        s.rot = nloc > 2 * np;
+        s.slots = s.rot && q41 && p.tile_n == 32 ? 6 : np;
+        s.rows = s.rot ? nloc : 2 * np;
+    } else if (p.family == MMF_K3S_MX) {
+        // pairs in flight: a wave's whole range for K <= 4096 (8 pairs) and K <= 2048 (4 pairs), longer K refills them in turn; two tiles per
+        // workgroup 4 pairs, three or four tiles 2 (Q4_1 carries three more registers per pair: 3 / 4 in turn)
+        s.rot = wmt >= 3 || nloc > (wmt == 2 ? 8 : 16);
+        s.slots = wmt >= 3 ? 2 : wmt == 2 ? (s.rot && q41 ? 3 : 4) : nloc <= 8 ? 4 : s.rot && q41 ? 4 : 8;
+        s.rows = nloc <= 8 ? 8 : nloc <= 16 ? 16 : nloc;
+    } else {
+        // int8: one tile per workgroup (and the 16-row tiles) a wave's range in 8 / 16 slots, longer K in rounds of 16; two tiles 8 slots, in rounds beyond K = 2048;
+        // (r5) three or four tiles four slots in turn.  Table rows: whole rounds of the slots.
+        s.slots = wmt >= 3 ? 4 : wmt == 2 || nloc <= 8 ? 8 : 16;
+        s.rot = nloc > s.slots;
+        s.rows = (int)cdiv(nloc, s.slots) * s.slots;
+    }
+    const int tab = KS8 * s.rows * p.tile_n * 4, xch = KS8 * p.tile_m * p.tile_n * 4;   // (the exchange: every wave's partial tile)
+    s.lds = tab > xch ? tab : xch;
+    return s;
+}
+
+// Grouped K3s: a workgroup picks its matrix from its index and runs the single-matrix kernel on it.  The rules of the single form, for the group's
+// shape; then a group is planned only where every member's own COMPUTE plan has the group's tree, so each member gets its own call's bits.
+mm_plan plan_mul_mat_group(int type, int ext_type, const int64_t *M, const int64_t *Mpad, int n, int64_t K, int64_t N) {
+    const mm_plan none = {};
+    const bool mx = type == GGML_TYPE_Q4_0 || type == GGML_TYPE_Q4_1;
+    if (n < 2 || n > 4 || N < 5 || N > 64 || ext_type != 0 || !(mx || type == GGML_TYPE_Q8_0) || K <= 0 || K % QK != 0) return none;
+    const uint64_t nbkp = (uint64_t)pad_kblocks(K / QK), Npad = (uint64_t)pad_act(N);
+    const int nloc = mx ? k3p_mx_nloc(K) : k3p_i8_nloc(K);  // (the single-matrix forms' ranges)
+    const int64_t ncol = cdiv(N, 32);                       // 32-column slices of src1
+    if (nloc > 128 || (int64_t)Npad < 32 * ncol || (mx ? K / QK < 64 || nbkp * 48 * Npad > LIM32 : nbkp * 2 * Npad * 16 > LIM32)) return none;
+    int64_t t32 = 0;
+    for (int i = 0; i < n; ++i) {
+        if (M[i] <= 0) return none;
+        t32 += cdiv(M[i], 32) * ncol;
+    }
+    // r5: THREE tiles per workgroup where that is the fewest that keeps the group inside one round of the chip (gate / up of a 7B model: 2 x 11008 rows are 230 workgroups of 96 rows,
+    // 172 of 128; Q8_0: it was 344 of 64, a second round a third full): geometry on the form's tree, like the other tile counts.  A 96-row tile may overhang the padded rows: it reads
+    // the neighbouring plane's bytes there (inside the buffer, or zeros past it) and stores nothing.  (Q4_1: two at most, plan_k3s_mx)
+    auto groups = [&](int t) { int64_t g = 0; for (int i = 0; i < n; ++i) g += cdiv(M[i], 32 * t) * ncol; return g; };
+    const int wmt = t32 <= 256 ? 1 : t32 <= 512 || type == GGML_TYPE_Q4_1 ? 2 : groups(3) <= 256 ? 3 : 4;
+    mm_plan g = none;
+    g.family = mx ? MMF_K3S_MX : MMF_K3S_I8; g.image = mx ? 3 : 0;
+    g.arith = mx ? (type == GGML_TYPE_Q4_1 ? 211 : 310) : k3_i8_arith(type);   // (plan_k3s_mx / plan_k3s_i8)
+    g.ksplit = KS8; g.kstyle = MMK_RANGES; g.kunit = nloc; g.nloc = nloc; g.wmt = wmt;
+    g.tile_m = 32 * wmt; g.tile_n = 32; g.waves = KS8; g.tiles_per_wave = wmt;
+    const uint32_t tree = plan_tree_id(g);
+    for (int i = 0; i < n; ++i) {
+        const uint64_t wq = mx ? (nbkp + K_LOOKAHEAD) * (uint64_t)Mpad[i] * 16 : nbkp * 2 * (uint64_t)Mpad[i] * 16;
+        if (wq > LIM32 || Mpad[i] % (wmt == 3 ? 32 : 32 * wmt) != 0) return none;
+        const mm_plan own = plan_mul_mat(type, ext_type, M[i], K, N, false);
+        // (Q8_0: the group runs where the first matrix's own plan is K3s, not K3p)
+        if (plan_tree_id(own) != tree || (!mx && i == 0 && own.family != MMF_K3S_I8)) return none;
+        g.wgs += cdiv(M[i], 32 * wmt) * ncol;
+    }
+    return g;
 }

@@ -89,6 +89,13 @@ struct mm_plan {
 // one_call = the product is computed by one entry (ggml_hip_mul_mat_dev: the fused mat-vec exists); false = the COMPUTE-only entry.
 mm_plan plan_mul_mat(int type, int ext_type, int64_t M, int64_t K, int64_t N, bool one_call = true);
 uint32_t plan_tree_id(const mm_plan &p);
+// 2..4 matrices of one type and K behind one activation image, in ONE K3s launch (gemm_qmx.hip / gemm_q8s.hip launch_*_multi): family
+// MMF_K3S_MX or MMF_K3S_I8 with nloc and wmt set (tile_m = 32 * wmt; wmt 3 only here), or MMF_NONE -- then each matrix runs its own call
+mm_plan plan_mul_mat_group(int type, int ext_type, const int64_t *M, const int64_t *Mpad, int n, int64_t K, int64_t N);
+// what a K3s plan (single or group) fixes for its launch: the k-block slots a wave keeps in flight (MX: pairs of blocks), whether they rotate
+// through a longer range, the rows of a wave's scale table, and the dynamic LDS bytes (the table or the waves' result exchange)
+struct k3s_slots { int slots; bool rot; int rows; int lds; };
+k3s_slots plan_k3s_slots(const mm_plan &p, int type);
 // the K1 image for (type, K, N) with no weight at hand (no M: the exception cannot apply)
 int plan_image_kind(int type, int64_t K, int64_t N);
 // thread-local test switch (ggml_hip_debug_force_gemm): 0 auto, 1 int8, 2 f16, 3 MX
