@@ -22,8 +22,9 @@ Q5_K = 113   # extension (include/ggml_hip_ext.h GGML_HIP_TYPE_Q5_K): upstream k
 Q4_K = 112   # ... and GGML_HIP_TYPE_Q4_K (r4): the same super-block without the fifth-bit bytes
 Q6_K = 114   # ... and GGML_HIP_TYPE_Q6_K (r4): sixteen sub-blocks of 16 six-bit weights, resident in the planar Q4_2 form on int8 planes
 Q3_K = 111   # ... and GGML_HIP_TYPE_Q3_K: sixteen sub-blocks of 16 three-bit weights, resident exactly as the Q6_K super-block it transcodes to
-# (BLCK_SIZE / TYPE_SIZE below are the tables tests/test_boundary_cpu.py holds against the host mirror, type by type; Q3_K (256 / 110) is
-# sized by the library alone -- row_bytes() asks it, for every type)
+Q2_K = 110   # ... and GGML_HIP_TYPE_Q2_K: sixteen sub-blocks of 16 two-bit weights with a scale and a min each; the block term in Q6_K's form
+# (BLCK_SIZE / TYPE_SIZE below are the tables tests/test_boundary_cpu.py holds against the host mirror, type by type; Q3_K (256 / 110) and
+# Q2_K (256 / 84) are sized by the library alone -- row_bytes() asks it, for every type)
 TYPE_NAME = {F32: "f32", F16: "f16", Q4_0: "q4_0", Q4_1: "q4_1", Q4_2: "q4_2", Q4_3: "q4_3", Q5_0: "q5_0",
              Q5_1: "q5_1", Q8_0: "q8_0", Q8_1: "q8_1", I8: "i8", I16: "i16", I32: "i32"}
 BLCK_SIZE = {F32: 1, F16: 1, Q4_0: 32, Q4_1: 32, Q4_2: 16, Q4_3: 16, Q5_0: 32, Q5_1: 32, Q8_0: 32, Q8_1: 32,
@@ -151,6 +152,7 @@ HIP_SYMBOLS = {
     "ggml_hip_act_image_kind": (C.c_int, [C.c_int, C.c_int64, C.c_int64]),
     "ggml_hip_mm_plan": (C.c_int, [C.c_int, C.c_int64, C.c_int64, C.c_int64, _P]),
     "ggml_hip_debug_force_gemm": (None, [C.c_int]),
+    "ggml_hip_debug_q2k_min_pass_dev": (C.c_int, [_P, C.c_int64, _P, C.c_int64, _P, C.c_size_t, C.c_int, _P]),
     "ggml_hip_quantize_act_dev": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p]),
     "ggml_hip_mul_mat_dev": (C.c_int, [_P, _P, C.c_int64, C.c_int64, _P, C.c_int64, _P, C.c_size_t, _P]),
     "ggml_hip_mul_mat_init_dev": (C.c_int, [_P, _P, C.c_int64, C.c_int64, _P, C.c_size_t, _P]),

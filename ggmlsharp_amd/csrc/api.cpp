@@ -428,7 +428,7 @@ static DeviceCtx *call_slot() {
 static int alloc_weight(DeviceCtx *c, int type, int64_t K, int64_t M, ggml_hip_weight **out, int kq_type = 0) {
     ggml_hip_weight *w = new ggml_hip_weight();
     memset(w, 0, sizeof *w);
-    const bool kq = kq_type != 0;                           // (a k-quant weight: Q5_K / Q4_K in the planar Q5_1 form, Q6_K / Q3_K in the planar Q4_2 form)
+    const bool kq = kq_type != 0;                           // (a k-quant weight: Q5_K / Q4_K in the planar Q5_1 form, Q6_K / Q3_K / Q2_K in the planar Q4_2 form)
     w->ext_type = kq_type;
     static std::atomic<uint64_t> next_uid{1};
     w->type = type; w->M = M; w->K = K; w->Mpad = pad_rows(M > 0 ? M : 1); w->device = c->device; w->uid = next_uid.fetch_add(1);
@@ -517,6 +517,7 @@ int make_weight(DeviceCtx *c, int type, const void *rows, bool rows_on_host, int
         auto to_planar = [&](const uint8_t *src, uint64_t pitch, int64_t first) {
             return type == GGML_HIP_TYPE_Q6_K ? launch_q6k_to_planar(src, pitch, first, rows_n, w, st)
                    : type == GGML_HIP_TYPE_Q3_K ? launch_q3k_to_planar(src, pitch, first, rows_n, w, st)
+                   : type == GGML_HIP_TYPE_Q2_K ? launch_q2k_to_planar(src, pitch, first, rows_n, w, st)
                                                 : launch_q5k_to_planar(type, src, pitch, first, rows_n, w, st);
         };
         rc = alloc_weight(c, kquant_resident_type(type), ne00, rows_n, &w, type);
@@ -684,6 +685,7 @@ int ggml_hip_weight_download(const ggml_hip_weight *w, void *host_rows, void *st
     HIP_TRY(hipMalloc(&staging, total));
     hipError_t e = w->ext_type == GGML_HIP_TYPE_Q6_K ? launch_planar_to_q6k(w, (uint8_t *)staging, st)
                    : w->ext_type == GGML_HIP_TYPE_Q3_K ? launch_planar_to_q3k(w, (uint8_t *)staging, st)
+                   : w->ext_type == GGML_HIP_TYPE_Q2_K ? launch_planar_to_q2k(w, (uint8_t *)staging, st)
                    : w->ext_type != 0 ? launch_planar_to_q5k(w, (uint8_t *)staging, st) : launch_planar_to_aos(w, (uint8_t *)staging, st);
     if (e == hipSuccess) e = hipMemcpyAsync(host_rows, staging, total, hipMemcpyDeviceToHost, st);
     if (e == hipSuccess) e = hipStreamSynchronize(st);
@@ -806,7 +808,24 @@ int ggml_hip_mul_mat_compute_dev(const ggml_hip_weight *w, int64_t N, float *d_d
     int rc = weight_device_current(w);
     if (rc) return rc;
     const mm_plan pl = weight_plan(w, N, false);            // (the COMPUTE-only entry: INIT wrote this plan's image)
-    HIP_TRY(launch_planned(w, pl, act_carve((void *)d_work, w->K, pad_act(N)), N, d_dst, ldd, (hipStream_t)stream, nullptr));
+    const act_planes p = act_carve((void *)d_work, w->K, pad_act(N));
+    HIP_TRY(launch_planned(w, pl, p, N, d_dst, ldd, (hipStream_t)stream, nullptr));
+    if (pl.flags & MM_FLAG_MIN_PASS) HIP_TRY(launch_q2k_min_pass(w, p, N, d_dst, ldd, (hipStream_t)stream));   // (Q2_K: dst -= its min term)
+    return GGML_HIP_OK;
+}
+
+// the Q2_K min pass alone, on the image ggml_hip_mul_mat_init_dev wrote (TEST HOOK: the two forms side by side, and the pass's own time)
+int ggml_hip_debug_q2k_min_pass_dev(const ggml_hip_weight *w, int64_t N, float *d_dst, int64_t ldd, const void *d_work, size_t work_bytes,
+                                    int form, void *stream) {
+    if (!w || !d_dst) return fail(GGML_HIP_ERR_ARG, "null argument");
+    if (!kquant_min_pass(w->ext_type)) return fail(GGML_HIP_ERR_TYPE, "the min pass is for Q2_K weights");
+    if (form < 0 || form > 2) return fail(GGML_HIP_ERR_ARG, "form %d (0 auto, 1, 2)", form);
+    if (N <= 0 || w->M <= 0) return GGML_HIP_OK;
+    if (ldd < w->M) return fail(GGML_HIP_ERR_SHAPE, "ldd < M");
+    if (!d_work || work_bytes < ggml_hip_mul_mat_work_size(w->type, w->K, N)) return fail(GGML_HIP_ERR_ARG, "work buffer too small");
+    int rc = weight_device_current(w);
+    if (rc) return rc;
+    HIP_TRY(launch_q2k_min_pass(w, act_carve((void *)d_work, w->K, pad_act(N)), N, d_dst, ldd, (hipStream_t)stream, form));
     return GGML_HIP_OK;
 }
 
@@ -907,7 +926,9 @@ int ggml_hip_mul_mat_epilogue_dev(const ggml_hip_weight *w, const float *d_src1,
 // and hand their columns to the peers with the column-push kernel (layout.hip) behind the product: the same bytes, one more launch.
 static bool push_is_fused(const ggml_hip_weight *w, int64_t N, int n_peers) {
     if (!is_q(w->type) || n_peers - 1 > MM_PUSH_MAX) return false;
-    const int f = weight_plan(w, N, true).family;
+    const mm_plan pl = weight_plan(w, N, true);
+    if (pl.flags & MM_FLAG_MIN_PASS) return false;          // (Q2_K: the min pass must run before the columns leave)
+    const int f = pl.family;
     return f == MMF_MX || f == MMF_K3P_MX || f == MMF_K3P_I8 || f == MMF_K3S_MX || f == MMF_K3S_I8;   // (r5: the batched-decode forms too -- a short shard at prompt sizes runs them)
 }
 int ggml_hip_mul_mat_push_fused(const ggml_hip_weight *w, int64_t N, int n_peers) { return w && push_is_fused(w, N, n_peers) ? 1 : 0; }
@@ -1073,6 +1094,7 @@ int ggml_hip_quantize_rows_dev(int type, const float *d_x, int64_t nrows, int64_
         if (((uintptr_t)d_x & 15) != 0) return fail(GGML_HIP_ERR_SHAPE, "k-quants: the rows must be 16-byte aligned");
         if (type == GGML_HIP_TYPE_Q6_K) HIP_TRY(launch_quantize_q6k(d_x, nrows, k, d_blocks, (hipStream_t)stream));
         else if (type == GGML_HIP_TYPE_Q3_K) HIP_TRY(launch_quantize_q3k(d_x, nrows, k, d_blocks, (hipStream_t)stream));
+        else if (type == GGML_HIP_TYPE_Q2_K) HIP_TRY(launch_quantize_q2k(d_x, nrows, k, d_blocks, (hipStream_t)stream));
         else HIP_TRY(launch_quantize_kq(type, d_x, nrows, k, d_blocks, (hipStream_t)stream));
         return GGML_HIP_OK;
     }
@@ -1090,6 +1112,7 @@ int ggml_hip_dequantize_rows_dev(int type, const void *d_blocks, int64_t nrows, 
         if (k % 256 != 0) return fail(GGML_HIP_ERR_SHAPE, "k-quants: k %% 256 != 0");
         if (type == GGML_HIP_TYPE_Q6_K) HIP_TRY(launch_dequantize_q6k(d_blocks, nrows, k, d_y, (hipStream_t)stream));
         else if (type == GGML_HIP_TYPE_Q3_K) HIP_TRY(launch_dequantize_q3k(d_blocks, nrows, k, d_y, (hipStream_t)stream));
+        else if (type == GGML_HIP_TYPE_Q2_K) HIP_TRY(launch_dequantize_q2k(d_blocks, nrows, k, d_y, (hipStream_t)stream));
         else HIP_TRY(launch_dequantize_q5k(type, d_blocks, nrows, k, d_y, (hipStream_t)stream));
         return GGML_HIP_OK;
     }

@@ -1,4 +1,4 @@
-// kquants.hip -- Q5_K (r4: and Q4_K, Q6_K; then Q3_K) weights (and the Q8_K activation rule) as an UNPINNED EXTRA.
+// kquants.hip -- Q5_K (r4: and Q4_K, Q6_K; then Q3_K and Q2_K) weights (and the Q8_K activation rule) as an UNPINNED EXTRA.
 //
 // The reference has no k-quants (TypeDefinitions.cs:153-169 stops at Q8_1; `grep -i q5_K` over /root/reference finds
 // nothing -- SURVEY 8(a) row K), BASELINE.json's north_star and config 4 name them anyway.  What is built here follows the
@@ -23,8 +23,9 @@
 // download returns the uploaded bytes.
 // Q6_K and Q3_K (sixteen sub-blocks of 16 with a signed scale each, no min) live in the planar Q4_2 form on int8 planes instead --
 // two scales per 32-element k-block -- and run the int8 kernels that take two scales per k-block; Q3_K's planes are exactly those of the
-// Q6_K super-block it transcodes to (see the two sections below).  Not built: Q2_K -- its sub-blocks of 16 each carry a min, and no
-// resident form has two mins per k-block (the min-term products of the Q5_1 form are built per 32 elements).
+// Q6_K super-block it transcodes to (see the two sections below).  Q2_K's sub-blocks of 16 each carry a min as well, which no resident
+// form has (the min-term products of the Q5_1 form are built per 32 elements): its block term lives in Q6_K's form and runs Q6_K's kernels,
+// and its min term is subtracted behind the product by a pass of its own (the Q2_K section at the end).
 #include "common.h"
 
 namespace {
@@ -643,6 +644,335 @@ __global__ void quantize_q3k_kernel(const float *__restrict__ x, int64_t nsb, ui
     }
 }
 
+
+// ---- Q2_K ----------------------------------------------------------------------------------------------------------------------------------
+//     block_q2_K = { u8 scales[16]; u8 qs[64]; half d; half dmin }                       84 bytes per 256 weights
+//     element e = 128 n + 32 s + l: q = (qs[32 n + l] >> 2 s) & 3 in 0..3;  w[e] = (d * sc_j) * q - dmin * m_j,  j = e / 16,
+//     sc_j = scales[j] & 15, m_j = scales[j] >> 4
+//     dot against Q8_K per super-block: (d * dy) * sum_j sc_j * <q_j, a_j>  -  (dmin * dy) * sum_j m_j * bsum_j
+// Resident form: the block term (d * sc_j) * q IS a Q6_K super-block (q6 = q + 32, scales[j] = sc_j, the same d), so k-block b = 4 n + s
+// becomes the two int8 planes of q and the scales d * sc_{2 b}, d * sc_{2 b + 1} (exact in f32: 11 + 4 significant bits) -- Q6_K's planes,
+// and every Q6_K kernel computes the block term B unchanged.  The 32-byte header slot of a super-block holds scales[16], d and dmin (bytes
+// 0..15, 16..17, 18..19): the download's header and the min pass's weight operand.
+// one thread per (row, k-block); rows fastest so the plane stores coalesce
+__global__ void q2k_to_planar_kernel(const uint8_t *__restrict__ aos, uint64_t nb01, int64_t row_begin, int64_t rows, int64_t Mpad,
+                                     uint8_t *__restrict__ i8p, float *__restrict__ d, float *__restrict__ mm, uint8_t *__restrict__ khdr) {
+    const int64_t m = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const int64_t b = blockIdx.y;
+    if (m >= rows) return;
+    const int64_t sb = b >> 3;
+    const int bq = (int)(b & 7), n = bq >> 2, s = bq & 3;
+    const uint8_t *blk = aos + (uint64_t)(row_begin + m) * nb01 + (uint64_t)sb * 84;
+    const uint8_t *qs = blk + 16 + 32 * n;
+    const float dd = h2f((uint16_t)(blk[80] | ((uint16_t)blk[81] << 8)));
+    const int64_t pi = b * Mpad + m;
+    d[pi] = dd * (float)(blk[2 * bq] & 15);                 // exact: 11 + 4 significant bits
+    mm[pi] = dd * (float)(blk[2 * bq + 1] & 15);
+    uint32_t ev[4] = {0, 0, 0, 0}, od[4] = {0, 0, 0, 0};
+#pragma unroll
+    for (int t = 0; t < 32; ++t) {
+        const uint32_t byte = ((uint32_t)(qs[t] >> (2 * s)) & 3u) << (8 * ((t >> 1) & 3));
+        if (t & 1) od[t >> 3] |= byte; else ev[t >> 3] |= byte;      // plane h byte j = element 2 j + h
+    }
+    *(uint4 *)(i8p + ((b * 2 + 0) * Mpad + m) * 16) = make_uint4(ev[0], ev[1], ev[2], ev[3]);
+    *(uint4 *)(i8p + ((b * 2 + 1) * Mpad + m) * 16) = make_uint4(od[0], od[1], od[2], od[3]);
+    if (bq == 0) {
+        uint32_t h[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+#pragma unroll
+        for (int i = 0; i < 16; ++i) h[i >> 2] |= (uint32_t)blk[i] << (8 * (i & 3));
+        h[4] = (uint32_t)blk[80] | ((uint32_t)blk[81] << 8) | ((uint32_t)blk[82] << 16) | ((uint32_t)blk[83] << 24);
+        uint4 *o = (uint4 *)(khdr + (sb * Mpad + m) * 32);
+        o[0] = make_uint4(h[0], h[1], h[2], h[3]);
+        o[1] = make_uint4(h[4], h[5], h[6], h[7]);
+    }
+}
+
+// exact inverse: one thread per (row, super-block)
+__global__ void planar_to_q2k_kernel(uint8_t *__restrict__ aos, uint64_t nb01, int64_t rows, int64_t Mpad, const uint8_t *__restrict__ i8p,
+                                     const uint8_t *__restrict__ khdr) {
+    const int64_t m = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const int64_t sb = blockIdx.y;
+    if (m >= rows) return;
+    uint8_t *blk = aos + (uint64_t)m * nb01 + (uint64_t)sb * 84;
+    for (int i = 16; i < 80; ++i) blk[i] = 0;
+    for (int bq = 0; bq < 8; ++bq) {
+        const int n = bq >> 2, s = bq & 3;
+        uint8_t *qs = blk + 16 + 32 * n;
+        const int64_t b = sb * 8 + bq;
+        for (int hsel = 0; hsel < 2; ++hsel) {
+            const uint4 w4 = *(const uint4 *)(i8p + ((b * 2 + hsel) * Mpad + m) * 16);
+            const uint32_t w[4] = {w4.x, w4.y, w4.z, w4.w};
+            for (int j = 0; j < 16; ++j) {
+                const int t = 2 * j + hsel;
+                qs[t] |= (uint8_t)(((w[j >> 2] >> (8 * (j & 3))) & 3u) << (2 * s));
+            }
+        }
+    }
+    const uint8_t *h = khdr + (sb * Mpad + m) * 32;
+    for (int i = 0; i < 16; ++i) blk[i] = h[i];
+    for (int i = 0; i < 4; ++i) blk[80 + i] = h[16 + i];
+}
+
+// dequantize_row_q2_K of the published format: one thread per (row-major) k-block of 32 outputs
+__global__ void dequantize_q2k_kernel(const uint8_t *__restrict__ in, int64_t nkb, float *__restrict__ y) {
+    const int64_t k = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (k >= nkb) return;
+    const uint8_t *blk = in + (k >> 3) * 84;
+    const int bq = (int)(k & 7), n = bq >> 2, s = bq & 3;
+    const uint8_t *qs = blk + 16 + 32 * n;
+    const float dd = h2f((uint16_t)(blk[80] | ((uint16_t)blk[81] << 8))), dmin = h2f((uint16_t)(blk[82] | ((uint16_t)blk[83] << 8)));
+    float *o = y + k * 32;
+    for (int hf = 0; hf < 2; ++hf) {
+        const uint32_t sc = blk[2 * bq + hf];
+        const float dl = dd * (float)(sc & 15u), ml = dmin * (float)(sc >> 4);
+        for (int t = 16 * hf; t < 16 * hf + 16; ++t)
+            o[t] = dl * (float)((qs[t] >> (2 * s)) & 3) - ml;   // upstream: dl * q - ml, one multiply then one subtract
+    }
+}
+
+// quantize_row_q2_K_reference of the published format, restated (tests/np_q2k.py quantize_q2_K is the same steps): per sub-block of 16
+// make_qkx1_quants(16, 3, x, L, &min, 5) (the steps of quantize_kq_kernel above over 16 elements); the sixteen scales and mins as 4-bit codes
+// nearest(15 / max * v) against d = half(max scale / 15) and dmin = half(max min / 15) (0 where the maximum is 0); the codes again under the
+// ROUNDED scales, l = nearest((x + dmin m) / (d sc)) in 0..3, where d sc != 0.  Every float operation a binary32 operation in the order
+// written (-ffp-contract=off), nearest = round half to even.  Sixteen lanes per super-block, one sub-block each.
+__global__ void quantize_q2k_kernel(const float *__restrict__ x, int64_t nsb, uint8_t *__restrict__ out) {
+    const int64_t tid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const int64_t sb_raw = tid >> 4;
+    const bool active = sb_raw < nsb;
+    const int64_t sb = active ? sb_raw : nsb - 1;           // (idle lanes of the last group shadow the last super-block: the shuffles want every lane)
+    const int j = (int)(tid & 15);
+    const float *xs = x + sb * 256 + 16 * j;
+    float v[16];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        const float4 t = ((const float4 *)xs)[i];
+        v[4 * i] = t.x; v[4 * i + 1] = t.y; v[4 * i + 2] = t.z; v[4 * i + 3] = t.w;
+    }
+    // make_qkx1_quants(16, nmax = 3, x, L, &the_min, ntry = 5)
+    int L[16];
+    float mn = v[0], mx = v[0];
+#pragma unroll
+    for (int i = 1; i < 16; ++i) { if (v[i] < mn) mn = v[i]; if (v[i] > mx) mx = v[i]; }
+    float scale = 0.0f, the_min = 0.0f;
+#pragma unroll
+    for (int i = 0; i < 16; ++i) L[i] = -1;                 // (upstream compares with an uninitialised L on the first try: every code "changes")
+    if (mx == mn) {
+#pragma unroll
+        for (int i = 0; i < 16; ++i) L[i] = 0;
+    } else {
+        if (mn > 0.0f) mn = 0.0f;
+        float iscale = 3.0f / (mx - mn);
+        scale = 1.0f / iscale;
+        for (int itry = 0; itry < 5; ++itry) {
+            float sumlx = 0.0f;
+            int suml2 = 0;
+            bool changed = false;
+#pragma unroll
+            for (int i = 0; i < 16; ++i) {
+                int l = (int)fminf(fmaxf(rintf(iscale * (v[i] - mn)), 0.0f), 3.0f);
+                if (l != L[i]) { L[i] = l; changed = true; }
+                sumlx += (v[i] - mn) * (float)l;
+                suml2 += l * l;
+            }
+            scale = sumlx / (float)suml2;
+            float sum = 0.0f;
+#pragma unroll
+            for (int i = 0; i < 16; ++i) sum += v[i] - scale * (float)L[i];
+            mn = sum / 16.0f;
+            if (mn > 0.0f) mn = 0.0f;
+            iscale = 1.0f / scale;
+            if (!changed) break;
+        }
+        the_min = -mn;
+    }
+    // the super-block's largest scale and min (upstream: `if (scale > max_scale)` from 0)
+    float max_scale = scale > 0.0f ? scale : 0.0f, max_min = the_min > 0.0f ? the_min : 0.0f;
+#pragma unroll
+    for (int o = 1; o < 16; o <<= 1) {
+        const float a = __shfl_xor(max_scale, o, 16), b = __shfl_xor(max_min, o, 16);
+        if (a > max_scale) max_scale = a;
+        if (b > max_min) max_min = b;
+    }
+    int ls = 0, lm = 0;
+    _Float16 dh = (_Float16)0.0f, dminh = (_Float16)0.0f;
+    if (max_scale > 0.0f) {
+        ls = (int)fminf(fmaxf(rintf((15.0f / max_scale) * scale), 0.0f), 15.0f);
+        dh = (_Float16)(max_scale / 15.0f);
+    }
+    if (max_min > 0.0f) {
+        lm = (int)fminf(fmaxf(rintf((15.0f / max_min) * the_min), 0.0f), 15.0f);
+        dminh = (_Float16)(max_min / 15.0f);
+    }
+    const float dd = (float)dh * (float)ls;
+    if (dd != 0.0f) {
+        const float dm = (float)dminh * (float)lm;
+#pragma unroll
+        for (int i = 0; i < 16; ++i) L[i] = (int)fminf(fmaxf(rintf((v[i] + dm) / dd), 0.0f), 3.0f);
+    }
+    uint8_t *blk = out + sb * 84;
+    // element 16 j + i = 128 n + 32 s + 16 h + i (j = 8 n + 2 s + h): its two bits go to bits 2 s, 2 s + 1 of qs[32 n + 16 h + i]
+    const int n = j >> 3, s = (j >> 1) & 3, h = j & 1;
+    uint32_t lo[4] = {0, 0, 0, 0};                          // sixteen bytes-to-be of bit pairs
+#pragma unroll
+    for (int i = 0; i < 16; ++i) lo[i >> 2] |= (uint32_t)(L[i] & 3) << (8 * (i & 3));
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const uint32_t l2 = __shfl_xor(lo[k], 2, 16), l4 = __shfl_xor(lo[k], 4, 16), l6 = __shfl_xor(lo[k], 6, 16);   // s ^ 1, s ^ 2, s ^ 3
+        if (active && s == 0) {
+            const uint32_t word = lo[k] | (l2 << 2) | (l4 << 4) | (l6 << 6);
+            uint8_t *q = blk + 16 + 32 * n + 16 * h + 4 * k;
+            q[0] = (uint8_t)word; q[1] = (uint8_t)(word >> 8); q[2] = (uint8_t)(word >> 16); q[3] = (uint8_t)(word >> 24);
+        }
+    }
+    if (active) {
+        blk[j] = (uint8_t)(ls | (lm << 4));
+        if (j == 0) {
+            const uint16_t hd = __builtin_bit_cast(uint16_t, dh), hm = __builtin_bit_cast(uint16_t, dminh);
+            blk[80] = (uint8_t)hd; blk[81] = (uint8_t)(hd >> 8); blk[82] = (uint8_t)hm; blk[83] = (uint8_t)(hm >> 8);
+        }
+    }
+}
+
+// ---- the Q2_K min pass ---------------------------------------------------------------------------------------------------------------------
+// Behind the product B of the block term (any family Q6_K's plan picks), in place:  dst[n][i] = fl(B[n][i] - T[n][i]) with T the min term
+// against K1's int8 image by the Q8_K rule (dy = the image's `ad` entry of the super-block's first k-block -- K1 writes the one super-block
+// scale d = 1 / iscale into all eight; bsum_j = the sum of the 16 quants of sub-block j: k-block 8 sb + j / 2, bytes 8 (j % 2) .. + 7 of both
+// planes).  Per output (n, i), fixed whatever the geometry, the family, M or the shard:
+//
+//     acc = +0.0f
+//     for sb = 0 .. K / 256 - 1 (ascending):
+//         S   = sum_j m_j * bsum_j             (|bsum| <= 2048, m <= 15: |S| < 2^19, every partial sum an integer below 2^24 -- exact in
+//                                               f32 in any order, so one v_mfma_f32_32x32x16_f16 per 32 x 32 tile with m and bsum as f16)
+//         c   = fl(dy[n, sb] * dmin[i, sb])
+//         acc = fl(acc + fl(c * (float)S))
+//     dst[n, i] = fl(dst[n, i] - acc)          (no fma contraction anywhere: -ffp-contract=off)
+//
+// The bits depend on (K, N) and the operands alone, so row shards, the K3s / K3p switch and the two-phase entries stay bitwise consistent.
+// Geometry: a workgroup of four waves owns 32 activation rows (n) x 128 TPW weight rows (i); wave w its TPW 32 x 32 tiles.  The super-blocks
+// go in chunks of CH: the workgroup sums the 32 rows' bsums of a chunk once into LDS (f16, the MFMA's A operand: row n, k = j), then each
+// lane loads its weight rows' slots of the chunk (scales[16] >> 4 as f16, the B operand: k = j, column i; dmin) and the chunk's products
+// follow in ascending order.  The next chunk's activation loads are in flight during this chunk's products; the weight-slot loads are not,
+// and at 256 VGPRs (one wave per SIMD) the pass is latency-bound.  Workgroups of one XCD take consecutive tiles (n-tile
+// major), so that the activation rows they share can stay in that XCD's L2.
+using q2_f16x8 = __attribute__((ext_vector_type(8))) _Float16;
+using q2_f32x16 = __attribute__((ext_vector_type(16))) float;
+
+__device__ __forceinline__ uint32_t q2_f16_bits(int v) { return (uint32_t)__builtin_bit_cast(uint16_t, (_Float16)(float)v); }   // exact: |v| <= 2048
+
+template <int TPW, int Q2_CH>
+__global__ __launch_bounds__(256) void q2k_min_pass_kernel(const uint8_t *__restrict__ khdr, int64_t Mpad, int64_t M, int64_t nsb,
+                                                           const int8_t *__restrict__ a8, const float *__restrict__ ad, int64_t Npad, int64_t N,
+                                                           float *__restrict__ dst, int64_t ldd, int64_t ntiles_i, int64_t ntiles, int64_t per_xcd) {
+    const int64_t tile = (int64_t)(blockIdx.x & 7) * per_xcd + (blockIdx.x >> 3);   // (workgroups go to the eight XCDs in turn)
+    if (tile >= ntiles) return;
+    const int64_t n0 = tile / ntiles_i * 32, i0 = tile % ntiles_i * (128 * TPW);
+    __shared__ __attribute__((aligned(16))) uint32_t s_bsum[Q2_CH][32][8];   // [super-block of the chunk][row][j / 2]: bsum_j, bsum_j+1 as f16
+    __shared__ __attribute__((aligned(16))) float s_dy[Q2_CH][32];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, r = lane & 31, h = lane >> 5;
+    // the bsum role of this thread: row arow of the tile, k-block aq (sub-blocks 2 aq, 2 aq + 1) of every super-block of a chunk
+    const int arow = tid & 31, aq = tid >> 5;
+    const int64_t an = n0 + arow;
+    const bool alive = an < N;                              // (rows past N: K1 wrote nothing there)
+    uint4 ev[Q2_CH], od[Q2_CH];
+    float dyv[Q2_CH];
+    auto load_act = [&](int64_t c0) {
+#pragma unroll
+        for (int u = 0; u < Q2_CH; ++u) {
+            const int64_t sb = c0 + u;
+            ev[u] = od[u] = make_uint4(0u, 0u, 0u, 0u);
+            dyv[u] = 0.0f;
+            if (alive && sb < nsb) {
+                const int64_t b = sb * 8 + aq;
+                ev[u] = *(const uint4 *)(a8 + ((b * 2 + 0) * Npad + an) * 16);
+                od[u] = *(const uint4 *)(a8 + ((b * 2 + 1) * Npad + an) * 16);
+                if (aq == 0) dyv[u] = ad[(sb * 8) * Npad + an];
+            }
+        }
+    };
+    q2_f32x16 acc[TPW];
+#pragma unroll
+    for (int t = 0; t < TPW; ++t)
+#pragma unroll
+        for (int e = 0; e < 16; ++e) acc[t][e] = 0.0f;
+    int64_t col[TPW];
+#pragma unroll
+    for (int t = 0; t < TPW; ++t) col[t] = i0 + (int64_t)(wave * TPW + t) * 32 + r;
+    load_act(0);
+    for (int64_t c0 = 0; c0 < nsb; c0 += Q2_CH) {
+        const int ones = 0x01010101;
+#pragma unroll
+        for (int u = 0; u < Q2_CH; ++u) {
+            int s0 = __builtin_amdgcn_sdot4((int)ev[u].x, ones, 0, false);
+            s0 = __builtin_amdgcn_sdot4((int)ev[u].y, ones, s0, false);
+            s0 = __builtin_amdgcn_sdot4((int)od[u].x, ones, s0, false);
+            s0 = __builtin_amdgcn_sdot4((int)od[u].y, ones, s0, false);
+            int s1 = __builtin_amdgcn_sdot4((int)ev[u].z, ones, 0, false);
+            s1 = __builtin_amdgcn_sdot4((int)ev[u].w, ones, s1, false);
+            s1 = __builtin_amdgcn_sdot4((int)od[u].z, ones, s1, false);
+            s1 = __builtin_amdgcn_sdot4((int)od[u].w, ones, s1, false);
+            s_bsum[u][arow][aq] = q2_f16_bits(s0) | (q2_f16_bits(s1) << 16);
+            if (aq == 0) s_dy[u][arow] = dyv[u];
+        }
+        __syncthreads();
+        load_act(c0 + Q2_CH);                               // (the next chunk's activations, in flight during this chunk's products)
+        uint2 sc[TPW][Q2_CH];
+        uint32_t dmb[TPW][Q2_CH];
+#pragma unroll
+        for (int t = 0; t < TPW; ++t)
+#pragma unroll
+            for (int u = 0; u < Q2_CH; ++u) {
+                sc[t][u] = make_uint2(0u, 0u);
+                dmb[t][u] = 0;
+                if (col[t] < M && c0 + u < nsb) {
+                    const uint8_t *slot = khdr + ((c0 + u) * Mpad + col[t]) * 32;
+                    sc[t][u] = *(const uint2 *)(slot + 8 * h);              // scales[8 h .. 8 h + 7]
+                    dmb[t][u] = *(const uint16_t *)(slot + 18);
+                }
+            }
+#pragma unroll
+        for (int u = 0; u < Q2_CH; ++u) {
+            if (c0 + u >= nsb) break;                       // (uniform over the workgroup)
+            const uint4 av = *(const uint4 *)&s_bsum[u][r][4 * h];          // A[row r][k = 8 h + jj] = bsum_{8 h + jj} of row n0 + r
+            const q2_f16x8 a = __builtin_bit_cast(q2_f16x8, av);
+            float dy[16];                                   // the rows of this lane's accumulators: (e & 3) + 8 (e >> 2) + 4 h
+#pragma unroll
+            for (int g = 0; g < 4; ++g) {
+                const float4 d4 = *(const float4 *)&s_dy[u][8 * g + 4 * h];
+                dy[4 * g] = d4.x; dy[4 * g + 1] = d4.y; dy[4 * g + 2] = d4.z; dy[4 * g + 3] = d4.w;
+            }
+#pragma unroll
+            for (int t = 0; t < TPW; ++t) {
+                const float dmin = h2f((uint16_t)dmb[t][u]);
+                q2_f16x8 bm;                                // B[k = 8 h + jj][column r] = m_{8 h + jj} = scales[8 h + jj] >> 4
+#pragma unroll
+                for (int jj = 0; jj < 8; ++jj) bm[jj] = (_Float16)(float)(((jj < 4 ? sc[t][u].x : sc[t][u].y) >> (8 * (jj & 3) + 4)) & 15u);
+                q2_f32x16 zero;
+#pragma unroll
+                for (int e = 0; e < 16; ++e) zero[e] = 0.0f;
+                const q2_f32x16 S = __builtin_amdgcn_mfma_f32_32x32x16_f16(a, bm, zero, 0, 0, 0);
+#pragma unroll
+                for (int e = 0; e < 16; ++e) {
+                    const float c = dy[e] * dmin;
+                    acc[t][e] = acc[t][e] + c * S[e];
+                }
+            }
+        }
+        __syncthreads();                                    // (the LDS of this chunk is read before the next chunk's sums overwrite it)
+    }
+#pragma unroll
+    for (int t = 0; t < TPW; ++t) {
+        if (col[t] >= M) continue;
+#pragma unroll
+        for (int e = 0; e < 16; ++e) {
+            const int64_t n = n0 + (e & 3) + 8 * (e >> 2) + 4 * h;
+            if (n < N) {
+                float *o = dst + n * ldd + col[t];
+                *o = *o - acc[t][e];
+            }
+        }
+    }
+}
+
 }  // namespace
 
 hipError_t launch_q5k_to_planar(int kq_type, const uint8_t *aos, uint64_t nb01, int64_t row_begin, int64_t rows, ggml_hip_weight *w, hipStream_t st) {
@@ -732,5 +1062,48 @@ hipError_t launch_quantize_q3k(const float *x, int64_t nrows, int64_t k, void *b
     const int64_t nsb = nrows * (k / 256);
     if (nsb <= 0) return hipSuccess;
     quantize_q3k_kernel<<<dim3((unsigned)((nsb * 16 + 127) / 128)), 128, 0, st>>>(x, nsb, (uint8_t *)blocks);
+    return hipGetLastError();
+}
+
+hipError_t launch_q2k_to_planar(const uint8_t *aos, uint64_t nb01, int64_t row_begin, int64_t rows, ggml_hip_weight *w, hipStream_t st) {
+    if (rows <= 0) return hipSuccess;
+    dim3 grid((unsigned)((rows + 127) / 128), (unsigned)w->nbk);
+    q2k_to_planar_kernel<<<grid, 128, 0, st>>>(aos, nb01, row_begin, rows, w->Mpad, w->i8p, w->d, w->m, w->khdr);
+    return hipGetLastError();
+}
+
+hipError_t launch_planar_to_q2k(const ggml_hip_weight *w, uint8_t *aos, hipStream_t st) {
+    if (w->M <= 0) return hipSuccess;
+    dim3 grid((unsigned)((w->M + 127) / 128), (unsigned)(w->nbk / 8));
+    planar_to_q2k_kernel<<<grid, 128, 0, st>>>(aos, (uint64_t)(w->nbk / 8) * 84, w->M, w->Mpad, w->i8p, w->khdr);
+    return hipGetLastError();
+}
+
+hipError_t launch_dequantize_q2k(const void *blocks, int64_t nrows, int64_t k, float *y, hipStream_t st) {
+    const int64_t nkb = nrows * (k / 32);
+    if (nkb <= 0) return hipSuccess;
+    dequantize_q2k_kernel<<<dim3((unsigned)((nkb + 127) / 128)), 128, 0, st>>>((const uint8_t *)blocks, nkb, y);
+    return hipGetLastError();
+}
+
+hipError_t launch_quantize_q2k(const float *x, int64_t nrows, int64_t k, void *blocks, hipStream_t st) {
+    const int64_t nsb = nrows * (k / 256);
+    if (nsb <= 0) return hipSuccess;
+    quantize_q2k_kernel<<<dim3((unsigned)((nsb * 16 + 127) / 128)), 128, 0, st>>>(x, nsb, (uint8_t *)blocks);
+    return hipGetLastError();
+}
+
+hipError_t launch_q2k_min_pass(const ggml_hip_weight *w, act_planes p, int64_t N, float *dst, int64_t ldd, hipStream_t st, int form) {
+    if (N <= 0 || w->M <= 0) return hipSuccess;
+    if (!w->khdr || w->K % 256 != 0 || p.Npad < (N + 31) / 32 * 32 || form < 0 || form > 2) return hipErrorInvalidValue;
+    const int64_t nt_n = (N + 31) / 32;
+    // two 32-column tiles per wave and chunks of 8 super-blocks where that still leaves a workgroup for every CU (fewer re-reads of the
+    // activation rows), else one tile per wave and chunks of 16 (half the round trips of the few workgroups there are).  The two forms
+    // compute every output in the same order: the same bits (tests/test_q2k.py runs both on the same inputs through `form`, 1 / 2).
+    const bool two = form == 0 ? nt_n * ((w->M + 255) / 256) >= 256 : form == 2;
+    const int64_t nt_i = two ? (w->M + 255) / 256 : (w->M + 127) / 128, ntiles = nt_n * nt_i, per = (ntiles + 7) / 8;
+    const dim3 grid((unsigned)(per * 8));
+    if (two) q2k_min_pass_kernel<2, 8><<<grid, 256, 0, st>>>(w->khdr, w->Mpad, w->M, w->K / 256, p.a8, p.ad, p.Npad, N, dst, ldd, nt_i, ntiles, per);
+    else q2k_min_pass_kernel<1, 16><<<grid, 256, 0, st>>>(w->khdr, w->Mpad, w->M, w->K / 256, p.a8, p.ad, p.Npad, N, dst, ldd, nt_i, ntiles, per);
     return hipGetLastError();
 }

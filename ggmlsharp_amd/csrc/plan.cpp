@@ -441,9 +441,7 @@ void plan_dense(mm_plan &p, int type, int64_t M, int64_t Mpad, int64_t K, int64_
     p.tile_m = p.tile_n = bigt ? 128 : 64; p.waves = 4; p.tiles_per_wave = 1; p.wgs = cdiv(M, p.tile_m) * cdiv(N, p.tile_n);
 }
 
-}  // namespace
-
-mm_plan plan_mul_mat(int type, int ext_type, int64_t M, int64_t K, int64_t N, bool one_call) {
+mm_plan plan_product(int type, int ext_type, int64_t M, int64_t K, int64_t N, bool one_call) {
     mm_plan p = {};
     p.ksplit = 1;
     const int64_t Mpad = pad_rows(M > 0 ? M : 1);
@@ -497,11 +495,23 @@ mm_plan plan_mul_mat(int type, int ext_type, int64_t M, int64_t K, int64_t N, bo
     return with_init();
 }
 
+}  // namespace
+
+mm_plan plan_mul_mat(int type, int ext_type, int64_t M, int64_t K, int64_t N, bool one_call) {
+    // Q2_K: the block term is a Q6_K product, planned as Q6_K's COMPUTE-only entry is (the fused mat-vec never: the min pass reads K1's image),
+    // and the min pass behind it (kquants.hip; its bits follow (K, N) alone, so tree_id keeps its promise with the flag mixed in)
+    if (!kquant_min_pass(ext_type)) return plan_product(type, ext_type, M, K, N, one_call);
+    mm_plan p = plan_product(type, ext_type, M, K, N, false);
+    if (p.family != MMF_NONE) p.flags |= MM_FLAG_MIN_PASS;
+    return p;
+}
+
 uint32_t plan_tree_id(const mm_plan &p) {
     // what fixes an element's bits, and nothing of the geometry
     uint32_t h = 2166136261u;
     const int parts[] = {p.arith, p.ksplit, p.kstyle, p.kunit, p.flags & MM_FLAG_Q8K};
     for (int v : parts) { h ^= (uint32_t)v; h *= 16777619u; }
+    if (p.flags & MM_FLAG_MIN_PASS) { h ^= (uint32_t)MM_FLAG_MIN_PASS; h *= 16777619u; }   // (only when set: every other tree_id keeps its value)
     return h;
 }
 

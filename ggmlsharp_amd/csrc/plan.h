@@ -34,7 +34,8 @@ enum mm_family {
 enum mm_kstyle { MMK_CHAIN = 0, MMK_STAGE_SETS = 1, MMK_RANGES = 2, MMK_WORKERS = 3 };
 
 enum { MM_FLAG_WIDE = 1, MM_FLAG_EPILOGUE_FUSED = 2, MM_FLAG_PERSISTENT = 4, MM_FLAG_Q8K = 8, MM_FLAG_NEEDS_WORK = 16,
-       MM_FLAG_MIN_PIECES = 32 /* INIT writes image 0 AND the three bf16 piece planes of d * sum (K3p-int8, min-term types) */ };
+       MM_FLAG_MIN_PIECES = 32 /* INIT writes image 0 AND the three bf16 piece planes of d * sum (K3p-int8, min-term types) */,
+       MM_FLAG_MIN_PASS = 64 /* Q2_K: the product is the block term; kquants.hip's min pass subtracts the min term behind it */ };
 
 // forms of the staged MX family (gemm_qmx.hip launch_typed): <WMT, WNT, WGM, WGN, KB, FB, KSP, VS>
 enum mx_form {
@@ -85,7 +86,8 @@ struct mm_plan {
 };
 
 // the plan of mul_mat(type, M, K, N); ext_type = GGML_HIP_TYPE_Q5_K / _Q4_K for a k-quant weight living in the planar Q5_1 form (type = Q5_1),
-// _Q6_K for one living in the planar Q4_2 form on int8 planes alone (type = Q4_2).
+// _Q6_K / _Q3_K / _Q2_K for one living in the planar Q4_2 form on int8 planes alone (type = Q4_2; Q2_K: Q6_K's COMPUTE-only plan -- no
+// fused mat-vec, so the min pass always finds K1's image -- with MM_FLAG_MIN_PASS).
 // one_call = the product is computed by one entry (ggml_hip_mul_mat_dev: the fused mat-vec exists); false = the COMPUTE-only entry.
 mm_plan plan_mul_mat(int type, int ext_type, int64_t M, int64_t K, int64_t N, bool one_call = true);
 uint32_t plan_tree_id(const mm_plan &p);

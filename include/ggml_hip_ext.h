@@ -6,7 +6,7 @@
  *   - neighbours of the path and their fused forms                      (ggml_hip_compute_forward_{cpy,add,mul,scale,rms_norm,silu,...})
  *   - device-level fused / grouped products                             (ggml_hip_norm_mul_mat_dev, _mul_mat_multi_dev, _mul_mat_epilogue_dev, ...)
  *   - several devices in one process, one process per device           (ggml_hip_split_weight_*, _mul_mat_split_dev, _ipc_*, _push_columns_dev, ...)
- *   - the k-quant extension types                                       (GGML_HIP_TYPE_Q5_K, _Q4_K, _Q6_K, _Q3_K)
+ *   - the k-quant extension types                                       (GGML_HIP_TYPE_Q5_K, _Q4_K, _Q6_K, _Q3_K, _Q2_K)
  *   - TEST HOOKS (ggml_hip_debug_*): inert unless called; ggml_hip_debug_force_gemm acts on the CALLING THREAD only.
  */
 #ifndef GGML_HIP_EXT_H
@@ -47,6 +47,16 @@ extern "C" {
  * download.  ggml_hip_quantize_rows_dev: quantize_row_q3_K_reference of the published format (make_q3_quants with its weighted refinement,
  * 6-bit scales against d = max scale / -32).  Accepted by the same entries as the other three; unpinned like them. */
 #define GGML_HIP_TYPE_Q3_K 111
+/* Q2_K of the same published format -- { u8 scales[16]; u8 qs[64]; half d; half dmin }, 84 bytes per 256 weights: sixteen sub-blocks of 16
+ * two-bit weights q (element e: n = e / 128, s = (e % 128) / 32, l = e % 32; q = bits 2 s, 2 s + 1 of qs[32 n + l]) with a 4-bit scale
+ * sc_j = scales[j] & 15 and a 4-bit min m_j = scales[j] >> 4 each (j = e / 16); y = (d * sc_j) * q - dmin * m_j.  The block term is a Q6_K
+ * super-block (q6 = q + 32, scales[j] = sc_j, the same d), so a Q2_K weight lives in Q6_K's resident form and runs Q6_K's kernels, never its
+ * fused mat-vec; the min term, sum over super-blocks of (dy * dmin) * sum_j m_j * bsum_j against the Q8_K activations, is subtracted from
+ * the product by one pass of its own (plan flag GGML_HIP_PLAN_MIN_PASS, its arithmetic in kquants.hip).  scales[16], d and dmin are kept per
+ * super-block for the download and the pass.  ggml_hip_quantize_rows_dev: quantize_row_q2_K_reference of the published format
+ * (make_qkx1_quants per sub-block, 4-bit scales / mins against d = max scale / 15 and dmin = max min / 15).  Accepted by the same entries as
+ * Q3_K; unpinned like the others. */
+#define GGML_HIP_TYPE_Q2_K 110
 
 
 /* OPT-IN, and a deviation from the reference's contract (which leaves EVERY node's data in host memory, Ggml.cs:3539-3704):
@@ -102,7 +112,8 @@ enum {  /* ggml_hip_mm_plan_t.flags */
     GGML_HIP_PLAN_EPILOGUE_FUSED = 2,  /* an add / scale node behind the product runs in the kernel's store phase */
     GGML_HIP_PLAN_PERSISTENT = 4, GGML_HIP_PLAN_Q8K = 8,
     GGML_HIP_PLAN_NEEDS_WORK = 16,     /* the product needs a work buffer of ggml_hip_mul_mat_work_size bytes */
-    GGML_HIP_PLAN_MIN_PIECES = 32      /* INIT writes image 0 AND the bf16 piece planes of d * sum (K3p-int8 behind Q5_1 / Q4_1 / Q5_K): image_kind 0 + 64 */
+    GGML_HIP_PLAN_MIN_PIECES = 32,     /* INIT writes image 0 AND the bf16 piece planes of d * sum (K3p-int8 behind Q5_1 / Q4_1 / Q5_K): image_kind 0 + 64 */
+    GGML_HIP_PLAN_MIN_PASS = 64        /* Q2_K: the per-16 min term is subtracted by a pass of its own behind the product (tree_id mixes it in) */
 };
 typedef struct ggml_hip_mm_plan_t {
     int32_t  family, image_kind, form;       /* which kernel, what INIT writes (-1 nothing, 0..3 K1's images, 0 + 64 image 0 with the min-term piece planes, 32 / 33 dense panels), which instantiation */
@@ -119,6 +130,11 @@ int    ggml_hip_mm_plan(int type, int64_t M, int64_t K, int64_t N, ggml_hip_mm_p
  * weight to have been uploaded while 3 was in force -- the digit planes are not built otherwise).  Same results within
  * the documented tolerance whichever runs. */
 void   ggml_hip_debug_force_gemm(int which);
+/* TEST HOOK: the Q2_K min pass alone -- d_dst[n][i] -= the min term (GGML_HIP_PLAN_MIN_PASS) against the image ggml_hip_mul_mat_init_dev
+ * wrote into d_work for this weight and N.  form: 0 the form ggml_hip_mul_mat_compute_dev runs, 1 / 2 one / two 32-column tiles per wave
+ * (the same bits whichever runs).  GGML_HIP_ERR_TYPE for any other weight type. */
+int    ggml_hip_debug_q2k_min_pass_dev(const ggml_hip_weight *w, int64_t N, float *d_dst, int64_t ldd, const void *d_work, size_t work_bytes,
+                                       int form, void *stream);
 /* Step 1 alone with an explicit layout: every src1 row -> Q8_0 (quantize_row_q8_0, Ggml.cs:733-762, the loop of
  * Ggml.cs:6641-6654) written as image `image_kind` (see above) into d_work.  image_kind + 16 (kinds 0..2, K % 256 == 0):
  * the Q8_K rule of the k-quant extension instead (one scale per 256 elements; see GGML_HIP_TYPE_Q5_K).  image_kind + 64 (kind 0 only,
