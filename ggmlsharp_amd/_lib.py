@@ -23,8 +23,9 @@ Q4_K = 112   # ... and GGML_HIP_TYPE_Q4_K (r4): the same super-block without the
 Q6_K = 114   # ... and GGML_HIP_TYPE_Q6_K (r4): sixteen sub-blocks of 16 six-bit weights, resident in the planar Q4_2 form on int8 planes
 Q3_K = 111   # ... and GGML_HIP_TYPE_Q3_K: sixteen sub-blocks of 16 three-bit weights, resident exactly as the Q6_K super-block it transcodes to
 Q2_K = 110   # ... and GGML_HIP_TYPE_Q2_K: sixteen sub-blocks of 16 two-bit weights with a scale and a min each; the block term in Q6_K's form
-# (BLCK_SIZE / TYPE_SIZE below are the tables tests/test_boundary_cpu.py holds against the host mirror, type by type; Q3_K (256 / 110) and
-# Q2_K (256 / 84) are sized by the library alone -- row_bytes() asks it, for every type)
+BF16 = 130   # ... and GGML_HIP_TYPE_BF16: upstream's bf16 (block 1, 2 bytes), resident in F16's form, its product on the bf16 matrix cores
+# (BLCK_SIZE / TYPE_SIZE below are the tables tests/test_boundary_cpu.py holds against the host mirror, type by type; Q3_K (256 / 110),
+# Q2_K (256 / 84) and BF16 (1 / 2) are sized by the library alone -- row_bytes() asks it, for every type)
 TYPE_NAME = {F32: "f32", F16: "f16", Q4_0: "q4_0", Q4_1: "q4_1", Q4_2: "q4_2", Q4_3: "q4_3", Q5_0: "q5_0",
              Q5_1: "q5_1", Q8_0: "q8_0", Q8_1: "q8_1", I8: "i8", I16: "i16", I32: "i32"}
 BLCK_SIZE = {F32: 1, F16: 1, Q4_0: 32, Q4_1: 32, Q4_2: 16, Q4_3: 16, Q5_0: 32, Q5_1: 32, Q8_0: 32, Q8_1: 32,

@@ -435,9 +435,9 @@ static int alloc_weight(DeviceCtx *c, int type, int64_t K, int64_t M, ggml_hip_w
     size_t off_qs = 0, off_d = 0, off_m = 0, off_qh = 0, off_6a = 0, off_6b = 0, off_kh = 0, off_gs = 0, off_i8 = 0, off_mp = 0, total = 0;
     bool with6 = false;
     size_t off_p16 = 0;
-    if (type == GGML_TYPE_F32 || type == GGML_TYPE_F16) {
+    if (type == GGML_TYPE_F32 || is_dense16(type)) {
         total = ((size_t)w->Mpad * K * (type == GGML_TYPE_F32 ? 4 : 2) + 255) / 256 * 256;
-        if (type == GGML_TYPE_F16) {   // k-panel copy for the f16 MFMA kernel (dense16.hip)
+        if (is_dense16(type)) {        // k-panel copy for the f16 / bf16 MFMA kernels (dense16.hip)
             off_p16 = total;
             total += (size_t)(dense16_kpad(K) / 8 + DENSE16_SPARE_PANELS) * w->Mpad * 16;
         } else {                       // the rows as three bf16 pieces per element (dense16.hip K10d)
@@ -472,9 +472,9 @@ static int alloc_weight(DeviceCtx *c, int type, int64_t K, int64_t M, ggml_hip_w
     hipError_t e = hipMalloc(&base, total);
     if (e != hipSuccess) { delete w; return fail(GGML_HIP_ERR_RUNTIME, "hipMalloc(%zu): %s", total, hipGetErrorString(e)); }
     w->bytes = total;
-    if (type == GGML_TYPE_F32 || type == GGML_TYPE_F16) {
+    if (type == GGML_TYPE_F32 || is_dense16(type)) {
         w->dense = base;
-        if (type == GGML_TYPE_F16) w->p16 = (uint8_t *)base + off_p16;
+        if (is_dense16(type)) w->p16 = (uint8_t *)base + off_p16;
         else w->p32 = (uint8_t *)base + off_p16;
     } else {
         w->qs = (uint8_t *)base + off_qs;
@@ -541,15 +541,16 @@ int make_weight(DeviceCtx *c, int type, const void *rows, bool rows_on_host, int
         *out = w;
         return GGML_HIP_OK;
     }
-    if (type < 0 || type >= GGML_TYPE_COUNT || !weight_type_ok(type))
+    // (BF16, an extension type: block 1, 2 bytes, the F16 resident form -- w->type keeps 130, ext_type stays 0)
+    if (!is_bf16(type) && (type < 0 || type >= GGML_TYPE_COUNT || !weight_type_ok(type)))
         return fail(GGML_HIP_ERR_TYPE, "type %d is not a supported weight type (Q4_3/Q8_1 have null slots, Ggml.cs:248,278-282)", type);
     if (!rows || ne00 <= 0 || ne01 < 0 || row_begin < 0 || row_end < row_begin || row_end > ne01)
         return fail(GGML_HIP_ERR_ARG, "bad weight arguments");
-    if (ne00 % BLCK[type] != 0 || (is_q(type) && ne00 % QK != 0))   // every dot product runs against 32-element Q8 blocks
+    if (!is_bf16(type) && (ne00 % BLCK[type] != 0 || (is_q(type) && ne00 % QK != 0)))   // every dot product runs against 32-element Q8 blocks
         return fail(GGML_HIP_ERR_SHAPE, "ne00 %% %d != 0 (Ggml.cs:6694)", is_q(type) ? QK : BLCK[type]);
-    const uint64_t row_bytes = (uint64_t)TSIZE[type] * (uint64_t)(ne00 / BLCK[type]);
+    const uint64_t row_bytes = is_bf16(type) ? 2 * (uint64_t)ne00 : (uint64_t)TSIZE[type] * (uint64_t)(ne00 / BLCK[type]);
     if (nb01 < row_bytes) return fail(GGML_HIP_ERR_SHAPE, "nb01 smaller than a row (transposed src0, Ggml.cs:8229)");
-    if (!rows_on_host && (type == GGML_TYPE_F32 || type == GGML_TYPE_F16) && (nb01 % 2 != 0 || ((uintptr_t)rows & 1)))
+    if (!rows_on_host && (type == GGML_TYPE_F32 || is_dense16(type)) && (nb01 % 2 != 0 || ((uintptr_t)rows & 1)))
         return fail(GGML_HIP_ERR_SHAPE, "dense device rows must be 2-byte aligned");
     int rc = c ? GGML_HIP_OK : ensure_init();
     if (rc) return rc;
@@ -603,8 +604,8 @@ using namespace ghip;
 
 extern "C" {
 
-int ggml_hip_blck_size(int type) { return is_kquant(type) ? 256 : (type >= 0 && type < GGML_TYPE_COUNT) ? BLCK[type] : 0; }
-size_t ggml_hip_type_size(int type) { return is_kquant(type) ? kquant_bytes(type) : (type >= 0 && type < GGML_TYPE_COUNT) ? TSIZE[type] : 0; }
+int ggml_hip_blck_size(int type) { return is_kquant(type) ? 256 : is_bf16(type) ? 1 : (type >= 0 && type < GGML_TYPE_COUNT) ? BLCK[type] : 0; }
+size_t ggml_hip_type_size(int type) { return is_kquant(type) ? kquant_bytes(type) : is_bf16(type) ? 2 : (type >= 0 && type < GGML_TYPE_COUNT) ? TSIZE[type] : 0; }
 
 int ggml_hip_device_count(void) {
     int n = 0;
@@ -678,7 +679,8 @@ int ggml_hip_weight_download(const ggml_hip_weight *w, void *host_rows, void *st
     rc = weight_device_current(w);
     if (rc) return rc;
     hipStream_t st = (hipStream_t)stream;
-    const size_t row_bytes = w->ext_type != 0 ? (size_t)(w->K / 256) * kquant_bytes(w->ext_type) : TSIZE[w->type] * (size_t)(w->K / BLCK[w->type]);
+    const size_t row_bytes = w->ext_type != 0 ? (size_t)(w->K / 256) * kquant_bytes(w->ext_type)
+                             : ggml_hip_type_size(w->type) * (size_t)(w->K / ggml_hip_blck_size(w->type));
     const size_t total = row_bytes * (size_t)w->M;
     if (total == 0) return GGML_HIP_OK;
     void *staging = nullptr;
@@ -710,7 +712,7 @@ int ggml_hip_weight_type(const ggml_hip_weight *w) { return w ? (w->ext_type ? w
 size_t ggml_hip_mul_mat_work_size(int type, int64_t K, int64_t N) {
     if (K <= 0 || N <= 0) return 0;
     if (is_kquant(type)) type = kquant_resident_type(type);     // same operand images
-    if (type == GGML_TYPE_F16) return (size_t)dense16_kpad(K) * (size_t)pad_act(N) * 2;   // src1 as Half (Ggml.cs:3356-3357), padded
+    if (is_dense16(type)) return (size_t)dense16_kpad(K) * (size_t)pad_act(N) * 2;   // src1 as Half (Ggml.cs:3356-3357), padded (BF16: as bf16)
     if (type == GGML_TYPE_F32) return N > 256 ? (size_t)dense16_kpad(K) * (size_t)pad_act(N) * 6 : 0;   // src1 as three bf16 pieces (dense16.hip K10d; the reference needs none)
     if (!is_q(type)) return 0;
     return act_bytes(K, pad_act(N));
@@ -741,7 +743,9 @@ int ggml_hip_mul_mat_init_dev(const ggml_hip_weight *w, const float *d_src1, int
     return GGML_HIP_OK;
 }
 
-int ggml_hip_act_image_kind(int type, int64_t K, int64_t N) { return act_image_kind(is_kquant(type) ? kquant_resident_type(type) : type, K, N); }
+int ggml_hip_act_image_kind(int type, int64_t K, int64_t N) {
+    return act_image_kind(is_kquant(type) ? kquant_resident_type(type) : is_bf16(type) ? GGML_TYPE_F16 : type, K, N);   // (BF16: F16's answer)
+}
 void ggml_hip_debug_force_gemm(int which) { plan_set_force_gemm(which); }
 
 // the plan of mul_mat(type, M, K, N) as ggml_hip_mul_mat_dev will run it; no device is needed (tests/test_plan_cpu.py)
@@ -749,8 +753,8 @@ int ggml_hip_mm_plan(int type, int64_t M, int64_t K, int64_t N, ggml_hip_mm_plan
     if (!out) return fail(GGML_HIP_ERR_ARG, "out is null");
     const bool kq = is_kquant(type);
     const int t = kq ? kquant_resident_type(type) : type;
-    if (t < 0 || t >= GGML_TYPE_COUNT || !weight_type_ok(t)) return fail(GGML_HIP_ERR_TYPE, "type %d is not a supported weight type", type);
-    if (M <= 0 || K <= 0 || N <= 0 || K % BLCK[t] != 0 || (is_q(t) && K % QK != 0) || (kq && K % 256 != 0)) return fail(GGML_HIP_ERR_SHAPE, "bad shape");
+    if (!is_bf16(t) && (t < 0 || t >= GGML_TYPE_COUNT || !weight_type_ok(t))) return fail(GGML_HIP_ERR_TYPE, "type %d is not a supported weight type", type);
+    if (M <= 0 || K <= 0 || N <= 0 || K % ggml_hip_blck_size(t) != 0 || (is_q(t) && K % QK != 0) || (kq && K % 256 != 0)) return fail(GGML_HIP_ERR_SHAPE, "bad shape");
     const mm_plan p = plan_mul_mat(t, kq ? type : 0, M, K, N, true);
     out->family = p.family; out->image_kind = p.image | ((p.flags & MM_FLAG_MIN_PIECES) ? ACT_IMAGE_MIN_PIECES : 0); out->form = p.form; out->tree_id = plan_tree_id(p);
     out->ksplit = p.ksplit; out->kstyle = p.kstyle; out->kunit = p.kunit; out->arith = p.arith;
@@ -847,7 +851,8 @@ int ggml_hip_mul_mat_dev(const ggml_hip_weight *w, const float *d_src1, int64_t 
                 return fail(GGML_HIP_ERR_ARG, "work buffer too small: this shape needs %zu bytes (ggml_hip_mul_mat_work_size)", ggml_hip_mul_mat_work_size(w->type, w->K, N));
             if (ld1 % 4 != 0 || ((uintptr_t)d_src1 & 15) != 0) return fail(GGML_HIP_ERR_SHAPE, "src1 rows must be 16-byte aligned (base and row stride) for this shape");
             if (pl.family == MMF_DENSE16) {
-                HIP_TRY(launch_dense16_init(d_src1, N, w->K, ld1, d_work, (hipStream_t)stream));       // INIT: src1 -> Half (Ggml.cs:6362-6379)
+                if (is_bf16(w->type)) HIP_TRY(launch_dense16_init_bf16(d_src1, N, w->K, ld1, d_work, (hipStream_t)stream));   // INIT: src1 -> bf16
+                else HIP_TRY(launch_dense16_init(d_src1, N, w->K, ld1, d_work, (hipStream_t)stream));  // INIT: src1 -> Half (Ggml.cs:6362-6379)
                 HIP_TRY(launch_dense16(w, pl, d_work, N, d_dst, ldd, (hipStream_t)stream));
             } else {
                 HIP_TRY(launch_dense32_init(d_src1, N, w->K, ld1, d_work, (hipStream_t)stream));
@@ -1089,6 +1094,11 @@ int ggml_hip_rms_norm_mul_rows_dev(const float *d_x, const float *d_g, float *d_
 int ggml_hip_quantize_rows_dev(int type, const float *d_x, int64_t nrows, int64_t k, void *d_blocks, void *stream) {
     if (nrows <= 0) return GGML_HIP_OK;  // empty input: nothing to do (buffers may be null)
     if (!d_x || !d_blocks) return fail(GGML_HIP_ERR_ARG, "null argument");
+    if (is_bf16(type)) {                                        // f32 -> bf16 by the one rule (dense16.hip; include/ggml_hip_ext.h)
+        if (k <= 0) return fail(GGML_HIP_ERR_SHAPE, "k <= 0");
+        HIP_TRY(launch_f32_to_bf16_rows(d_x, nrows * k, (uint16_t *)d_blocks, (hipStream_t)stream));
+        return GGML_HIP_OK;
+    }
     if (is_kquant(type)) {                                      // unpinned extra (kquants.hip, r4)
         if (k % 256 != 0) return fail(GGML_HIP_ERR_SHAPE, "k-quants: k %% 256 != 0");
         if (((uintptr_t)d_x & 15) != 0) return fail(GGML_HIP_ERR_SHAPE, "k-quants: the rows must be 16-byte aligned");
@@ -1108,6 +1118,11 @@ int ggml_hip_quantize_rows_dev(int type, const float *d_x, int64_t nrows, int64_
 int ggml_hip_dequantize_rows_dev(int type, const void *d_blocks, int64_t nrows, int64_t k, float *d_y, void *stream) {
     if (nrows <= 0) return GGML_HIP_OK;
     if (!d_y || !d_blocks) return fail(GGML_HIP_ERR_ARG, "null argument");
+    if (is_bf16(type)) {                                        // bf16 -> f32, exact
+        if (k <= 0) return fail(GGML_HIP_ERR_SHAPE, "k <= 0");
+        HIP_TRY(launch_bf16_to_f32_rows((const uint16_t *)d_blocks, nrows * k, d_y, (hipStream_t)stream));
+        return GGML_HIP_OK;
+    }
     if (is_kquant(type)) {                                      // unpinned extra (kquants.hip)
         if (k % 256 != 0) return fail(GGML_HIP_ERR_SHAPE, "k-quants: k %% 256 != 0");
         if (type == GGML_HIP_TYPE_Q6_K) HIP_TRY(launch_dequantize_q6k(d_blocks, nrows, k, d_y, (hipStream_t)stream));

@@ -351,6 +351,21 @@ hipError_t launch_dense16(const ggml_hip_weight *w, const mm_plan &pl, const voi
 hipError_t launch_f32_rows_to_split_panels(ggml_hip_weight *w, hipStream_t st);
 hipError_t launch_dense32_init(const float *x, int64_t N, int64_t K, int64_t ld1, void *work, hipStream_t st);
 hipError_t launch_dense32(const ggml_hip_weight *w, const void *work, int64_t N, float *dst, int64_t ldd, hipStream_t st);
+// BF16 weights (GGML_HIP_TYPE_BF16, an extension type: w->type holds 130 itself, so no F16 branch can take it): the F16 resident form with
+// bf16 bits (row-major copy + k-panels, launch_f16_rows_to_panels moves 16-bit words whatever they mean) and bf16 twins of the F16 kernels
+static inline bool is_bf16(int t) { return t == GGML_HIP_TYPE_BF16; }
+static inline bool is_dense16(int t) { return t == GGML_TYPE_F16 || t == GGML_HIP_TYPE_BF16; }   // 2-byte dense weights: F16 or BF16
+// f32 -> bf16, THE rule of every conversion (include/ggml_hip_ext.h GGML_HIP_TYPE_BF16): a NaN stays a quiet NaN with its sign and high
+// payload (the bare integer form would turn a NaN whose payload sits in the low bits into an infinity or carry it into the exponent: the
+// separate select); anything else rounds to nearest even, subnormals kept, overflow to +-inf.  The select is written as a mask: as a
+// conditional hipcc branched on it per element, and each branch drained the loads in flight (the BF16 mat-vec ran at a fifth of F16's rate)
+__host__ __device__ static inline uint32_t f32_to_bf16_bits(uint32_t u) {
+    const uint32_t nan = 0u - (uint32_t)((u & 0x7FFFFFFFu) > 0x7F800000u);      // all ones for a NaN
+    return (((u + 0x7FFFu + ((u >> 16) & 1u)) >> 16) & ~nan) | (((u >> 16) | 0x0040u) & nan);
+}
+hipError_t launch_dense16_init_bf16(const float *x, int64_t N, int64_t K, int64_t ld1, void *work, hipStream_t st);
+hipError_t launch_f32_to_bf16_rows(const float *x, int64_t n, uint16_t *y, hipStream_t st);      // n contiguous elements
+hipError_t launch_bf16_to_f32_rows(const uint16_t *x, int64_t n, float *y, hipStream_t st);
 // eltwise.hip (op: 0 add, 1 mul; contiguous f32)
 hipError_t launch_binary_f32(int op, const float *x, const float *y, float *z, int64_t n, hipStream_t st);
 hipError_t launch_scale_f32(float *z, int64_t n, float v, hipStream_t st);

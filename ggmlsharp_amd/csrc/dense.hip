@@ -19,9 +19,23 @@ using f32x16 = __attribute__((ext_vector_type(16))) float;
 #define DK 32    // k per stage
 #define DLD 33   // padded LDS row (floats): column reads hit 32 distinct banks
 
+// 16-bit weights: BF = false F16 (src1 as (Half)x, Ggml.cs:6369), true BF16 (src1 by the bf16 rule of common.h f32_to_bf16_bits).  Both
+// conversions of the weight are exact, so the products below are those of the matrix-core forms.
+template <bool BF>
+__device__ __forceinline__ float w16_to_f32(uint32_t bits) {
+    if constexpr (BF) return __uint_as_float(bits << 16);
+    else return __half2float(__ushort_as_half((unsigned short)bits));
+}
+template <bool BF>
+__device__ __forceinline__ float round_src1(float x) {
+    if constexpr (BF) return __uint_as_float(f32_to_bf16_bits(__float_as_uint(x)) << 16);
+    else return __half2float(__float2half_rn(x));
+}
+
 // VEC: K % 8 == 0, ld1 % 4 == 0 and src1 16-byte aligned -- a thread's 8 consecutive k are two 16-byte loads per operand
 // (one for f16 weights) instead of 8 scalar ones (the scalar form spends its time in the texture addresser: 28 -> 70 TFLOP/s)
-template <bool W_F16, bool VEC>
+// (W_F16 with BF: a BF16 weight)
+template <bool W_F16, bool VEC, bool BF = false>
 __global__ __launch_bounds__(256) void dense_kernel(const void *__restrict__ wv, const float *__restrict__ x,
                                                    float *__restrict__ dst, int64_t M, int64_t N, int64_t K, int64_t ld1,
                                                    int64_t ldd) {
@@ -49,11 +63,11 @@ __global__ __launch_bounds__(256) void dense_kernel(const void *__restrict__ wv,
                 const uint32_t u[4] = {q.x, q.y, q.z, q.w};
 #pragma unroll
                 for (int e = 0; e < 4; ++e) {
-                    wv8[2 * e + 0] = __half2float(__ushort_as_half((unsigned short)(u[e] & 0xFFFFu)));
-                    wv8[2 * e + 1] = __half2float(__ushort_as_half((unsigned short)(u[e] >> 16)));
+                    wv8[2 * e + 0] = w16_to_f32<BF>(u[e] & 0xFFFFu);
+                    wv8[2 * e + 1] = w16_to_f32<BF>(u[e] >> 16);
                 }
 #pragma unroll
-                for (int e = 0; e < 8; ++e) xv[e] = __half2float(__float2half_rn(xv[e]));   // (Half)src1, Ggml.cs:6369
+                for (int e = 0; e < 8; ++e) xv[e] = round_src1<BF>(xv[e]);   // (Half)src1, Ggml.cs:6369 (BF16: the bf16 rule)
             } else {
                 const float4 w0 = *(const float4 *)((const float *)wv + wr * K + k0 + sk), w1 = *(const float4 *)((const float *)wv + wr * K + k0 + sk + 4);
                 wv8[0] = w0.x; wv8[1] = w0.y; wv8[2] = w0.z; wv8[3] = w0.w; wv8[4] = w1.x; wv8[5] = w1.y; wv8[6] = w1.z; wv8[7] = w1.w;
@@ -65,9 +79,9 @@ __global__ __launch_bounds__(256) void dense_kernel(const void *__restrict__ wv,
             float xe = k < K ? xp[k] : 0.0f;
             float we;
             if (W_F16) {
-                const __half *wp = (const __half *)wv + wr * K;
-                we = k < K ? __half2float(wp[k]) : 0.0f;
-                xe = __half2float(__float2half_rn(xe));  // (Half)src1, Ggml.cs:6369
+                const uint16_t *wp = (const uint16_t *)wv + wr * K;
+                we = k < K ? w16_to_f32<BF>(wp[k]) : 0.0f;
+                xe = round_src1<BF>(xe);  // (Half)src1, Ggml.cs:6369 (BF16: the bf16 rule)
             } else {
                 const float *wp = (const float *)wv + wr * K;
                 we = k < K ? wp[k] : 0.0f;
@@ -257,7 +271,7 @@ __global__ __launch_bounds__(512) void dense_f32_ksplit_kernel(const float *__re
 //      ~1e-6 relative at these K), a fixed xor-shuffle tree across the wave.  F16 weights: src1 is rounded to Half first
 //      (Ggml.cs:6369).  A piece of src1 is loaded once for the wave's DGR rows (with one row per wave the L2 reads of src1
 //      were 2 .. 16 x the weight stream: 32000 x 4096 f16, N = 8: 146 us). ----
-template <bool W_F16, int NC, int DGR>                       // DGR rows per wave: 1 for one or two columns (more waves in flight), 4 above
+template <bool W_F16, int NC, int DGR, bool BF = false>      // DGR rows per wave: 1 for one or two columns (more waves in flight), 4 above; BF: a BF16 weight
 __global__ __launch_bounds__(256) void dense_gemv_kernel(const void *__restrict__ wv, const float *__restrict__ x, float *__restrict__ dst,
                                                         int64_t M, int N, int64_t K, int64_t ld1, int64_t ldd) {
     const int lane = threadIdx.x & 63;
@@ -280,8 +294,8 @@ __global__ __launch_bounds__(256) void dense_gemv_kernel(const void *__restrict_
                 const uint32_t u[4] = {q.x, q.y, q.z, q.w};
 #pragma unroll
                 for (int e = 0; e < 4; ++e) {
-                    wf[r][2 * e + 0] = __half2float(__ushort_as_half((unsigned short)(u[e] & 0xFFFFu)));
-                    wf[r][2 * e + 1] = __half2float(__ushort_as_half((unsigned short)(u[e] >> 16)));
+                    wf[r][2 * e + 0] = w16_to_f32<BF>(u[e] & 0xFFFFu);
+                    wf[r][2 * e + 1] = w16_to_f32<BF>(u[e] >> 16);
                 }
             } else {
                 const float4 q = *(const float4 *)((const float *)wv + m * K + k);
@@ -294,7 +308,7 @@ __global__ __launch_bounds__(256) void dense_gemv_kernel(const void *__restrict_
 #pragma unroll
             for (int e = 0; e < E; ++e) {
                 float xe = xp[e];
-                if (W_F16) xe = __half2float(__float2half_rn(xe));
+                if (W_F16) xe = round_src1<BF>(xe);
 #pragma unroll
                 for (int r = 0; r < DGR; ++r) acc[r][c] = fmaf(wf[r][e], xe, acc[r][c]);
             }
@@ -305,11 +319,11 @@ __global__ __launch_bounds__(256) void dense_gemv_kernel(const void *__restrict_
 #pragma unroll
             for (int r = 0; r < DGR; ++r) {
                 const int64_t m = m0 + r < M ? m0 + r : M - 1;
-                const float we = W_F16 ? __half2float(((const __half *)wv)[m * K + k]) : ((const float *)wv)[m * K + k];
+                const float we = W_F16 ? w16_to_f32<BF>(((const uint16_t *)wv)[m * K + k]) : ((const float *)wv)[m * K + k];
 #pragma unroll
                 for (int c = 0; c < NC; ++c) {
                     float xe = x[(int64_t)(c < N ? c : N - 1) * ld1 + k];
-                    if (W_F16) xe = __half2float(__float2half_rn(xe));
+                    if (W_F16) xe = round_src1<BF>(xe);
                     acc[r][c] = fmaf(we, xe, acc[r][c]);
                 }
             }
@@ -331,7 +345,7 @@ hipError_t launch_dense(const ggml_hip_weight *w, const mm_plan &pl, const float
     if (N <= 0 || w->M <= 0) return hipSuccess;
     if (pl.family != MMF_DENSE && pl.family != MMF_DENSE_GEMV) return hipErrorInvalidValue;
     // mat-vec form: rows of the resident copy are K elements apart, so 16-byte pieces need K % 8 (f16) / K % 4 (f32) == 0
-    const bool f16 = w->type == GGML_TYPE_F16;
+    const bool f16 = is_dense16(w->type), bf = is_bf16(w->type);   // (BF16: the F16 forms' bf16 twins)
     // up to 16 rows (plan.cpp plan_dense): passes of 8 columns over the weights (4096 x 4096 x 16: two passes 53 us, the tile kernel
     // below 121 us; at 32 rows and M = 11008 the tile kernel is ahead, 121 against 243 us)
     if (pl.family == MMF_DENSE_GEMV) {
@@ -339,9 +353,10 @@ hipError_t launch_dense(const ggml_hip_weight *w, const mm_plan &pl, const float
             const int n = (int)(N - c0 < 8 ? N - c0 : 8);
             const float *xc = x + c0 * ld1;
             float *dc = dst + c0 * ldd;
-#define DG(F, NC) dense_gemv_kernel<F, NC, (NC <= 2 ? 1 : 4)><<<dim3((unsigned)((w->M + 4 * (NC <= 2 ? 1 : 4) - 1) / (4 * (NC <= 2 ? 1 : 4)))), 256, 0, st>>>(w->dense, xc, dc, w->M, n, w->K, ld1, ldd)
-            if (f16) { if (n <= 1) DG(true, 1); else if (n <= 2) DG(true, 2); else if (n <= 4) DG(true, 4); else DG(true, 8); }
-            else { if (n <= 1) DG(false, 1); else if (n <= 2) DG(false, 2); else if (n <= 4) DG(false, 4); else DG(false, 8); }
+#define DG(F, NC, B) dense_gemv_kernel<F, NC, (NC <= 2 ? 1 : 4), B><<<dim3((unsigned)((w->M + 4 * (NC <= 2 ? 1 : 4) - 1) / (4 * (NC <= 2 ? 1 : 4)))), 256, 0, st>>>(w->dense, xc, dc, w->M, n, w->K, ld1, ldd)
+            if (bf) { if (n <= 1) DG(true, 1, true); else if (n <= 2) DG(true, 2, true); else if (n <= 4) DG(true, 4, true); else DG(true, 8, true); }
+            else if (f16) { if (n <= 1) DG(true, 1, false); else if (n <= 2) DG(true, 2, false); else if (n <= 4) DG(true, 4, false); else DG(true, 8, false); }
+            else { if (n <= 1) DG(false, 1, false); else if (n <= 2) DG(false, 2, false); else if (n <= 4) DG(false, 4, false); else DG(false, 8, false); }
 #undef DG
         }
         return hipGetLastError();
@@ -366,7 +381,10 @@ hipError_t launch_dense(const ggml_hip_weight *w, const mm_plan &pl, const float
             return hipGetLastError();
         }
     }
-    if (w->type == GGML_TYPE_F16) {
+    if (bf) {
+        if (vec) dense_kernel<true, true, true><<<grid, 256, 0, st>>>(w->dense, x, dst, w->M, N, w->K, ld1, ldd);
+        else dense_kernel<true, false, true><<<grid, 256, 0, st>>>(w->dense, x, dst, w->M, N, w->K, ld1, ldd);
+    } else if (f16) {
         if (vec) dense_kernel<true, true><<<grid, 256, 0, st>>>(w->dense, x, dst, w->M, N, w->K, ld1, ldd);
         else dense_kernel<true, false><<<grid, 256, 0, st>>>(w->dense, x, dst, w->M, N, w->K, ld1, ldd);
     } else {

@@ -23,6 +23,7 @@
 namespace {
 
 using f16x8 = __attribute__((ext_vector_type(8))) _Float16;
+using bf16x8 = __attribute__((ext_vector_type(8))) __bf16;
 using f32x16 = __attribute__((ext_vector_type(16))) float;
 using u32x4 = __attribute__((ext_vector_type(4))) uint32_t;
 using u32x2 = __attribute__((ext_vector_type(2))) uint32_t;
@@ -45,7 +46,9 @@ __device__ __forceinline__ void static_for(F &&f) {
 }
 
 // ---- INIT: src1 f32 rows -> f16 panel image [Kpad/8][Npad][16 B]; lane = 8 * row_in_wave + t owns 4 consecutive floats ----
+// BF: the bf16 image of a BF16 weight's product instead, by the one f32 -> bf16 rule (common.h f32_to_bf16_bits)
 #define CV_CH 4   // 128-byte chunks (32 floats = 4 panels) per lane group and workgroup column
+template <bool BF>
 __global__ __launch_bounds__(256) void convert_act_f16_kernel(const float *__restrict__ x, int64_t N, int64_t K, int64_t Kpad, int64_t ld1,
                                                              uint8_t *__restrict__ img, int64_t Npad) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, t = lane & 7;
@@ -63,9 +66,15 @@ __global__ __launch_bounds__(256) void convert_act_f16_kernel(const float *__res
             if (k + 1 < K) v.y = row[k + 1];
             if (k + 2 < K) v.z = row[k + 2];
         }
-        // (Half)x: round-to-nearest-even, overflow to infinity (Ggml.cs:6369)
-        const uint32_t h0 = __builtin_bit_cast(uint16_t, (_Float16)v.x), h1 = __builtin_bit_cast(uint16_t, (_Float16)v.y);
-        const uint32_t h2 = __builtin_bit_cast(uint16_t, (_Float16)v.z), h3 = __builtin_bit_cast(uint16_t, (_Float16)v.w);
+        uint32_t h0, h1, h2, h3;
+        if constexpr (BF) {
+            h0 = f32_to_bf16_bits(__float_as_uint(v.x)); h1 = f32_to_bf16_bits(__float_as_uint(v.y));
+            h2 = f32_to_bf16_bits(__float_as_uint(v.z)); h3 = f32_to_bf16_bits(__float_as_uint(v.w));
+        } else {
+            // (Half)x: round-to-nearest-even, overflow to infinity (Ggml.cs:6369)
+            h0 = __builtin_bit_cast(uint16_t, (_Float16)v.x); h1 = __builtin_bit_cast(uint16_t, (_Float16)v.y);
+            h2 = __builtin_bit_cast(uint16_t, (_Float16)v.z); h3 = __builtin_bit_cast(uint16_t, (_Float16)v.w);
+        }
         if (live) *(uint2 *)(img + ((k >> 3) * Npad + n) * 16 + 8 * (t & 1)) = make_uint2(h0 | (h1 << 16), h2 | (h3 << 16));
     }
 }
@@ -134,7 +143,8 @@ struct Cfg {
 // VS = 2: the two-way tree WITHOUT the second wave group ("virtual" split, as gemm_qmx.hip): one group runs the stage sets of both groups one
 // after the other, banks the first sum and adds the second to it -- group 0 + group 1, the addition the split form makes, bit for bit -- on
 // the 4-wave geometry that keeps two workgroups per CU.  For grids of many tiles, where the 8-wave form's one workgroup per CU costs rounds.
-template <int WMT, int WNT, int WGM, int WGN, int KSP, int VS = 1>
+// BF: a BF16 weight against the bf16 image -- the same panels, stages and order on v_mfma_f32_32x32x16_bf16 (the f16 rate, MI355X_MICROARCH)
+template <int WMT, int WNT, int WGM, int WGN, int KSP, int VS = 1, bool BF = false>
 __global__ __launch_bounds__(WGM * WGN * 64 * KSP, 2)
 void dense16_kernel(const uint8_t *__restrict__ wpan, const uint8_t *__restrict__ apan, float *__restrict__ dst, int M, int N, int Mpad,
                     int Npad, int nstages, int ldd, int tiles_m, int tiles_n, uint32_t w_bytes, uint32_t a_bytes) {
@@ -220,8 +230,12 @@ void dense16_kernel(const uint8_t *__restrict__ wpan, const uint8_t *__restrict_
                 if constexpr (g + AF_AHEAD < NSTEP) fetch_af(std::integral_constant<int, g + AF_AHEAD>{});
                 const f16x8 af = afr[g % (AF_AHEAD + 1)];
 #pragma unroll
-                for (int i = 0; i < WMT; ++i)
-                    acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(af, __builtin_bit_cast(f16x8, bq[ks % RING][i]), acc[i][j], 0, 0, 0);
+                for (int i = 0; i < WMT; ++i) {
+                    if constexpr (BF)
+                        acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, af), __builtin_bit_cast(bf16x8, bq[ks % RING][i]), acc[i][j], 0, 0, 0);
+                    else
+                        acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(af, __builtin_bit_cast(f16x8, bq[ks % RING][i]), acc[i][j], 0, 0, 0);
+                }
                 // hipcc's scheduler otherwise sinks the look-ahead reads (LDS fragments, weight ring) down to their uses
                 __builtin_amdgcn_sched_barrier(0);
             });
@@ -359,7 +373,7 @@ struct CfgS {
     static_assert(ROUNDS <= (KS32 - 1) * WNT, "all DMA pieces are issued before the stage's last k-step");
 };
 
-template <int WMT, int WNT, int WGM, int WGN>
+template <int WMT, int WNT, int WGM, int WGN, bool BF = false>   // BF: v_mfma_f32_16x16x32_bf16 on a BF16 weight (dense16_kernel)
 __global__ __launch_bounds__(WGM * WGN * 64, 2)
 void dense16s_kernel(const uint8_t *__restrict__ wpan, const uint8_t *__restrict__ apan, float *__restrict__ dst, int M, int N, int Mpad,
                      int Npad, int nstages, int ldd, int tiles_m, int tiles_n, uint32_t w_bytes, uint32_t a_bytes) {
@@ -432,8 +446,12 @@ void dense16s_kernel(const uint8_t *__restrict__ wpan, const uint8_t *__restrict
                 if constexpr (g + AF_AHEAD < C::NSTEP) fetch_af(std::integral_constant<int, g + AF_AHEAD>{});
                 const f16x8 af = afr[g % (AF_AHEAD + 1)];
 #pragma unroll
-                for (int i = 0; i < WMT; ++i)
-                    acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(af, __builtin_bit_cast(f16x8, bq[ks % RING32][i]), acc[i][j], 0, 0, 0);
+                for (int i = 0; i < WMT; ++i) {
+                    if constexpr (BF)
+                        acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, af), __builtin_bit_cast(bf16x8, bq[ks % RING32][i]), acc[i][j], 0, 0, 0);
+                    else
+                        acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(af, __builtin_bit_cast(f16x8, bq[ks % RING32][i]), acc[i][j], 0, 0, 0);
+                }
                 __builtin_amdgcn_sched_barrier(0);
             });
             // next stage's DMA pieces landed before the barrier: all but the weight loads issued since the last piece (see dense16_kernel)
@@ -505,7 +523,7 @@ void dense16s_kernel(const uint8_t *__restrict__ wpan, const uint8_t *__restrict
     }
 }
 
-template <int WMT, int WNT, int WGM, int WGN>
+template <int WMT, int WNT, int WGM, int WGN, bool BF>
 hipError_t launch_cfg_s(const ggml_hip_weight *w, const uint8_t *apan, int64_t N, int64_t Npad, float *dst, int64_t ldd, hipStream_t st) {
     using C = CfgS<WMT, WNT, WGM, WGN>;
     if (w->Mpad % C::TM != 0 || Npad % C::TN != 0) return hipErrorInvalidValue;
@@ -513,11 +531,11 @@ hipError_t launch_cfg_s(const ggml_hip_weight *w, const uint8_t *apan, int64_t N
     const int tiles_m = (int)((w->M + C::TM - 1) / C::TM), tiles_n = (int)((N + C::TN - 1) / C::TN);
     const uint64_t w_bytes = (uint64_t)(Kpad / 8 + DENSE16_SPARE_PANELS) * w->Mpad * 16, a_bytes = (uint64_t)(Kpad / 8) * Npad * 16;
     if (w_bytes > 0xFFFFFFFFull || a_bytes > 0xFFFFFFFFull || (uint64_t)C::TN * ldd * 4 > 0xFFFFFFFFull) return hipErrorNotSupported;
-    return launch_lds(kfn<dense16s_kernel<WMT, WNT, WGM, WGN>>, dim3((unsigned)(tiles_m * tiles_n)), C::NT, C::TOTAL, C::TOTAL, st, w->p16, apan, dst,
+    return launch_lds(kfn<dense16s_kernel<WMT, WNT, WGM, WGN, BF>>, dim3((unsigned)(tiles_m * tiles_n)), C::NT, C::TOTAL, C::TOTAL, st, w->p16, apan, dst,
                       (int)w->M, (int)N, (int)w->Mpad, (int)Npad, (int)(Kpad / (16 * KS)), (int)ldd, tiles_m, tiles_n, (uint32_t)w_bytes, (uint32_t)a_bytes);
 }
 
-template <int WMT, int WNT, int WGM, int WGN, int KSP = 1, int VS = 1>
+template <int WMT, int WNT, int WGM, int WGN, int KSP, int VS, bool BF>
 hipError_t launch_cfg(const ggml_hip_weight *w, const uint8_t *apan, int64_t N, int64_t Npad, float *dst, int64_t ldd, hipStream_t st) {
     using C = Cfg<WMT, WNT, WGM, WGN>;
     if (w->Mpad % C::TM != 0 || Npad % C::TN != 0) return hipErrorInvalidValue;
@@ -525,7 +543,7 @@ hipError_t launch_cfg(const ggml_hip_weight *w, const uint8_t *apan, int64_t N, 
     const int tiles_m = (int)((w->M + C::TM - 1) / C::TM), tiles_n = (int)((N + C::TN - 1) / C::TN);
     const uint64_t w_bytes = (uint64_t)(Kpad / 8 + DENSE16_SPARE_PANELS) * w->Mpad * 16, a_bytes = (uint64_t)(Kpad / 8) * Npad * 16;
     if (w_bytes > 0xFFFFFFFFull || a_bytes > 0xFFFFFFFFull || (uint64_t)C::TN * ldd * 4 > 0xFFFFFFFFull) return hipErrorNotSupported;
-    return launch_lds(kfn<dense16_kernel<WMT, WNT, WGM, WGN, KSP, VS>>, dim3((unsigned)(tiles_m * tiles_n)), C::NT * KSP, C::TOTAL * KSP, C::TOTAL * KSP, st,
+    return launch_lds(kfn<dense16_kernel<WMT, WNT, WGM, WGN, KSP, VS, BF>>, dim3((unsigned)(tiles_m * tiles_n)), C::NT * KSP, C::TOTAL * KSP, C::TOTAL * KSP, st,
                       w->p16, apan, dst, (int)w->M, (int)N, (int)w->Mpad, (int)Npad, (int)(Kpad / (16 * KS)), (int)ldd, tiles_m, tiles_n, (uint32_t)w_bytes,
                       (uint32_t)a_bytes);
 }
@@ -586,8 +604,6 @@ __global__ void f32_rows_to_split_panels_kernel(const float *__restrict__ rows, 
 #pragma unroll
     for (int pl = 0; pl < 3; ++pl) *(uint4 *)(pan + ((p * 3 + pl) * Mpad + m) * 16) = make_uint4(w[pl][0], w[pl][1], w[pl][2], w[pl][3]);
 }
-
-using bf16x8 = __attribute__((ext_vector_type(8))) __bf16;
 
 __global__ __launch_bounds__(256, 2)
 void dense32s_kernel(const uint8_t *__restrict__ wpan, const uint8_t *__restrict__ apan, float *__restrict__ dst, int M, int N, int Mpad,
@@ -742,11 +758,18 @@ hipError_t launch_f16_rows_to_panels(ggml_hip_weight *w, hipStream_t st) {
     return hipGetLastError();
 }
 
-hipError_t launch_dense16_init(const float *x, int64_t N, int64_t K, int64_t ld1, void *work, hipStream_t st) {
+template <bool BF>
+static hipError_t launch_convert_act(const float *x, int64_t N, int64_t K, int64_t ld1, void *work, hipStream_t st) {
     const int64_t Kpad = dense16_kpad(K), Npad = pad_act(N);
     dim3 grid((unsigned)((Kpad / 32 + CV_CH - 1) / CV_CH), (unsigned)((N + 31) / 32));
-    convert_act_f16_kernel<<<grid, 256, 0, st>>>(x, N, K, Kpad, ld1, (uint8_t *)work, Npad);
+    convert_act_f16_kernel<BF><<<grid, 256, 0, st>>>(x, N, K, Kpad, ld1, (uint8_t *)work, Npad);
     return hipGetLastError();
+}
+hipError_t launch_dense16_init(const float *x, int64_t N, int64_t K, int64_t ld1, void *work, hipStream_t st) {
+    return launch_convert_act<false>(x, N, K, ld1, work, st);
+}
+hipError_t launch_dense16_init_bf16(const float *x, int64_t N, int64_t K, int64_t ld1, void *work, hipStream_t st) {
+    return launch_convert_act<true>(x, N, K, ld1, work, st);
 }
 
 // The form was chosen by plan.cpp (plan_dense: the shape of the matrix instruction and the K split by N and K, the tile by the tile count):
@@ -754,22 +777,28 @@ hipError_t launch_dense16_init(const float *x, int64_t N, int64_t K, int64_t ld1
 //   * up to 128 rows K split four ways inside the workgroup, on 32-row tiles, or on 128-row tiles of 16 waves where those cover the chip;
 //   * prompt-sized batches: two wave groups splitting K -- on 128 x 128 tiles from 160 such tiles on (4096 x 4096 x 512 44.1 -> 37.5 us), as a
 //     VIRTUAL split on 4-wave workgroups for vocabulary-sized matrices (32000 x 4096 x 512: 229 us on the 8-wave form -> 203), else 128 x 64.
+// BF16 weights: the same forms on the bf16 MFMAs (BF), against the image launch_dense16_init_bf16 wrote
+template <bool BF>
+static hipError_t launch_dense16_t(const ggml_hip_weight *w, const mm_plan &pl, const uint8_t *a, int64_t N, int64_t Npad, float *dst, int64_t ldd,
+                                   hipStream_t st) {
+    switch (pl.form) {
+    case D16F_S_256x128:  return launch_cfg_s<4, 8, 4, 1, BF>(w, a, N, Npad, dst, ldd, st);
+    case D16F_S_128x128:  return launch_cfg_s<4, 4, 2, 2, BF>(w, a, N, Npad, dst, ldd, st);
+    case D16F_S4_H128:    return launch_cfg<1, 2, 4, 1, 4, 1, BF>(w, a, N, Npad, dst, ldd, st);
+    case D16F_S4_H32:     return launch_cfg<1, 2, 1, 1, 4, 1, BF>(w, a, N, Npad, dst, ldd, st);
+    case D16F_V2_128x128: return launch_cfg<2, 2, 2, 2, 1, 2, BF>(w, a, N, Npad, dst, ldd, st);
+    case D16F_S2_128x128: return launch_cfg<2, 2, 2, 2, 2, 1, BF>(w, a, N, Npad, dst, ldd, st);
+    case D16F_S2_128x64:  return launch_cfg<1, 2, 4, 1, 2, 1, BF>(w, a, N, Npad, dst, ldd, st);
+    case D16F_128x128:    return launch_cfg<2, 2, 2, 2, 1, 1, BF>(w, a, N, Npad, dst, ldd, st);
+    default: break;
+    }
+    return hipErrorInvalidValue;
+}
 hipError_t launch_dense16(const ggml_hip_weight *w, const mm_plan &pl, const void *work, int64_t N, float *dst, int64_t ldd, hipStream_t st) {
     const int64_t Npad = pad_act(N);
     const uint8_t *a = (const uint8_t *)work;
     if (pl.family != MMF_DENSE16 || !w->p16) return hipErrorInvalidValue;
-    switch (pl.form) {
-    case D16F_S_256x128:  return launch_cfg_s<4, 8, 4, 1>(w, a, N, Npad, dst, ldd, st);
-    case D16F_S_128x128:  return launch_cfg_s<4, 4, 2, 2>(w, a, N, Npad, dst, ldd, st);
-    case D16F_S4_H128:    return launch_cfg<1, 2, 4, 1, 4>(w, a, N, Npad, dst, ldd, st);
-    case D16F_S4_H32:     return launch_cfg<1, 2, 1, 1, 4>(w, a, N, Npad, dst, ldd, st);
-    case D16F_V2_128x128: return launch_cfg<2, 2, 2, 2, 1, 2>(w, a, N, Npad, dst, ldd, st);
-    case D16F_S2_128x128: return launch_cfg<2, 2, 2, 2, 2>(w, a, N, Npad, dst, ldd, st);
-    case D16F_S2_128x64:  return launch_cfg<1, 2, 4, 1, 2>(w, a, N, Npad, dst, ldd, st);
-    case D16F_128x128:    return launch_cfg<2, 2, 2, 2>(w, a, N, Npad, dst, ldd, st);
-    default: break;
-    }
-    return hipErrorInvalidValue;
+    return is_bf16(w->type) ? launch_dense16_t<true>(w, pl, a, N, Npad, dst, ldd, st) : launch_dense16_t<false>(w, pl, a, N, Npad, dst, ldd, st);
 }
 
 // ---- K10d host side ----
@@ -799,4 +828,39 @@ hipError_t launch_dense32(const ggml_hip_weight *w, const void *work, int64_t N,
     if (w_bytes > 0xFFFFFFFFull || a_bytes > 0xFFFFFFFFull || (uint64_t)128 * ldd * 4 > 0xFFFFFFFFull) return hipErrorNotSupported;
     return launch_lds(kfn<dense32s_kernel>, dim3((unsigned)(tiles_m * tiles_n)), 256, LDS, LDS, st, w->p32, (const uint8_t *)work, dst, (int)w->M, (int)N,
                       (int)w->Mpad, (int)Npad, (int)(Kpad / 32), (int)ldd, tiles_m, tiles_n, (uint32_t)w_bytes, (uint32_t)a_bytes);
+}
+
+// ---- BF16 rows (ggml_hip_quantize_rows_dev / _dequantize_rows_dev, GGML_HIP_TYPE_BF16): f32 -> bf16 by the one rule, bf16 -> f32 exactly.
+//      Element-wise over n contiguous elements, two per thread (4-byte stores of bf16 pairs where the pair is aligned); grid-stride. ----
+namespace {
+__global__ __launch_bounds__(256) void f32_to_bf16_kernel(const float *__restrict__ x, int64_t n, uint16_t *__restrict__ y) {
+    const int64_t stride = (int64_t)gridDim.x * 256 * 2;
+    for (int64_t i = ((int64_t)blockIdx.x * 256 + threadIdx.x) * 2; i < n; i += stride) {
+        const uint32_t lo = f32_to_bf16_bits(__float_as_uint(x[i]));
+        if (i + 1 < n && ((uintptr_t)(y + i) & 3) == 0) *(uint32_t *)(y + i) = lo | (f32_to_bf16_bits(__float_as_uint(x[i + 1])) << 16);
+        else {
+            y[i] = (uint16_t)lo;
+            if (i + 1 < n) y[i + 1] = (uint16_t)f32_to_bf16_bits(__float_as_uint(x[i + 1]));
+        }
+    }
+}
+__global__ __launch_bounds__(256) void bf16_to_f32_kernel(const uint16_t *__restrict__ x, int64_t n, float *__restrict__ y) {
+    const int64_t stride = (int64_t)gridDim.x * 256;
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += stride) y[i] = __uint_as_float((uint32_t)x[i] << 16);
+}
+unsigned convert_blocks(int64_t work) {                      // at most 8 workgroups per CU, the rest by the grid stride
+    const int64_t b = (work + 255) / 256;
+    return (unsigned)(b < 2048 ? (b > 0 ? b : 1) : 2048);
+}
+}  // namespace
+
+hipError_t launch_f32_to_bf16_rows(const float *x, int64_t n, uint16_t *y, hipStream_t st) {
+    if (n <= 0) return hipSuccess;
+    f32_to_bf16_kernel<<<convert_blocks((n + 1) / 2), 256, 0, st>>>(x, n, y);
+    return hipGetLastError();
+}
+hipError_t launch_bf16_to_f32_rows(const uint16_t *x, int64_t n, float *y, hipStream_t st) {
+    if (n <= 0) return hipSuccess;
+    bf16_to_f32_kernel<<<convert_blocks(n), 256, 0, st>>>(x, n, y);
+    return hipGetLastError();
 }

@@ -394,7 +394,7 @@ hipError_t launch_nibbles_to_bf6(ggml_hip_weight *w, hipStream_t st) {
 hipError_t launch_repack_to_planar(int type, const uint8_t *aos, uint64_t nb01, int64_t row_begin, int64_t rows,
                                    ggml_hip_weight *w, hipStream_t st) {
     if (rows <= 0) return hipSuccess;
-    if (type == GGML_TYPE_F32 || type == GGML_TYPE_F16) {
+    if (type == GGML_TYPE_F32 || is_dense16(type)) {                 // (BF16 too: 16-bit words copied as they are)
         const int64_t row_bytes = w->K * (type == GGML_TYPE_F32 ? 4 : 2);
         dim3 grid((unsigned)(((row_bytes + 3) / 4 + 255) / 256), (unsigned)(rows < 65535 ? rows : 65535));
         copy_rows_kernel<<<grid, 256, 0, st>>>(aos + (uint64_t)row_begin * nb01, nb01, (uint8_t *)w->dense,
@@ -416,7 +416,7 @@ hipError_t launch_repack_to_planar(int type, const uint8_t *aos, uint64_t nb01, 
 
 hipError_t launch_planar_to_aos(const ggml_hip_weight *w, uint8_t *aos, hipStream_t st) {
     if (w->M <= 0) return hipSuccess;
-    if (w->type == GGML_TYPE_F32 || w->type == GGML_TYPE_F16) {
+    if (w->type == GGML_TYPE_F32 || is_dense16(w->type)) {
         const int64_t row_bytes = w->K * (w->type == GGML_TYPE_F32 ? 4 : 2);
         dim3 grid((unsigned)(((row_bytes + 3) / 4 + 255) / 256), (unsigned)(w->M < 65535 ? w->M : 65535));
         copy_rows_kernel<<<grid, 256, 0, st>>>((const uint8_t *)w->dense, (uint64_t)row_bytes, aos, (uint64_t)row_bytes,

@@ -373,7 +373,11 @@ void plan_i8(mm_plan &p, int type, int64_t M, int64_t N) {
 }
 
 void plan_dense(mm_plan &p, int type, int64_t M, int64_t Mpad, int64_t K, int64_t N) {
-    const bool f16 = type == GGML_TYPE_F16;
+    // BF16 (GGML_HIP_TYPE_BF16) is planned as F16 is -- the same families, forms and bounds on the bf16 twins of its kernels (the same bytes,
+    // the same MFMA rate) -- under arithmetic labels of its own (F16's + 50), so no tree_id of F16 is one of BF16's.  Its bounds are F16's,
+    // unchanged: DESIGN.md row B has the measurement.
+    const bool bf = type == GGML_HIP_TYPE_BF16, f16 = type == GGML_TYPE_F16 || bf;
+    const int bfa = bf ? 50 : 0;
     const uint64_t Kpad = (uint64_t)dense16_kpad(K), Npad = (uint64_t)pad_act(N);
     p.image = -1;
     // F16, more than 4 src1 rows: the f16 matrix cores (by N alone; K % 4: the INIT kernel reads src1 rows in 16-byte pieces, and a
@@ -389,7 +393,7 @@ void plan_dense(mm_plan &p, int type, int64_t M, int64_t Mpad, int64_t K, int64_
             p.kunit = 8;
             auto take = [&](int f, int tm, int tn, int waves, int ks, int shape16) {
                 p.form = f; p.tile_m = tm; p.tile_n = tn; p.waves = waves; p.ksplit = ks; p.kstyle = ks > 1 ? MMK_STAGE_SETS : MMK_CHAIN;
-                p.arith = 700 + shape16; p.wgs = cdiv(M, tm) * cdiv(N, tn);
+                p.arith = 700 + bfa + shape16; p.wgs = cdiv(M, tm) * cdiv(N, tn);
                 p.tiles_per_wave = tm * tn / 1024 * ks / waves > 0 ? tm * tn / 1024 * ks / waves : 1;
             };
             if (N > 512)   // (v_mfma_f32_16x16x32_f16, by N alone: the two tile sizes sum alike)
@@ -430,14 +434,14 @@ void plan_dense(mm_plan &p, int type, int64_t M, int64_t Mpad, int64_t K, int64_
     // K % 8 (f16) / K % 4 (f32)); else the 64 x 64 tile kernel (F32: 128 x 128 tiles where they fill the chip -- bitwise the same result)
     if (N <= 16 && K % (f16 ? 8 : 4) == 0 && K >= 512) {
         p.family = MMF_DENSE_GEMV; p.form = 8;
-        p.arith = 720 + (f16 ? 1 : 0); p.ksplit = 64; p.kstyle = MMK_WORKERS; p.kunit = 1;
+        p.arith = 720 + bfa + (f16 ? 1 : 0); p.ksplit = 64; p.kstyle = MMK_WORKERS; p.kunit = 1;
         p.tile_m = 4; p.tile_n = 8; p.waves = 4; p.tiles_per_wave = 1; p.wgs = cdiv(M, 16);
         return;
     }
     const int64_t tm = cdiv(M, 128), tn = cdiv(N, 128);
     const bool bigt = !f16 && K % 32 == 0 && tm * tn >= 256 && tm * tn < (1 << 30) && Mpad % 128 == 0;
     p.family = MMF_DENSE; p.form = bigt ? DNF_BIG : DNF_TILE;
-    p.arith = 730 + (f16 ? 1 : 0); p.ksplit = 1; p.kstyle = MMK_CHAIN; p.kunit = 32;
+    p.arith = 730 + bfa + (f16 ? 1 : 0); p.ksplit = 1; p.kstyle = MMK_CHAIN; p.kunit = 32;
     p.tile_m = p.tile_n = bigt ? 128 : 64; p.waves = 4; p.tiles_per_wave = 1; p.wgs = cdiv(M, p.tile_m) * cdiv(N, p.tile_n);
 }
 
@@ -445,7 +449,7 @@ mm_plan plan_product(int type, int ext_type, int64_t M, int64_t K, int64_t N, bo
     mm_plan p = {};
     p.ksplit = 1;
     const int64_t Mpad = pad_rows(M > 0 ? M : 1);
-    if (type == GGML_TYPE_F32 || type == GGML_TYPE_F16) { plan_dense(p, type, M, Mpad, K, N); return p; }
+    if (type == GGML_TYPE_F32 || type == GGML_TYPE_F16 || type == GGML_HIP_TYPE_BF16) { plan_dense(p, type, M, Mpad, K, N); return p; }
     if (!is_quant(type) || K <= 0 || K % QK != 0) return p;
     if (ext_type != 0) p.flags |= MM_FLAG_Q8K;
     // the stated exception: planes that do not fit 32-bit buffer offsets (> 4 GiB per plane) are served by the int8 family and its image,

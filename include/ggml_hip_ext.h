@@ -7,6 +7,7 @@
  *   - device-level fused / grouped products                             (ggml_hip_norm_mul_mat_dev, _mul_mat_multi_dev, _mul_mat_epilogue_dev, ...)
  *   - several devices in one process, one process per device           (ggml_hip_split_weight_*, _mul_mat_split_dev, _ipc_*, _push_columns_dev, ...)
  *   - the k-quant extension types                                       (GGML_HIP_TYPE_Q5_K, _Q4_K, _Q6_K, _Q3_K, _Q2_K)
+ *   - the BF16 extension type                                           (GGML_HIP_TYPE_BF16)
  *   - TEST HOOKS (ggml_hip_debug_*): inert unless called; ggml_hip_debug_force_gemm acts on the CALLING THREAD only.
  */
 #ifndef GGML_HIP_EXT_H
@@ -57,6 +58,19 @@ extern "C" {
  * (make_qkx1_quants per sub-block, 4-bit scales / mins against d = max scale / 15 and dmin = max min / 15).  Accepted by the same entries as
  * Q3_K; unpinned like the others. */
 #define GGML_HIP_TYPE_Q2_K 110
+/* BF16 weights (upstream GGML_TYPE_BF16 = 30; the k-quants' rule "upstream id + 100"): block 1, 2 bytes per element, the upper half of an
+ * IEEE f32.  The product is upstream's BF16 rule, dst = sum_k bf16(w) * bf16(x): src1 is rounded to bf16 in every kernel form (the mat-vec
+ * included), each product is exact in f32 and the sum is accumulated in f32 -- the same deviation from the reference's f64 sum as F16 has.
+ * Every f32 -> bf16 conversion (src1, ggml_hip_quantize_rows_dev) is ONE rule, that of upstream's current ggml_compute_fp32_to_bf16: for f32
+ * bits u, a NaN ((u & 0x7fffffff) > 0x7f800000) becomes (u >> 16) | 0x0040 (quiet, sign kept); any other value (u + 0x7fff + ((u >> 16) & 1))
+ * >> 16, round to nearest even, subnormals KEPT and overflow to +-inf.  (An early upstream revision flushed subnormals to zero; this does not.)
+ * bf16 -> f32 is bits << 16, exact.  Resident as a row-major bf16 copy (mat-vec, tile kernel, byte-exact download) and the k-panels of F16,
+ * 4 B per weight; served by bf16 twins of the F16 kernels (the v_mfma_*_bf16 forms where F16 runs its matrix-core forms), planned as F16 is
+ * with arithmetic labels (tree_ids) of its own.  Accepted by the entries that accept an F16 weight (ggml_hip_weight_upload / _from_device /
+ * _download, ggml_hip_mul_mat_dev, _work_size, ggml_hip_mm_plan, ggml_hip_act_image_kind, the split weight) and by
+ * ggml_hip_quantize_rows_dev / ggml_hip_dequantize_rows_dev (f32 rows -> bf16 rows by the rule above, and back); refused with F16's error
+ * code wherever F16 is refused.  Never inside a ggml_tensor: the reference's enum cannot express it. */
+#define GGML_HIP_TYPE_BF16 130
 
 
 /* OPT-IN, and a deviation from the reference's contract (which leaves EVERY node's data in host memory, Ggml.cs:3539-3704):
