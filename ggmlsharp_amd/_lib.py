@@ -24,8 +24,10 @@ Q6_K = 114   # ... and GGML_HIP_TYPE_Q6_K (r4): sixteen sub-blocks of 16 six-bit
 Q3_K = 111   # ... and GGML_HIP_TYPE_Q3_K: sixteen sub-blocks of 16 three-bit weights, resident exactly as the Q6_K super-block it transcodes to
 Q2_K = 110   # ... and GGML_HIP_TYPE_Q2_K: sixteen sub-blocks of 16 two-bit weights with a scale and a min each; the block term in Q6_K's form
 BF16 = 130   # ... and GGML_HIP_TYPE_BF16: upstream's bf16 (block 1, 2 bytes), resident in F16's form, its product on the bf16 matrix cores
+IQ4_NL = 120  # ... and GGML_HIP_TYPE_IQ4_NL: 4-bit indices into a 16-entry int8 codebook, a half scale per 32; a plain Q8_0 weight once resident
+IQ4_XS = 123  # ... and GGML_HIP_TYPE_IQ4_XS: the same codebook, 6-bit scales per 32 under a half d per 256; resident in Q6_K's form
 # (BLCK_SIZE / TYPE_SIZE below are the tables tests/test_boundary_cpu.py holds against the host mirror, type by type; Q3_K (256 / 110),
-# Q2_K (256 / 84) and BF16 (1 / 2) are sized by the library alone -- row_bytes() asks it, for every type)
+# Q2_K (256 / 84), BF16 (1 / 2), IQ4_NL (32 / 18) and IQ4_XS (256 / 136) are sized by the library alone -- row_bytes() asks it, for every type)
 TYPE_NAME = {F32: "f32", F16: "f16", Q4_0: "q4_0", Q4_1: "q4_1", Q4_2: "q4_2", Q4_3: "q4_3", Q5_0: "q5_0",
              Q5_1: "q5_1", Q8_0: "q8_0", Q8_1: "q8_1", I8: "i8", I16: "i16", I32: "i32"}
 BLCK_SIZE = {F32: 1, F16: 1, Q4_0: 32, Q4_1: 32, Q4_2: 16, Q4_3: 16, Q5_0: 32, Q5_1: 32, Q8_0: 32, Q8_1: 32,

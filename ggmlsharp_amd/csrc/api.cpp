@@ -425,11 +425,12 @@ static DeviceCtx *call_slot() {
     return slot(b >= 0 ? b : 0);
 }
 
-static int alloc_weight(DeviceCtx *c, int type, int64_t K, int64_t M, ggml_hip_weight **out, int kq_type = 0) {
+static int alloc_weight(DeviceCtx *c, int type, int64_t K, int64_t M, ggml_hip_weight **out, int kq_type = 0, int up_type = 0) {
     ggml_hip_weight *w = new ggml_hip_weight();
     memset(w, 0, sizeof *w);
-    const bool kq = kq_type != 0;                           // (a k-quant weight: Q5_K / Q4_K in the planar Q5_1 form, Q6_K / Q3_K / Q2_K in the planar Q4_2 form)
+    const bool kq = kq_type != 0;                           // (a k-quant weight: Q5_K / Q4_K in the planar Q5_1 form, Q6_K / Q3_K / Q2_K / IQ4_XS in the planar Q4_2 form)
     w->ext_type = kq_type;
+    w->up_type = up_type;                                   // (IQ4_NL: type == Q8_0, the planes of a plain Q8_0 weight)
     static std::atomic<uint64_t> next_uid{1};
     w->type = type; w->M = M; w->K = K; w->Mpad = pad_rows(M > 0 ? M : 1); w->device = c->device; w->uid = next_uid.fetch_add(1);
     size_t off_qs = 0, off_d = 0, off_m = 0, off_qh = 0, off_6a = 0, off_6b = 0, off_kh = 0, off_gs = 0, off_i8 = 0, off_mp = 0, total = 0;
@@ -518,6 +519,7 @@ int make_weight(DeviceCtx *c, int type, const void *rows, bool rows_on_host, int
             return type == GGML_HIP_TYPE_Q6_K ? launch_q6k_to_planar(src, pitch, first, rows_n, w, st)
                    : type == GGML_HIP_TYPE_Q3_K ? launch_q3k_to_planar(src, pitch, first, rows_n, w, st)
                    : type == GGML_HIP_TYPE_Q2_K ? launch_q2k_to_planar(src, pitch, first, rows_n, w, st)
+                   : type == GGML_HIP_TYPE_IQ4_XS ? launch_iq4xs_to_planar(src, pitch, first, rows_n, w, st)
                                                 : launch_q5k_to_planar(type, src, pitch, first, rows_n, w, st);
         };
         rc = alloc_weight(c, kquant_resident_type(type), ne00, rows_n, &w, type);
@@ -542,13 +544,17 @@ int make_weight(DeviceCtx *c, int type, const void *rows, bool rows_on_host, int
         return GGML_HIP_OK;
     }
     // (BF16, an extension type: block 1, 2 bytes, the F16 resident form -- w->type keeps 130, ext_type stays 0)
+    // (IQ4_NL, an extension type: after the codebook lookup a plain Q8_0 weight -- w->type = Q8_0, up_type remembers IQ4_NL; iq4.hip)
+    const bool nl = is_iq4nl(type);
+    const int up = type;
+    if (nl) type = GGML_TYPE_Q8_0;
     if (!is_bf16(type) && (type < 0 || type >= GGML_TYPE_COUNT || !weight_type_ok(type)))
         return fail(GGML_HIP_ERR_TYPE, "type %d is not a supported weight type (Q4_3/Q8_1 have null slots, Ggml.cs:248,278-282)", type);
     if (!rows || ne00 <= 0 || ne01 < 0 || row_begin < 0 || row_end < row_begin || row_end > ne01)
         return fail(GGML_HIP_ERR_ARG, "bad weight arguments");
     if (!is_bf16(type) && (ne00 % BLCK[type] != 0 || (is_q(type) && ne00 % QK != 0)))   // every dot product runs against 32-element Q8 blocks
         return fail(GGML_HIP_ERR_SHAPE, "ne00 %% %d != 0 (Ggml.cs:6694)", is_q(type) ? QK : BLCK[type]);
-    const uint64_t row_bytes = is_bf16(type) ? 2 * (uint64_t)ne00 : (uint64_t)TSIZE[type] * (uint64_t)(ne00 / BLCK[type]);
+    const uint64_t row_bytes = is_bf16(type) ? 2 * (uint64_t)ne00 : nl ? 18 * (uint64_t)(ne00 / QK) : (uint64_t)TSIZE[type] * (uint64_t)(ne00 / BLCK[type]);
     if (nb01 < row_bytes) return fail(GGML_HIP_ERR_SHAPE, "nb01 smaller than a row (transposed src0, Ggml.cs:8229)");
     if (!rows_on_host && (type == GGML_TYPE_F32 || is_dense16(type)) && (nb01 % 2 != 0 || ((uintptr_t)rows & 1)))
         return fail(GGML_HIP_ERR_SHAPE, "dense device rows must be 2-byte aligned");
@@ -559,19 +565,22 @@ int make_weight(DeviceCtx *c, int type, const void *rows, bool rows_on_host, int
     if (rc) return rc;
     const int64_t rows_n = row_end - row_begin;
     ggml_hip_weight *w = nullptr;
-    rc = alloc_weight(c, type, ne00, rows_n, &w);
+    rc = alloc_weight(c, type, ne00, rows_n, &w, 0, nl ? up : 0);
     if (rc) return rc;
     hipError_t e = hipMemsetAsync(weight_base(w), 0, w->bytes, st);
     const uint8_t *dev_rows = (const uint8_t *)rows;
     void *staging = nullptr;
+    auto to_planar = [&](const uint8_t *src, uint64_t pitch, int64_t first) {   // (IQ4_NL: its own converter onto Q8_0's planes)
+        return nl ? launch_iq4nl_to_planar(src, pitch, first, rows_n, w, st) : launch_repack_to_planar(type, src, pitch, first, rows_n, w, st);
+    };
     if (e == hipSuccess && rows_on_host && rows_n > 0) {
         e = hipMalloc(&staging, (size_t)rows_n * row_bytes);
         if (e == hipSuccess)
             e = hipMemcpy2DAsync(staging, row_bytes, (const uint8_t *)rows + (uint64_t)row_begin * nb01, nb01, row_bytes,
                                  (size_t)rows_n, hipMemcpyHostToDevice, st);
-        if (e == hipSuccess) e = launch_repack_to_planar(type, (const uint8_t *)staging, row_bytes, 0, rows_n, w, st);
+        if (e == hipSuccess) e = to_planar((const uint8_t *)staging, row_bytes, 0);
     } else if (e == hipSuccess) {
-        e = launch_repack_to_planar(type, dev_rows, nb01, row_begin, rows_n, w, st);
+        e = to_planar(dev_rows, nb01, row_begin);
     }
     if (e == hipSuccess) e = launch_nibbles_to_bf6(w, st);
     if (e == hipSuccess) e = launch_q5_to_i8(w, st);
@@ -604,8 +613,12 @@ using namespace ghip;
 
 extern "C" {
 
-int ggml_hip_blck_size(int type) { return is_kquant(type) ? 256 : is_bf16(type) ? 1 : (type >= 0 && type < GGML_TYPE_COUNT) ? BLCK[type] : 0; }
-size_t ggml_hip_type_size(int type) { return is_kquant(type) ? kquant_bytes(type) : is_bf16(type) ? 2 : (type >= 0 && type < GGML_TYPE_COUNT) ? TSIZE[type] : 0; }
+int ggml_hip_blck_size(int type) {
+    return is_kquant(type) ? 256 : is_bf16(type) ? 1 : is_iq4nl(type) ? 32 : (type >= 0 && type < GGML_TYPE_COUNT) ? BLCK[type] : 0;
+}
+size_t ggml_hip_type_size(int type) {
+    return is_kquant(type) ? kquant_bytes(type) : is_bf16(type) ? 2 : is_iq4nl(type) ? 18 : (type >= 0 && type < GGML_TYPE_COUNT) ? TSIZE[type] : 0;
+}
 
 int ggml_hip_device_count(void) {
     int n = 0;
@@ -679,8 +692,8 @@ int ggml_hip_weight_download(const ggml_hip_weight *w, void *host_rows, void *st
     rc = weight_device_current(w);
     if (rc) return rc;
     hipStream_t st = (hipStream_t)stream;
-    const size_t row_bytes = w->ext_type != 0 ? (size_t)(w->K / 256) * kquant_bytes(w->ext_type)
-                             : ggml_hip_type_size(w->type) * (size_t)(w->K / ggml_hip_blck_size(w->type));
+    const int ut = ggml_hip_weight_type(w);                 // (the uploaded type: IQ4_NL's rows are not its resident Q8_0's)
+    const size_t row_bytes = ggml_hip_type_size(ut) * (size_t)(w->K / ggml_hip_blck_size(ut));
     const size_t total = row_bytes * (size_t)w->M;
     if (total == 0) return GGML_HIP_OK;
     void *staging = nullptr;
@@ -688,7 +701,9 @@ int ggml_hip_weight_download(const ggml_hip_weight *w, void *host_rows, void *st
     hipError_t e = w->ext_type == GGML_HIP_TYPE_Q6_K ? launch_planar_to_q6k(w, (uint8_t *)staging, st)
                    : w->ext_type == GGML_HIP_TYPE_Q3_K ? launch_planar_to_q3k(w, (uint8_t *)staging, st)
                    : w->ext_type == GGML_HIP_TYPE_Q2_K ? launch_planar_to_q2k(w, (uint8_t *)staging, st)
-                   : w->ext_type != 0 ? launch_planar_to_q5k(w, (uint8_t *)staging, st) : launch_planar_to_aos(w, (uint8_t *)staging, st);
+                   : w->ext_type == GGML_HIP_TYPE_IQ4_XS ? launch_planar_to_iq4xs(w, (uint8_t *)staging, st)
+                   : w->ext_type != 0 ? launch_planar_to_q5k(w, (uint8_t *)staging, st)
+                   : is_iq4nl(w->up_type) ? launch_planar_to_iq4nl(w, (uint8_t *)staging, st) : launch_planar_to_aos(w, (uint8_t *)staging, st);
     if (e == hipSuccess) e = hipMemcpyAsync(host_rows, staging, total, hipMemcpyDeviceToHost, st);
     if (e == hipSuccess) e = hipStreamSynchronize(st);
     (void)hipFree(staging);
@@ -707,11 +722,12 @@ void ggml_hip_weight_free(ggml_hip_weight *w) {
 }
 int64_t ggml_hip_weight_rows(const ggml_hip_weight *w) { return w ? w->M : 0; }
 int64_t ggml_hip_weight_cols(const ggml_hip_weight *w) { return w ? w->K : 0; }
-int ggml_hip_weight_type(const ggml_hip_weight *w) { return w ? (w->ext_type ? w->ext_type : w->type) : -1; }
+int ggml_hip_weight_type(const ggml_hip_weight *w) { return w ? (w->up_type ? w->up_type : w->ext_type ? w->ext_type : w->type) : -1; }
 
 size_t ggml_hip_mul_mat_work_size(int type, int64_t K, int64_t N) {
     if (K <= 0 || N <= 0) return 0;
     if (is_kquant(type)) type = kquant_resident_type(type);     // same operand images
+    if (is_iq4nl(type)) type = GGML_TYPE_Q8_0;
     if (is_dense16(type)) return (size_t)dense16_kpad(K) * (size_t)pad_act(N) * 2;   // src1 as Half (Ggml.cs:3356-3357), padded (BF16: as bf16)
     if (type == GGML_TYPE_F32) return N > 256 ? (size_t)dense16_kpad(K) * (size_t)pad_act(N) * 6 : 0;   // src1 as three bf16 pieces (dense16.hip K10d; the reference needs none)
     if (!is_q(type)) return 0;
@@ -744,7 +760,8 @@ int ggml_hip_mul_mat_init_dev(const ggml_hip_weight *w, const float *d_src1, int
 }
 
 int ggml_hip_act_image_kind(int type, int64_t K, int64_t N) {
-    return act_image_kind(is_kquant(type) ? kquant_resident_type(type) : is_bf16(type) ? GGML_TYPE_F16 : type, K, N);   // (BF16: F16's answer)
+    return act_image_kind(is_kquant(type) ? kquant_resident_type(type) : is_bf16(type) ? GGML_TYPE_F16 : is_iq4nl(type) ? GGML_TYPE_Q8_0 : type,
+                          K, N);   // (BF16: F16's answer; IQ4_NL: Q8_0's)
 }
 void ggml_hip_debug_force_gemm(int which) { plan_set_force_gemm(which); }
 
@@ -752,7 +769,7 @@ void ggml_hip_debug_force_gemm(int which) { plan_set_force_gemm(which); }
 int ggml_hip_mm_plan(int type, int64_t M, int64_t K, int64_t N, ggml_hip_mm_plan_t *out) {
     if (!out) return fail(GGML_HIP_ERR_ARG, "out is null");
     const bool kq = is_kquant(type);
-    const int t = kq ? kquant_resident_type(type) : type;
+    const int t = kq ? kquant_resident_type(type) : is_iq4nl(type) ? GGML_TYPE_Q8_0 : type;   // (IQ4_NL: a plain Q8_0 weight)
     if (!is_bf16(t) && (t < 0 || t >= GGML_TYPE_COUNT || !weight_type_ok(t))) return fail(GGML_HIP_ERR_TYPE, "type %d is not a supported weight type", type);
     if (M <= 0 || K <= 0 || N <= 0 || K % ggml_hip_blck_size(t) != 0 || (is_q(t) && K % QK != 0) || (kq && K % 256 != 0)) return fail(GGML_HIP_ERR_SHAPE, "bad shape");
     const mm_plan p = plan_mul_mat(t, kq ? type : 0, M, K, N, true);
@@ -1105,7 +1122,14 @@ int ggml_hip_quantize_rows_dev(int type, const float *d_x, int64_t nrows, int64_
         if (type == GGML_HIP_TYPE_Q6_K) HIP_TRY(launch_quantize_q6k(d_x, nrows, k, d_blocks, (hipStream_t)stream));
         else if (type == GGML_HIP_TYPE_Q3_K) HIP_TRY(launch_quantize_q3k(d_x, nrows, k, d_blocks, (hipStream_t)stream));
         else if (type == GGML_HIP_TYPE_Q2_K) HIP_TRY(launch_quantize_q2k(d_x, nrows, k, d_blocks, (hipStream_t)stream));
+        else if (type == GGML_HIP_TYPE_IQ4_XS) HIP_TRY(launch_quantize_iq4(type, d_x, nrows, k, d_blocks, (hipStream_t)stream));
         else HIP_TRY(launch_quantize_kq(type, d_x, nrows, k, d_blocks, (hipStream_t)stream));
+        return GGML_HIP_OK;
+    }
+    if (is_iq4nl(type)) {                                       // unpinned extra (iq4.hip)
+        if (k % QK != 0) return fail(GGML_HIP_ERR_SHAPE, "IQ4_NL: k %% 32 != 0");
+        if (((uintptr_t)d_x & 15) != 0) return fail(GGML_HIP_ERR_SHAPE, "IQ4_NL: the rows must be 16-byte aligned");
+        HIP_TRY(launch_quantize_iq4(type, d_x, nrows, k, d_blocks, (hipStream_t)stream));
         return GGML_HIP_OK;
     }
     if (!(wq_ok(type) || type == GGML_TYPE_Q8_1))
@@ -1128,7 +1152,13 @@ int ggml_hip_dequantize_rows_dev(int type, const void *d_blocks, int64_t nrows, 
         if (type == GGML_HIP_TYPE_Q6_K) HIP_TRY(launch_dequantize_q6k(d_blocks, nrows, k, d_y, (hipStream_t)stream));
         else if (type == GGML_HIP_TYPE_Q3_K) HIP_TRY(launch_dequantize_q3k(d_blocks, nrows, k, d_y, (hipStream_t)stream));
         else if (type == GGML_HIP_TYPE_Q2_K) HIP_TRY(launch_dequantize_q2k(d_blocks, nrows, k, d_y, (hipStream_t)stream));
+        else if (type == GGML_HIP_TYPE_IQ4_XS) HIP_TRY(launch_dequantize_iq4(type, d_blocks, nrows, k, d_y, (hipStream_t)stream));
         else HIP_TRY(launch_dequantize_q5k(type, d_blocks, nrows, k, d_y, (hipStream_t)stream));
+        return GGML_HIP_OK;
+    }
+    if (is_iq4nl(type)) {                                       // unpinned extra (iq4.hip)
+        if (k % QK != 0) return fail(GGML_HIP_ERR_SHAPE, "IQ4_NL: k %% 32 != 0");
+        HIP_TRY(launch_dequantize_iq4(type, d_blocks, nrows, k, d_y, (hipStream_t)stream));
         return GGML_HIP_OK;
     }
     if (!wq_ok(type))

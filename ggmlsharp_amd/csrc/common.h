@@ -75,7 +75,9 @@ struct ggml_hip_weight {
                       //   [ceil(nbk / 8) * 3 (+ pad to whole pairs of k-groups)][Mpad][16 B]: plane 3 * (b / 8) + piece holds 8 consecutive k-blocks of a row --
                       //   the B operand of v_mfma_f32_32x32x16_bf16 for K3p's min-term product (gemm_qmp.hip); 0.19 B / weight
     uint8_t *khdr;    // k-quants only (kquant_hdr_bytes; Q6_K: 32 B per super-block, scales[16] + d; Q2_K: 32 B, scales[16] + d + dmin; Q3_K: scales[12] + d): the 16 header bytes (d, dmin, scales[12]) of every super-block, [K/256][Mpad][16 B]
-    int      ext_type; // 0, or GGML_HIP_TYPE_Q5_K / _Q4_K (type == Q5_1) / _Q6_K / _Q3_K / _Q2_K (type == Q4_2): the weight was uploaded as k-quant super-blocks and lives in the planar Q5_1 form (type == Q5_1)
+    int      ext_type; // 0, or GGML_HIP_TYPE_Q5_K / _Q4_K (type == Q5_1) / _Q6_K / _Q3_K / _Q2_K / _IQ4_XS (type == Q4_2): the weight was uploaded as k-quant super-blocks and lives in the planar Q5_1 form (type == Q5_1)
+    int      up_type;  // 0, or GGML_HIP_TYPE_IQ4_NL: uploaded as that type and resident as a PLAIN Q8_0 weight (type == Q8_0, ext_type == 0; iq4.hip) --
+                       //   read by the download, ggml_hip_weight_type and the size queries alone, never by the plan or a kernel
     size_t   bytes;
     int      device;
     uint64_t uid;     // never reused: identifies the weight in cached launch graphs
@@ -294,22 +296,29 @@ hipError_t launch_push_columns(const float *src, int64_t lds, int64_t N, int64_t
 hipError_t launch_quantize_act(const float *x, int64_t N, int64_t K, int64_t ld1, act_planes p, int image, hipStream_t st, bool q8k = false);
 // kquants.hip (Q5_K as an unpinned extra: the published upstream format, no oracle in the reference)
 // (r4: Q4_K beside it -- the same super-block without the fifth-bit bytes: `kq_type` = GGML_HIP_TYPE_Q5_K or _Q4_K; a weight's own ext_type)
+// (IQ4_XS, iq4.hip: a super-block of 256 with its activations by the Q8_K rule -- a k-quant to every predicate here)
 static inline bool is_kquant(int t) {
-    return t == GGML_HIP_TYPE_Q5_K || t == GGML_HIP_TYPE_Q4_K || t == GGML_HIP_TYPE_Q6_K || t == GGML_HIP_TYPE_Q3_K || t == GGML_HIP_TYPE_Q2_K;
+    return t == GGML_HIP_TYPE_Q5_K || t == GGML_HIP_TYPE_Q4_K || t == GGML_HIP_TYPE_Q6_K || t == GGML_HIP_TYPE_Q3_K || t == GGML_HIP_TYPE_Q2_K ||
+           t == GGML_HIP_TYPE_IQ4_XS;
 }
 static inline size_t kquant_bytes(int t) {   // per 256 weights
-    return t == GGML_HIP_TYPE_Q5_K ? 176 : t == GGML_HIP_TYPE_Q6_K ? 210 : t == GGML_HIP_TYPE_Q3_K ? 110 : t == GGML_HIP_TYPE_Q2_K ? 84 : 144;
+    return t == GGML_HIP_TYPE_Q5_K ? 176 : t == GGML_HIP_TYPE_Q6_K ? 210 : t == GGML_HIP_TYPE_Q3_K ? 110 : t == GGML_HIP_TYPE_Q2_K ? 84
+           : t == GGML_HIP_TYPE_IQ4_XS ? 136 : 144;
 }
 // Q6_K, Q3_K and Q2_K: sixteen sub-blocks of 16 with a scale each -- resident in the two-scale int8 form (the planar Q4_2 form on its int8
-// planes alone, kquants.hip); Q5_K / Q4_K live in the planar Q5_1 form
-static inline bool kquant_two_scale(int t) { return t == GGML_HIP_TYPE_Q6_K || t == GGML_HIP_TYPE_Q3_K || t == GGML_HIP_TYPE_Q2_K; }
+// planes alone, kquants.hip); IQ4_XS too, both scales of a k-block equal (iq4.hip); Q5_K / Q4_K live in the planar Q5_1 form
+static inline bool kquant_two_scale(int t) {
+    return t == GGML_HIP_TYPE_Q6_K || t == GGML_HIP_TYPE_Q3_K || t == GGML_HIP_TYPE_Q2_K || t == GGML_HIP_TYPE_IQ4_XS;
+}
+// IQ4_NL (iq4.hip): after the codebook lookup a plain Q8_0 weight (type == Q8_0, ext_type == 0, up_type == IQ4_NL)
+static inline bool is_iq4nl(int t) { return t == GGML_HIP_TYPE_IQ4_NL; }
 // Q2_K: a min per sub-block of 16 as well, which no kernel family's product carries -- the product runs on the block term alone (the
 // two-scale form) and the min term is subtracted behind it by kquants.hip's min pass (plan flag MM_FLAG_MIN_PASS)
 static inline bool kquant_min_pass(int t) { return t == GGML_HIP_TYPE_Q2_K; }
 // the reference type whose resident planar form (and kernels) a k-quant weight lives in: Q5_K / Q4_K as Q5_1, Q6_K / Q3_K as Q4_2 (two scales per k-block)
 static inline int kquant_resident_type(int t) { return kquant_two_scale(t) ? GGML_TYPE_Q4_2 : GGML_TYPE_Q5_1; }
 // the slot per super-block of a weight's khdr plane: Q6_K's scales[16] + d (18 B) and Q2_K's scales[16] + d + dmin (20 B; the min pass's
-// weight operand) in 32, the others' 16 header bytes (Q3_K: scales[12] + d, 14 B) in 16
+// weight operand) in 32, the others' 16 header bytes (Q3_K: scales[12] + d, 14 B; IQ4_XS: d, scales_h, scales_l[4], 8 B) in 16
 static inline size_t kquant_hdr_bytes(int t) { return t == GGML_HIP_TYPE_Q6_K || t == GGML_HIP_TYPE_Q2_K ? 32 : 16; }
 hipError_t launch_q5k_to_planar(int kq_type, const uint8_t *aos, uint64_t nb01, int64_t row_begin, int64_t rows, ggml_hip_weight *w, hipStream_t st);
 hipError_t launch_planar_to_q5k(const ggml_hip_weight *w, uint8_t *aos, hipStream_t st);
@@ -333,6 +342,14 @@ hipError_t launch_quantize_q2k(const float *x, int64_t nrows, int64_t k, void *b
 // dst[n][i] -= the min term of a Q2_K weight against K1's int8 image by the Q8_K rule (columns i < M, rows n < N; kquants.hip);
 // form 0: the launcher's choice, 1 / 2: one / two 32-column tiles per wave (the same bits; a test hook selects them)
 hipError_t launch_q2k_min_pass(const ggml_hip_weight *w, act_planes p, int64_t N, float *dst, int64_t ldd, hipStream_t st, int form = 0);
+// iq4.hip: IQ4_NL in Q8_0's planar form (its qs / d planes), IQ4_XS in Q6_K's resident form; dequantizer and quantizer for both (type =
+// GGML_HIP_TYPE_IQ4_NL or _IQ4_XS; x: contiguous rows, 16-byte aligned)
+hipError_t launch_iq4nl_to_planar(const uint8_t *aos, uint64_t nb01, int64_t row_begin, int64_t rows, ggml_hip_weight *w, hipStream_t st);
+hipError_t launch_planar_to_iq4nl(const ggml_hip_weight *w, uint8_t *aos, hipStream_t st);
+hipError_t launch_iq4xs_to_planar(const uint8_t *aos, uint64_t nb01, int64_t row_begin, int64_t rows, ggml_hip_weight *w, hipStream_t st);
+hipError_t launch_planar_to_iq4xs(const ggml_hip_weight *w, uint8_t *aos, hipStream_t st);
+hipError_t launch_dequantize_iq4(int type, const void *blocks, int64_t nrows, int64_t k, float *y, hipStream_t st);
+hipError_t launch_quantize_iq4(int type, const float *x, int64_t nrows, int64_t k, void *blocks, hipStream_t st);
 hipError_t launch_q8_aos_to_planes(int q8type, const void *blocks, int64_t N, int64_t K, act_planes p, hipStream_t st);
 hipError_t launch_quantize_rows(int type, int src_type, const void *x, int64_t ld, int64_t nrows, int64_t k, void *blocks,
                                 hipStream_t st);

@@ -7,6 +7,7 @@
  *   - device-level fused / grouped products                             (ggml_hip_norm_mul_mat_dev, _mul_mat_multi_dev, _mul_mat_epilogue_dev, ...)
  *   - several devices in one process, one process per device           (ggml_hip_split_weight_*, _mul_mat_split_dev, _ipc_*, _push_columns_dev, ...)
  *   - the k-quant extension types                                       (GGML_HIP_TYPE_Q5_K, _Q4_K, _Q6_K, _Q3_K, _Q2_K)
+ *   - the IQ4 extension types                                           (GGML_HIP_TYPE_IQ4_NL, _IQ4_XS)
  *   - the BF16 extension type                                           (GGML_HIP_TYPE_BF16)
  *   - TEST HOOKS (ggml_hip_debug_*): inert unless called; ggml_hip_debug_force_gemm acts on the CALLING THREAD only.
  */
@@ -58,6 +59,44 @@ extern "C" {
  * (make_qkx1_quants per sub-block, 4-bit scales / mins against d = max scale / 15 and dmin = max min / 15).  Accepted by the same entries as
  * Q3_K; unpinned like the others. */
 #define GGML_HIP_TYPE_Q2_K 110
+/* IQ4_NL of the published upstream format (upstream id 20 + 100) -- { half d; u8 qs[16] }, 18 bytes per 32 weights: element j < 16 is the
+ * low nibble of qs[j], element j + 16 its high nibble, each a 4-bit index into the codebook
+ *     kv = { -127, -104, -83, -65, -49, -35, -22, -10, 1, 13, 25, 38, 53, 69, 89, 113 }   (upstream kvalues_iq4nl)
+ * and y = d * kv[idx].  After the lookup a block IS a Q8_0 block of this library (f32 d = the half d, exact; qs[j] = kv[idx_j]): the weight
+ * lives in Q8_0's resident form, is a plain Q8_0 weight to the plan and to every kernel (its product is bitwise the product of the
+ * transcoded Q8_0 weight, activations by Q8_0's rule, where upstream multiplies IQ4_NL against Q8_0 too) and reaches every entry a Q8_0
+ * weight reaches; ggml_hip_weight_type, the download (every bit pattern of d comes back) and the size queries report IQ4_NL.  K % 32.
+ * ggml_hip_quantize_rows_dev: upstream quantize_row_iq4_nl_impl without importance weights, ntry = 7, restated below.  Unpinned: the
+ * reference has no IQ types and no upstream source exists here; this text and tests/np_iq4.py are the yardstick. */
+#define GGML_HIP_TYPE_IQ4_NL 120
+/* IQ4_XS of the same published family (upstream id 23 + 100) -- { half d; u16 scales_h; u8 scales_l[4]; u8 qs[128] }, 136 bytes per 256
+ * weights, little-endian: sub-block ib < 8 has the code ls = ((scales_l[ib / 2] >> 4 (ib % 2)) & 15) | (((scales_h >> 2 ib) & 3) << 4),
+ * its 32 elements on qs[16 ib .. 16 ib + 15] in IQ4_NL's nibble order, y = (d * (ls - 32)) * kv[idx] with the product d * (ls - 32) formed
+ * first (exact in f32: 11 + 6 significant bits).  A super-block is eight k-blocks of Q6_K's resident form with both per-16 scales of a
+ * k-block equal to d * (ls - 32): Q6_K's plan and kernels serve it, activations by the Q8_K rule as upstream's; its 8 header bytes are kept
+ * for the download.  K % 256.  Accepted by the entries that accept Q3_K; unpinned like IQ4_NL.
+ * ggml_hip_quantize_rows_dev for both (IQ4_NL: super block = block = 32; IQ4_XS: super block 256, block 32).  Every step is ONE binary32
+ * operation in the order written, subnormals kept, nearest(x) = round half to even:
+ *     best_index(x): x <= kv[0] -> 0; x >= kv[15] -> 15; else ml = 0, mu = 15, while mu - ml > 1 { mav = (ml + mu) / 2;
+ *                    x < kv[mav] ? mu = mav : ml = mav }; return x - kv[mu - 1] < kv[mu] - x ? mu - 1 : mu
+ *     per block b of 32 (xb): w[j] = xb[j] * xb[j]; amax, max = the largest |xb[j]| and its signed value, the FIRST (strict >, from 0);
+ *         if amax < 1e-15f: scale[b] = 0, next block;  d = -max / kv[0]; id = 1 / d;
+ *         sumqx = sumq2 = 0; for j: q = kv[best_index(id * xb[j])]; sumqx += (w[j] * q) * xb[j]; sumq2 += (w[j] * q) * q;
+ *         d = sumqx / sumq2; best = d * sumqx;
+ *         for itry = -7 .. 7: id = (float)(itry + kv[0]) / max; the sums again; if sumq2 > 0 && sumqx * sumqx > best * sumq2:
+ *             d = sumqx / sumq2; best = d * sumqx
+ *         scale[b] = d; max_scale = the scale[b] of largest |.| (the first, strict >, from 0)
+ *     IQ4_XS: D = -max_scale / 32; d = half(D) (round to nearest even); iD = D != 0 ? 1 / D : 0; per b: l = clamp(nearest(iD * scale[b]),
+ *             -32, 31); dl = D * l; idl = dl != 0 ? 1 / dl : 0; L[j] = best_index(idl * xb[j]); ls = l + 32
+ *     IQ4_NL: d = half(scale[0]); i = scale[0] != 0 ? 1 / scale[0] : 0; L[j] = best_index(i * x[j])
+ *     Non-finite intermediates: where |x| exceeds about 1.8e18, w * q * q overflows and a block's fit gives sumqx / sumq2 = inf / inf,
+ *     a NaN scale.  It never becomes max_scale (strict >), nearest(NaN) is 0 (what upstream's nearest_int gives), so an IQ4_XS sub-block
+ *     with a NaN scale gets ls = 32 and every index 8; an IQ4_NL block stores a NaN d (its sign and payload are not specified) and every
+ *     index 15 (best_index(NaN)).
+ *     qs[j] = L[j] | L[j + 16] << 4 per 32 elements
+ * (so an all-zero IQ4_NL block is d = +0 with every qs byte 0x88, an all-zero IQ4_XS super-block d = 0x8000 -- -0 from -0.0f / 32 --,
+ * scales_h = 0xAAAA, scales_l = 0 and every qs byte 0x88).  Both types are never inside a ggml_tensor. */
+#define GGML_HIP_TYPE_IQ4_XS 123
 /* BF16 weights (upstream GGML_TYPE_BF16 = 30; the k-quants' rule "upstream id + 100"): block 1, 2 bytes per element, the upper half of an
  * IEEE f32.  The product is upstream's BF16 rule, dst = sum_k bf16(w) * bf16(x): src1 is rounded to bf16 in every kernel form (the mat-vec
  * included), each product is exact in f32 and the sum is accumulated in f32 -- the same deviation from the reference's f64 sum as F16 has.

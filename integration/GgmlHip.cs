@@ -11,6 +11,9 @@ internal static unsafe partial class GgmlHip
 
     // include/ggml_hip.h -- status codes
     public const int OK = 0, ERR_NO_DEVICE = -1, ERR_TYPE = -2, ERR_SHAPE = -3, ERR_ARG = -4, ERR_RUNTIME = -5;
+    // include/ggml_hip_ext.h -- extension weight types (upstream formats; the weight and _dev entries only, never in a ggml_tensor)
+    public const int TYPE_Q2_K = 110, TYPE_Q3_K = 111, TYPE_Q4_K = 112, TYPE_Q5_K = 113, TYPE_Q6_K = 114, TYPE_IQ4_NL = 120, TYPE_IQ4_XS = 123,
+                     TYPE_BF16 = 130;
 
     [DllImport(Lib)] public static extern int ggml_hip_device_count();
     [DllImport(Lib)] public static extern int ggml_hip_init(int device);                          // one device slot
