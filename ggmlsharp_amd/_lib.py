@@ -187,6 +187,14 @@ HIP_SYMBOLS = {
     "ggml_hip_quantize_rows_src_dev": (C.c_int, [C.c_int, C.c_int, _P, C.c_int64, C.c_int64, C.c_int64, _P, _P]),
     "ggml_hip_add_q_f32_rows_dev": (C.c_int, [C.c_int, _P, _P, C.c_int64, C.c_int64, _P, _P]),
     "ggml_hip_relayout_gathered_dev": (C.c_int, [_P, C.c_int, C.c_int64, C.c_int64, _P, C.c_int64, C.c_int64, _P]),
+    # expert-routed products (upstream's ggml_mul_mat_id): the expert set, its route / work size (and their twins by (type, M, K)), the product
+    "ggml_hip_expert_set_create": (C.c_int, [_PP, C.c_int, _P, C.POINTER(_P)]),
+    "ggml_hip_expert_set_free": (None, [_P]),
+    "ggml_hip_mul_mat_id_route": (C.c_int, [_P, C.c_int64, C.c_int]),
+    "ggml_hip_mul_mat_id_work_size": (C.c_size_t, [_P, C.c_int64, C.c_int]),
+    "ggml_hip_mul_mat_id_route_for": (C.c_int, [C.c_int, C.c_int64, C.c_int64, C.c_int, C.c_int64, C.c_int]),
+    "ggml_hip_mul_mat_id_work_size_for": (C.c_size_t, [C.c_int, C.c_int64, C.c_int64, C.c_int, C.c_int64, C.c_int]),
+    "ggml_hip_mul_mat_id_dev": (C.c_int, [_P, _P, _P, C.c_int64, C.c_int, _P, C.c_int64, C.c_int64, _P, C.c_int64, _P, C.c_size_t, _P]),
 }
 SYMBOLS = HIP_SYMBOLS
 

@@ -412,6 +412,20 @@ bool gemv_fused_has_epilogue(int64_t N);       // the kernel form that serves N 
 // the same launch with the rms_norm -> mul prologue (N <= 4 only: gemv_fused_has_epilogue)
 hipError_t launch_gemv_q_fused_pro(const ggml_hip_weight *w, const float *x, int64_t ld1, const mm_prologue &pro, int64_t N, float *dst,
                                    int64_t ldd, hipStream_t st, const mm_epilogue *ep = nullptr);
+// The by-id mat-vec of ggml_hip_mul_mat_id_dev (route 1): pair p = t * n_used + s runs the fused mat-vec at N = 1 on src1 row
+// x + t * ld1_token + s * ld1_slot against expert ids[p], whose operand plane and side image come from the set's device table `tab` --
+// the single-matrix call's bits.  An id outside [0, n_expert) writes the pair's M outputs as +0.0f without reading the table.
+// w0: any member of the set (type, ext_type, M, Mpad, nbk: the same for all).  hipErrorNotSupported where the fused mat-vec has no form.
+struct moe_expert { const uint8_t *qs; const uint32_t *gs; };
+hipError_t launch_gemv_q_fused_byid(const ggml_hip_weight *w0, const moe_expert *tab, int n_expert, const int32_t *ids, int64_t npairs, int n_used,
+                                    const float *x, int64_t ld1_token, int64_t ld1_slot, float *dst, int64_t ldd, hipStream_t st);
+// moe.hip: the batch route's gather / scatter, a slice of the row map by value per launch
+#define MOE_MAP_CHUNK 896
+struct moe_map { int32_t v[MOE_MAP_CHUNK]; };
+hipError_t launch_moe_gather(const moe_map &map, int n, int64_t j0, int n_used, const float *x, int64_t ld1_token, int64_t ld1_slot,
+                             int64_t K, float *g, int64_t ldg, hipStream_t st);
+hipError_t launch_moe_scatter(const moe_map &map, int n, int64_t p0, const float *r, int64_t ldr, int64_t M, float *dst, int64_t ldd,
+                              hipStream_t st);
 hipError_t launch_gemm_q(const ggml_hip_weight *w, const mm_plan &pl, act_planes p, int64_t N, float *dst, int64_t ldd, hipStream_t st);
 // Q8_0, 5 <= N <= 64, K >= 2048: the stage-free batched-decode form on the int8 matrix cores (gemm_q8s.hip; image 0 of K1); ep: add / scale in the store phase
 hipError_t launch_gemm_q8_small(const ggml_hip_weight *w, const mm_plan &pl, act_planes p, int64_t N, float *dst, int64_t ldd, hipStream_t st, const mm_epilogue *ep);

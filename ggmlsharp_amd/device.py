@@ -109,6 +109,59 @@ def mul_mat_compute(w, N, out, work):
           "ggml_hip_mul_mat_compute_dev")
 
 
+class ExpertSet:
+    """The experts of one mixture-of-experts projection: 2 .. 1024 resident weights of one type and shape on one device.  The set keeps the
+    Weight objects alive (the library's set does not own them)."""
+
+    def __init__(self, weights):
+        self.weights = list(weights)
+        self.M, self.K, self.type = self.weights[0].M, self.weights[0].K, self.weights[0].type
+        hw = (C.c_void_p * len(self.weights))(*[w.handle for w in self.weights])
+        h = C.c_void_p()
+        check(lib().ggml_hip_expert_set_create(hw, len(self.weights), _stream(), C.byref(h)), "ggml_hip_expert_set_create")
+        self.handle = h
+
+    def route(self, n_tokens, n_used):
+        return int(lib().ggml_hip_mul_mat_id_route(self.handle, n_tokens, n_used))
+
+    def work_size(self, n_tokens, n_used):
+        return int(lib().ggml_hip_mul_mat_id_work_size(self.handle, n_tokens, n_used))
+
+    def free(self):
+        if self.handle:
+            lib().ggml_hip_expert_set_free(self.handle)
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:
+            pass
+
+
+def mul_mat_id(es, ids, x, h_ids=None, out=None, work=None):
+    """dst[n_tokens, n_used, M]: pair (t, s) = expert ids[t, s] of the set against its src1 row, on the current stream.
+    ids int32 [n_tokens, n_used] on the device; x f32 [n_tokens, K] (one row per token, upstream's broadcast) or [n_tokens, n_used, K];
+    h_ids: the same ids as a numpy int32 array (the batch route then runs without a synchronize)."""
+    assert ids.is_cuda and ids.dtype == torch.int32 and ids.dim() == 2 and ids.is_contiguous()
+    assert x.is_cuda and x.dtype == torch.float32 and x.stride(-1) == 1 and x.shape[0] == ids.shape[0]
+    n_tokens, n_used = ids.shape
+    ld1_slot = 0 if x.dim() == 2 else x.stride(1)
+    if out is None:
+        out = torch.empty((n_tokens, n_used, es.M), dtype=torch.float32, device=x.device)
+    if work is None:
+        work = torch.empty(max(es.work_size(n_tokens, n_used), 16), dtype=torch.uint8, device=x.device)
+    hp = None
+    if h_ids is not None:
+        h_ids = np.ascontiguousarray(h_ids, dtype=np.int32)
+        assert h_ids.size == n_tokens * n_used
+        hp = h_ids.ctypes.data_as(C.c_void_p)
+    check(lib().ggml_hip_mul_mat_id_dev(es.handle, C.c_void_p(ids.data_ptr()), hp, n_tokens, n_used, C.c_void_p(x.data_ptr()), x.stride(0), ld1_slot,
+                                        C.c_void_p(out.data_ptr()), out.stride(1), C.c_void_p(work.data_ptr()), work.numel(), _stream()),
+          "ggml_hip_mul_mat_id_dev")
+    return out
+
+
 def quantize_rows(type, x):
     """x f32 [nrows, k] on the device -> uint8 [nrows, k/32*type_size] reference-format blocks."""
     assert x.is_cuda and x.dtype == torch.float32 and x.is_contiguous()

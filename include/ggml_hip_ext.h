@@ -9,6 +9,7 @@
  *   - the k-quant extension types                                       (GGML_HIP_TYPE_Q5_K, _Q4_K, _Q6_K, _Q3_K, _Q2_K)
  *   - the IQ4 extension types                                           (GGML_HIP_TYPE_IQ4_NL, _IQ4_XS)
  *   - the BF16 extension type                                           (GGML_HIP_TYPE_BF16)
+ *   - expert-routed products of a mixture-of-experts layer             (ggml_hip_expert_set_*, ggml_hip_mul_mat_id_*)
  *   - TEST HOOKS (ggml_hip_debug_*): inert unless called; ggml_hip_debug_force_gemm acts on the CALLING THREAD only.
  */
 #ifndef GGML_HIP_EXT_H
@@ -359,6 +360,54 @@ int ggml_hip_mul_mat_push_fused(const ggml_hip_weight *w, int64_t N, int n_peers
  * the last rank beyond M are dropped. */
 int ggml_hip_relayout_gathered_dev(const float *d_gathered, int G, int64_t N, int64_t Ms, float *d_dst,
                                    int64_t M, int64_t ldd, void *stream);
+
+/* ---------------- expert-routed products: upstream's ggml_mul_mat_id (a mixture-of-experts layer) ----------------
+ * EXTENSION: the reference has no such node, so there is no seam and no host mirror for it -- a device-resident entry like the
+ * multi-weight and push entries.  Upstream's shapes: as [K, M, n_expert], b [K, n_used or 1, n_tokens], ids [n_used, n_tokens],
+ * dst [M, n_used, n_tokens].  A PAIR is p = t * n_used + s (token t, slot s) and
+ *     dst[p * ldd + m] = sum_k deq(W[ids[p]][m, k]) * q(X[t * ld1_token + s * ld1_slot + k])
+ * with this library's arithmetic for the type (Q8_0 / Q8_1 / Q8_K activations, exact block dots, the type's f32 scale statement).
+ * ld1_slot = 0 is upstream's broadcast (gate / up: one src1 row per token); a non-zero stride is the down projection's own row per slot.
+ * No epilogue and no prologue on this entry.
+ *
+ * The EXPERT SET: 2 <= n_expert <= 1024 resident weights on ONE device with the same type, ext_type, up_type, K and M (else
+ * GGML_HIP_ERR_ARG / _SHAPE).  The set owns a small device table of each expert's plane pointers and NOT the weights: every weight must
+ * outlive the set (freeing a weight before the set is the caller's error).  Weights uploaded whole or as row shards alike: a set of row
+ * shards [r0, r1) of every expert computes columns [r0, r1) of the whole set's result, bit for bit, on both routes.
+ *
+ * TWO ROUTES, a function of the set and the shape alone -- never of the routing, n_expert or n_used (ggml_hip_mul_mat_id_route; the twin
+ * _route_for / _work_size_for answer for (type, M, K) with no weight and no device at hand, like ggml_hip_mm_plan, and the set's entries
+ * are the same function of the set's type, M and K):
+ *   1  the by-id mat-vec: n_tokens <= 4 and the plan of mul_mat(type, M, K, N = 1) is the fused mat-vec (GGML_HIP_MMF_GEMV_FUSED).  ONE
+ *      launch, no host synchronize, no allocation, no work buffer (work size 0): the kernel reads d_ids[p] and takes that expert's
+ *      pointers from the set's table, so the call can be captured and replayed with other ids in d_ids.  h_ids is not read.  Pair p's M
+ *      outputs are bit for bit ggml_hip_mul_mat_dev(expert ids[p], the row of p, N = 1).
+ *   2  the batch route, every other case and every weight type: the pairs are counting-sorted by expert (ascending p inside an expert),
+ *      their src1 rows gathered into expert-contiguous order in d_work, the planned product of ggml_hip_mul_mat_dev run per non-empty
+ *      expert on its contiguous batch (Q2_K's min pass and the Q8_K rule come along), and the [count_e][M] results scattered to dst[p].
+ *      Pair p's outputs are bitwise what ggml_hip_mul_mat_dev(expert e, its gathered batch, N = count_e) returns for that row: the
+ *      summation tree is a function of (type, K, count_e), as upstream's is of the batch.  The launch sizes need the counts on the HOST:
+ *      with h_ids (the same n_tokens * n_used ids in host memory) the call is asynchronous on `stream` -- the sort is host work and the
+ *      gather / scatter maps travel inside their launches, so the call may be captured (the routing is then part of the graph); with
+ *      h_ids == NULL d_ids is copied back with ONE synchronize of `stream`, and on a capturing stream that is GGML_HIP_ERR_ARG (the
+ *      capture is left intact).
+ * IDS outside [0, n_expert) are not a fault.  With h_ids on the batch route the call is refused on the host with GGML_HIP_ERR_ARG
+ * before anything is launched; wherever the ids are only known on the device (route 1; route 2 with h_ids == NULL) that pair's M
+ * outputs are written as +0.0f, and no address is ever formed from the bad id.
+ * d_ids may be NULL only on the batch route with h_ids given.  d_src1: 16-byte aligned, ld1_token and ld1_slot multiples of 4.
+ * d_work / work_bytes: ggml_hip_mul_mat_id_work_size bytes (the gathered rows, the sorted results and the largest per-expert work
+ * buffer any routing can need); missing or short is GGML_HIP_ERR_ARG.  n_tokens = 0 returns 0 and writes nothing.
+ * ggml_hip_mul_mat_id_route: 1 / 2, or < 0 (an error code).  n_expert takes no part in either answer. */
+typedef struct ggml_hip_expert_set ggml_hip_expert_set;
+int  ggml_hip_expert_set_create(const ggml_hip_weight *const *w, int n_expert, void *stream, ggml_hip_expert_set **out);
+void ggml_hip_expert_set_free(ggml_hip_expert_set *s);
+int    ggml_hip_mul_mat_id_route(const ggml_hip_expert_set *s, int64_t n_tokens, int n_used);   /* host only: 1 by-id mat-vec, 2 batch route, < 0 error */
+size_t ggml_hip_mul_mat_id_work_size(const ggml_hip_expert_set *s, int64_t n_tokens, int n_used);
+int    ggml_hip_mul_mat_id_route_for(int type, int64_t M, int64_t K, int n_expert, int64_t n_tokens, int n_used);
+size_t ggml_hip_mul_mat_id_work_size_for(int type, int64_t M, int64_t K, int n_expert, int64_t n_tokens, int n_used);
+int    ggml_hip_mul_mat_id_dev(const ggml_hip_expert_set *s, const int32_t *d_ids, const int32_t *h_ids,
+                               int64_t n_tokens, int n_used, const float *d_src1, int64_t ld1_token, int64_t ld1_slot,
+                               float *d_dst, int64_t ldd, void *d_work, size_t work_bytes, void *stream);
 
 #if defined(__GNUC__)
 #pragma GCC visibility pop

@@ -55,6 +55,19 @@ internal static unsafe partial class GgmlHip
     // rms_norm, mul, mul_mat [, add]: the pre-projection chain of a decoder block, ONE launch for decode-sized batches (addend / addDst null without an add node)
     [DllImport(Lib)] public static extern int ggml_hip_compute_forward_norm_mul_mat(ggml_compute_params* @params, ggml_tensor* x, ggml_tensor* g, ggml_tensor* normDst, ggml_tensor* mulDst, ggml_tensor* src0, ggml_tensor* mmDst, ggml_tensor* addend, ggml_tensor* addDst);
 
+    // include/ggml_hip_ext.h -- expert-routed products (upstream's ggml_mul_mat_id; a device-resident extension entry: no seam, the reference has no such node).
+    // Handles are opaque; the ids, src1, dst and work pointers are DEVICE memory (ggml_hip_slot_malloc / _upload), hIds the same ids in host memory or null.
+    [DllImport(Lib)] public static extern int ggml_hip_weight_upload(int type, void* hostRows, long ne00, long ne01, ulong nb01, long rowBegin, long rowEnd, void* stream, void** weight);
+    [DllImport(Lib)] public static extern void ggml_hip_weight_free(void* weight);
+    [DllImport(Lib)] public static extern int ggml_hip_expert_set_create(void** weights, int nExpert, void* stream, void** set);   // the set does not own the weights
+    [DllImport(Lib)] public static extern void ggml_hip_expert_set_free(void* set);
+    [DllImport(Lib)] public static extern int ggml_hip_mul_mat_id_route(void* set, long nTokens, int nUsed);            // 1 by-id mat-vec, 2 batch route, < 0 error
+    [DllImport(Lib)] public static extern nuint ggml_hip_mul_mat_id_work_size(void* set, long nTokens, int nUsed);
+    [DllImport(Lib)] public static extern int ggml_hip_mul_mat_id_route_for(int type, long m, long k, int nExpert, long nTokens, int nUsed);   // no weight, no device needed
+    [DllImport(Lib)] public static extern nuint ggml_hip_mul_mat_id_work_size_for(int type, long m, long k, int nExpert, long nTokens, int nUsed);
+    [DllImport(Lib)] public static extern int ggml_hip_mul_mat_id_dev(void* set, int* dIds, int* hIds, long nTokens, int nUsed, float* dSrc1, long ld1Token, long ld1Slot,
+        float* dDst, long ldd, void* dWork, nuint workBytes, void* stream);
+
     // Seam 2: the quantize_fns_t slots (TypeDefinitions.cs:334-342), type-indexed
     [DllImport(Lib)] public static extern int ggml_hip_quantize_row(int type, float* x, void* y, int k);
     [DllImport(Lib)] public static extern int ggml_hip_dequantize_row(int type, void* x, float* y, int k);
