@@ -195,6 +195,12 @@ HIP_SYMBOLS = {
     "ggml_hip_mul_mat_id_route_for": (C.c_int, [C.c_int, C.c_int64, C.c_int64, C.c_int, C.c_int64, C.c_int]),
     "ggml_hip_mul_mat_id_work_size_for": (C.c_size_t, [C.c_int, C.c_int64, C.c_int64, C.c_int, C.c_int64, C.c_int]),
     "ggml_hip_mul_mat_id_dev": (C.c_int, [_P, _P, _P, C.c_int64, C.c_int, _P, C.c_int64, C.c_int64, _P, C.c_int64, _P, C.c_size_t, _P]),
+    # ... and the grouped route: the ids read on the device alone, one K3s launch over every expert's tiles
+    "ggml_hip_mul_mat_id_grouped_serves": (C.c_int, [_P]),
+    "ggml_hip_mul_mat_id_grouped_serves_for": (C.c_int, [C.c_int, C.c_int64, C.c_int64]),
+    "ggml_hip_mul_mat_id_grouped_work_size": (C.c_size_t, [_P, C.c_int64, C.c_int]),
+    "ggml_hip_mul_mat_id_grouped_work_size_for": (C.c_size_t, [C.c_int, C.c_int64, C.c_int64, C.c_int, C.c_int64, C.c_int]),
+    "ggml_hip_mul_mat_id_grouped_dev": (C.c_int, [_P, _P, C.c_int64, C.c_int, _P, C.c_int64, C.c_int64, _P, C.c_int64, _P, C.c_size_t, _P]),
 }
 SYMBOLS = HIP_SYMBOLS
 

@@ -426,6 +426,27 @@ hipError_t launch_moe_gather(const moe_map &map, int n, int64_t j0, int n_used, 
                              int64_t K, float *g, int64_t ldg, hipStream_t st);
 hipError_t launch_moe_scatter(const moe_map &map, int n, int64_t p0, const float *r, int64_t ldr, int64_t M, float *dst, int64_t ldd,
                               hipStream_t st);
+// ---- the grouped, device-routed product of ggml_hip_mul_mat_id_grouped_dev (moe.cpp; plan.h plan_mul_mat_id_grouped has the bounds) ----
+// an expert's operand planes and block scales as the K3s bodies take them: Q8_0 a = qs, Q5_0 a = i8p (b unused), Q4_0 a = q6a, b = q6b
+struct moe_gexpert { const uint8_t *a; const uint8_t *b; const float *d; const void *spare; };
+// column tile t of the sorted rows: its expert, its first sorted row (32 t: every segment is padded to whole tiles) and how many of its 32 rows are pairs
+struct moe_tile { int32_t expert, first, rows, spare; };
+// the routing tables, all in the caller's work buffer: count / first [n_expert] (pairs of an expert, first sorted row of its segment),
+// n_tiles [1], pos [P] (sorted row of pair p, -1: id outside the set), order [rows] (pair of sorted row j, -1: padding), tiles [max_tiles]
+struct moe_route { int32_t *count, *first, *n_tiles, *pos, *order; moe_tile *tiles; };
+// moe.hip: ids [P] -> the tables (three launches; stable: ascending p inside an expert; integer work only); rows = 32 * max_tiles
+hipError_t launch_moe_route(const int32_t *ids, int64_t P, int n_expert, const moe_route &r, int64_t max_tiles, hipStream_t st);
+// sorted row j < rows <- the src1 row of pair order[j], zeros where order[j] < 0 (x 16-byte aligned, strides and ldg multiples of 4)
+hipError_t launch_moe_gather_dev(const int32_t *order, int64_t rows, int n_used, const float *x, int64_t ld1_token, int64_t ld1_slot, int64_t K, float *g,
+                                 int64_t ldg, hipStream_t st);
+// pair p < P <- sorted row pos[p] of r, +0.0f where pos[p] < 0
+hipError_t launch_moe_scatter_dev(const int32_t *pos, int64_t P, const float *r, int64_t ldr, int64_t M, float *dst, int64_t ldd, hipStream_t st);
+// gemm_q8s.hip / gemm_qmx.hip: ONE K3s launch over the tile table -- workgroup -> (weight tile group, column tile t); t >= *n_tiles leaves at once;
+// the expert's planes come from tab[tiles[t].expert], the 32 sorted rows at 32 t of the image p (K1's image of `32 * max_tiles` rows); res [rows][ldr]
+hipError_t launch_gemm_q8_small_grouped(const mm_plan &g, int type, const moe_gexpert *tab, const moe_tile *tiles, const int32_t *n_tiles, int64_t max_tiles,
+                                        int64_t M, int64_t Mpad, int64_t nbk, act_planes p, float *res, int64_t ldr, hipStream_t st);
+hipError_t launch_gemm_qmx_small_grouped(const mm_plan &g, int type, const moe_gexpert *tab, const moe_tile *tiles, const int32_t *n_tiles, int64_t max_tiles,
+                                         int64_t M, int64_t Mpad, int64_t nbk, act_planes p, float *res, int64_t ldr, hipStream_t st);
 hipError_t launch_gemm_q(const ggml_hip_weight *w, const mm_plan &pl, act_planes p, int64_t N, float *dst, int64_t ldd, hipStream_t st);
 // Q8_0, 5 <= N <= 64, K >= 2048: the stage-free batched-decode form on the int8 matrix cores (gemm_q8s.hip; image 0 of K1); ep: add / scale in the store phase
 hipError_t launch_gemm_q8_small(const ggml_hip_weight *w, const mm_plan &pl, act_planes p, int64_t N, float *dst, int64_t ldd, hipStream_t st, const mm_epilogue *ep);

@@ -518,6 +518,54 @@ void gemm_q8_small_multi_kernel(const q8s_set ws, const int8_t *__restrict__ a8,
 #undef Q8S
 }
 
+// The grouped product of ggml_hip_mul_mat_id_grouped_dev: the sorted pairs of ALL experts in one launch.  The image holds N = 32 * max_tiles sorted
+// rows (every expert's segment padded to whole 32-row column tiles), so to the body this is one product of N src1 rows whose column tile ct happens
+// to have its own weight matrix: the workgroup reads, from device memory, how many tiles the routing filled and which expert owns its tile, takes
+// that expert's planes from the set's table -- all uniform, once -- and everything after that is the single-matrix kernel: the tile's pairs get the
+// bits of their expert's own call at 32 src1 rows.  A workgroup past the filled tiles leaves before it touches LDS or a barrier (n_tiles is one value
+// for the launch: all of its waves leave).  Results go to the sorted rows of `res`; moe.hip's scatter takes them to their pairs.
+template <int KS, int NB, bool ROT, int WMT, bool Q5>
+__global__ __launch_bounds__(KS * 64, 1)
+void gemm_q8_small_grouped_kernel(const moe_gexpert *__restrict__ tab, const moe_tile *__restrict__ tiles, const int32_t *__restrict__ n_tiles,
+                                  const int8_t *__restrict__ a8, const float *__restrict__ ad, float *__restrict__ res, int M, int N, int Mpad, int Npad, int nbk,
+                                  int nloc, int64_t ldr, int ntw, uint32_t w_bytes, uint32_t a_bytes) {
+    int rt, ct;
+    k3s_tile_of((int)blockIdx.x, ntw, N / 32, rt, ct);      // (the body's own map: N is whole tiles)
+    if (ct >= *n_tiles) return;
+    const moe_gexpert x = tab[tiles[ct].expert];
+    const mm_epilogue ep{0, nullptr, 0, nullptr, 0, 1.0f};
+    gemm_q8_small_body<KS, NB, ROT, WMT, Q5>(x.a, x.d, a8, ad, res, M, N, Mpad, Npad, nbk, nloc, ldr, ep, ntw, w_bytes, a_bytes, (int)blockIdx.x);
+}
+
+template <bool Q5>
+hipError_t launch_q8_small_grouped(const mm_plan &g, int type, const moe_gexpert *tab, const moe_tile *tiles, const int32_t *n_tiles, int64_t max_tiles, int64_t M,
+                                   int64_t Mpad, int64_t nbk, act_planes p, float *res, int64_t ldr, hipStream_t st) {
+    constexpr int KS = 8;
+    const int nbkp = (int)pad_kblocks(nbk);
+    const int nloc = g.nloc, wmt = g.wmt;
+    const int64_t N = 32 * max_tiles;
+    const uint64_t wq_bytes = (uint64_t)nbkp * 2 * (uint64_t)Mpad * 16, aq_bytes = (uint64_t)nbkp * 2 * (uint64_t)p.Npad * 16;
+    const int64_t ntw = (M + 32 * wmt - 1) / (32 * wmt);
+    if (g.tile_m != 32 * wmt || g.tile_n != 32 || nloc > 128 || KS * nloc < nbkp || p.Npad < N || Mpad % (32 * wmt) != 0 || wq_bytes > 0xFFFFFFFFull ||
+        aq_bytes > 0xFFFFFFFFull || ntw * max_tiles != g.wgs)
+        return hipErrorInvalidValue;
+    const k3s_slots s = plan_k3s_slots(g, type);
+    if (s.lds > 160 * 1024) return hipErrorInvalidValue;
+    (void)hipGetLastError();
+    auto go = [&](auto k) {
+        return launch_lds(k, dim3((unsigned)g.wgs), KS * 64, s.lds, 160 * 1024, st, tab, tiles, n_tiles, p.a8, p.ad, res, (int)M, (int)N, (int)Mpad, (int)p.Npad,
+                          (int)nbk, nloc, ldr, (int)ntw, (uint32_t)wq_bytes, (uint32_t)aq_bytes);
+    };
+    switch (wmt) {                                          // (the slots plan_k3s_slots gives: launch_q8_small_multi's instantiations)
+    case 4: return s.rot ? go(kfn<gemm_q8_small_grouped_kernel<KS, 4, true, 4, Q5>>) : go(kfn<gemm_q8_small_grouped_kernel<KS, 4, false, 4, Q5>>);
+    case 2: return s.rot ? go(kfn<gemm_q8_small_grouped_kernel<KS, 8, true, 2, Q5>>) : go(kfn<gemm_q8_small_grouped_kernel<KS, 8, false, 2, Q5>>);
+    case 1:
+        if (s.rot) return go(kfn<gemm_q8_small_grouped_kernel<KS, 16, true, 1, Q5>>);
+        return s.slots == 8 ? go(kfn<gemm_q8_small_grouped_kernel<KS, 8, false, 1, Q5>>) : go(kfn<gemm_q8_small_grouped_kernel<KS, 16, false, 1, Q5>>);
+    default: return hipErrorInvalidValue;
+    }
+}
+
 // the instantiation for a weight form (TY: gemm_q8_small_kernel's numbering) -- R16: the 16-row kernel, W its 16-column slices, else W tiles per workgroup
 template <int NB, bool ROT, int W, int TY, bool R16>
 constexpr auto q8s_kernel() {
@@ -640,4 +688,12 @@ hipError_t launch_gemm_q8_small_multi(const mm_plan &g, const ggml_hip_weight *c
     for (int i = 0; i < n_w; ++i)
         if (!w[i] || w[i]->type != GGML_TYPE_Q8_0) return hipErrorNotSupported;
     return launch_q8_small_multi(g, w, n_w, p, N, dst, ldd, st);
+}
+
+hipError_t launch_gemm_q8_small_grouped(const mm_plan &g, int type, const moe_gexpert *tab, const moe_tile *tiles, const int32_t *n_tiles, int64_t max_tiles,
+                                        int64_t M, int64_t Mpad, int64_t nbk, act_planes p, float *res, int64_t ldr, hipStream_t st) {
+    if (g.family != MMF_K3S_I8 || max_tiles <= 0 || M <= 0) return hipErrorInvalidValue;
+    if (type == GGML_TYPE_Q8_0) return launch_q8_small_grouped<false>(g, type, tab, tiles, n_tiles, max_tiles, M, Mpad, nbk, p, res, ldr, st);
+    if (type == GGML_TYPE_Q5_0) return launch_q8_small_grouped<true>(g, type, tab, tiles, n_tiles, max_tiles, M, Mpad, nbk, p, res, ldr, st);
+    return hipErrorInvalidValue;
 }

@@ -1072,6 +1072,52 @@ void gemm_qmx_small_multi_kernel(const mxs_set ws, const uint8_t *__restrict__ a
 #undef MXS
 }
 
+// The grouped product of ggml_hip_mul_mat_id_grouped_dev on the MX cores (Q4_0): gemm_q8s.hip gemm_q8_small_grouped_kernel has the story -- the image
+// holds N = 32 * max_tiles sorted rows, column tile ct belongs to expert tiles[ct].expert, whose planes come from the set's table; a workgroup past
+// the tiles the routing filled leaves before any LDS or barrier use; the rest is the single-matrix body, untouched.
+template <int KS, int NP, bool ROT, int WMT>
+__global__ __launch_bounds__(KS * 64, 1)
+void gemm_qmx_small_grouped_kernel(const moe_gexpert *__restrict__ tab, const moe_tile *__restrict__ tiles, const int32_t *__restrict__ n_tiles,
+                                   const uint8_t *__restrict__ a6, const float *__restrict__ ad, const float *__restrict__ asd, float *__restrict__ res, int M, int N,
+                                   int Mpad, int Npad, int nbkp, int nloc, int ldr, uint32_t w6a_bytes, uint32_t wd_bytes, uint32_t a_bytes, uint32_t ad_bytes, int ntw) {
+    int rt, ct;
+    k3s_tile_of((int)blockIdx.x, ntw, N / 32, rt, ct);      // (the body's own map: N is whole tiles)
+    if (ct >= *n_tiles) return;
+    const moe_gexpert x = tab[tiles[ct].expert];
+    const mm_epilogue ep{0, nullptr, 0, nullptr, 0, 1.0f};
+    gemm_qmx_small_body<GGML_TYPE_Q4_0, KS, NP, ROT, WMT>(x.a, x.b, x.d, nullptr, a6, ad, asd, res, M, N, Mpad, Npad, nbkp, nloc, ldr, w6a_bytes, wd_bytes, a_bytes,
+                                                          ad_bytes, ep, (int)blockIdx.x, ntw);
+}
+
+hipError_t launch_small_grouped(const mm_plan &g, const moe_gexpert *tab, const moe_tile *tiles, const int32_t *n_tiles, int64_t max_tiles, int64_t M, int64_t Mpad,
+                                int64_t nbk, act_planes p, float *res, int64_t ldr, hipStream_t st) {
+    constexpr int KS = 8;
+    const int nbkp = (int)pad_kblocks(nbk);
+    const int nloc = g.nloc, wmt = g.wmt;
+    const int64_t N = 32 * max_tiles;
+    const uint64_t nba = (uint64_t)nbkp;
+    const uint64_t wq_bytes = (nba + K_LOOKAHEAD) * (uint64_t)Mpad * 16, wd_bytes = (nba + K_LOOKAHEAD) * (uint64_t)Mpad * 4;
+    const uint64_t a_bytes = nba * 48 * (uint64_t)p.Npad, ad_bytes = nba * (uint64_t)p.Npad * 4;
+    const int64_t ntw = (M + 32 * wmt - 1) / (32 * wmt);
+    const k3s_slots s = plan_k3s_slots(g, GGML_TYPE_Q4_0);
+    if (g.tile_m != 32 * wmt || g.tile_n != 32 || nloc > 128 || (nloc & 1) || KS * nloc < nbkp || p.Npad < N || Mpad % (32 * wmt) != 0 || wq_bytes > 0xFFFFFFFFull ||
+        a_bytes > 0xFFFFFFFFull || s.lds > 160 * 1024 || ntw * max_tiles != g.wgs || ldr > 0x7FFFFFFF)
+        return hipErrorInvalidValue;
+    (void)hipGetLastError();
+    auto go = [&](auto k) {
+        return launch_lds(k, dim3((unsigned)g.wgs), KS * 64, s.lds, 160 * 1024, st, tab, tiles, n_tiles, (const uint8_t *)p.a8, p.ad, (const float *)p.as, res, (int)M,
+                          (int)N, (int)Mpad, (int)p.Npad, nbkp, nloc, (int)ldr, (uint32_t)wq_bytes, (uint32_t)wd_bytes, (uint32_t)a_bytes, (uint32_t)ad_bytes, (int)ntw);
+    };
+    switch (wmt) {                                          // (the slots plan_k3s_slots gives Q4_0: launch_small's instantiations)
+    case 4: return go(kfn<gemm_qmx_small_grouped_kernel<KS, 2, true, 4>>);
+    case 2: return s.rot ? go(kfn<gemm_qmx_small_grouped_kernel<KS, 4, true, 2>>) : go(kfn<gemm_qmx_small_grouped_kernel<KS, 4, false, 2>>);
+    case 1:
+        if (s.rot) return go(kfn<gemm_qmx_small_grouped_kernel<KS, 8, true, 1>>);
+        return s.slots == 4 ? go(kfn<gemm_qmx_small_grouped_kernel<KS, 4, false, 1>>) : go(kfn<gemm_qmx_small_grouped_kernel<KS, 8, false, 1>>);
+    default: return hipErrorInvalidValue;
+    }
+}
+
 template <int TYPE, int WMT, int WNT, int WGM, int WGN, int KB, int FB, int KSP = 1, int VS = 1>
 hipError_t launch_cfg(const ggml_hip_weight *w, act_planes p, int64_t N, float *dst, int64_t ldd, hipStream_t st, const mm_epilogue *ep) {
     using C = Cfg<TYPE, WMT, WNT, WGM, WGN, KB>;
@@ -1253,6 +1299,12 @@ hipError_t launch_gemm_qmx_multi(const mm_plan &g, const ggml_hip_weight *const 
     case GGML_TYPE_Q4_1: return launch_small_multi<GGML_TYPE_Q4_1>(g, w, n_w, p, N, dst, ldd, st);
     default: return hipErrorInvalidValue;
     }
+}
+
+hipError_t launch_gemm_qmx_small_grouped(const mm_plan &g, int type, const moe_gexpert *tab, const moe_tile *tiles, const int32_t *n_tiles, int64_t max_tiles,
+                                         int64_t M, int64_t Mpad, int64_t nbk, act_planes p, float *res, int64_t ldr, hipStream_t st) {
+    if (g.family != MMF_K3S_MX || type != GGML_TYPE_Q4_0 || max_tiles <= 0 || M <= 0) return hipErrorInvalidValue;
+    return launch_small_grouped(g, tab, tiles, n_tiles, max_tiles, M, Mpad, nbk, p, res, ldr, st);
 }
 
 hipError_t launch_gemm_qmx(const ggml_hip_weight *w, const mm_plan &pl, act_planes p, int64_t N, float *dst, int64_t ldd, hipStream_t st,

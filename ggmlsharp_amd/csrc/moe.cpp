@@ -7,6 +7,12 @@
 //            expert on its contiguous batch, scatter (moe.hip).  The maps travel inside the gather / scatter launches.
 // The route is a function of (type, M, K, n_tokens) alone: route_of below is the one place that decides it, for the set's entries and for
 // their device-free twins alike.
+//
+// Beside them, reached through its own entry only (ggml_hip_mul_mat_id_grouped_dev), the GROUPED route: the ids are read on the device alone --
+// routing kernels (moe.hip) sort the pairs by expert into segments padded to 32-row column tiles, a gather and ONE INIT over the bounded row
+// count write the activation image, ONE K3s launch (gemm_q8s.hip / gemm_qmx.hip) runs every tile against its expert's planes, a scatter takes
+// the sorted results to their pairs.  Seven launches whatever the routing and n_expert; no synchronize, no allocation; capturable.  What it
+// serves, its geometry and its bounds are plan.cpp's (plan_mul_mat_id_grouped).
 #include "ctx.h"
 
 #include <algorithm>
@@ -16,6 +22,8 @@ using namespace ghip;
 struct ggml_hip_expert_set {
     std::vector<const ggml_hip_weight *> w;
     moe_expert *d_tab = nullptr;          // [n_expert] operand plane + side image of every expert (what the by-id mat-vec reads)
+    moe_gexpert *d_gtab = nullptr;        // [n_expert] behind it in the same allocation: operand planes + block scales as the K3s bodies take them (the grouped route)
+    bool grouped_planes = false;          // every expert has the planes the grouped route's kernel of this type reads
     int device = -1;
     int type = 0, ext_type = 0;           // the resident type and the k-quant it was uploaded as (ggml_hip_weight's fields)
     int64_t M = 0, K = 0;
@@ -66,6 +74,40 @@ int resolve_type(int type, int64_t M, int64_t K, int *t, int *ext) {
     return GGML_HIP_OK;
 }
 
+// ---- the grouped route ----
+// its work buffer, each piece on a 256-byte boundary behind a base rounded up to one: the routing tables (count, first [n_expert]; n_tiles; pos [P];
+// order [rows]; tiles [max_tiles]), the gathered src1 rows and the sorted results ([rows] each), the activation image of `rows` rows.
+// rows = 32 * max_tiles, the bound of plan.h -- it grows with min(n_expert, P).
+struct grouped_work { size_t count, first, n_tiles, pos, order, tiles, gathered, results, image, image_bytes, total; int64_t max_tiles, rows; };
+grouped_work grouped_work_of(int64_t M, int64_t K, int n_expert, int64_t P) {
+    grouped_work o;
+    o.max_tiles = moe_grouped_tiles(n_expert, P); o.rows = 32 * o.max_tiles;
+    o.count = 0;
+    o.first = o.count + align_up((size_t)n_expert * 4);
+    o.n_tiles = o.first + align_up((size_t)n_expert * 4);
+    o.pos = o.n_tiles + MOE_ALIGN;
+    o.order = o.pos + align_up((size_t)P * 4);
+    o.tiles = o.order + align_up((size_t)o.rows * 4);
+    o.gathered = o.tiles + align_up((size_t)o.max_tiles * sizeof(moe_tile));
+    o.results = o.gathered + align_up((size_t)o.rows * (size_t)ld4(K) * 4);
+    o.image = o.results + align_up((size_t)o.rows * (size_t)ld4(M) * 4);
+    o.image_bytes = act_bytes(K, pad_act(o.rows));
+    o.total = o.image + align_up(o.image_bytes) + MOE_ALIGN;
+    return o;
+}
+
+int grouped_check_shape(int64_t n_tokens, int n_used) {
+    if (n_tokens < 0 || n_used < 1) return fail(GGML_HIP_ERR_ARG, "n_tokens %lld, n_used %d", (long long)n_tokens, n_used);
+    if (n_tokens > MOE_GROUPED_MAX_PAIRS / n_used) return fail(GGML_HIP_ERR_SHAPE, "more than 2^20 (token, slot) pairs");
+    return GGML_HIP_OK;
+}
+
+size_t grouped_work_size(int type, int ext_type, int64_t M, int64_t K, int n_expert, int64_t n_tokens, int n_used) {
+    if (n_tokens <= 0 || n_used < 1 || n_tokens > MOE_GROUPED_MAX_PAIRS / n_used || n_expert < 1 || n_expert > 1024) return 0;
+    if (plan_mul_mat_id_grouped(type, ext_type, M, K, n_expert, n_tokens * n_used).family == MMF_NONE) return 0;
+    return grouped_work_of(M, K, n_expert, n_tokens * n_used).total;
+}
+
 }  // namespace
 
 extern "C" {
@@ -87,14 +129,28 @@ int ggml_hip_expert_set_create(const ggml_hip_weight *const *w, int n_expert, vo
     if (w[0]->M <= 0) return fail(GGML_HIP_ERR_SHAPE, "the experts have no rows");
     int rc = device_current(w[0]->device);
     if (rc) return rc;
-    std::vector<moe_expert> tab((size_t)n_expert);
+    // one table for each kernel that picks an expert on the device, in one allocation: [n_expert] moe_expert, then [n_expert] moe_gexpert
+    static_assert(sizeof(moe_expert) == 16 && sizeof(moe_gexpert) == 32, "the second table starts on a 32-byte boundary");
+    const size_t tab_bytes = (size_t)n_expert * sizeof(moe_expert), all_bytes = tab_bytes + (size_t)n_expert * sizeof(moe_gexpert);
+    std::vector<uint8_t> host(all_bytes);
+    moe_expert *tab = (moe_expert *)host.data();
+    moe_gexpert *gtab = (moe_gexpert *)(host.data() + tab_bytes);
     const bool i8x2 = w[0]->ext_type != 0 && w[0]->type == GGML_TYPE_Q4_2;      // (the two-scale k-quants: their mat-vec reads the int8 planes)
-    for (int e = 0; e < n_expert; ++e) { tab[(size_t)e].qs = i8x2 ? w[e]->i8p : w[e]->qs; tab[(size_t)e].gs = w[e]->gs; }
+    const int ty = w[0]->type;
+    bool planes = true;
+    for (int e = 0; e < n_expert; ++e) {
+        tab[e].qs = i8x2 ? w[e]->i8p : w[e]->qs; tab[e].gs = w[e]->gs;
+        gtab[e] = ty == GGML_TYPE_Q4_0 ? moe_gexpert{w[e]->q6a, w[e]->q6b, w[e]->d, nullptr}
+                                       : moe_gexpert{ty == GGML_TYPE_Q5_0 ? w[e]->i8p : w[e]->qs, nullptr, w[e]->d, nullptr};
+        planes = planes && gtab[e].a && gtab[e].d && (ty != GGML_TYPE_Q4_0 || gtab[e].b);
+    }
     ggml_hip_expert_set *s = new ggml_hip_expert_set();
     s->w.assign(w, w + n_expert);
     s->device = w[0]->device; s->type = w[0]->type; s->ext_type = w[0]->ext_type; s->M = w[0]->M; s->K = w[0]->K;
-    hipError_t e = hipMalloc((void **)&s->d_tab, tab.size() * sizeof(moe_expert));
-    if (e == hipSuccess) e = hipMemcpyAsync(s->d_tab, tab.data(), tab.size() * sizeof(moe_expert), hipMemcpyHostToDevice, (hipStream_t)stream);
+    s->grouped_planes = planes;
+    hipError_t e = hipMalloc((void **)&s->d_tab, all_bytes);
+    if (e == hipSuccess) s->d_gtab = (moe_gexpert *)((uint8_t *)s->d_tab + tab_bytes);
+    if (e == hipSuccess) e = hipMemcpyAsync(s->d_tab, host.data(), all_bytes, hipMemcpyHostToDevice, (hipStream_t)stream);
     if (e == hipSuccess) e = hipStreamSynchronize((hipStream_t)stream);       // (the host table goes away with this call)
     if (e != hipSuccess) {
         (void)hipGetLastError();
@@ -232,6 +288,71 @@ int ggml_hip_mul_mat_id_dev(const ggml_hip_expert_set *s, const int32_t *d_ids, 
         memcpy(map.v, pos.data() + p0, (size_t)n * 4);
         HIP_TRY(launch_moe_scatter(map, n, p0, r, ldr, M, d_dst, ldd, st));
     }
+    return GGML_HIP_OK;
+}
+
+int ggml_hip_mul_mat_id_grouped_serves_for(int type, int64_t M, int64_t K) {
+    const bool kq = is_kquant(type);
+    const int t = kq ? kquant_resident_type(type) : is_iq4nl(type) ? GGML_TYPE_Q8_0 : type;   // (IQ4_NL: a plain Q8_0 weight; a k-quant: never served)
+    if (M <= 0 || K <= 0 || K % QK != 0 || (kq && K % 256 != 0)) return 0;
+    return plan_mul_mat_id_grouped_serves(t, kq ? type : 0, M, K) ? 1 : 0;
+}
+
+int ggml_hip_mul_mat_id_grouped_serves(const ggml_hip_expert_set *s) {
+    if (!s) return fail(GGML_HIP_ERR_ARG, "null expert set");
+    return plan_mul_mat_id_grouped_serves(s->type, s->ext_type, s->M, s->K) ? 1 : 0;
+}
+
+size_t ggml_hip_mul_mat_id_grouped_work_size_for(int type, int64_t M, int64_t K, int n_expert, int64_t n_tokens, int n_used) {
+    const bool kq = is_kquant(type);
+    if (M <= 0 || K <= 0 || K % QK != 0 || (kq && K % 256 != 0)) return 0;
+    return grouped_work_size(kq ? kquant_resident_type(type) : is_iq4nl(type) ? GGML_TYPE_Q8_0 : type, kq ? type : 0, M, K, n_expert, n_tokens, n_used);
+}
+
+size_t ggml_hip_mul_mat_id_grouped_work_size(const ggml_hip_expert_set *s, int64_t n_tokens, int n_used) {
+    if (!s) return 0;
+    return grouped_work_size(s->type, s->ext_type, s->M, s->K, (int)s->w.size(), n_tokens, n_used);
+}
+
+int ggml_hip_mul_mat_id_grouped_dev(const ggml_hip_expert_set *s, const int32_t *d_ids, int64_t n_tokens, int n_used, const float *d_src1, int64_t ld1_token,
+                                    int64_t ld1_slot, float *d_dst, int64_t ldd, void *d_work, size_t work_bytes, void *stream) {
+    if (!s) return fail(GGML_HIP_ERR_ARG, "null expert set");
+    int rc = grouped_check_shape(n_tokens, n_used);
+    if (rc) return rc;
+    if (n_tokens == 0) return GGML_HIP_OK;
+    const int64_t M = s->M, K = s->K, P = n_tokens * n_used;
+    const int n_expert = (int)s->w.size();
+    if (s->ext_type != 0 || !(s->type == GGML_TYPE_Q8_0 || s->type == GGML_TYPE_Q5_0 || s->type == GGML_TYPE_Q4_0))
+        return fail(GGML_HIP_ERR_TYPE, "the grouped route serves Q8_0, Q5_0, IQ4_NL and Q4_0 sets (ggml_hip_mul_mat_id_grouped_serves); this set's type is %d",
+                    ggml_hip_weight_type(s->w[0]));
+    const mm_plan g = plan_mul_mat_id_grouped(s->type, s->ext_type, M, K, n_expert, P);
+    if (g.family == MMF_NONE)
+        return fail(GGML_HIP_ERR_SHAPE, "the grouped route does not serve %lld x %lld with %lld pairs (K / 32 in 32 .. 1024 where the plan at 32 rows is K3s)",
+                    (long long)M, (long long)K, (long long)P);
+    if (!d_ids || !d_src1 || !d_dst) return fail(GGML_HIP_ERR_ARG, "null argument (the ids are read on the device: d_ids)");
+    if (ldd < M || ld1_token < 0 || ld1_slot < 0 || (n_tokens > 1 && ld1_token < K) || (ld1_slot != 0 && ld1_slot < K))
+        return fail(GGML_HIP_ERR_SHAPE, "ldd < M, or a src1 stride below K (ld1_slot may be 0: one row per token)");
+    if (((uintptr_t)d_src1 & 15) != 0 || ld1_token % 4 != 0 || ld1_slot % 4 != 0)
+        return fail(GGML_HIP_ERR_SHAPE, "src1 must be 16-byte aligned with strides that are multiples of 4 elements");
+    const grouped_work wk = grouped_work_of(M, K, n_expert, P);
+    if (!d_work || work_bytes < wk.total) return fail(GGML_HIP_ERR_ARG, "work buffer too small: need %zu (ggml_hip_mul_mat_id_grouped_work_size)", wk.total);
+    if (!s->grouped_planes) return fail(GGML_HIP_ERR_RUNTIME, "an expert of the set has no operand planes for the grouped kernel");
+    rc = device_current(s->device);
+    if (rc) return rc;
+    hipStream_t st = (hipStream_t)stream;
+    uint8_t *base = (uint8_t *)(((uintptr_t)d_work + MOE_ALIGN - 1) / MOE_ALIGN * MOE_ALIGN);
+    const moe_route rt = {(int32_t *)(base + wk.count), (int32_t *)(base + wk.first), (int32_t *)(base + wk.n_tiles), (int32_t *)(base + wk.pos),
+                          (int32_t *)(base + wk.order), (moe_tile *)(base + wk.tiles)};
+    float *gth = (float *)(base + wk.gathered), *res = (float *)(base + wk.results);
+    const int64_t ldg = ld4(K), ldr = ld4(M);
+    const act_planes pl = act_carve(base + wk.image, K, pad_act(wk.rows));
+    HIP_TRY(launch_moe_route(d_ids, P, n_expert, rt, wk.max_tiles, st));
+    HIP_TRY(launch_moe_gather_dev(rt.order, wk.rows, n_used, d_src1, ld1_token, ld1_slot, K, gth, ldg, st));
+    HIP_TRY(launch_quantize_act(gth, wk.rows, K, ldg, pl, g.image, st, false));     // (the image ggml_hip_mul_mat_init_dev writes for N = rows)
+    const ggml_hip_weight *w0 = s->w[0];
+    if (g.family == MMF_K3S_MX) HIP_TRY(launch_gemm_qmx_small_grouped(g, s->type, s->d_gtab, rt.tiles, rt.n_tiles, wk.max_tiles, M, w0->Mpad, w0->nbk, pl, res, ldr, st));
+    else HIP_TRY(launch_gemm_q8_small_grouped(g, s->type, s->d_gtab, rt.tiles, rt.n_tiles, wk.max_tiles, M, w0->Mpad, w0->nbk, pl, res, ldr, st));
+    HIP_TRY(launch_moe_scatter_dev(rt.pos, P, res, ldr, M, d_dst, ldd, st));
     return GGML_HIP_OK;
 }
 

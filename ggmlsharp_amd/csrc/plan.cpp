@@ -584,3 +584,32 @@ mm_plan plan_mul_mat_group(int type, int ext_type, const int64_t *M, const int64
     }
     return g;
 }
+
+// The grouped, device-routed product (plan.h has the bounds).  One decision: the family and tree of the single product at 32 src1 rows, on
+// 32-row weight tiles -- two or four of them per workgroup once the BOUND of tile groups passes 256 / 512, the single forms' rule (every
+// workgroup pulls its 32 activation columns through its CU's memory path once per launch, whatever the number of weight tiles behind them).
+bool plan_mul_mat_id_grouped_serves(int type, int ext_type, int64_t M, int64_t K) {
+    if (ext_type != 0 || !(type == GGML_TYPE_Q8_0 || type == GGML_TYPE_Q5_0 || type == GGML_TYPE_Q4_0) || M <= 0 || K <= 0 || K % QK != 0) return false;
+    const int f = plan_mul_mat(type, 0, M, K, 32, true).family;
+    return f == MMF_K3S_I8 || f == MMF_K3S_MX;
+}
+
+mm_plan plan_mul_mat_id_grouped(int type, int ext_type, int64_t M, int64_t K, int n_expert, int64_t P) {
+    const mm_plan none = {};
+    if (P < 1 || P > MOE_GROUPED_MAX_PAIRS || n_expert < 1 || !plan_mul_mat_id_grouped_serves(type, ext_type, M, K)) return none;
+    const mm_plan one = plan_mul_mat(type, 0, M, K, 32, true);
+    const bool mx = one.family == MMF_K3S_MX;
+    const int64_t tiles = moe_grouped_tiles(n_expert, P);
+    const uint64_t nbkp = (uint64_t)pad_kblocks(K / QK), Npad = (uint64_t)pad_act(32 * tiles);
+    if (mx ? nbkp * 48 * Npad > LIM32 : nbkp * 2 * Npad * 16 > LIM32) return none;
+    const int64_t t32 = cdiv(M, 32) * tiles;
+    const int wmt = t32 <= 256 ? 1 : t32 <= 512 ? 2 : 4;
+    mm_plan g = none;
+    g.family = one.family; g.image = one.image; g.form = 8;
+    g.arith = one.arith; g.ksplit = one.ksplit; g.kstyle = one.kstyle; g.kunit = one.kunit; g.flags = one.flags & MM_FLAG_NEEDS_WORK;   // (the tree of the single product)
+    g.nloc = one.nloc; g.wmt = wmt;
+    g.tile_m = 32 * wmt; g.tile_n = 32; g.waves = KS8; g.tiles_per_wave = wmt;
+    g.wgs = cdiv(M, 32 * wmt) * tiles;
+    if (g.wgs > 0x7FFFFFFF || plan_k3s_slots(g, type).lds > 160 * 1024) return none;
+    return g;
+}

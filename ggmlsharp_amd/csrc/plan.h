@@ -98,6 +98,18 @@ mm_plan plan_mul_mat_group(int type, int ext_type, const int64_t *M, const int64
 // through a longer range, the rows of a wave's scale table, and the dynamic LDS bytes (the table or the waves' result exchange)
 struct k3s_slots { int slots; bool rot; int rows; int lds; };
 k3s_slots plan_k3s_slots(const mm_plan &p, int type);
+// The grouped, device-routed product of ggml_hip_mul_mat_id_grouped_dev (moe.cpp): P = n_tokens * n_used pairs sorted by expert ON THE DEVICE,
+// every expert's segment padded to whole 32-row column tiles, ONE K3s launch over all of them.  The counts are unknown on the host, so
+// everything is sized by bounds: at most min(n_expert, P) segments are non-empty and each pads by at most 31 rows --
+//     sorted rows <= P + 31 * min(n_expert, P), and their sum is whole tiles: tiles <= floor((P + 31 * min(n_expert, P)) / 32).
+// The TREE is that of plan_mul_mat(type, M, K, N = 32) -- the K3s tree, a function of (type, K) alone; the geometry (32-row weight tiles,
+// wmt of them per workgroup by the tile bound) is this plan's own.  Served: Q8_0 / Q5_0 / Q4_0 (ext_type 0) where that plan is K3s.
+constexpr int64_t MOE_GROUPED_MAX_PAIRS = 1 << 20;
+inline int64_t moe_grouped_tiles(int n_expert, int64_t P) { return (P + 31 * (P < n_expert ? P : (int64_t)n_expert)) / 32; }
+bool plan_mul_mat_id_grouped_serves(int type, int ext_type, int64_t M, int64_t K);
+// family MMF_K3S_I8 / MMF_K3S_MX with nloc, wmt, tile_m = 32 * wmt, tile_n = 32 and wgs = the grid bound (tile bound x weight tile groups),
+// or MMF_NONE: not served, P outside 1 .. 2^20, or an activation image of the bounded rows beyond the kernels' 32-bit offsets
+mm_plan plan_mul_mat_id_grouped(int type, int ext_type, int64_t M, int64_t K, int n_expert, int64_t P);
 // the K1 image for (type, K, N) with no weight at hand (no M: the exception cannot apply)
 int plan_image_kind(int type, int64_t K, int64_t N);
 // thread-local test switch (ggml_hip_debug_force_gemm): 0 auto, 1 int8, 2 f16, 3 MX

@@ -127,6 +127,12 @@ class ExpertSet:
     def work_size(self, n_tokens, n_used):
         return int(lib().ggml_hip_mul_mat_id_work_size(self.handle, n_tokens, n_used))
 
+    def grouped_serves(self):
+        return int(lib().ggml_hip_mul_mat_id_grouped_serves(self.handle))
+
+    def grouped_work_size(self, n_tokens, n_used):
+        return int(lib().ggml_hip_mul_mat_id_grouped_work_size(self.handle, n_tokens, n_used))
+
     def free(self):
         if self.handle:
             lib().ggml_hip_expert_set_free(self.handle)
@@ -159,6 +165,23 @@ def mul_mat_id(es, ids, x, h_ids=None, out=None, work=None):
     check(lib().ggml_hip_mul_mat_id_dev(es.handle, C.c_void_p(ids.data_ptr()), hp, n_tokens, n_used, C.c_void_p(x.data_ptr()), x.stride(0), ld1_slot,
                                         C.c_void_p(out.data_ptr()), out.stride(1), C.c_void_p(work.data_ptr()), work.numel(), _stream()),
           "ggml_hip_mul_mat_id_dev")
+    return out
+
+
+def mul_mat_id_grouped(es, ids, x, out=None, work=None):
+    """mul_mat_id's result through the grouped route: the ids are read on the device alone, the launches do not depend on them (capturable;
+    a replay follows the ids it finds).  Arguments as mul_mat_id's, without h_ids; the set must be served (es.grouped_serves())."""
+    assert ids.is_cuda and ids.dtype == torch.int32 and ids.dim() == 2 and ids.is_contiguous()
+    assert x.is_cuda and x.dtype == torch.float32 and x.stride(-1) == 1 and x.shape[0] == ids.shape[0]
+    n_tokens, n_used = ids.shape
+    ld1_slot = 0 if x.dim() == 2 else x.stride(1)
+    if out is None:
+        out = torch.empty((n_tokens, n_used, es.M), dtype=torch.float32, device=x.device)
+    if work is None:
+        work = torch.empty(max(es.grouped_work_size(n_tokens, n_used), 16), dtype=torch.uint8, device=x.device)
+    check(lib().ggml_hip_mul_mat_id_grouped_dev(es.handle, C.c_void_p(ids.data_ptr()), n_tokens, n_used, C.c_void_p(x.data_ptr()), x.stride(0), ld1_slot,
+                                                C.c_void_p(out.data_ptr()), out.stride(1), C.c_void_p(work.data_ptr()), work.numel(), _stream()),
+          "ggml_hip_mul_mat_id_grouped_dev")
     return out
 
 

@@ -409,6 +409,42 @@ int    ggml_hip_mul_mat_id_dev(const ggml_hip_expert_set *s, const int32_t *d_id
                                int64_t n_tokens, int n_used, const float *d_src1, int64_t ld1_token, int64_t ld1_slot,
                                float *d_dst, int64_t ldd, void *d_work, size_t work_bytes, void *stream);
 
+/* ---------------- the GROUPED route: a device-routed grouped product for mul_mat_id batches ----------------
+ * An entry of its own beside the two routes above (ggml_hip_mul_mat_id_route{,_for} and ggml_hip_mul_mat_id_dev answer exactly as before:
+ * 1 or 2).  For batches whose ids come out of a top-k kernel ON THE DEVICE -- a prompt-sized mixture-of-experts layer inside a decoder's
+ * graph: the ids are read only on the device (no h_ids, no host synchronize, no allocation), the number of launches is fixed for a shape
+ * (seven: three of routing, a gather, one INIT, ONE product, a scatter -- never a function of the routing or of n_expert), the call is
+ * legal on a capturing stream and a captured call replayed with other contents in d_ids computes the new routing.
+ * The same conventions as ggml_hip_mul_mat_id_dev: pair p = t * n_used + s, ld1_slot = 0 as the broadcast, d_src1 16-byte aligned with
+ * strides that are multiples of 4 (GGML_HIP_ERR_SHAPE), ldd >= M, the error codes; n_tokens = 0 returns 0 and writes nothing.
+ * An id outside [0, n_expert) writes that pair's M outputs as +0.0f; no address is formed from it.
+ * P = n_tokens * n_used up to 2^20; more is GGML_HIP_ERR_SHAPE.
+ *
+ * SERVED (ggml_hip_mul_mat_id_grouped_serves = 1; _serves_for answers for (type, M, K) with no weight and no device, 1 / 0 only):
+ *   - the type is Q8_0, Q5_0, IQ4_NL (a Q8_0 weight to every kernel) or Q4_0, AND
+ *   - the plan of mul_mat(type, M, K, N = 32) is GGML_HIP_MMF_K3S_I8 or GGML_HIP_MMF_K3S_MX: today K / 32 in 32 .. 1024.
+ * Every other type answers 0 and the entry returns GGML_HIP_ERR_TYPE; every shape outside that range answers 0 and the entry returns
+ * GGML_HIP_ERR_SHAPE.  OUT OF SCOPE: the min-term types (Q4_1, Q5_1, Q5_K, Q4_K), the two-scale types (Q4_2, and Q6_K / Q3_K / Q2_K /
+ * IQ4_XS in their resident forms), the dense types (F32, F16, BF16) -- they keep the batch route.
+ *
+ * ARITHMETIC.  The counts are not known on the host, so the summation tree cannot follow count_e as the batch route's does: it is fixed
+ * by (type, K) alone, the tree of ggml_hip_mm_plan(type, M, K, 32) -- eight contiguous k-block ranges, a range's blocks in ascending
+ * order with the type's f32 statement per block, the eight partial sums added in wave order.  Pair p's M outputs are BIT FOR BIT the row
+ * that ggml_hip_mul_mat_dev(expert ids[p], a batch of 32 rows that holds p's src1 row at any position, N = 32) returns for that row.
+ * A set of row shards [r0, r1) computes columns [r0, r1) of the whole set's result, bit for bit.
+ *
+ * d_work / work_bytes: ggml_hip_mul_mat_id_grouped_work_size bytes; missing or short is GGML_HIP_ERR_ARG.  The size is a function of
+ * (type, M, K, n_expert, P) -- it DEPENDS ON n_expert, unlike the batch route's: the sorted rows are padded per expert to whole column
+ * tiles of 32, so everything is sized by the bound P + 31 * min(n_expert, P) rows.  It is the same for every (n_tokens, n_used) with one
+ * P, 0 for n_tokens = 0 and for a set the route does not serve; the _for twin and the set's entry are the same function. */
+int    ggml_hip_mul_mat_id_grouped_serves(const ggml_hip_expert_set *s);                 /* 1 / 0, < 0 error */
+int    ggml_hip_mul_mat_id_grouped_serves_for(int type, int64_t M, int64_t K);           /* no device needed */
+size_t ggml_hip_mul_mat_id_grouped_work_size(const ggml_hip_expert_set *s, int64_t n_tokens, int n_used);
+size_t ggml_hip_mul_mat_id_grouped_work_size_for(int type, int64_t M, int64_t K, int n_expert, int64_t n_tokens, int n_used);
+int    ggml_hip_mul_mat_id_grouped_dev(const ggml_hip_expert_set *s, const int32_t *d_ids, int64_t n_tokens, int n_used,
+                                       const float *d_src1, int64_t ld1_token, int64_t ld1_slot,
+                                       float *d_dst, int64_t ldd, void *d_work, size_t work_bytes, void *stream);
+
 #if defined(__GNUC__)
 #pragma GCC visibility pop
 #endif

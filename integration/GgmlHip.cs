@@ -67,6 +67,13 @@ internal static unsafe partial class GgmlHip
     [DllImport(Lib)] public static extern nuint ggml_hip_mul_mat_id_work_size_for(int type, long m, long k, int nExpert, long nTokens, int nUsed);
     [DllImport(Lib)] public static extern int ggml_hip_mul_mat_id_dev(void* set, int* dIds, int* hIds, long nTokens, int nUsed, float* dSrc1, long ld1Token, long ld1Slot,
         float* dDst, long ldd, void* dWork, nuint workBytes, void* stream);
+    // ... the grouped route: the ids are read on the device alone (no hIds), a fixed number of launches, capturable; Q8_0 / Q5_0 / IQ4_NL / Q4_0 where it serves
+    [DllImport(Lib)] public static extern int ggml_hip_mul_mat_id_grouped_serves(void* set);                             // 1 / 0, < 0 error
+    [DllImport(Lib)] public static extern int ggml_hip_mul_mat_id_grouped_serves_for(int type, long m, long k);          // no weight, no device needed
+    [DllImport(Lib)] public static extern nuint ggml_hip_mul_mat_id_grouped_work_size(void* set, long nTokens, int nUsed);
+    [DllImport(Lib)] public static extern nuint ggml_hip_mul_mat_id_grouped_work_size_for(int type, long m, long k, int nExpert, long nTokens, int nUsed);
+    [DllImport(Lib)] public static extern int ggml_hip_mul_mat_id_grouped_dev(void* set, int* dIds, long nTokens, int nUsed, float* dSrc1, long ld1Token, long ld1Slot,
+        float* dDst, long ldd, void* dWork, nuint workBytes, void* stream);
 
     // Seam 2: the quantize_fns_t slots (TypeDefinitions.cs:334-342), type-indexed
     [DllImport(Lib)] public static extern int ggml_hip_quantize_row(int type, float* x, void* y, int k);
