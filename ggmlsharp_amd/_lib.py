@@ -201,6 +201,10 @@ HIP_SYMBOLS = {
     "ggml_hip_mul_mat_id_grouped_work_size": (C.c_size_t, [_P, C.c_int64, C.c_int]),
     "ggml_hip_mul_mat_id_grouped_work_size_for": (C.c_size_t, [C.c_int, C.c_int64, C.c_int64, C.c_int, C.c_int64, C.c_int]),
     "ggml_hip_mul_mat_id_grouped_dev": (C.c_int, [_P, _P, C.c_int64, C.c_int, _P, C.c_int64, C.c_int64, _P, C.c_int64, _P, C.c_size_t, _P]),
+    # ... and the ends of the block: router logits -> ids and gate weights, the weighted sum of the pair rows, the SwiGLU pair on device rows
+    "ggml_hip_moe_route_dev": (C.c_int, [_P, C.c_int64, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, _P, _P, _P]),
+    "ggml_hip_moe_combine_dev": (C.c_int, [_P, C.c_int64, _P, C.c_int64, C.c_int, C.c_int64, _P, C.c_int64, _P, C.c_int64, _P]),
+    "ggml_hip_silu_mul_rows_dev": (C.c_int, [_P, _P, _P, _P, C.c_int64, C.c_int64, _P]),
 }
 SYMBOLS = HIP_SYMBOLS
 

@@ -390,7 +390,7 @@ hipError_t launch_rms_norm_f32(const float *x, float *y, int64_t nr, int64_t nc,
 hipError_t launch_silu_f32(const float *x, float *y, int64_t n, hipStream_t st);
 // fused.hip: two nodes, one launch (both outputs written)
 hipError_t launch_rms_norm_mul_f32(const float *x, const float *g, float *n_out, float *y_out, int64_t nr, int64_t nc, hipStream_t st);
-hipError_t launch_silu_mul_f32(const float *a, const float *b, float *s_out, float *y_out, int64_t n, hipStream_t st);
+hipError_t launch_silu_mul_f32(const float *a, const float *b, float *s_out, float *y_out, int64_t n, hipStream_t st);   // (s_out may be null: only y_out is written)
 // gemv.hip / gemm_q.hip / dense.hip
 hipError_t launch_gemv_q(const ggml_hip_weight *w, act_planes p, int64_t N, float *dst, int64_t ldd, hipStream_t st);
 // Up to four weight matrices of one type and K behind ONE activation matrix (the q / k / v or the gate / up projections of a
@@ -441,6 +441,13 @@ hipError_t launch_moe_gather_dev(const int32_t *order, int64_t rows, int n_used,
                                  int64_t ldg, hipStream_t st);
 // pair p < P <- sorted row pos[p] of r, +0.0f where pos[p] < 0
 hipError_t launch_moe_scatter_dev(const int32_t *pos, int64_t P, const float *r, int64_t ldr, int64_t M, float *dst, int64_t ldd, hipStream_t st);
+// moe_route.hip: the router and the combine of a mixture-of-experts block (ggml_hip_moe_route_dev / ggml_hip_moe_combine_dev, moe.cpp)
+// logits [n_tokens] rows of n_expert (ld apart) -> ids / weights [n_tokens * n_used]: one wave per token, exact selection, no LDS
+hipError_t launch_moe_topk(const float *logits, int64_t ld, int64_t n_tokens, int n_expert, int n_used, int gating, int normalize, float scale,
+                           int32_t *ids, float *weights, hipStream_t st);
+// dst[t] = sum over s (ascending) of w[t * n_used + s] * y[(t * n_used + s) * ldy ..] [+ addend[t]]: 16-byte accesses where every pointer and stride allows
+hipError_t launch_moe_combine(const float *y, int64_t ldy, const float *w, int64_t n_tokens, int n_used, int64_t M, const float *addend, int64_t ld_add,
+                              float *dst, int64_t ldd, hipStream_t st);
 // gemm_q8s.hip / gemm_qmx.hip: ONE K3s launch over the tile table -- workgroup -> (weight tile group, column tile t); t >= *n_tiles leaves at once;
 // the expert's planes come from tab[tiles[t].expert], the 32 sorted rows at 32 t of the image p (K1's image of `32 * max_tiles` rows); res [rows][ldr]
 hipError_t launch_gemm_q8_small_grouped(const mm_plan &g, int type, const moe_gexpert *tab, const moe_tile *tiles, const int32_t *n_tiles, int64_t max_tiles,

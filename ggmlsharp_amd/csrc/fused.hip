@@ -38,7 +38,7 @@ __global__ __launch_bounds__(256) void silu_mul_kernel(const float *__restrict__
     const float f = (float)(_Float16)a[i];
     const float e = (float)exp(-(double)f);
     const float s = (float)(_Float16)(f / (1.0f + e));
-    s_out[i] = s;
+    if (s_out) s_out[i] = s;                                       // (null: a device caller without a silu node)
     y_out[i] = s * b[i];
 }
 

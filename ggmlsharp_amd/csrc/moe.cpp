@@ -356,4 +356,42 @@ int ggml_hip_mul_mat_id_grouped_dev(const ggml_hip_expert_set *s, const int32_t 
     return GGML_HIP_OK;
 }
 
+// ---- the router and the combine around the products (moe_route.hip), and the SwiGLU pair between them on device rows ----
+// no set, no work buffer, nothing but launches on `stream`: they run on the current device like ggml_hip_rms_norm_mul_rows_dev
+
+int ggml_hip_moe_route_dev(const float *d_logits, int64_t ld_logits, int64_t n_tokens, int n_expert, int n_used, int gating, int normalize, float scale,
+                           int32_t *d_ids, float *d_weights, void *stream) {
+    if (n_tokens < 0) return fail(GGML_HIP_ERR_ARG, "n_tokens %lld", (long long)n_tokens);
+    if (n_expert < 1 || n_expert > 1024) return fail(GGML_HIP_ERR_SHAPE, "n_expert %d (1 .. 1024)", n_expert);
+    if (n_used < 1 || n_used > 64 || n_used > n_expert) return fail(GGML_HIP_ERR_SHAPE, "n_used %d (1 .. min(n_expert, 64))", n_used);
+    if (n_tokens > MOE_GROUPED_MAX_PAIRS / n_used) return fail(GGML_HIP_ERR_SHAPE, "more than 2^20 (token, slot) pairs");
+    if (gating != 0 && gating != 1) return fail(GGML_HIP_ERR_ARG, "gating %d (0 softmax, 1 sigmoid)", gating);
+    if (ld_logits < n_expert) return fail(GGML_HIP_ERR_ARG, "ld_logits %lld < n_expert %d", (long long)ld_logits, n_expert);
+    if (n_tokens == 0) return GGML_HIP_OK;
+    if (!d_logits || !d_ids || !d_weights) return fail(GGML_HIP_ERR_ARG, "null argument");
+    HIP_TRY(launch_moe_topk(d_logits, ld_logits, n_tokens, n_expert, n_used, gating, normalize, scale, d_ids, d_weights, (hipStream_t)stream));
+    return GGML_HIP_OK;
+}
+
+int ggml_hip_moe_combine_dev(const float *d_y, int64_t ldy, const float *d_weights, int64_t n_tokens, int n_used, int64_t M, const float *d_addend,
+                             int64_t ld_add, float *d_dst, int64_t ldd, void *stream) {
+    if (n_tokens < 0) return fail(GGML_HIP_ERR_ARG, "n_tokens %lld", (long long)n_tokens);
+    if (n_used < 1 || n_used > 64) return fail(GGML_HIP_ERR_SHAPE, "n_used %d (1 .. 64)", n_used);
+    if (n_tokens > MOE_GROUPED_MAX_PAIRS / n_used) return fail(GGML_HIP_ERR_SHAPE, "more than 2^20 (token, slot) pairs");
+    if (M < 1 || ldy < M || ldd < M || (d_addend && ld_add < M)) return fail(GGML_HIP_ERR_SHAPE, "M < 1, or a row stride below M");
+    if (n_tokens == 0) return GGML_HIP_OK;
+    if (!d_y || !d_weights || !d_dst) return fail(GGML_HIP_ERR_ARG, "null argument");
+    if (M > ((int64_t)1 << 31)) return fail(GGML_HIP_ERR_SHAPE, "M %lld", (long long)M);
+    HIP_TRY(launch_moe_combine(d_y, ldy, d_weights, n_tokens, n_used, M, d_addend, ld_add, d_dst, ldd, (hipStream_t)stream));
+    return GGML_HIP_OK;
+}
+
+int ggml_hip_silu_mul_rows_dev(const float *d_a, const float *d_b, float *d_silu, float *d_y, int64_t nrows, int64_t k, void *stream) {
+    if (nrows <= 0 || k <= 0) return GGML_HIP_OK;
+    if (!d_a || !d_b || !d_y) return fail(GGML_HIP_ERR_ARG, "null argument (d_silu alone may be null)");
+    if (nrows > ((int64_t)1 << 39) / k) return fail(GGML_HIP_ERR_SHAPE, "more than 2^39 elements");
+    HIP_TRY(launch_silu_mul_f32(d_a, d_b, d_silu, d_y, nrows * k, (hipStream_t)stream));
+    return GGML_HIP_OK;
+}
+
 }  // extern "C"

@@ -185,6 +185,52 @@ def mul_mat_id_grouped(es, ids, x, out=None, work=None):
     return out
 
 
+def moe_route(logits, n_used, gating=0, normalize=True, scale=1.0, ids=None, weights=None):
+    """router logits f32 [n_tokens, n_expert] on the device (row stride may exceed n_expert) -> (ids int32, weights f32), both
+    [n_tokens, n_used]: the n_used largest logits of a token in rank order (ties: the smaller index) and their gate weights
+    (gating 0 softmax over all experts, 1 sigmoid; normalize: over the selected ones; then * scale).  On the current stream."""
+    assert logits.is_cuda and logits.dtype == torch.float32 and logits.dim() == 2 and logits.stride(1) == 1
+    n_tokens, n_expert = logits.shape
+    if ids is None:
+        ids = torch.empty((n_tokens, n_used), dtype=torch.int32, device=logits.device)
+    if weights is None:
+        weights = torch.empty((n_tokens, n_used), dtype=torch.float32, device=logits.device)
+    assert ids.is_contiguous() and weights.is_contiguous() and ids.dtype == torch.int32 and weights.dtype == torch.float32
+    check(lib().ggml_hip_moe_route_dev(C.c_void_p(logits.data_ptr()), logits.stride(0), n_tokens, n_expert, n_used, int(gating), int(bool(normalize)),
+                                       float(scale), C.c_void_p(ids.data_ptr()), C.c_void_p(weights.data_ptr()), _stream()), "ggml_hip_moe_route_dev")
+    return ids, weights
+
+
+def moe_combine(y, weights, addend=None, out=None):
+    """out[t] = sum over the slots s (ascending) of weights[t, s] * y[t, s] (+ addend[t]): y f32 [n_tokens, n_used, M] as the mul_mat_id
+    entries write it, weights f32 [n_tokens, n_used]; out may be addend itself.  On the current stream."""
+    assert y.is_cuda and y.dtype == torch.float32 and y.dim() == 3 and y.stride(2) == 1 and y.stride(0) == y.shape[1] * y.stride(1)
+    assert weights.is_cuda and weights.dtype == torch.float32 and weights.is_contiguous() and tuple(weights.shape) == tuple(y.shape[:2])
+    n_tokens, n_used, M = y.shape
+    if out is None:
+        out = torch.empty((n_tokens, M), dtype=torch.float32, device=y.device)
+    assert out.dtype == torch.float32 and out.dim() == 2 and out.stride(1) == 1
+    ap, ld_add = None, 0
+    if addend is not None:
+        assert addend.is_cuda and addend.dtype == torch.float32 and addend.dim() == 2 and addend.stride(1) == 1
+        ap, ld_add = C.c_void_p(addend.data_ptr()), addend.stride(0)
+    check(lib().ggml_hip_moe_combine_dev(C.c_void_p(y.data_ptr()), y.stride(1), C.c_void_p(weights.data_ptr()), n_tokens, n_used, M, ap, ld_add,
+                                         C.c_void_p(out.data_ptr()), out.stride(0), _stream()), "ggml_hip_moe_combine_dev")
+    return out
+
+
+def silu_mul_rows(a, b, silu=None, out=None):
+    """out = silu(a) * b on contiguous f32 rows (the SwiGLU pair, the reference's GGML_SILU_FP16 form); silu, when given, receives silu(a)."""
+    assert a.is_cuda and b.is_cuda and a.dtype == b.dtype == torch.float32 and a.is_contiguous() and b.is_contiguous() and a.shape == b.shape
+    if out is None:
+        out = torch.empty_like(a)
+    assert out.is_contiguous() and (silu is None or silu.is_contiguous())
+    k = a.shape[-1] if a.dim() else 1
+    check(lib().ggml_hip_silu_mul_rows_dev(C.c_void_p(a.data_ptr()), C.c_void_p(b.data_ptr()), C.c_void_p(silu.data_ptr()) if silu is not None else None,
+                                           C.c_void_p(out.data_ptr()), a.numel() // max(k, 1), k, _stream()), "ggml_hip_silu_mul_rows_dev")
+    return out
+
+
 def quantize_rows(type, x):
     """x f32 [nrows, k] on the device -> uint8 [nrows, k/32*type_size] reference-format blocks."""
     assert x.is_cuda and x.dtype == torch.float32 and x.is_contiguous()

@@ -445,6 +445,50 @@ int    ggml_hip_mul_mat_id_grouped_dev(const ggml_hip_expert_set *s, const int32
                                        const float *d_src1, int64_t ld1_token, int64_t ld1_slot,
                                        float *d_dst, int64_t ldd, void *d_work, size_t work_bytes, void *stream);
 
+/* ---------------- the ends of a mixture-of-experts block: the ROUTER in front of the products, the COMBINE behind them ----------------
+ * With ggml_hip_mul_mat_dev for the router matrix, the grouped route above and ggml_hip_silu_mul_rows_dev these make a whole MoE FFN block
+ * out of device entries: router product -> route -> gate / up (ld1_slot = 0) -> silu_mul_rows -> down (a row per slot) -> combine.  All three
+ * entries are stream-ordered on `stream` on the current device; they do not synchronize, do not allocate, take no work buffer and may be
+ * captured.  n_tokens = 0 (nrows = 0) returns 0 and writes nothing.  EXTENSIONS like the products: the reference has no such nodes.
+ *
+ * ggml_hip_moe_route_dev: upstream's soft_max -> top_k -> get_rows [-> sum_rows, div] [-> scale] chain for its two gate functions.
+ * d_logits: f32, [n_tokens] rows of n_expert, ld_logits >= n_expert elements apart (the dst of ggml_hip_mul_mat_dev for the router matrix: no
+ * alignment beyond 4 bytes).  d_ids[t * n_used + s], d_weights[t * n_used + s]: the pair order p = t * n_used + s the products read.
+ *   SELECTION is exact f32 comparison alone, so the ids are defined bit for bit:
+ *     - slot s of token t holds the expert of rank s under "larger logit first; equal logits: smaller index first";
+ *     - -0.0 and +0.0 compare equal;
+ *     - a NaN logit ranks below every non-NaN one, -inf included; NaNs rank among themselves by index;
+ *     - so a token's n_used ids are always distinct and inside [0, n_expert), whatever the logits hold;
+ *     - the selection is on the LOGITS.  Both gates are monotone, so this is upstream's order wherever upstream's is defined, and where
+ *       rounding makes two probabilities tie this rule still decides.
+ *   WEIGHTS, every operation one binary32 rounding, expf the correctly-specified library function (no fast-math form):
+ *     - gating 0, softmax over ALL experts: w = expf(l - lmax) / S, lmax the rank-0 logit, S the sum of expf(l_e - lmax) over all experts in
+ *       a fixed order that no scheduling changes (no atomics): expert e belongs to lane e % 64, a lane adds its experts in ascending e, the
+ *       64 partial sums meet in a butterfly (lane distance 32, 16, .., 1);
+ *     - gating 1, sigmoid: w = 1 / (1 + expf(-l)) of each selected expert;
+ *     - normalize != 0: w_s = w_s / (w_0 + w_1 + ...), the sum in slot order;
+ *     - then w_s = w_s * scale, always (1.0f is exact).
+ *     - a token whose logits hold a NaN, or whose rank-0 logit is +-inf, has UNSPECIFIED weight values; its ids still follow the rule.
+ *   1 <= n_expert <= 1024, 1 <= n_used <= min(n_expert, 64), n_tokens * n_used <= 2^20: else GGML_HIP_ERR_SHAPE.  A null pointer,
+ *   ld_logits < n_expert, n_tokens < 0 or gating outside {0, 1}: GGML_HIP_ERR_ARG. */
+int ggml_hip_moe_route_dev(const float *d_logits, int64_t ld_logits, int64_t n_tokens, int n_expert, int n_used,
+                           int gating, int normalize, float scale,
+                           int32_t *d_ids, float *d_weights, void *stream);
+/* ggml_hip_moe_combine_dev: the weighted sum over a token's slots -- upstream's ggml_mul then ggml_add of the slot views in ascending slot
+ * order.  d_y: the pair rows, [n_tokens * n_used] rows of M, ldy >= M elements apart (the dst of either mul_mat_id entry).  Every product and
+ * every sum is ONE binary32 rounding, no fused multiply-add:
+ *     acc = w[t,0] * y[t,0,m];  for s = 1 .. n_used-1: acc = acc + w[t,s] * y[t,s,m];  dst[t,m] = d_addend ? acc + addend[t,m] : acc
+ * d_addend (the residual, or a shared expert's output) may be NULL; d_dst may EQUAL d_addend (an element is read and then written by one
+ * thread); d_dst may not overlap d_y.  Any M >= 1: 16-byte accesses where every pointer is 16-byte aligned and every stride a multiple of
+ * 4, one element at a time otherwise -- the same bits.  ldy, ldd or ld_add below M: GGML_HIP_ERR_SHAPE; n_used in 1 .. 64 and
+ * n_tokens * n_used <= 2^20 as above; a null d_y, d_weights or d_dst: GGML_HIP_ERR_ARG. */
+int ggml_hip_moe_combine_dev(const float *d_y, int64_t ldy, const float *d_weights, int64_t n_tokens, int n_used, int64_t M,
+                             const float *d_addend, int64_t ld_add, float *d_dst, int64_t ldd, void *stream);
+/* The SwiGLU pair on contiguous device rows [nrows][k], the device twin of ggml_hip_rms_norm_mul_rows_dev: d_silu = silu(d_a) in the
+ * reference's GGML_SILU_FP16 form (Ggml.cs:5705-5748), d_y = d_silu * d_b -- the kernel and the bits of ggml_hip_compute_forward_silu_mul.
+ * d_silu may be NULL (a device caller has no node whose data must exist): only d_y is written. */
+int ggml_hip_silu_mul_rows_dev(const float *d_a, const float *d_b, float *d_silu, float *d_y, int64_t nrows, int64_t k, void *stream);
+
 #if defined(__GNUC__)
 #pragma GCC visibility pop
 #endif

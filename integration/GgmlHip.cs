@@ -74,6 +74,14 @@ internal static unsafe partial class GgmlHip
     [DllImport(Lib)] public static extern nuint ggml_hip_mul_mat_id_grouped_work_size_for(int type, long m, long k, int nExpert, long nTokens, int nUsed);
     [DllImport(Lib)] public static extern int ggml_hip_mul_mat_id_grouped_dev(void* set, int* dIds, long nTokens, int nUsed, float* dSrc1, long ld1Token, long ld1Slot,
         float* dDst, long ldd, void* dWork, nuint workBytes, void* stream);
+    // ... the ends of the block, device entries like the products (stream-ordered, no synchronize, no work buffer, capturable): router logits -> the
+    // n_used expert ids and gate weights of every token (gating 0 softmax, 1 sigmoid); the weighted sum of a token's pair rows (+ an addend, which
+    // may be dDst itself); the SwiGLU pair on contiguous device rows (dSilu may be null)
+    [DllImport(Lib)] public static extern int ggml_hip_moe_route_dev(float* dLogits, long ldLogits, long nTokens, int nExpert, int nUsed, int gating, int normalize, float scale,
+        int* dIds, float* dWeights, void* stream);
+    [DllImport(Lib)] public static extern int ggml_hip_moe_combine_dev(float* dY, long ldy, float* dWeights, long nTokens, int nUsed, long m, float* dAddend, long ldAdd,
+        float* dDst, long ldd, void* stream);
+    [DllImport(Lib)] public static extern int ggml_hip_silu_mul_rows_dev(float* dA, float* dB, float* dSilu, float* dY, long nrows, long k, void* stream);
 
     // Seam 2: the quantize_fns_t slots (TypeDefinitions.cs:334-342), type-indexed
     [DllImport(Lib)] public static extern int ggml_hip_quantize_row(int type, float* x, void* y, int k);
