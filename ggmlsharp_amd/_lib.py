@@ -80,6 +80,12 @@ class ggml_cgraph(C.Structure):
 
 assert C.sizeof(ggml_cgraph) == 98360
 
+class ggml_hip_attn_plan_t(C.Structure):
+    """include/ggml_hip_ext.h: the plan of one attention call (csrc/plan.cpp plan_attn)"""
+    _fields_ = [("form", C.c_int32), ("chunk", C.c_int32), ("q_tile", C.c_int32), ("launches", C.c_int32),
+                ("n_chunks", C.c_int64), ("workgroups", C.c_int64)]
+
+
 class ggml_hip_mm_plan_t(C.Structure):
     """include/ggml_hip_ext.h: the plan of one product (csrc/plan.cpp)"""
     _fields_ = [("family", C.c_int32), ("image_kind", C.c_int32), ("form", C.c_int32), ("tree_id", C.c_uint32),
@@ -205,6 +211,12 @@ HIP_SYMBOLS = {
     "ggml_hip_moe_route_dev": (C.c_int, [_P, C.c_int64, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, _P, _P, _P]),
     "ggml_hip_moe_combine_dev": (C.c_int, [_P, C.c_int64, _P, C.c_int64, C.c_int, C.c_int64, _P, C.c_int64, _P, C.c_int64, _P]),
     "ggml_hip_silu_mul_rows_dev": (C.c_int, [_P, _P, _P, _P, C.c_int64, C.c_int64, _P]),
+    # attention over an F16 / Q8_0 KV cache: rows into the cache, the attention itself, its plan and work size
+    "ggml_hip_kv_store_dev": (C.c_int, [C.c_int, _P, C.c_int64, C.c_int64, C.c_int64, _P, C.c_int64, C.c_int64, C.c_int64, _P, _P]),
+    "ggml_hip_attn_plan": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int64, C.c_int64, _P]),
+    "ggml_hip_attn_work_size": (C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int64, C.c_int64]),
+    "ggml_hip_attn_dev": (C.c_int, [C.c_int, _P, C.c_int64, C.c_int64, _P, _P, C.c_int64, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int64, C.c_int64, _P,
+                                    C.c_int64, C.c_int, C.c_float, _P, C.c_float, C.c_float, _P, _P, C.c_int64, C.c_int64, _P, C.c_size_t, _P]),
 }
 SYMBOLS = HIP_SYMBOLS
 

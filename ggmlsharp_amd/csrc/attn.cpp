@@ -1,0 +1,102 @@
+// attn.cpp -- the C-ABI of include/ggml_hip_ext.h, attention over a KV cache: rows into the cache (ggml_hip_kv_store_dev), the attention
+// itself (ggml_hip_attn_dev), its plan and work size.  The kernels and their arithmetic are attn.hip's, the form is plan.cpp's (plan_attn).
+// No set, no handle: stream-ordered launches on the current device, no synchronize, no allocation; capturable.
+#include "ctx.h"
+
+using namespace ghip;
+
+namespace {
+
+constexpr size_t ATTN_ALIGN = 256;
+
+int kv_type_ok(int kv_type) { return kv_type == GGML_TYPE_F16 || kv_type == GGML_TYPE_Q8_0; }
+
+// the shape rules of ggml_hip_attn_dev shared by the plan and the work size; 0 or an error code
+int check_attn_shape(int kv_type, int D, int n_head, int n_head_kv, int64_t n_q, int64_t n_kv_max) {
+    if (!kv_type_ok(kv_type)) return fail(GGML_HIP_ERR_TYPE, "kv_type %d: the cache is F16 or Q8_0", kv_type);
+    if (D != 64 && D != 128) return fail(GGML_HIP_ERR_SHAPE, "head size %d (64 or 128)", D);
+    if (n_head < 1 || n_head_kv < 1 || n_head % n_head_kv != 0 || n_head / n_head_kv > 16 || n_head > 65535)
+        return fail(GGML_HIP_ERR_SHAPE, "n_head %d over n_head_kv %d: the group size must be an integer in 1 .. 16", n_head, n_head_kv);
+    if (n_q < 0 || n_kv_max < 0) return fail(GGML_HIP_ERR_ARG, "n_q %lld, n_kv_max %lld", (long long)n_q, (long long)n_kv_max);
+    if (n_q > (1 << 20) || n_kv_max > (1 << 24) || n_q * n_head > 0x7FFFFFFF)
+        return fail(GGML_HIP_ERR_SHAPE, "n_q %lld (<= 2^20), n_kv_max %lld (<= 2^24)", (long long)n_q, (long long)n_kv_max);
+    return GGML_HIP_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int ggml_hip_kv_store_dev(int kv_type, const float *d_src, int64_t ld, int64_t n_rows, int64_t row_elems, void *d_cache, int64_t nb_pos,
+                          int64_t n_pos_max, int64_t pos0, const int32_t *d_pos0, void *stream) {
+    if (!kv_type_ok(kv_type)) return fail(GGML_HIP_ERR_TYPE, "kv_type %d: the cache is F16 or Q8_0", kv_type);
+    if (n_rows < 0 || n_pos_max < 0) return fail(GGML_HIP_ERR_ARG, "n_rows %lld, n_pos_max %lld", (long long)n_rows, (long long)n_pos_max);
+    const int64_t unit = kv_type == GGML_TYPE_Q8_0 ? QK : 4;
+    if (row_elems < 1 || row_elems % unit != 0 || row_elems > ((int64_t)1 << 24) || n_rows > ((int64_t)1 << 24))
+        return fail(GGML_HIP_ERR_SHAPE, "row_elems %lld (a multiple of %lld, <= 2^24), n_rows %lld (<= 2^24)", (long long)row_elems, (long long)unit, (long long)n_rows);
+    const int64_t row_bytes = kv_type == GGML_TYPE_Q8_0 ? row_elems / QK * (int64_t)sizeof(block_q8_0) : row_elems * 2;
+    if (ld < row_elems || ld % 4 != 0 || nb_pos < row_bytes || nb_pos % 16 != 0)
+        return fail(GGML_HIP_ERR_SHAPE, "ld %lld (>= row_elems, a multiple of 4), nb_pos %lld (>= %lld row bytes, a multiple of 16)", (long long)ld, (long long)nb_pos,
+                    (long long)row_bytes);
+    if (n_rows == 0) return GGML_HIP_OK;
+    if (!d_src || !d_cache) return fail(GGML_HIP_ERR_ARG, "null argument");
+    if (((uintptr_t)d_src & 15) != 0 || ((uintptr_t)d_cache & 15) != 0) return fail(GGML_HIP_ERR_SHAPE, "d_src and d_cache must be 16-byte aligned");
+    HIP_TRY(launch_kv_store(kv_type, d_src, ld, n_rows, row_elems, d_cache, nb_pos, n_pos_max, pos0, d_pos0, (hipStream_t)stream));
+    return GGML_HIP_OK;
+}
+
+int ggml_hip_attn_plan(int kv_type, int D, int n_head, int n_head_kv, int64_t n_q, int64_t n_kv_max, ggml_hip_attn_plan_t *out) {
+    if (!out) return fail(GGML_HIP_ERR_ARG, "out is null");
+    const int rc = check_attn_shape(kv_type, D, n_head, n_head_kv, n_q, n_kv_max);
+    if (rc) return rc;
+    if (n_q == 0) { *out = ggml_hip_attn_plan_t{}; out->chunk = ATTN_CHUNK; return GGML_HIP_OK; }
+    const attn_plan p = plan_attn(kv_type, D, n_head, n_head_kv, n_q, n_kv_max);
+    if (p.form == ATTN_FORM_NONE) return fail(GGML_HIP_ERR_SHAPE, "the shape is not served");
+    out->form = p.form; out->chunk = p.chunk; out->q_tile = p.q_tile; out->launches = p.launches;
+    out->n_chunks = p.n_chunks; out->workgroups = p.wgs;
+    return GGML_HIP_OK;
+}
+
+size_t ggml_hip_attn_work_size(int kv_type, int D, int n_head, int n_head_kv, int64_t n_q, int64_t n_kv_max) {
+    if (!kv_type_ok(kv_type) || n_q <= 0) return 0;
+    const attn_plan p = plan_attn(kv_type, D, n_head, n_head_kv, n_q, n_kv_max);
+    if (p.form == ATTN_FORM_NONE || p.work_bytes == 0) return 0;
+    return (p.work_bytes + ATTN_ALIGN - 1) / ATTN_ALIGN * ATTN_ALIGN + ATTN_ALIGN;   // (the base is rounded up to a 256-byte boundary)
+}
+
+int ggml_hip_attn_dev(int kv_type, const float *d_q, int64_t ldq_tok, int64_t ldq_head, const void *d_k, const void *d_v, int64_t nb_pos, int64_t nb_head,
+                      int n_head, int n_head_kv, int D, int64_t n_q, int64_t n_kv, const int32_t *d_n_kv, int64_t n_kv_max, int causal, float scale,
+                      const void *d_mask, float max_bias, float logit_softcap, const float *d_sinks, float *d_dst, int64_t ldd_tok, int64_t ldd_head,
+                      void *d_work, size_t work_bytes, void *stream) {
+    if (d_mask || d_sinks || max_bias != 0.0f || logit_softcap != 0.0f)
+        return fail(GGML_HIP_ERR_ARG, "a mask tensor, ALiBi (max_bias), a soft-cap and sinks are not served: pass NULL / 0");
+    int rc = check_attn_shape(kv_type, D, n_head, n_head_kv, n_q, n_kv_max);
+    if (rc) return rc;
+    if (!d_n_kv && (n_kv < 0 || n_kv > n_kv_max)) return fail(GGML_HIP_ERR_ARG, "n_kv %lld outside [0, n_kv_max %lld]", (long long)n_kv, (long long)n_kv_max);
+    const int64_t row_bytes = kv_type == GGML_TYPE_Q8_0 ? D / QK * (int64_t)sizeof(block_q8_0) : D * 2;
+    if (ldq_tok % 4 != 0 || ldq_head % 4 != 0 || ldd_tok % 4 != 0 || ldd_head % 4 != 0 || ldq_head < D || ldd_head < D || ldq_tok < 0 || ldd_tok < 0 ||
+        (n_q > 1 && (ldq_tok < D || ldd_tok < D)))
+        return fail(GGML_HIP_ERR_SHAPE, "the strides of q and dst are multiples of 4 elements, at least D");
+    if (nb_pos % 16 != 0 || nb_head % 16 != 0 || nb_pos < row_bytes || nb_head < row_bytes)
+        return fail(GGML_HIP_ERR_SHAPE, "nb_pos %lld, nb_head %lld: multiples of 16 bytes, at least the %lld bytes of a row", (long long)nb_pos, (long long)nb_head,
+                    (long long)row_bytes);
+    if (n_q == 0) return GGML_HIP_OK;
+    if (!d_q || !d_dst || (n_kv_max > 0 && (!d_k || !d_v))) return fail(GGML_HIP_ERR_ARG, "null argument");
+    if ((((uintptr_t)d_q | (uintptr_t)d_dst | (uintptr_t)d_k | (uintptr_t)d_v) & 15) != 0) return fail(GGML_HIP_ERR_SHAPE, "q, dst, K and V must be 16-byte aligned");
+    const attn_plan p = plan_attn(kv_type, D, n_head, n_head_kv, n_q, n_kv_max);
+    if (p.form == ATTN_FORM_NONE) return fail(GGML_HIP_ERR_SHAPE, "the shape is not served");
+    const size_t need = ggml_hip_attn_work_size(kv_type, D, n_head, n_head_kv, n_q, n_kv_max);
+    if (need && (!d_work || work_bytes < need)) return fail(GGML_HIP_ERR_ARG, "work buffer too small: need %zu (ggml_hip_attn_work_size)", need);
+    attn_args a;
+    a.kv_type = kv_type; a.D = D; a.n_head = n_head; a.n_head_kv = n_head_kv; a.causal = causal != 0;
+    a.q = d_q; a.ldq_tok = ldq_tok; a.ldq_head = ldq_head;
+    a.k = d_k; a.v = d_v; a.nb_pos = nb_pos; a.nb_head = nb_head;
+    a.n_q = n_q; a.n_kv = d_n_kv ? 0 : n_kv; a.d_n_kv = d_n_kv; a.n_kv_max = n_kv_max;
+    a.scale = scale;
+    a.dst = d_dst; a.ldd_tok = ldd_tok; a.ldd_head = ldd_head;
+    a.work = need ? (void *)(((uintptr_t)d_work + ATTN_ALIGN - 1) / ATTN_ALIGN * ATTN_ALIGN) : nullptr;
+    HIP_TRY(launch_attn(p, a, (hipStream_t)stream));
+    return GGML_HIP_OK;
+}
+
+}  // extern "C"

@@ -1,0 +1,541 @@
+// attn.hip -- attention over an F16 or Q8_0 KV cache on the device (include/ggml_hip_ext.h ggml_hip_kv_store_dev, ggml_hip_attn_dev;
+// attn.cpp has the C-ABI, plan.cpp plan_attn chooses the form from n_q alone).  Upstream's ggml_flash_attn_ext without mask tensor, ALiBi,
+// soft-cap and sinks; an EXTENSION like mul_mat_id (the reference has the op's id and no dispatch).
+//
+// A cache row is (position j, kv head hk): D elements in reference block format at  base + j * nb_pos + hk * nb_head  (F16: 2 D bytes of IEEE
+// halves; Q8_0: D / 32 blocks {f32 d; int8 qs[32]} of 36 bytes).  deq(row)[i] is the half widened (exact), or (float)qs[i] * d in ONE binary32
+// rounding -- what ggml_hip_dequantize_rows_dev returns.  Query head h reads kv head h / G, G = n_head / n_head_kv.
+// VISIBLE positions of query row t:  j < vis(t),  vis(t) = causal ? clamp(n_kv - n_q + t + 1, 0, n_kv) : n_kv.
+// CHUNK: the positions are cut into chunks of ATTN_CHUNK = 128, chunk c = [128 c, 128 c + 128), for every (kv_type, D), both forms.
+//
+// ---- kv_store ----  one thread per 32 elements (Q8_0) or 4 elements (F16) of a source row.  Q8_0: quantize.hip's statement of
+// quantize_row_q8_0 (amax; d = amax / 127; id = d ? 1 / d : 0; q = rint(v * id); the library is built without contraction and with the
+// correctly rounded division), bit for bit ggml_hip_quantize_rows_dev.  F16: IEEE round to nearest even by integer arithmetic (subnormals
+// kept, overflow to inf, a NaN stays a NaN).  A row whose position is outside [0, n_pos_max) leaves before any address is formed.
+//
+// ---- DECODE form (n_q <= 8), all f32 ----
+// A workgroup (256 threads) serves ONE kv head and ONE chunk for all R = G * n_q query rows of that kv head: it copies the chunk's K and V
+// rows into LDS as they are (raw halves / raw Q8_0 blocks, each byte of the cache read once per launch), then for the rows, eight at a time:
+//     s_j   = scale * dot(q, deq(K_j))       the dot an f32 fma chain over d ascending from 0.0f; q is f32 as given
+//     m     = max of s_j over the chunk's visible j                                         (exact)
+//     p_j   = s_j == m ? 1 : expf(s_j - m)
+//     l     = sum of p_j: lane L of a wave holds p_L + p_(L+64), the 64 lane sums meet in a butterfly (lane distance 32, 16, .., 1)
+//     a[d]  = p_0 * deq(V_0)[d], then a[d] = fma(p_j, deq(V_j)[d], a[d]) for j ascending  (one thread per four columns d)
+// and writes the partial (m, l, a[D]) of (row, chunk) into the work buffer.  An invisible position takes no part in any of it (it is
+// never multiplied by zero: what the cache holds there does not matter).  A second launch, one workgroup per query row, MERGES:
+//     M = max over the row's chunks c of m_c;  b_c = m_c == M ? 1 : expf(m_c - M)
+//     L = l_0 * b_0, A[d] = a_0[d] * b_0, then L = fma(l_c, b_c, L), A[d] = fma(a_c[d], b_c, A[d]) for c ASCENDING
+//     dst[d] = A[d] / L                                                                      (+0.0f for a row with no visible position)
+// No atomics: nothing depends on scheduling, on n_head, on n_kv_max, on the strides or on how many rows share the workgroup.
+// With one visible position p = 1, l = 1, b = 1: dst is deq(V_0) bit for bit.
+//
+// ---- PROMPT form (n_q > 8), matrix cores ----
+// A workgroup (4 waves) owns 128 consecutive query rows of one head, a wave 32 of them, and walks the chunks that hold a visible position
+// of its rows in ascending order; chunks above the causal diagonal are skipped, the diagonal chunk is masked per element.  Per chunk K is
+// staged in LDS as f16 [position][D], V as f16 TRANSPOSED [d][position]; a Q8_0 row is dequantized while staged: (float)q * d rounded to
+// f16 (RNE).  Rows of the chunk at or beyond n_kv are staged as zeros.  Q is rounded to f16 (RNE) once.  All on v_mfma_f32_32x32x16_f16:
+//     S^T   = K Q^T             f16 products exact, f32 accumulation; a lane owns one query, its registers hold the positions
+//     s_j   = scale * S_j       (f32);  invisible j: -inf
+//     m'    = max(m, max_j s_j);  alpha = expf(m - m') (0 for the first chunk);  p_j = expf(s_j - m'), 0 where invisible
+//     P_j   = f16(p_j)          RNE;  l = l * alpha + sum_j P_j  -- the sum is of the ROUNDED weights, so dst is a true weighted mean of V
+//     O^T   = O^T * alpha + V^T P^T   (f32 accumulators: the online-softmax state m, l, O stays in f32 registers)
+//     dst   = O / l             (+0.0f where l == 0: no visible position)
+// With one visible position P = 1, l = 1: dst is the STAGED V row bit for bit -- deq(V_0) for an F16 cache, f16(deq(V_0)) for a Q8_0 cache.
+// A masked weight is a ZERO operand of the matrix core here, so the cache must hold finite values at every position below n_kv.
+//
+// V CONSTANT over the positions: neither form returns the constant exactly in general -- a[d] = sum of fl(p_j * c) and l = sum of p_j round
+// independently, a / l is c only up to the accumulation error -- so that case is held to the tolerance, not to bits.
+#include "common.h"
+#include "plan.h"
+
+namespace {
+
+using f16x8 = __attribute__((ext_vector_type(8))) _Float16;
+using f16x4 = __attribute__((ext_vector_type(4))) _Float16;
+using f32x16 = __attribute__((ext_vector_type(16))) float;
+
+constexpr int C = ATTN_CHUNK;
+
+__device__ __forceinline__ uint32_t f32_to_f16_bits(float f) {      // (Half)f, IEEE round to nearest even (quantize.hip's algorithm)
+    const uint32_t x = __float_as_uint(f);
+    const uint32_t sign = (x >> 16) & 0x8000u;
+    const uint32_t exp = (x >> 23) & 0xFFu;
+    uint32_t man = x & 0x7FFFFFu;
+    if (exp == 0xFF) return man == 0 ? (sign | 0x7C00u) : (sign | 0x7C00u | 0x0200u | (man >> 13));
+    const int e = (int)exp - 127 + 15;
+    if (e >= 31) return sign | 0x7C00u;
+    if (e <= 0) {
+        if (e < -10) return sign;
+        man |= 0x800000u;
+        const int shift = 14 - e;
+        uint32_t hm = man >> shift;
+        const uint32_t rem = man & ((1u << shift) - 1u);
+        const uint32_t halfway = 1u << (shift - 1);
+        if (rem > halfway || (rem == halfway && (hm & 1u))) hm++;
+        return sign | hm;
+    }
+    uint32_t half = ((uint32_t)e << 10) | (man >> 13);
+    const uint32_t rem = man & 0x1FFFu;
+    if (rem > 0x1000u || (rem == 0x1000u && (half & 1u))) half++;
+    return sign | half;
+}
+
+__device__ __forceinline__ float f16_bits_to_f32(uint32_t h) { return (float)__builtin_bit_cast(_Float16, (uint16_t)h); }   // exact
+
+__device__ __forceinline__ int visible(int t, int n_kv, int n_q, int causal) {
+    if (!causal) return n_kv;
+    const int v = n_kv - n_q + t + 1;
+    return v < 0 ? 0 : v > n_kv ? n_kv : v;
+}
+
+__device__ __forceinline__ int device_count(const int32_t *d_n, int host_n, int n_max) {
+    int n = d_n ? *d_n : host_n;
+    n = n < 0 ? 0 : n;
+    return n > n_max ? n_max : n;
+}
+
+// ------------------------------------------------------------------------------------------------ kv_store
+template <bool Q8>
+__global__ __launch_bounds__(256) void kv_store_kernel(const float *__restrict__ src, int64_t ld, int64_t n_rows, int units_per_row, uint8_t *__restrict__ cache,
+                                                       int64_t nb_pos, int64_t n_pos_max, int64_t pos0, const int32_t *__restrict__ d_pos0) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n_rows * units_per_row) return;
+    const int64_t r = i / units_per_row;
+    const int u = (int)(i - r * units_per_row);
+    const int64_t pos = (d_pos0 ? (int64_t)*d_pos0 : pos0) + r;
+    if (pos < 0 || pos >= n_pos_max) return;                        // (before any address is formed from it)
+    uint8_t *row = cache + pos * nb_pos;
+    if constexpr (Q8) {
+        const float4 *x = (const float4 *)(src + r * ld + 32 * u);
+        float v[QK];
+#pragma unroll
+        for (int k = 0; k < 8; ++k) { const float4 f = x[k]; v[4 * k] = f.x; v[4 * k + 1] = f.y; v[4 * k + 2] = f.z; v[4 * k + 3] = f.w; }
+        float amax = 0.0f;
+#pragma unroll
+        for (int l = 0; l < QK; ++l) amax = fmaxf(amax, fabsf(v[l]));
+        const float d = amax / 127.0f;
+        const float id = d != 0.0f ? 1.0f / d : 0.0f;
+        uint32_t w[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+#pragma unroll
+        for (int l = 0; l < QK; ++l) {
+            const int q = (int)rintf(v[l] * id);
+            w[l / 4] |= ((uint32_t)q & 0xFFu) << (8 * (l & 3));
+        }
+        uint32_t *o = (uint32_t *)(row + 36 * (int64_t)u);
+        o[0] = __float_as_uint(d);
+#pragma unroll
+        for (int k = 0; k < 8; ++k) o[1 + k] = w[k];
+    } else {
+        const float4 f = *(const float4 *)(src + r * ld + 4 * u);
+        uint2 o;
+        o.x = f32_to_f16_bits(f.x) | (f32_to_f16_bits(f.y) << 16);
+        o.y = f32_to_f16_bits(f.z) | (f32_to_f16_bits(f.w) << 16);
+        *(uint2 *)(row + 8 * (int64_t)u) = o;
+    }
+}
+
+// ------------------------------------------------------------------------------------------------ DECODE form
+// bytes of a cache row, and its stride in the LDS stage (F16: + 8, rows of 8-byte reads spread over all banks; Q8_0: + 4, an odd word count)
+template <bool Q8> __host__ __device__ constexpr int row_bytes_of(int D) { return Q8 ? D / 32 * 36 : 2 * D; }
+template <bool Q8> __host__ __device__ constexpr int stage_stride(int D) { return row_bytes_of<Q8>(D) + (Q8 ? 4 : 8); }
+constexpr int DEC_RT = 8;                                           // query rows per pass of a decode workgroup
+
+template <bool Q8>
+__device__ __forceinline__ void load8(const uint8_t *row, int d8, float (&k)[8]) {      // elements 8 d8 .. 8 d8 + 7 of a staged row
+    if constexpr (Q8) {
+        const uint32_t *b = (const uint32_t *)(row + 36 * (d8 >> 2));
+        const float d = __uint_as_float(b[0]);
+        const uint32_t w0 = b[1 + 2 * (d8 & 3)], w1 = b[2 + 2 * (d8 & 3)];
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            k[i] = (float)(int)(int8_t)((w0 >> (8 * i)) & 0xFFu) * d;
+            k[4 + i] = (float)(int)(int8_t)((w1 >> (8 * i)) & 0xFFu) * d;
+        }
+    } else {
+        const uint2 a = *(const uint2 *)(row + 16 * d8), b = *(const uint2 *)(row + 16 * d8 + 8);
+        k[0] = f16_bits_to_f32(a.x & 0xFFFFu); k[1] = f16_bits_to_f32(a.x >> 16); k[2] = f16_bits_to_f32(a.y & 0xFFFFu); k[3] = f16_bits_to_f32(a.y >> 16);
+        k[4] = f16_bits_to_f32(b.x & 0xFFFFu); k[5] = f16_bits_to_f32(b.x >> 16); k[6] = f16_bits_to_f32(b.y & 0xFFFFu); k[7] = f16_bits_to_f32(b.y >> 16);
+    }
+}
+
+template <bool Q8>
+__device__ __forceinline__ void load4(const uint8_t *row, int d4, float (&v)[4]) {      // elements 4 d4 .. 4 d4 + 3 of a staged row
+    if constexpr (Q8) {
+        const uint32_t *b = (const uint32_t *)(row + 36 * (d4 >> 3));
+        const float d = __uint_as_float(b[0]);
+        const uint32_t w = b[1 + (d4 & 7)];
+#pragma unroll
+        for (int i = 0; i < 4; ++i) v[i] = (float)(int)(int8_t)((w >> (8 * i)) & 0xFFu) * d;
+    } else {
+        const uint2 a = *(const uint2 *)(row + 8 * d4);
+        v[0] = f16_bits_to_f32(a.x & 0xFFFFu); v[1] = f16_bits_to_f32(a.x >> 16); v[2] = f16_bits_to_f32(a.y & 0xFFFFu); v[3] = f16_bits_to_f32(a.y >> 16);
+    }
+}
+
+// the work buffer: partial (row gr = t * n_head + h, chunk c) at ((gr * n_chunks_max) + c) * (D + 4) floats: m, l, two spare, a[D]
+template <bool Q8, int D>
+__global__ __launch_bounds__(256) void attn_decode_kernel(const float *__restrict__ q, int64_t ldq_tok, int64_t ldq_head, const uint8_t *__restrict__ kc,
+                                                          const uint8_t *__restrict__ vc, int64_t nb_pos, int64_t nb_head, int n_head, int G, int n_q,
+                                                          int n_kv_host, const int32_t *__restrict__ d_n_kv, int n_kv_max, int causal, float scale,
+                                                          float *__restrict__ work, int n_chunks_max) {
+    constexpr int RB = row_bytes_of<Q8>(D), ST = stage_stride<Q8>(D), PPR = RB / 8;
+    extern __shared__ __attribute__((aligned(16))) uint8_t lds[];
+    uint8_t *kst = lds, *vst = lds + C * ST;
+    float *qt = (float *)(lds + 2 * C * ST);                         // [DEC_RT][D]
+    float *sc = qt + DEC_RT * D;                                     // [DEC_RT][C]
+    static_assert((2 * C * ST) % 16 == 0, "the query tile is read as float4");
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int c = blockIdx.x, hk = blockIdx.y;
+    const int n_kv = device_count(d_n_kv, n_kv_host, n_kv_max);
+    const int j0 = c * C;
+    if (j0 >= n_kv) return;                                          // (the whole workgroup: no barrier was reached)
+    const int cnt = min(C, n_kv - j0);                               // rows of this chunk the cache holds: all below n_kv <= n_kv_max
+    // ---- the chunk's K and V rows into LDS, as they are: 8-byte pieces, each read once ----
+    {
+        const uint8_t *kb = kc + (int64_t)j0 * nb_pos + (int64_t)hk * nb_head, *vb = vc + (int64_t)j0 * nb_pos + (int64_t)hk * nb_head;
+        const int per = cnt * PPR;
+        constexpr int UN = 8;                                        // loads in flight per thread: all issued before the first is stored
+        for (int i0 = tid; i0 < 2 * per; i0 += 256 * UN) {
+            uint2 w[UN];
+#pragma unroll
+            for (int u = 0; u < UN; ++u) {
+                const int i = i0 + 256 * u;
+                if (i < 2 * per) {
+                    const bool isv = i >= per;
+                    const int e = isv ? i - per : i, j = e / PPR, p = e - j * PPR;
+                    w[u] = *(const uint2 *)((isv ? vb : kb) + (int64_t)j * nb_pos + 8 * p);
+                }
+            }
+#pragma unroll
+            for (int u = 0; u < UN; ++u) {
+                const int i = i0 + 256 * u;
+                if (i < 2 * per) {
+                    const bool isv = i >= per;
+                    const int e = isv ? i - per : i, j = e / PPR, p = e - j * PPR;
+                    uint32_t *o = (uint32_t *)((isv ? vst : kst) + j * ST + 8 * p);
+                    o[0] = w[u].x; o[1] = w[u].y;
+                }
+            }
+        }
+    }
+    const int R = G * n_q;                                           // row r of this kv head: query t = r / G, head h = hk * G + r % G
+    for (int r0 = 0; r0 < R; r0 += DEC_RT) {
+        // ---- the pass's query rows (zeros past R) ----
+        for (int i = tid; i < DEC_RT * (D / 4); i += 256) {
+            const int ri = i / (D / 4), d4 = i - ri * (D / 4), r = r0 + ri;
+            float4 f = make_float4(0.f, 0.f, 0.f, 0.f);
+            if (r < R) f = *(const float4 *)(q + (int64_t)(r / G) * ldq_tok + (int64_t)(hk * G + r % G) * ldq_head + 4 * d4);
+            *(float4 *)(qt + ri * D + 4 * d4) = f;
+        }
+        __syncthreads();
+        // ---- scores: thread (position j, half hs) takes rows 4 hs .. 4 hs + 3 of the pass ----
+        {
+            const int j = tid & (C - 1), hs = tid >> 7;
+            float acc[4] = {0.f, 0.f, 0.f, 0.f};
+            if (j < cnt) {
+                const uint8_t *krow = kst + j * ST;
+#pragma unroll 2
+                for (int d8 = 0; d8 < D / 8; ++d8) {
+                    float k[8];
+                    load8<Q8>(krow, d8, k);
+#pragma unroll
+                    for (int i = 0; i < 4; ++i) {
+                        const float4 qa = *(const float4 *)(qt + (4 * hs + i) * D + 8 * d8), qb = *(const float4 *)(qt + (4 * hs + i) * D + 8 * d8 + 4);
+                        float a = acc[i];
+                        a = fmaf(qa.x, k[0], a); a = fmaf(qa.y, k[1], a); a = fmaf(qa.z, k[2], a); a = fmaf(qa.w, k[3], a);
+                        a = fmaf(qb.x, k[4], a); a = fmaf(qb.y, k[5], a); a = fmaf(qb.z, k[6], a); a = fmaf(qb.w, k[7], a);
+                        acc[i] = a;
+                    }
+                }
+            }
+#pragma unroll
+            for (int i = 0; i < 4; ++i) sc[(4 * hs + i) * C + j] = scale * acc[i];
+        }
+        __syncthreads();
+        // ---- the chunk's softmax pieces: wave w takes rows w and w + 4 of the pass ----
+#pragma unroll
+        for (int k = 0; k < 2; ++k) {
+            const int ri = wave + 4 * k, r = r0 + ri;
+            if (r >= R) continue;                                    // (wave-uniform)
+            const int vis = visible(r / G, n_kv, n_q, causal) - j0;
+            if (vis <= 0) continue;
+            const int n = min(vis, C);
+            const float ninf = -__builtin_inff();
+            const float s0 = lane < n ? sc[ri * C + lane] : ninf, s1 = lane + 64 < n ? sc[ri * C + lane + 64] : ninf;
+            float m = fmaxf(s0, s1);
+#pragma unroll
+            for (int dd = 32; dd >= 1; dd >>= 1) m = fmaxf(m, __shfl_xor(m, dd));
+            const float p0 = lane < n ? (s0 == m ? 1.0f : expf(s0 - m)) : 0.0f, p1 = lane + 64 < n ? (s1 == m ? 1.0f : expf(s1 - m)) : 0.0f;
+            sc[ri * C + lane] = p0; sc[ri * C + lane + 64] = p1;
+            float l = p0 + p1;
+#pragma unroll
+            for (int dd = 32; dd >= 1; dd >>= 1) l = l + __shfl_xor(l, dd);
+            if (lane == 0) {
+                const int64_t gr = (int64_t)(r / G) * n_head + hk * G + r % G;
+                float *part = work + (gr * n_chunks_max + c) * (D + 4);
+                part[0] = m; part[1] = l;
+            }
+        }
+        __syncthreads();
+        // ---- a[d] = sum of p_j deq(V_j)[d], j ascending: a group of D / 4 threads per row, a thread per four columns ----
+        {
+            constexpr int TPR = D / 4, NG = 256 / TPR;
+            const int g = tid / TPR, d4 = tid - g * TPR;
+            for (int ri = g; ri < DEC_RT; ri += NG) {
+                const int r = r0 + ri;
+                if (r >= R) break;
+                const int vis = visible(r / G, n_kv, n_q, causal) - j0;
+                if (vis <= 0) continue;
+                const int n = min(vis, C);
+                float v[4], a[4];
+                load4<Q8>(vst, d4, v);
+                const float pf = sc[ri * C];
+#pragma unroll
+                for (int i = 0; i < 4; ++i) a[i] = pf * v[i];
+#pragma unroll 4
+                for (int j = 1; j < n; ++j) {
+                    load4<Q8>(vst + j * ST, d4, v);
+                    const float p = sc[ri * C + j];
+#pragma unroll
+                    for (int i = 0; i < 4; ++i) a[i] = fmaf(p, v[i], a[i]);
+                }
+                const int64_t gr = (int64_t)(r / G) * n_head + hk * G + r % G;
+                *(float4 *)(work + (gr * n_chunks_max + c) * (D + 4) + 4 + 4 * d4) = make_float4(a[0], a[1], a[2], a[3]);
+            }
+        }
+        __syncthreads();                                             // (the next pass rewrites the query tile and the scores)
+    }
+}
+
+// the merge: one workgroup of D threads per query row (t, h); thread d owns column d, every thread the row's (M, L)
+template <int D>
+__global__ __launch_bounds__(D) void attn_merge_kernel(const float *__restrict__ work, int n_chunks_max, int n_head, int n_q, int n_kv_host,
+                                                       const int32_t *__restrict__ d_n_kv, int n_kv_max, int causal, float *__restrict__ dst, int64_t ldd_tok,
+                                                       int64_t ldd_head) {
+    const int t = blockIdx.x / n_head, h = blockIdx.x - t * n_head, d = threadIdx.x;
+    const int n_kv = device_count(d_n_kv, n_kv_host, n_kv_max);
+    const int vis = visible(t, n_kv, n_q, causal);
+    float *out = dst + (int64_t)t * ldd_tok + (int64_t)h * ldd_head + d;
+    if (vis <= 0) { *out = 0.0f; return; }
+    const int nc = (vis + C - 1) / C;                                // <= n_chunks_max: vis <= n_kv <= n_kv_max
+    const float *part = work + (int64_t)blockIdx.x * n_chunks_max * (D + 4);
+    float M = part[0];
+    for (int c = 1; c < nc; ++c) M = fmaxf(M, part[(int64_t)c * (D + 4)]);
+    float L, A;
+    {
+        const float m = part[0], b = m == M ? 1.0f : expf(m - M);
+        L = part[1] * b; A = part[4 + d] * b;
+    }
+#pragma unroll 4
+    for (int c = 1; c < nc; ++c) {
+        const float *p = part + (int64_t)c * (D + 4);
+        const float m = p[0], b = m == M ? 1.0f : expf(m - M);
+        L = fmaf(p[1], b, L); A = fmaf(p[4 + d], b, A);
+    }
+    *out = A / L;
+}
+
+// ------------------------------------------------------------------------------------------------ PROMPT form
+// LDS: K [C positions][D + 8 halves] (16-byte fragment reads, rows 4 banks apart), V^T [D][C + 4 halves] (8-byte fragment reads, rows 2 banks apart)
+template <int D> constexpr int prompt_k_stride() { return 2 * D + 16; }
+constexpr int PROMPT_VT_STRIDE = 2 * C + 8;
+template <int D> constexpr int prompt_lds() { return C * prompt_k_stride<D>() + D * PROMPT_VT_STRIDE; }
+
+template <bool Q8>
+__device__ __forceinline__ f16x8 stage_load8(const uint8_t *row, int d8) {             // elements 8 d8 .. of a cache row in global memory, as f16
+    if constexpr (Q8) {
+        const uint32_t *b = (const uint32_t *)(row + 36 * (d8 >> 2));
+        const float d = __uint_as_float(b[0]);
+        const uint32_t w0 = b[1 + 2 * (d8 & 3)], w1 = b[2 + 2 * (d8 & 3)];
+        f16x8 o;
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            o[i] = (_Float16)((float)(int)(int8_t)((w0 >> (8 * i)) & 0xFFu) * d);       // (v_cvt_f16_f32: round to nearest even)
+            o[4 + i] = (_Float16)((float)(int)(int8_t)((w1 >> (8 * i)) & 0xFFu) * d);
+        }
+        return o;
+    } else {
+        return *(const f16x8 *)(row + 16 * d8);
+    }
+}
+
+template <bool Q8, int D>
+__global__ __launch_bounds__(256) void attn_prompt_kernel(const float *__restrict__ q, int64_t ldq_tok, int64_t ldq_head, const uint8_t *__restrict__ kc,
+                                                          const uint8_t *__restrict__ vc, int64_t nb_pos, int64_t nb_head, int G, int n_q, int n_kv_host,
+                                                          const int32_t *__restrict__ d_n_kv, int n_kv_max, int causal, float scale, float *__restrict__ dst,
+                                                          int64_t ldd_tok, int64_t ldd_head) {
+    constexpr int KS = prompt_k_stride<D>(), VS = PROMPT_VT_STRIDE, NKS = D / 16, NDT = D / 32, NCT = C / 32;
+    extern __shared__ __attribute__((aligned(16))) uint8_t lds[];
+    uint8_t *kst = lds, *vt = lds + C * KS;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, r = lane & 31, hh = lane >> 5;
+    const int h = blockIdx.y, hk = h / G;
+    const int q0 = blockIdx.x * 128, qw = q0 + 32 * wave;             // the workgroup's and the wave's first query row
+    const int n_kv = device_count(d_n_kv, n_kv_host, n_kv_max);
+    const int tq = min(qw + r, n_q - 1);                             // this lane's query (a lane past n_q computes a copy and stores nothing)
+    const int vis = visible(tq, n_kv, n_q, causal);
+    const int wg_vis = visible(min(q0 + 127, n_q - 1), n_kv, n_q, causal);         // vis is monotone in t: the workgroup's largest
+    const int wave_vis = qw < n_q ? visible(min(qw + 31, n_q - 1), n_kv, n_q, causal) : 0;
+    // Q^T as the B operand: lane (query r, half hh) holds Q[tq][16 ks + 8 hh + i], rounded to f16
+    f16x8 qf[NKS];
+    {
+        const float *qrow = q + (int64_t)tq * ldq_tok + (int64_t)h * ldq_head;
+#pragma unroll
+        for (int ks = 0; ks < NKS; ++ks) {
+            const float4 a = *(const float4 *)(qrow + 16 * ks + 8 * hh), b = *(const float4 *)(qrow + 16 * ks + 8 * hh + 4);
+            qf[ks][0] = (_Float16)a.x; qf[ks][1] = (_Float16)a.y; qf[ks][2] = (_Float16)a.z; qf[ks][3] = (_Float16)a.w;
+            qf[ks][4] = (_Float16)b.x; qf[ks][5] = (_Float16)b.y; qf[ks][6] = (_Float16)b.z; qf[ks][7] = (_Float16)b.w;
+        }
+    }
+    f32x16 o[NDT];
+#pragma unroll
+    for (int dt = 0; dt < NDT; ++dt)
+#pragma unroll
+        for (int i = 0; i < 16; ++i) o[dt][i] = 0.0f;
+    const float ninf = -__builtin_inff();
+    float m = ninf, l = 0.0f;
+    const int nc = (wg_vis + C - 1) / C;
+    for (int c = 0; c < nc; ++c) {
+        const int j0 = c * C, cnt = min(C, n_kv - j0);               // (j0 < wg_vis <= n_kv: cnt >= 1)
+        if (c > 0) __syncthreads();                                  // (every wave is done with the previous stage)
+        // ---- stage: K rows as they lie, V transposed; 16 bytes of f16 per item, consecutive lanes along a row ----
+        {
+            const uint8_t *kb = kc + (int64_t)j0 * nb_pos + (int64_t)hk * nb_head, *vb = vc + (int64_t)j0 * nb_pos + (int64_t)hk * nb_head;
+            for (int i = tid; i < C * (D / 8); i += 256) {
+                const int j = i / (D / 8), d8 = i - j * (D / 8);
+                f16x8 kv, vv;
+                if (j < cnt) {
+                    kv = stage_load8<Q8>(kb + (int64_t)j * nb_pos, d8);
+                    vv = stage_load8<Q8>(vb + (int64_t)j * nb_pos, d8);
+                } else {
+#pragma unroll
+                    for (int e = 0; e < 8; ++e) { kv[e] = (_Float16)0.0f; vv[e] = (_Float16)0.0f; }
+                }
+                *(f16x8 *)(kst + j * KS + 16 * d8) = kv;
+#pragma unroll
+                for (int e = 0; e < 8; ++e) *(_Float16 *)(vt + (8 * d8 + e) * VS + 2 * j) = vv[e];
+            }
+        }
+        __syncthreads();
+        if (j0 >= wave_vis) continue;                                // (wave-uniform: nothing of this chunk is visible to the wave's rows)
+        // ---- S^T = K Q^T: tile ct holds positions j0 + 32 ct + row(i, hh) of this lane's query ----
+        f32x16 s[NCT];
+#pragma unroll
+        for (int ct = 0; ct < NCT; ++ct) {
+#pragma unroll
+            for (int i = 0; i < 16; ++i) s[ct][i] = 0.0f;
+#pragma unroll
+            for (int ks = 0; ks < NKS; ++ks) {
+                const f16x8 a = *(const f16x8 *)(kst + (32 * ct + r) * KS + 2 * (16 * ks + 8 * hh));
+                s[ct] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a, qf[ks], s[ct], 0, 0, 0);
+            }
+        }
+        // ---- the online softmax of this lane's query; register i of a tile is row (i & 3) + 8 (i >> 2) + 4 hh ----
+        float cm = ninf;
+#pragma unroll
+        for (int ct = 0; ct < NCT; ++ct)
+#pragma unroll
+            for (int i = 0; i < 16; ++i) {
+                const int j = j0 + 32 * ct + (i & 3) + 8 * (i >> 2) + 4 * hh;
+                const float v = j < vis ? scale * s[ct][i] : ninf;
+                s[ct][i] = v;
+                cm = fmaxf(cm, v);
+            }
+        cm = fmaxf(cm, __shfl_xor(cm, 32));
+        const float mn = fmaxf(m, cm);
+        const bool any = mn != ninf;                                 // (false: this query has seen no visible position yet)
+        const float alpha = m == ninf ? 0.0f : expf(m - mn);
+        float cs = 0.0f;
+        f16x8 pf[NCT][2];
+#pragma unroll
+        for (int ct = 0; ct < NCT; ++ct)
+#pragma unroll
+            for (int i = 0; i < 16; ++i) {
+                const float p = (any && s[ct][i] != ninf) ? expf(s[ct][i] - mn) : 0.0f;
+                const _Float16 ph = (_Float16)p;
+                pf[ct][i >> 3][i & 7] = ph;
+                cs = cs + (float)ph;
+            }
+        cs = cs + __shfl_xor(cs, 32);
+        l = l * alpha + cs;
+        m = mn;
+        // ---- O^T = O^T alpha + V^T P^T: the P tile is the B operand as it stands -- element i of k-step ks is position 16 ks + (i & 3) + 8 (i >> 2) + 4 hh,
+        //      and the A operand V^T[d][.] is read at the same positions ----
+#pragma unroll
+        for (int dt = 0; dt < NDT; ++dt) {
+#pragma unroll
+            for (int i = 0; i < 16; ++i) o[dt][i] = o[dt][i] * alpha;
+#pragma unroll
+            for (int ct = 0; ct < NCT; ++ct)
+#pragma unroll
+                for (int ks = 0; ks < 2; ++ks) {
+                    const uint8_t *vrow = vt + (32 * dt + r) * VS + 2 * (32 * ct + 16 * ks + 4 * hh);
+                    const f16x4 lo = *(const f16x4 *)vrow, hi = *(const f16x4 *)(vrow + 16);
+                    f16x8 a;
+                    a[0] = lo[0]; a[1] = lo[1]; a[2] = lo[2]; a[3] = lo[3]; a[4] = hi[0]; a[5] = hi[1]; a[6] = hi[2]; a[7] = hi[3];
+                    o[dt] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a, pf[ct][ks], o[dt], 0, 0, 0);
+                }
+        }
+    }
+    // ---- dst[tq][h][d] = O^T[d][query] / l: register i of tile dt is d = 32 dt + (i & 3) + 8 (i >> 2) + 4 hh ----
+    if (qw + r < n_q) {
+        float *out = dst + (int64_t)tq * ldd_tok + (int64_t)h * ldd_head;
+#pragma unroll
+        for (int dt = 0; dt < NDT; ++dt)
+#pragma unroll
+            for (int g = 0; g < 4; ++g) {
+                float4 f = make_float4(0.f, 0.f, 0.f, 0.f);
+                if (l != 0.0f) f = make_float4(o[dt][4 * g] / l, o[dt][4 * g + 1] / l, o[dt][4 * g + 2] / l, o[dt][4 * g + 3] / l);
+                *(float4 *)(out + 32 * dt + 8 * g + 4 * hh) = f;
+            }
+    }
+}
+
+template <bool Q8, int D> constexpr int decode_lds() { return 2 * C * stage_stride<Q8>(D) + DEC_RT * D * 4 + DEC_RT * C * 4; }
+
+}  // namespace
+
+hipError_t launch_kv_store(int kv_type, const float *src, int64_t ld, int64_t n_rows, int64_t row_elems, void *cache, int64_t nb_pos, int64_t n_pos_max,
+                           int64_t pos0, const int32_t *d_pos0, hipStream_t st) {
+    if (n_rows <= 0) return hipSuccess;
+    const bool q8 = kv_type == GGML_TYPE_Q8_0;
+    const int64_t upr = row_elems / (q8 ? 32 : 4), total = n_rows * upr;
+    if (upr <= 0 || upr > 0x7FFFFFFF || total > (int64_t)0x7FFFFFFF * 256) return hipErrorInvalidValue;
+    const dim3 grid((unsigned)((total + 255) / 256));
+    if (q8) kv_store_kernel<true><<<grid, 256, 0, st>>>(src, ld, n_rows, (int)upr, (uint8_t *)cache, nb_pos, n_pos_max, pos0, d_pos0);
+    else kv_store_kernel<false><<<grid, 256, 0, st>>>(src, ld, n_rows, (int)upr, (uint8_t *)cache, nb_pos, n_pos_max, pos0, d_pos0);
+    return hipGetLastError();
+}
+
+hipError_t launch_attn(const attn_plan &pl, const attn_args &a, hipStream_t st) {
+    const bool q8 = a.kv_type == GGML_TYPE_Q8_0;
+    const int G = a.n_head / a.n_head_kv;
+    const uint8_t *kc = (const uint8_t *)a.k, *vc = (const uint8_t *)a.v;
+    if (pl.form == ATTN_FORM_DECODE) {
+        const dim3 grid((unsigned)pl.n_chunks, (unsigned)a.n_head_kv);
+        float *work = (float *)a.work;
+#define DECODE(Q, DD)                                                                                                                                 \
+    do {                                                                                                                                              \
+        hipError_t e = launch_lds(kfn<attn_decode_kernel<Q, DD>>, grid, dim3(256), (size_t)decode_lds<Q, DD>(), decode_lds<Q, DD>(), st, a.q, a.ldq_tok,  \
+                                  a.ldq_head, kc, vc, a.nb_pos, a.nb_head, a.n_head, G, (int)a.n_q, (int)a.n_kv, a.d_n_kv, (int)a.n_kv_max, a.causal, \
+                                  a.scale, work, (int)pl.n_chunks);                                                                                  \
+        if (e != hipSuccess) return e;                                                                                                                \
+        attn_merge_kernel<DD><<<dim3((unsigned)(a.n_q * a.n_head)), DD, 0, st>>>(work, (int)pl.n_chunks, a.n_head, (int)a.n_q, (int)a.n_kv, a.d_n_kv,  \
+                                                                                (int)a.n_kv_max, a.causal, a.dst, a.ldd_tok, a.ldd_head);             \
+    } while (0)
+        if (q8 && a.D == 64) DECODE(true, 64);
+        else if (q8) DECODE(true, 128);
+        else if (a.D == 64) DECODE(false, 64);
+        else DECODE(false, 128);
+#undef DECODE
+        return hipGetLastError();
+    }
+    const dim3 grid((unsigned)((a.n_q + 127) / 128), (unsigned)a.n_head);
+#define PROMPT(Q, DD)                                                                                                                                  \
+    return launch_lds(kfn<attn_prompt_kernel<Q, DD>>, grid, dim3(256), (size_t)prompt_lds<DD>(), prompt_lds<DD>(), st, a.q, a.ldq_tok, a.ldq_head, kc, vc, \
+                      a.nb_pos, a.nb_head, G, (int)a.n_q, (int)a.n_kv, a.d_n_kv, (int)a.n_kv_max, a.causal, a.scale, a.dst, a.ldd_tok, a.ldd_head)
+    if (q8 && a.D == 64) PROMPT(true, 64);
+    else if (q8) PROMPT(true, 128);
+    else if (a.D == 64) PROMPT(false, 64);
+    else PROMPT(false, 128);
+#undef PROMPT
+}

@@ -448,6 +448,20 @@ hipError_t launch_moe_topk(const float *logits, int64_t ld, int64_t n_tokens, in
 // dst[t] = sum over s (ascending) of w[t * n_used + s] * y[(t * n_used + s) * ldy ..] [+ addend[t]]: 16-byte accesses where every pointer and stride allows
 hipError_t launch_moe_combine(const float *y, int64_t ldy, const float *w, int64_t n_tokens, int n_used, int64_t M, const float *addend, int64_t ld_add,
                               float *dst, int64_t ldd, hipStream_t st);
+// attn.hip: rows into a KV cache, attention over it (ggml_hip_kv_store_dev / ggml_hip_attn_dev, attn.cpp; the form is plan.h's plan_attn)
+struct attn_plan;
+struct attn_args {
+    int kv_type, D, n_head, n_head_kv, causal;
+    const float *q; int64_t ldq_tok, ldq_head;
+    const void *k, *v; int64_t nb_pos, nb_head;
+    int64_t n_q, n_kv; const int32_t *d_n_kv; int64_t n_kv_max;
+    float scale;
+    float *dst; int64_t ldd_tok, ldd_head;
+    void *work;                                                      // 16-byte aligned (DECODE: plan_attn's work_bytes)
+};
+hipError_t launch_kv_store(int kv_type, const float *src, int64_t ld, int64_t n_rows, int64_t row_elems, void *cache, int64_t nb_pos, int64_t n_pos_max,
+                           int64_t pos0, const int32_t *d_pos0, hipStream_t st);
+hipError_t launch_attn(const attn_plan &pl, const attn_args &a, hipStream_t st);
 // gemm_q8s.hip / gemm_qmx.hip: ONE K3s launch over the tile table -- workgroup -> (weight tile group, column tile t); t >= *n_tiles leaves at once;
 // the expert's planes come from tab[tiles[t].expert], the 32 sorted rows at 32 t of the image p (K1's image of `32 * max_tiles` rows); res [rows][ldr]
 hipError_t launch_gemm_q8_small_grouped(const mm_plan &g, int type, const moe_gexpert *tab, const moe_tile *tiles, const int32_t *n_tiles, int64_t max_tiles,

@@ -613,3 +613,24 @@ mm_plan plan_mul_mat_id_grouped(int type, int ext_type, int64_t M, int64_t K, in
     if (g.wgs > 0x7FFFFFFF || plan_k3s_slots(g, type).lds > 160 * 1024) return none;
     return g;
 }
+
+// Attention over a KV cache (attn.hip).  One decision: n_q <= ATTN_DECODE_MAX_Q is the split-KV DECODE form, everything above the
+// matrix-core PROMPT form; the chunk is ATTN_CHUNK for every served (kv_type, D).  What is served: F16 / Q8_0, D 64 / 128, G in 1 .. 16.
+attn_plan plan_attn(int kv_type, int D, int n_head, int n_head_kv, int64_t n_q, int64_t n_kv_max) {
+    attn_plan p = {};
+    if (!(kv_type == GGML_TYPE_F16 || kv_type == GGML_TYPE_Q8_0) || !(D == 64 || D == 128)) return p;
+    if (n_head < 1 || n_head_kv < 1 || n_head % n_head_kv != 0 || n_head / n_head_kv > 16 || n_head > 65535) return p;
+    if (n_q < 1 || n_q > (1 << 20) || n_kv_max < 0 || n_kv_max > (1 << 24) || n_q * n_head > 0x7FFFFFFF) return p;
+    p.chunk = ATTN_CHUNK;
+    p.n_chunks = cdiv(n_kv_max, ATTN_CHUNK);
+    if (n_q <= ATTN_DECODE_MAX_Q) {
+        p.form = ATTN_FORM_DECODE; p.q_tile = (int)(n_q * (n_head / n_head_kv)); p.launches = 2;
+        p.wgs = p.n_chunks * n_head_kv;
+        p.work_bytes = (size_t)n_q * (size_t)n_head * (size_t)p.n_chunks * (size_t)(D + 4) * 4;
+    } else {
+        p.form = ATTN_FORM_PROMPT; p.q_tile = 128; p.launches = 1;
+        p.wgs = cdiv(n_q, 128) * n_head;
+        p.work_bytes = 0;
+    }
+    return p;
+}

@@ -110,6 +110,25 @@ bool plan_mul_mat_id_grouped_serves(int type, int ext_type, int64_t M, int64_t K
 // family MMF_K3S_I8 / MMF_K3S_MX with nloc, wmt, tile_m = 32 * wmt, tile_n = 32 and wgs = the grid bound (tile bound x weight tile groups),
 // or MMF_NONE: not served, P outside 1 .. 2^20, or an activation image of the bounded rows beyond the kernels' 32-bit offsets
 mm_plan plan_mul_mat_id_grouped(int type, int ext_type, int64_t M, int64_t K, int n_expert, int64_t P);
+// ---- attention over a KV cache (attn.hip; ggml_hip_attn_dev) ----
+// The FORM is a function of n_q alone, the CHUNK (positions per partial / per softmax step) of (kv_type, D) alone -- today one constant.
+// Neither follows the device, the grid, n_head or n_kv_max, so a query row's bits do not either.
+constexpr int ATTN_CHUNK = 128;
+// DECODE up to this many query rows: the G * n_q rows that share a kv head ride one pass over its cache on the f32 VALU -- per chunk
+// G * n_q * 128 * D * 2 fma against 2 * 128 * row bytes streamed, which at G = 4 stays under the stream's time up to about 8 rows; beyond,
+// a 32-row matrix-core tile is at least a quarter full and the PROMPT form takes over.
+constexpr int ATTN_DECODE_MAX_Q = 8;
+enum attn_form { ATTN_FORM_NONE = 0, ATTN_FORM_DECODE = 1, ATTN_FORM_PROMPT = 2 };
+struct attn_plan {
+    int form;             // attn_form; NONE: the shape is not served
+    int chunk;            // positions per chunk
+    int q_tile;           // query rows a workgroup owns (DECODE: all G * n_q rows of its kv head)
+    int launches;         // DECODE 2 (partials, merge), PROMPT 1
+    int64_t n_chunks;     // ceil(n_kv_max / chunk): DECODE's grid and partial count per row
+    int64_t wgs;          // workgroups of the main launch
+    size_t work_bytes;    // DECODE: the partials, n_q * n_head * n_chunks * (D + 4) floats; PROMPT 0
+};
+attn_plan plan_attn(int kv_type, int D, int n_head, int n_head_kv, int64_t n_q, int64_t n_kv_max);
 // the K1 image for (type, K, N) with no weight at hand (no M: the exception cannot apply)
 int plan_image_kind(int type, int64_t K, int64_t N);
 // thread-local test switch (ggml_hip_debug_force_gemm): 0 auto, 1 int8, 2 f16, 3 MX

@@ -231,6 +231,59 @@ def silu_mul_rows(a, b, silu=None, out=None):
     return out
 
 
+def kv_row_bytes(kv_type, D):
+    """bytes of one cache row of D elements (F16 or Q8_0) in reference block format"""
+    return row_bytes(kv_type, D)
+
+
+def kv_store(kv_type, x, cache, nb_pos, n_pos_max, pos0=0, d_pos0=None):
+    """append rows to a KV cache: x f32 [n_rows, row_elems] on the device (row stride a multiple of 4) -> rows of kv_type (F16 / Q8_0) at
+    cache + (pos0 + i) * nb_pos bytes; cache: a uint8 tensor whose first byte is position 0 (a view selects a head of a head-major cache).
+    d_pos0: an int32 tensor on the device read instead of pos0 (a captured call follows it).  Positions outside [0, n_pos_max) write nothing."""
+    assert x.is_cuda and x.dtype == torch.float32 and x.dim() == 2 and x.stride(1) == 1
+    assert cache.is_cuda and cache.dtype == torch.uint8
+    assert d_pos0 is None or (d_pos0.is_cuda and d_pos0.dtype == torch.int32)
+    n_rows, row_elems = x.shape
+    check(lib().ggml_hip_kv_store_dev(kv_type, C.c_void_p(x.data_ptr()), x.stride(0), n_rows, row_elems, C.c_void_p(cache.data_ptr()), nb_pos, n_pos_max,
+                                      int(pos0), C.c_void_p(d_pos0.data_ptr()) if d_pos0 is not None else None, _stream()), "ggml_hip_kv_store_dev")
+
+
+def attn_plan(kv_type, D, n_head, n_head_kv, n_q, n_kv_max):
+    """(form, chunk, q_tile, launches, n_chunks, workgroups) of one attention call: form 1 DECODE, 2 PROMPT (0 for n_q = 0); no device needed"""
+    out = _lib.ggml_hip_attn_plan_t()
+    check(lib().ggml_hip_attn_plan(kv_type, D, n_head, n_head_kv, n_q, n_kv_max, C.byref(out)), "ggml_hip_attn_plan")
+    return out
+
+
+def attn_work_size(kv_type, D, n_head, n_head_kv, n_q, n_kv_max):
+    return int(lib().ggml_hip_attn_work_size(kv_type, D, n_head, n_head_kv, n_q, n_kv_max))
+
+
+def attention(kv_type, q, k, v, nb_pos, nb_head, n_head_kv, n_kv, d_n_kv=None, n_kv_max=None, causal=True, scale=None, out=None, work=None):
+    """out[t, h] = softmax_j(scale * q[t, h] . K[j, h / G]) V[j, h / G] over the visible j of an F16 / Q8_0 cache, on the current stream.
+    q f32 [n_q, n_head, D] (last stride 1); k, v: uint8 tensors whose first byte is row (position 0, kv head 0), rows nb_pos / nb_head bytes
+    apart; causal: the batch is the last n_q of the n_kv positions.  d_n_kv: an int32 tensor on the device read instead of n_kv (clamped to
+    n_kv_max, which sizes the launch; default n_kv).  scale defaults to 1 / sqrt(D)."""
+    assert q.is_cuda and q.dtype == torch.float32 and q.dim() == 3 and q.stride(2) == 1
+    assert k.is_cuda and v.is_cuda and k.dtype == torch.uint8 and v.dtype == torch.uint8
+    assert d_n_kv is None or (d_n_kv.is_cuda and d_n_kv.dtype == torch.int32)
+    n_q, n_head, D = q.shape
+    if n_kv_max is None:
+        n_kv_max = n_kv
+    if scale is None:
+        scale = 1.0 / float(np.sqrt(np.float64(D)))
+    if out is None:
+        out = torch.empty((n_q, n_head, D), dtype=torch.float32, device=q.device)
+    assert out.dtype == torch.float32 and out.dim() == 3 and out.stride(2) == 1 and tuple(out.shape) == (n_q, n_head, D)
+    if work is None:
+        work = torch.empty(max(attn_work_size(kv_type, D, n_head, n_head_kv, n_q, n_kv_max), 16), dtype=torch.uint8, device=q.device)
+    check(lib().ggml_hip_attn_dev(kv_type, C.c_void_p(q.data_ptr()), q.stride(0), q.stride(1), C.c_void_p(k.data_ptr()), C.c_void_p(v.data_ptr()), nb_pos, nb_head,
+                                  n_head, n_head_kv, D, n_q, int(n_kv), C.c_void_p(d_n_kv.data_ptr()) if d_n_kv is not None else None, n_kv_max,
+                                  int(bool(causal)), float(scale), None, 0.0, 0.0, None, C.c_void_p(out.data_ptr()), out.stride(0), out.stride(1),
+                                  C.c_void_p(work.data_ptr()), work.numel(), _stream()), "ggml_hip_attn_dev")
+    return out
+
+
 def quantize_rows(type, x):
     """x f32 [nrows, k] on the device -> uint8 [nrows, k/32*type_size] reference-format blocks."""
     assert x.is_cuda and x.dtype == torch.float32 and x.is_contiguous()

@@ -489,6 +489,70 @@ int ggml_hip_moe_combine_dev(const float *d_y, int64_t ldy, const float *d_weigh
  * d_silu may be NULL (a device caller has no node whose data must exist): only d_y is written. */
 int ggml_hip_silu_mul_rows_dev(const float *d_a, const float *d_b, float *d_silu, float *d_y, int64_t nrows, int64_t k, void *stream);
 
+/* ---------------- ATTENTION over an F16 or Q8_0 KV cache: rows into the cache, softmax(scale Q K^T + causal mask) V over it ----------------
+ * Upstream's ggml_flash_attn_ext, an EXTENSION like mul_mat_id (the reference has the op's id and no dispatch): device-resident entries only.
+ * With ggml_hip_rms_norm_mul_rows_dev, ggml_hip_mul_mat_multi_dev (q / k / v in one launch) and the add / scale epilogues these make a decoder
+ * layer's attention half out of device entries: projections -> kv_store -> attention -> output projection.  Both entries are stream-ordered on
+ * `stream` on the current device; they do not synchronize and do not allocate, and may be captured.  (Rope stays the host's.)
+ *
+ * THE CACHE.  kv_type is GGML_TYPE_F16 or GGML_TYPE_Q8_0, the same for K and V (anything else: GGML_HIP_ERR_TYPE).  A cache ROW is
+ * (position j, kv head hk): D elements in reference block format -- F16: 2 D bytes of IEEE halves, what ggml_cpy f32 -> f16 writes; Q8_0:
+ * D / 32 blocks of ggml_hip_type_size(Q8_0) = 36 bytes { f32 d; int8 qs[32] }, quantize_row_q8_0 (Ggml.cs:733-762) -- at byte offset
+ * j * nb_pos + hk * nb_head from d_k / d_v.  deq(row)[i] is the half widened, or (float)qs[i] * d in one binary32 rounding
+ * (ggml_hip_dequantize_rows_dev).  nb_pos and nb_head are multiples of 16 and at least a row's bytes; either may be the larger one.
+ *
+ * ggml_hip_kv_store_dev: n_rows f32 rows of row_elems elements (row i at d_src + i * ld; d_src 16-byte aligned, ld a multiple of 4 and
+ * >= row_elems) -> cache rows at d_cache + (p0 + i) * nb_pos, p0 = d_pos0 ? *d_pos0 (an int32 on the device, read by the kernel: a captured
+ * call appends at a new position on every replay) : pos0.  row_elems = n_head_kv * D where the heads of a position lie back to back
+ * (nb_head = a row's bytes), or D with one call per head otherwise (a Q8_0 cache of D = 64 has 72-byte rows: its heads are 80 apart, one call
+ * each).  Q8_0 (row_elems a multiple of 32): bit for bit ggml_hip_quantize_rows_dev(Q8_0), i.e. the oracle.  F16 (a multiple of 4): IEEE round
+ * to nearest even, subnormals kept, overflow to +-inf -- numpy's astype(float16).  A row whose position is < 0 or >= n_pos_max writes
+ * nothing, and no address is formed from it.  d_cache 16-byte aligned, nb_pos a multiple of 16 (GGML_HIP_ERR_SHAPE).
+ *
+ * ggml_hip_attn_dev:
+ *     dst[t][h][:] = sum over the VISIBLE j of p[t,h,j] * deq(V[j][h / G][:]),   p[t,h,.] = softmax_j(scale * q[t][h][:] . deq(K[j][h / G][:]))
+ *   q, dst: f32 [n_q][n_head][D] with element strides (ldq_tok, ldq_head) / (ldd_tok, ldd_head), 16-byte aligned, strides multiples of 4.
+ *   G = n_head / n_head_kv an integer in 1 .. 16 (upstream's broadcast), D 64 or 128: else GGML_HIP_ERR_SHAPE, as are misaligned strides.
+ *   VISIBLE: causal != 0: j < n_kv - n_q + t + 1 (the batch is the LAST n_q positions of the cache); causal == 0: j < n_kv.
+ *   n_kv: the host argument (0 .. n_kv_max), or, when d_n_kv != NULL, that int32 on the device clamped to [0, n_kv_max].  n_kv_max sizes
+ *   the launches and the work buffer and bounds every address; dst does not depend on it.  A captured decode step can therefore be
+ *   replayed while the cache grows: the same launches, a fixed number of them for a shape.
+ *   A query row with no visible position writes +0.0f.
+ *   REFUSED before anything is launched: a mask tensor, ALiBi (max_bias != 0), a soft-cap, sinks (GGML_HIP_ERR_ARG: pass NULL / 0).
+ *   d_work / work_bytes: ggml_hip_attn_work_size bytes; missing or short is GGML_HIP_ERR_ARG.  0 for n_q = 0 (which returns 0 and writes
+ *   nothing) and for the PROMPT form; monotone in n_kv_max.
+ *
+ * TWO FORMS, chosen from n_q alone (ggml_hip_attn_plan shows the choice; no device needed).  The positions are cut into CHUNKS of 128,
+ * chunk c = [128 c, 128 c + 128), for every kv_type and D -- never a function of the device, the grid, n_head or n_kv_max.
+ *   DECODE (n_q <= 8; all f32).  A workgroup serves one kv head and one chunk for ALL G * n_q query rows that share the kv head: each byte
+ *   of the cache is read once per launch.  Per (row, chunk): s_j = scale * dot(q, deq(K_j)) (an f32 fma chain over d ascending);
+ *   m = max s_j; p_j = expf(s_j - m); l = sum p_j (lane L of 64 holds p_L + p_(L+64), then a butterfly, lane distance 32 .. 1);
+ *   a[d] = p_0 deq(V_0)[d], then fma(p_j, deq(V_j)[d], a[d]) for j ascending.  A second launch merges a row's partials: M = max m_c,
+ *   b_c = expf(m_c - M), L and A[d] the fma chains of l_c b_c and a_c[d] b_c over c ASCENDING, dst = A / L.  No atomics; Q8_0 rows are read
+ *   as blocks and never expanded in memory.  An invisible position takes part in nothing.  One visible position: dst = deq(V_0) bit for bit.
+ *   dst[t][h] is bit for bit independent of n_head, of the strides, of n_kv_max, of where n_kv comes from and of n_q within the form.
+ *   PROMPT (n_q > 8; v_mfma_f32_32x32x16_f16).  A workgroup owns 128 query rows of one head and walks the chunks below the causal diagonal
+ *   (the others are skipped, the diagonal chunk is masked per element).  Q is rounded to f16; a Q8_0 row is dequantized to f16 while staged
+ *   ((float)q * d, then RNE); S = Q K^T and O += P V accumulate in f32; per chunk m' = max(m, max s_j), alpha = expf(m - m'),
+ *   P_j = f16(expf(s_j - m')), l = l alpha + sum of the ROUNDED P_j, O = O alpha + P V; dst = O / l.  One visible position: dst is the staged
+ *   V row bit for bit -- deq(V_0) for F16, f16(deq(V_0)) for Q8_0.  A masked weight is a zero operand here: the cache must hold finite values
+ *   below n_kv.
+ *   NEITHER form returns a V that is constant over the positions exactly: a and l round independently; that case is inside the tolerance. */
+enum { GGML_HIP_ATTN_DECODE = 1, GGML_HIP_ATTN_PROMPT = 2 };      /* ggml_hip_attn_plan_t.form */
+typedef struct ggml_hip_attn_plan_t {
+    int32_t form, chunk, q_tile, launches;   /* the form; positions per chunk; query rows per workgroup; launches of one call (2 / 1) */
+    int64_t n_chunks, workgroups;            /* ceil(n_kv_max / chunk); workgroups of the main launch */
+} ggml_hip_attn_plan_t;
+int    ggml_hip_kv_store_dev(int kv_type, const float *d_src, int64_t ld, int64_t n_rows, int64_t row_elems,
+                             void *d_cache, int64_t nb_pos, int64_t n_pos_max, int64_t pos0, const int32_t *d_pos0, void *stream);
+int    ggml_hip_attn_plan(int kv_type, int D, int n_head, int n_head_kv, int64_t n_q, int64_t n_kv_max, ggml_hip_attn_plan_t *out);
+size_t ggml_hip_attn_work_size(int kv_type, int D, int n_head, int n_head_kv, int64_t n_q, int64_t n_kv_max);
+int    ggml_hip_attn_dev(int kv_type, const float *d_q, int64_t ldq_tok, int64_t ldq_head,
+                         const void *d_k, const void *d_v, int64_t nb_pos, int64_t nb_head,
+                         int n_head, int n_head_kv, int D, int64_t n_q, int64_t n_kv, const int32_t *d_n_kv, int64_t n_kv_max,
+                         int causal, float scale, const void *d_mask, float max_bias, float logit_softcap, const float *d_sinks,
+                         float *d_dst, int64_t ldd_tok, int64_t ldd_head, void *d_work, size_t work_bytes, void *stream);
+
 #if defined(__GNUC__)
 #pragma GCC visibility pop
 #endif

@@ -82,6 +82,16 @@ internal static unsafe partial class GgmlHip
     [DllImport(Lib)] public static extern int ggml_hip_moe_combine_dev(float* dY, long ldy, float* dWeights, long nTokens, int nUsed, long m, float* dAddend, long ldAdd,
         float* dDst, long ldd, void* stream);
     [DllImport(Lib)] public static extern int ggml_hip_silu_mul_rows_dev(float* dA, float* dB, float* dSilu, float* dY, long nrows, long k, void* stream);
+    // ... attention over an F16 / Q8_0 KV cache (device entries, capturable): f32 rows into the cache at pos0 or at the int32 *dPos0 on the device;
+    // softmax(scale Q K^T + causal mask) V over it, n_kv from the host or from the int32 *dNKv on the device (clamped to nKvMax); no mask tensor,
+    // ALiBi, soft-cap or sinks (pass null / 0); the plan (form 1 decode, 2 prompt) and the work size need no device
+    [DllImport(Lib)] public static extern int ggml_hip_kv_store_dev(int kvType, float* dSrc, long ld, long nRows, long rowElems, void* dCache, long nbPos, long nPosMax,
+        long pos0, int* dPos0, void* stream);
+    [DllImport(Lib)] public static extern int ggml_hip_attn_plan(int kvType, int d, int nHead, int nHeadKv, long nQ, long nKvMax, void* plan);
+    [DllImport(Lib)] public static extern nuint ggml_hip_attn_work_size(int kvType, int d, int nHead, int nHeadKv, long nQ, long nKvMax);
+    [DllImport(Lib)] public static extern int ggml_hip_attn_dev(int kvType, float* dQ, long ldqTok, long ldqHead, void* dK, void* dV, long nbPos, long nbHead,
+        int nHead, int nHeadKv, int d, long nQ, long nKv, int* dNKv, long nKvMax, int causal, float scale, void* dMask, float maxBias, float logitSoftcap, float* dSinks,
+        float* dDst, long lddTok, long lddHead, void* dWork, nuint workBytes, void* stream);
 
     // Seam 2: the quantize_fns_t slots (TypeDefinitions.cs:334-342), type-indexed
     [DllImport(Lib)] public static extern int ggml_hip_quantize_row(int type, float* x, void* y, int k);
