@@ -69,6 +69,12 @@ bool contiguous_f32(const ggml_tensor *t) {
 namespace {
 bool has_min_plane(int t) { return t == GGML_TYPE_Q4_1 || t == GGML_TYPE_Q5_1 || t == GGML_TYPE_Q4_2; }   // Q4_2: its second scale
 bool has_qh_plane(int t) { return t == GGML_TYPE_Q5_0 || t == GGML_TYPE_Q5_1; }
+bool has_i8_planes(int t) { return t == GGML_TYPE_Q5_0 || t == GGML_TYPE_Q5_1 || t == GGML_TYPE_Q4_1 || t == GGML_TYPE_Q4_2; }   // int8 operand planes (gemm_qmp.hip)
+bool has_min_pieces(int t) { return t == GGML_TYPE_Q5_1 || t == GGML_TYPE_Q4_1; }                 // the min plane as three bf16 pieces (K3p-int8's min-term product)
+// a line of the reference's source belongs in a message about one of ITS types only
+const char *ref_cite(const wtype *r, const char *cite) { return r->id < GGML_TYPE_COUNT ? cite : ""; }
+// the row of the type a weight was uploaded as
+const wtype *weight_row(const ggml_hip_weight *w) { return wtype_of(ggml_hip_weight_type(w)); }
 }  // namespace
 
 // Kernel selection lives in plan.cpp (plan.h): ONE decision per product -- family, form, summation tree -- that every launcher consumes.
@@ -425,138 +431,77 @@ static DeviceCtx *call_slot() {
     return slot(b >= 0 ? b : 0);
 }
 
-static int alloc_weight(DeviceCtx *c, int type, int64_t K, int64_t M, ggml_hip_weight **out, int kq_type = 0, int up_type = 0) {
+// a weight of row r's resident form, its planes carved from one allocation (a plane the form does not have stays null)
+static int alloc_weight(DeviceCtx *c, const wtype *r, int64_t K, int64_t M, ggml_hip_weight **out) {
     ggml_hip_weight *w = new ggml_hip_weight();
     memset(w, 0, sizeof *w);
-    const bool kq = kq_type != 0;                           // (a k-quant weight: Q5_K / Q4_K in the planar Q5_1 form, Q6_K / Q3_K / Q2_K / IQ4_XS in the planar Q4_2 form)
-    w->ext_type = kq_type;
-    w->up_type = up_type;                                   // (IQ4_NL: type == Q8_0, the planes of a plain Q8_0 weight)
+    const int type = r->resident;
+    if (r->origin == WT_ORIGIN_EXT) w->ext_type = r->id;    // (a k-quant weight: Q5_K / Q4_K in the planar Q5_1 form, the two-scale types in the planar Q4_2 form)
+    if (r->origin == WT_ORIGIN_UP) w->up_type = r->id;      // (IQ4_NL: type == Q8_0, the planes of a plain Q8_0 weight)
     static std::atomic<uint64_t> next_uid{1};
     w->type = type; w->M = M; w->K = K; w->Mpad = pad_rows(M > 0 ? M : 1); w->device = c->device; w->uid = next_uid.fetch_add(1);
-    size_t off_qs = 0, off_d = 0, off_m = 0, off_qh = 0, off_6a = 0, off_6b = 0, off_kh = 0, off_gs = 0, off_i8 = 0, off_mp = 0, total = 0;
-    bool with6 = false;
-    size_t off_p16 = 0;
-    if (type == GGML_TYPE_F32 || is_dense16(type)) {
+    const bool dense = type == GGML_TYPE_F32 || is_dense16(type);
+    constexpr size_t NONE = ~(size_t)0;
+    size_t total = 0;
+    auto take = [&](bool have, size_t bytes) { if (!have) return NONE; const size_t off = total; total += bytes; return off; };
+    size_t off_p = NONE, off_qs = NONE, off_d = NONE, off_m = NONE, off_qh = NONE, off_gs = NONE, off_i8 = NONE, off_mp = NONE, off_kh = NONE, off_6a = NONE, off_6b = NONE;
+    if (dense) {
         total = ((size_t)w->Mpad * K * (type == GGML_TYPE_F32 ? 4 : 2) + 255) / 256 * 256;
-        if (is_dense16(type)) {        // k-panel copy for the f16 / bf16 MFMA kernels (dense16.hip)
-            off_p16 = total;
-            total += (size_t)(dense16_kpad(K) / 8 + DENSE16_SPARE_PANELS) * w->Mpad * 16;
-        } else {                       // the rows as three bf16 pieces per element (dense16.hip K10d)
-            off_p16 = total;
-            total += (size_t)(dense16_kpad(K) / 8 * 3 + DENSE32_SPARE_PANELS) * w->Mpad * 16;
-        }
+        // F16 / BF16: the k-panel copy for the MFMA kernels; F32: the rows as three bf16 pieces per element (dense16.hip K10d)
+        off_p = take(true, (size_t)(is_dense16(type) ? dense16_kpad(K) / 8 + DENSE16_SPARE_PANELS : dense16_kpad(K) / 8 * 3 + DENSE32_SPARE_PANELS) * w->Mpad * 16);
     } else {
         w->nbk = K / QK;
-        const int64_t nba = pad_kblocks(w->nbk) + K_LOOKAHEAD;   // allocated k-blocks (zero past the real end)
-        // (Q6_K / Q3_K live in the planar Q4_2 form on its int8 planes alone -- no kernel they are planned onto reads the nibble plane: a stub)
-        const size_t qs_bytes = kq && kquant_two_scale(kq_type) ? 256 : (size_t)nba * w->Mpad * (type == GGML_TYPE_Q8_0 ? 32 : 16);
-        const size_t plane = (size_t)nba * w->Mpad * 4;
-        off_qs = 0; total = qs_bytes;
-        off_d = total; total += plane;
-        if (has_min_plane(type)) { off_m = total; total += plane; }
-        if (has_qh_plane(type)) { off_qh = total; total += plane; }
-        off_gs = total; total += (size_t)w->nbk * w->Mpad * 4 * gemv_side_planes(type);       // the mat-vec's tile-major copy of d / m / qh
+        const size_t nba = (size_t)(pad_kblocks(w->nbk) + K_LOOKAHEAD);   // allocated k-blocks (zero past the real end)
+        const size_t plane = nba * w->Mpad * 4;
+        // (the two-scale form lives on the int8 planes alone -- no kernel it is planned onto reads the nibble plane: a stub)
+        off_qs = take(true, r->own_i8 ? 256 : nba * w->Mpad * (type == GGML_TYPE_Q8_0 ? 32 : 16));
+        off_d = take(true, plane);
+        off_m = take(has_min_plane(type), plane);
+        off_qh = take(has_qh_plane(type), plane);
+        off_gs = take(true, (size_t)w->nbk * w->Mpad * 4 * gemv_side_planes(type));       // the mat-vec's tile-major copy of d / m / qh
+        off_i8 = take(has_i8_planes(type), nba * w->Mpad * 32);                           // zero past the end of K
+        off_mp = take(has_min_pieces(type), (size_t)((w->nbk + 15) / 16 * 2 * 3) * w->Mpad * 16);   // whole pairs of k-groups, zero past the end of K
+        off_kh = take(r->hdr_slot != 0, (size_t)(w->nbk / 8 + 1) * w->Mpad * r->hdr_slot);  // super-block headers, for the byte-exact download
+        // bf6 operand planes of the MX mat-mat kernel: 0.75 B / weight and digit (Q5_0, Q8_0: two digits)
         const bool q4 = type == GGML_TYPE_Q4_0 || type == GGML_TYPE_Q4_1;
-        with6 = q4 || (plan_force_gemm() == 3 && (type == GGML_TYPE_Q5_0 || type == GGML_TYPE_Q8_0));
-        if (type == GGML_TYPE_Q5_0 || type == GGML_TYPE_Q5_1 || type == GGML_TYPE_Q4_1 || type == GGML_TYPE_Q4_2) { off_i8 = total; total += (size_t)nba * w->Mpad * 32; }   // int8 operand planes (gemm_qmp.hip), zero past the end of K
-        // the min plane as three bf16 pieces (K3p-int8's min-term product): whole pairs of k-groups, zero past the end of K
-        if (type == GGML_TYPE_Q5_1 || type == GGML_TYPE_Q4_1) { off_mp = total; total += (size_t)((w->nbk + 15) / 16 * 2 * 3) * w->Mpad * 16; }
-        if (kq) { off_kh = total; total += (size_t)(w->nbk / 8 + 1) * w->Mpad * kquant_hdr_bytes(kq_type); }   // super-block headers, for the byte-exact download
-        if (with6) {   // bf6 operand planes of the MX mat-mat kernel: 0.75 B / weight and digit (Q5_0, Q8_0: two digits)
-            const size_t nf = q4 ? 1 : 2;
-            off_6a = total; total += (size_t)nba * nf * w->Mpad * 16;
-            off_6b = total; total += (size_t)nba * nf * w->Mpad * 8;
-        }
+        const bool with6 = q4 || (plan_force_gemm() == 3 && (type == GGML_TYPE_Q5_0 || type == GGML_TYPE_Q8_0));
+        off_6a = take(with6, nba * (q4 ? 1 : 2) * w->Mpad * 16);
+        off_6b = take(with6, nba * (q4 ? 1 : 2) * w->Mpad * 8);
     }
     if (total == 0) total = 16;
     void *base = nullptr;
     hipError_t e = hipMalloc(&base, total);
     if (e != hipSuccess) { delete w; return fail(GGML_HIP_ERR_RUNTIME, "hipMalloc(%zu): %s", total, hipGetErrorString(e)); }
     w->bytes = total;
-    if (type == GGML_TYPE_F32 || is_dense16(type)) {
+    auto at = [&](size_t off) { return off == NONE ? nullptr : (uint8_t *)base + off; };
+    if (dense) {
         w->dense = base;
-        if (is_dense16(type)) w->p16 = (uint8_t *)base + off_p16;
-        else w->p32 = (uint8_t *)base + off_p16;
-    } else {
-        w->qs = (uint8_t *)base + off_qs;
-        w->d = (float *)((uint8_t *)base + off_d);
-        if (has_min_plane(type)) w->m = (float *)((uint8_t *)base + off_m);
-        if (has_qh_plane(type)) w->qh = (uint32_t *)((uint8_t *)base + off_qh);
-        w->gs = (uint32_t *)((uint8_t *)base + off_gs);
-        if (with6) { w->q6a = (uint8_t *)base + off_6a; w->q6b = (uint8_t *)base + off_6b; }
-        if (kq) w->khdr = (uint8_t *)base + off_kh;
-        if (type == GGML_TYPE_Q5_0 || type == GGML_TYPE_Q5_1 || type == GGML_TYPE_Q4_1 || type == GGML_TYPE_Q4_2) w->i8p = (uint8_t *)base + off_i8;
-        if (type == GGML_TYPE_Q5_1 || type == GGML_TYPE_Q4_1) w->mp3 = (uint8_t *)base + off_mp;
+        (is_dense16(type) ? w->p16 : w->p32) = at(off_p);
     }
+    w->qs = at(off_qs); w->d = (float *)at(off_d); w->m = (float *)at(off_m); w->qh = (uint32_t *)at(off_qh); w->gs = (uint32_t *)at(off_gs);
+    w->i8p = at(off_i8); w->mp3 = at(off_mp); w->khdr = at(off_kh); w->q6a = at(off_6a); w->q6b = at(off_6b);
     *out = w;
     return GGML_HIP_OK;
 }
 
 static void *weight_base(const ggml_hip_weight *w) { return w->dense ? w->dense : (void *)w->qs; }
 
+// One sequence for every type, driven by its row: the file-format rows (staged to the device when they are the host's) go through the row's
+// converter into the resident planes, then the operand images built from those planes -- each pass a no-op on a weight without the plane it fills.
 int make_weight(DeviceCtx *c, int type, const void *rows, bool rows_on_host, int64_t ne00, int64_t ne01, uint64_t nb01,
                 int64_t row_begin, int64_t row_end, hipStream_t st, ggml_hip_weight **out) {
     if (!out) return fail(GGML_HIP_ERR_ARG, "out is null");
     *out = nullptr;
-    // Q5_K (unpinned extra, kquants.hip): super-blocks of 256 are re-laid-out as eight k-blocks of the planar Q5_1 form
-    // (r4: Q4_K the same way -- its super-block is Q5_K's without the fifth-bit bytes; the fifth-bit plane stays zero; Q6_K and Q3_K in the
-    // planar Q4_2 form on int8 planes, each by its own converter)
-    const bool kq = is_kquant(type);
-    if (kq) {
-        if (!rows || ne00 <= 0 || ne01 < 0 || row_begin < 0 || row_end < row_begin || row_end > ne01) return fail(GGML_HIP_ERR_ARG, "bad weight arguments");
-        if (ne00 % 256 != 0) return fail(GGML_HIP_ERR_SHAPE, "k-quants: ne00 %% 256 != 0 (QK_K)");
-        if (nb01 < (uint64_t)(ne00 / 256) * kquant_bytes(type)) return fail(GGML_HIP_ERR_SHAPE, "nb01 smaller than a row");
-        int rc = c ? GGML_HIP_OK : ensure_init();
-        if (rc) return rc;
-        if (!c) c = call_slot();
-        rc = c->make_current();
-        if (rc) return rc;
-        const int64_t rows_n = row_end - row_begin;
-        const uint64_t rb = (uint64_t)(ne00 / 256) * kquant_bytes(type);
-        ggml_hip_weight *w = nullptr;
-        const bool two_scale = kquant_two_scale(type);         // (the planar Q4_2 form on int8 planes: kquants.hip)
-        auto to_planar = [&](const uint8_t *src, uint64_t pitch, int64_t first) {
-            return type == GGML_HIP_TYPE_Q6_K ? launch_q6k_to_planar(src, pitch, first, rows_n, w, st)
-                   : type == GGML_HIP_TYPE_Q3_K ? launch_q3k_to_planar(src, pitch, first, rows_n, w, st)
-                   : type == GGML_HIP_TYPE_Q2_K ? launch_q2k_to_planar(src, pitch, first, rows_n, w, st)
-                   : type == GGML_HIP_TYPE_IQ4_XS ? launch_iq4xs_to_planar(src, pitch, first, rows_n, w, st)
-                                                : launch_q5k_to_planar(type, src, pitch, first, rows_n, w, st);
-        };
-        rc = alloc_weight(c, kquant_resident_type(type), ne00, rows_n, &w, type);
-        if (rc) return rc;
-        hipError_t e = hipMemsetAsync(w->qs, 0, w->bytes, st);
-        void *staging = nullptr;
-        if (e == hipSuccess && rows_on_host && rows_n > 0) {
-            e = hipMalloc(&staging, (size_t)rows_n * rb);
-            if (e == hipSuccess)
-                e = hipMemcpy2DAsync(staging, rb, (const uint8_t *)rows + (uint64_t)row_begin * nb01, nb01, rb, (size_t)rows_n, hipMemcpyHostToDevice, st);
-            if (e == hipSuccess) e = to_planar((const uint8_t *)staging, rb, 0);
-        } else if (e == hipSuccess) {
-            e = to_planar((const uint8_t *)rows, nb01, row_begin);
-        }
-        if (e == hipSuccess && !two_scale) e = launch_q5_to_i8(w, st);      // (the planar Q5_1 form's int8 operand planes: gemm_qmp.hip serves prompt-sized batches; Q6_K's / Q3_K's converters write them themselves)
-        if (e == hipSuccess && !two_scale) e = launch_min_pieces(w, st);
-        if (e == hipSuccess) e = launch_gemv_side_image(w, st);
-        if (e == hipSuccess) e = hipStreamSynchronize(st);
-        if (staging) (void)hipFree(staging);
-        if (e != hipSuccess) { (void)hipFree(w->qs); delete w; return fail(GGML_HIP_ERR_RUNTIME, "k-quant weight upload: %s", hipGetErrorString(e)); }
-        *out = w;
-        return GGML_HIP_OK;
-    }
-    // (BF16, an extension type: block 1, 2 bytes, the F16 resident form -- w->type keeps 130, ext_type stays 0)
-    // (IQ4_NL, an extension type: after the codebook lookup a plain Q8_0 weight -- w->type = Q8_0, up_type remembers IQ4_NL; iq4.hip)
-    const bool nl = is_iq4nl(type);
-    const int up = type;
-    if (nl) type = GGML_TYPE_Q8_0;
-    if (!is_bf16(type) && (type < 0 || type >= GGML_TYPE_COUNT || !weight_type_ok(type)))
+    const wtype *r = wtype_of(type);
+    if (!r || !r->to_planar)
         return fail(GGML_HIP_ERR_TYPE, "type %d is not a supported weight type (Q4_3/Q8_1 have null slots, Ggml.cs:248,278-282)", type);
     if (!rows || ne00 <= 0 || ne01 < 0 || row_begin < 0 || row_end < row_begin || row_end > ne01)
         return fail(GGML_HIP_ERR_ARG, "bad weight arguments");
-    if (!is_bf16(type) && (ne00 % BLCK[type] != 0 || (is_q(type) && ne00 % QK != 0)))   // every dot product runs against 32-element Q8 blocks
-        return fail(GGML_HIP_ERR_SHAPE, "ne00 %% %d != 0 (Ggml.cs:6694)", is_q(type) ? QK : BLCK[type]);
-    const uint64_t row_bytes = is_bf16(type) ? 2 * (uint64_t)ne00 : nl ? 18 * (uint64_t)(ne00 / QK) : (uint64_t)TSIZE[type] * (uint64_t)(ne00 / BLCK[type]);
+    if (ne00 % k_unit(r) != 0) return fail(GGML_HIP_ERR_SHAPE, "ne00 %% %d != 0%s", (int)k_unit(r), ref_cite(r, " (Ggml.cs:6694)"));
+    const uint64_t row_bytes = (uint64_t)r->bytes * (uint64_t)(ne00 / r->blck);
     if (nb01 < row_bytes) return fail(GGML_HIP_ERR_SHAPE, "nb01 smaller than a row (transposed src0, Ggml.cs:8229)");
-    if (!rows_on_host && (type == GGML_TYPE_F32 || is_dense16(type)) && (nb01 % 2 != 0 || ((uintptr_t)rows & 1)))
+    const bool dense = r->resident == GGML_TYPE_F32 || is_dense16(r->resident);
+    if (!rows_on_host && dense && (nb01 % 2 != 0 || ((uintptr_t)rows & 1)))
         return fail(GGML_HIP_ERR_SHAPE, "dense device rows must be 2-byte aligned");
     int rc = c ? GGML_HIP_OK : ensure_init();
     if (rc) return rc;
@@ -565,25 +510,21 @@ int make_weight(DeviceCtx *c, int type, const void *rows, bool rows_on_host, int
     if (rc) return rc;
     const int64_t rows_n = row_end - row_begin;
     ggml_hip_weight *w = nullptr;
-    rc = alloc_weight(c, type, ne00, rows_n, &w, 0, nl ? up : 0);
+    rc = alloc_weight(c, r, ne00, rows_n, &w);
     if (rc) return rc;
     hipError_t e = hipMemsetAsync(weight_base(w), 0, w->bytes, st);
-    const uint8_t *dev_rows = (const uint8_t *)rows;
     void *staging = nullptr;
-    auto to_planar = [&](const uint8_t *src, uint64_t pitch, int64_t first) {   // (IQ4_NL: its own converter onto Q8_0's planes)
-        return nl ? launch_iq4nl_to_planar(src, pitch, first, rows_n, w, st) : launch_repack_to_planar(type, src, pitch, first, rows_n, w, st);
-    };
     if (e == hipSuccess && rows_on_host && rows_n > 0) {
         e = hipMalloc(&staging, (size_t)rows_n * row_bytes);
         if (e == hipSuccess)
             e = hipMemcpy2DAsync(staging, row_bytes, (const uint8_t *)rows + (uint64_t)row_begin * nb01, nb01, row_bytes,
                                  (size_t)rows_n, hipMemcpyHostToDevice, st);
-        if (e == hipSuccess) e = to_planar((const uint8_t *)staging, row_bytes, 0);
+        if (e == hipSuccess) e = r->to_planar(type, (const uint8_t *)staging, row_bytes, 0, rows_n, w, st);
     } else if (e == hipSuccess) {
-        e = to_planar(dev_rows, nb01, row_begin);
+        e = r->to_planar(type, (const uint8_t *)rows, nb01, row_begin, rows_n, w, st);
     }
     if (e == hipSuccess) e = launch_nibbles_to_bf6(w, st);
-    if (e == hipSuccess) e = launch_q5_to_i8(w, st);
+    if (e == hipSuccess && !r->own_i8) e = launch_q5_to_i8(w, st);      // (the two-scale converters write the int8 planes themselves)
     if (e == hipSuccess) e = launch_min_pieces(w, st);
     if (e == hipSuccess) e = launch_gemv_side_image(w, st);
     if (e == hipSuccess) e = launch_f16_rows_to_panels(w, st);
@@ -613,12 +554,8 @@ using namespace ghip;
 
 extern "C" {
 
-int ggml_hip_blck_size(int type) {
-    return is_kquant(type) ? 256 : is_bf16(type) ? 1 : is_iq4nl(type) ? 32 : (type >= 0 && type < GGML_TYPE_COUNT) ? BLCK[type] : 0;
-}
-size_t ggml_hip_type_size(int type) {
-    return is_kquant(type) ? kquant_bytes(type) : is_bf16(type) ? 2 : is_iq4nl(type) ? 18 : (type >= 0 && type < GGML_TYPE_COUNT) ? TSIZE[type] : 0;
-}
+int ggml_hip_blck_size(int type) { const wtype *r = wtype_of(type); return r ? r->blck : 0; }
+size_t ggml_hip_type_size(int type) { const wtype *r = wtype_of(type); return r ? r->bytes : 0; }
 
 int ggml_hip_device_count(void) {
     int n = 0;
@@ -692,18 +629,12 @@ int ggml_hip_weight_download(const ggml_hip_weight *w, void *host_rows, void *st
     rc = weight_device_current(w);
     if (rc) return rc;
     hipStream_t st = (hipStream_t)stream;
-    const int ut = ggml_hip_weight_type(w);                 // (the uploaded type: IQ4_NL's rows are not its resident Q8_0's)
-    const size_t row_bytes = ggml_hip_type_size(ut) * (size_t)(w->K / ggml_hip_blck_size(ut));
-    const size_t total = row_bytes * (size_t)w->M;
+    const wtype *r = weight_row(w);                         // (the uploaded type: IQ4_NL's rows are not its resident Q8_0's)
+    const size_t total = r->bytes * (size_t)(w->K / r->blck) * (size_t)w->M;
     if (total == 0) return GGML_HIP_OK;
     void *staging = nullptr;
     HIP_TRY(hipMalloc(&staging, total));
-    hipError_t e = w->ext_type == GGML_HIP_TYPE_Q6_K ? launch_planar_to_q6k(w, (uint8_t *)staging, st)
-                   : w->ext_type == GGML_HIP_TYPE_Q3_K ? launch_planar_to_q3k(w, (uint8_t *)staging, st)
-                   : w->ext_type == GGML_HIP_TYPE_Q2_K ? launch_planar_to_q2k(w, (uint8_t *)staging, st)
-                   : w->ext_type == GGML_HIP_TYPE_IQ4_XS ? launch_planar_to_iq4xs(w, (uint8_t *)staging, st)
-                   : w->ext_type != 0 ? launch_planar_to_q5k(w, (uint8_t *)staging, st)
-                   : is_iq4nl(w->up_type) ? launch_planar_to_iq4nl(w, (uint8_t *)staging, st) : launch_planar_to_aos(w, (uint8_t *)staging, st);
+    hipError_t e = r->from_planar(w, (uint8_t *)staging, st);
     if (e == hipSuccess) e = hipMemcpyAsync(host_rows, staging, total, hipMemcpyDeviceToHost, st);
     if (e == hipSuccess) e = hipStreamSynchronize(st);
     (void)hipFree(staging);
@@ -726,8 +657,7 @@ int ggml_hip_weight_type(const ggml_hip_weight *w) { return w ? (w->up_type ? w-
 
 size_t ggml_hip_mul_mat_work_size(int type, int64_t K, int64_t N) {
     if (K <= 0 || N <= 0) return 0;
-    if (is_kquant(type)) type = kquant_resident_type(type);     // same operand images
-    if (is_iq4nl(type)) type = GGML_TYPE_Q8_0;
+    if (const wtype *r = wtype_of(type)) type = r->resident;    // same operand images
     if (is_dense16(type)) return (size_t)dense16_kpad(K) * (size_t)pad_act(N) * 2;   // src1 as Half (Ggml.cs:3356-3357), padded (BF16: as bf16)
     if (type == GGML_TYPE_F32) return N > 256 ? (size_t)dense16_kpad(K) * (size_t)pad_act(N) * 6 : 0;   // src1 as three bf16 pieces (dense16.hip K10d; the reference needs none)
     if (!is_q(type)) return 0;
@@ -754,25 +684,24 @@ int ggml_hip_mul_mat_init_dev(const ggml_hip_weight *w, const float *d_src1, int
     rc = weight_device_current(w);
     if (rc) return rc;
     act_planes p = act_carve(d_work, w->K, pad_act(N));
-    HIP_TRY(launch_quantize_act(d_src1, N, w->K, ld1, p, weight_image_kind(w, N), (hipStream_t)stream,
-                                w->ext_type != 0));                      // k-quant weights: the Q8_K rule (one scale per 256)
+    HIP_TRY(launch_quantize_act(d_src1, N, w->K, ld1, p, weight_image_kind(w, N), (hipStream_t)stream, weight_row(w)->q8k));
     return GGML_HIP_OK;
 }
 
 int ggml_hip_act_image_kind(int type, int64_t K, int64_t N) {
-    return act_image_kind(is_kquant(type) ? kquant_resident_type(type) : is_bf16(type) ? GGML_TYPE_F16 : is_iq4nl(type) ? GGML_TYPE_Q8_0 : type,
-                          K, N);   // (BF16: F16's answer; IQ4_NL: Q8_0's)
+    const wtype *r = wtype_of(type);
+    const int t = r ? r->resident : type;
+    return act_image_kind(is_dense16(t) ? GGML_TYPE_F16 : t, K, N);   // (BF16: F16's answer)
 }
 void ggml_hip_debug_force_gemm(int which) { plan_set_force_gemm(which); }
 
 // the plan of mul_mat(type, M, K, N) as ggml_hip_mul_mat_dev will run it; no device is needed (tests/test_plan_cpu.py)
 int ggml_hip_mm_plan(int type, int64_t M, int64_t K, int64_t N, ggml_hip_mm_plan_t *out) {
     if (!out) return fail(GGML_HIP_ERR_ARG, "out is null");
-    const bool kq = is_kquant(type);
-    const int t = kq ? kquant_resident_type(type) : is_iq4nl(type) ? GGML_TYPE_Q8_0 : type;   // (IQ4_NL: a plain Q8_0 weight)
-    if (!is_bf16(t) && (t < 0 || t >= GGML_TYPE_COUNT || !weight_type_ok(t))) return fail(GGML_HIP_ERR_TYPE, "type %d is not a supported weight type", type);
-    if (M <= 0 || K <= 0 || N <= 0 || K % ggml_hip_blck_size(t) != 0 || (is_q(t) && K % QK != 0) || (kq && K % 256 != 0)) return fail(GGML_HIP_ERR_SHAPE, "bad shape");
-    const mm_plan p = plan_mul_mat(t, kq ? type : 0, M, K, N, true);
+    const wtype *r = wtype_of(type);
+    if (!r || !r->to_planar) return fail(GGML_HIP_ERR_TYPE, "type %d is not a supported weight type", type);
+    if (M <= 0 || K <= 0 || N <= 0 || K % k_unit(r) != 0) return fail(GGML_HIP_ERR_SHAPE, "bad shape");
+    const mm_plan p = plan_mul_mat(r->resident, wtype_ext(r), M, K, N, true);
     out->family = p.family; out->image_kind = p.image | ((p.flags & MM_FLAG_MIN_PIECES) ? ACT_IMAGE_MIN_PIECES : 0); out->form = p.form; out->tree_id = plan_tree_id(p);
     out->ksplit = p.ksplit; out->kstyle = p.kstyle; out->kunit = p.kunit; out->arith = p.arith;
     out->tile_m = p.tile_m; out->tile_n = p.tile_n; out->waves = p.waves; out->tiles_per_wave = p.tiles_per_wave;
@@ -1111,60 +1040,23 @@ int ggml_hip_rms_norm_mul_rows_dev(const float *d_x, const float *d_g, float *d_
 int ggml_hip_quantize_rows_dev(int type, const float *d_x, int64_t nrows, int64_t k, void *d_blocks, void *stream) {
     if (nrows <= 0) return GGML_HIP_OK;  // empty input: nothing to do (buffers may be null)
     if (!d_x || !d_blocks) return fail(GGML_HIP_ERR_ARG, "null argument");
-    if (is_bf16(type)) {                                        // f32 -> bf16 by the one rule (dense16.hip; include/ggml_hip_ext.h)
-        if (k <= 0) return fail(GGML_HIP_ERR_SHAPE, "k <= 0");
-        HIP_TRY(launch_f32_to_bf16_rows(d_x, nrows * k, (uint16_t *)d_blocks, (hipStream_t)stream));
-        return GGML_HIP_OK;
-    }
-    if (is_kquant(type)) {                                      // unpinned extra (kquants.hip, r4)
-        if (k % 256 != 0) return fail(GGML_HIP_ERR_SHAPE, "k-quants: k %% 256 != 0");
-        if (((uintptr_t)d_x & 15) != 0) return fail(GGML_HIP_ERR_SHAPE, "k-quants: the rows must be 16-byte aligned");
-        if (type == GGML_HIP_TYPE_Q6_K) HIP_TRY(launch_quantize_q6k(d_x, nrows, k, d_blocks, (hipStream_t)stream));
-        else if (type == GGML_HIP_TYPE_Q3_K) HIP_TRY(launch_quantize_q3k(d_x, nrows, k, d_blocks, (hipStream_t)stream));
-        else if (type == GGML_HIP_TYPE_Q2_K) HIP_TRY(launch_quantize_q2k(d_x, nrows, k, d_blocks, (hipStream_t)stream));
-        else if (type == GGML_HIP_TYPE_IQ4_XS) HIP_TRY(launch_quantize_iq4(type, d_x, nrows, k, d_blocks, (hipStream_t)stream));
-        else HIP_TRY(launch_quantize_kq(type, d_x, nrows, k, d_blocks, (hipStream_t)stream));
-        return GGML_HIP_OK;
-    }
-    if (is_iq4nl(type)) {                                       // unpinned extra (iq4.hip)
-        if (k % QK != 0) return fail(GGML_HIP_ERR_SHAPE, "IQ4_NL: k %% 32 != 0");
-        if (((uintptr_t)d_x & 15) != 0) return fail(GGML_HIP_ERR_SHAPE, "IQ4_NL: the rows must be 16-byte aligned");
-        HIP_TRY(launch_quantize_iq4(type, d_x, nrows, k, d_blocks, (hipStream_t)stream));
-        return GGML_HIP_OK;
-    }
-    if (!(wq_ok(type) || type == GGML_TYPE_Q8_1))
-        return fail(GGML_HIP_ERR_TYPE, "quantize: unsupported type %d", type);
-    if (k % QK != 0) return fail(GGML_HIP_ERR_SHAPE, "k %% 32 != 0 (Ggml.cs:336)");
-    HIP_TRY(launch_quantize_rows(type, GGML_TYPE_F32, d_x, k, nrows, k, d_blocks, (hipStream_t)stream));
+    const wtype *r = wtype_of(type);
+    if (!r || !r->quantize) return fail(GGML_HIP_ERR_TYPE, "quantize: unsupported type %d", type);
+    if (r->blck == 1 && k <= 0) return fail(GGML_HIP_ERR_SHAPE, "k <= 0");
+    if (k % k_unit(r) != 0) return fail(GGML_HIP_ERR_SHAPE, "k %% %d != 0%s", (int)k_unit(r), ref_cite(r, " (Ggml.cs:336)"));
+    if (r->x_align && ((uintptr_t)d_x & (uintptr_t)(r->x_align - 1)) != 0) return fail(GGML_HIP_ERR_SHAPE, "the rows must be %d-byte aligned", r->x_align);
+    HIP_TRY(r->quantize(type, d_x, nrows, k, d_blocks, (hipStream_t)stream));
     return GGML_HIP_OK;
 }
 
 int ggml_hip_dequantize_rows_dev(int type, const void *d_blocks, int64_t nrows, int64_t k, float *d_y, void *stream) {
     if (nrows <= 0) return GGML_HIP_OK;
     if (!d_y || !d_blocks) return fail(GGML_HIP_ERR_ARG, "null argument");
-    if (is_bf16(type)) {                                        // bf16 -> f32, exact
-        if (k <= 0) return fail(GGML_HIP_ERR_SHAPE, "k <= 0");
-        HIP_TRY(launch_bf16_to_f32_rows((const uint16_t *)d_blocks, nrows * k, d_y, (hipStream_t)stream));
-        return GGML_HIP_OK;
-    }
-    if (is_kquant(type)) {                                      // unpinned extra (kquants.hip)
-        if (k % 256 != 0) return fail(GGML_HIP_ERR_SHAPE, "k-quants: k %% 256 != 0");
-        if (type == GGML_HIP_TYPE_Q6_K) HIP_TRY(launch_dequantize_q6k(d_blocks, nrows, k, d_y, (hipStream_t)stream));
-        else if (type == GGML_HIP_TYPE_Q3_K) HIP_TRY(launch_dequantize_q3k(d_blocks, nrows, k, d_y, (hipStream_t)stream));
-        else if (type == GGML_HIP_TYPE_Q2_K) HIP_TRY(launch_dequantize_q2k(d_blocks, nrows, k, d_y, (hipStream_t)stream));
-        else if (type == GGML_HIP_TYPE_IQ4_XS) HIP_TRY(launch_dequantize_iq4(type, d_blocks, nrows, k, d_y, (hipStream_t)stream));
-        else HIP_TRY(launch_dequantize_q5k(type, d_blocks, nrows, k, d_y, (hipStream_t)stream));
-        return GGML_HIP_OK;
-    }
-    if (is_iq4nl(type)) {                                       // unpinned extra (iq4.hip)
-        if (k % QK != 0) return fail(GGML_HIP_ERR_SHAPE, "IQ4_NL: k %% 32 != 0");
-        HIP_TRY(launch_dequantize_iq4(type, d_blocks, nrows, k, d_y, (hipStream_t)stream));
-        return GGML_HIP_OK;
-    }
-    if (!wq_ok(type))
-        return fail(GGML_HIP_ERR_TYPE, "dequantize: unsupported type %d (Q8_1 slot is null, Ggml.cs:278)", type);
-    if (k % QK != 0) return fail(GGML_HIP_ERR_SHAPE, "k %% 32 != 0 (Ggml.cs:839)");
-    HIP_TRY(launch_dequantize_rows(type, d_blocks, nrows, k, d_y, (hipStream_t)stream));
+    const wtype *r = wtype_of(type);
+    if (!r || !r->dequantize) return fail(GGML_HIP_ERR_TYPE, "dequantize: unsupported type %d (Q8_1 slot is null, Ggml.cs:278)", type);
+    if (r->blck == 1 && k <= 0) return fail(GGML_HIP_ERR_SHAPE, "k <= 0");
+    if (k % k_unit(r) != 0) return fail(GGML_HIP_ERR_SHAPE, "k %% %d != 0%s", (int)k_unit(r), ref_cite(r, " (Ggml.cs:839)"));
+    HIP_TRY(r->dequantize(type, d_blocks, nrows, k, d_y, (hipStream_t)stream));
     return GGML_HIP_OK;
 }
 

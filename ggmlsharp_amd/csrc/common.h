@@ -74,9 +74,11 @@ struct ggml_hip_weight {
     uint8_t *mp3;     // Q5_1 / Q4_1 (and the Q5_K extension living in the Q5_1 form): the min plane split EXACTLY into three bf16 pieces,
                       //   [ceil(nbk / 8) * 3 (+ pad to whole pairs of k-groups)][Mpad][16 B]: plane 3 * (b / 8) + piece holds 8 consecutive k-blocks of a row --
                       //   the B operand of v_mfma_f32_32x32x16_bf16 for K3p's min-term product (gemm_qmp.hip); 0.19 B / weight
-    uint8_t *khdr;    // k-quants only (kquant_hdr_bytes; Q6_K: 32 B per super-block, scales[16] + d; Q2_K: 32 B, scales[16] + d + dmin; Q3_K: scales[12] + d): the 16 header bytes (d, dmin, scales[12]) of every super-block, [K/256][Mpad][16 B]
-    int      ext_type; // 0, or GGML_HIP_TYPE_Q5_K / _Q4_K (type == Q5_1) / _Q6_K / _Q3_K / _Q2_K / _IQ4_XS (type == Q4_2): the weight was uploaded as k-quant super-blocks and lives in the planar Q5_1 form (type == Q5_1)
-    int      up_type;  // 0, or GGML_HIP_TYPE_IQ4_NL: uploaded as that type and resident as a PLAIN Q8_0 weight (type == Q8_0, ext_type == 0; iq4.hip) --
+    uint8_t *khdr;    // types with a wtype::hdr_slot only: the header bytes of every super-block that the planes do not hold, for the byte-exact download (and
+                      //   Q2_K's min pass), [K/256][Mpad][hdr_slot B]
+    int      ext_type; // 0, or the id of a WT_ORIGIN_EXT row of the type table (wtypes.cpp): the weight was uploaded as that type's super-blocks and lives in the
+                       //   planar form of the row's resident type (`type`); the plan sees it
+    int      up_type;  // 0, or the id of a WT_ORIGIN_UP row (IQ4_NL): uploaded as that type and resident as a PLAIN weight of `type` (Q8_0, ext_type == 0; iq4.hip) --
                        //   read by the download, ggml_hip_weight_type and the size queries alone, never by the plan or a kernel
     size_t   bytes;
     int      device;
@@ -294,60 +296,45 @@ hipError_t launch_push_columns(const float *src, int64_t lds, int64_t N, int64_t
                                int64_t col0, hipStream_t st);
 // quantize.hip
 hipError_t launch_quantize_act(const float *x, int64_t N, int64_t K, int64_t ld1, act_planes p, int image, hipStream_t st, bool q8k = false);
-// kquants.hip (Q5_K as an unpinned extra: the published upstream format, no oracle in the reference)
-// (r4: Q4_K beside it -- the same super-block without the fifth-bit bytes: `kq_type` = GGML_HIP_TYPE_Q5_K or _Q4_K; a weight's own ext_type)
-// (IQ4_XS, iq4.hip: a super-block of 256 with its activations by the Q8_K rule -- a k-quant to every predicate here)
-static inline bool is_kquant(int t) {
-    return t == GGML_HIP_TYPE_Q5_K || t == GGML_HIP_TYPE_Q4_K || t == GGML_HIP_TYPE_Q6_K || t == GGML_HIP_TYPE_Q3_K || t == GGML_HIP_TYPE_Q2_K ||
-           t == GGML_HIP_TYPE_IQ4_XS;
-}
-static inline size_t kquant_bytes(int t) {   // per 256 weights
-    return t == GGML_HIP_TYPE_Q5_K ? 176 : t == GGML_HIP_TYPE_Q6_K ? 210 : t == GGML_HIP_TYPE_Q3_K ? 110 : t == GGML_HIP_TYPE_Q2_K ? 84
-           : t == GGML_HIP_TYPE_IQ4_XS ? 136 : 144;
-}
-// Q6_K, Q3_K and Q2_K: sixteen sub-blocks of 16 with a scale each -- resident in the two-scale int8 form (the planar Q4_2 form on its int8
-// planes alone, kquants.hip); IQ4_XS too, both scales of a k-block equal (iq4.hip); Q5_K / Q4_K live in the planar Q5_1 form
-static inline bool kquant_two_scale(int t) {
-    return t == GGML_HIP_TYPE_Q6_K || t == GGML_HIP_TYPE_Q3_K || t == GGML_HIP_TYPE_Q2_K || t == GGML_HIP_TYPE_IQ4_XS;
-}
-// IQ4_NL (iq4.hip): after the codebook lookup a plain Q8_0 weight (type == Q8_0, ext_type == 0, up_type == IQ4_NL)
-static inline bool is_iq4nl(int t) { return t == GGML_HIP_TYPE_IQ4_NL; }
-// Q2_K: a min per sub-block of 16 as well, which no kernel family's product carries -- the product runs on the block term alone (the
-// two-scale form) and the min term is subtracted behind it by kquants.hip's min pass (plan flag MM_FLAG_MIN_PASS)
-static inline bool kquant_min_pass(int t) { return t == GGML_HIP_TYPE_Q2_K; }
-// the reference type whose resident planar form (and kernels) a k-quant weight lives in: Q5_K / Q4_K as Q5_1, Q6_K / Q3_K as Q4_2 (two scales per k-block)
-static inline int kquant_resident_type(int t) { return kquant_two_scale(t) ? GGML_TYPE_Q4_2 : GGML_TYPE_Q5_1; }
-// the slot per super-block of a weight's khdr plane: Q6_K's scales[16] + d (18 B) and Q2_K's scales[16] + d + dmin (20 B; the min pass's
-// weight operand) in 32, the others' 16 header bytes (Q3_K: scales[12] + d, 14 B; IQ4_XS: d, scales_h, scales_l[4], 8 B) in 16
-static inline size_t kquant_hdr_bytes(int t) { return t == GGML_HIP_TYPE_Q6_K || t == GGML_HIP_TYPE_Q2_K ? 32 : 16; }
-hipError_t launch_q5k_to_planar(int kq_type, const uint8_t *aos, uint64_t nb01, int64_t row_begin, int64_t rows, ggml_hip_weight *w, hipStream_t st);
-hipError_t launch_planar_to_q5k(const ggml_hip_weight *w, uint8_t *aos, hipStream_t st);
-hipError_t launch_dequantize_q5k(int kq_type, const void *blocks, int64_t nrows, int64_t k, float *y, hipStream_t st);
-hipError_t launch_quantize_kq(int kq_type, const float *x, int64_t nrows, int64_t k, void *blocks, hipStream_t st);   // x: contiguous rows, 16-byte aligned
-// (Q6_K: its own converters -- the planar Q4_2 form on int8 planes)
-hipError_t launch_q6k_to_planar(const uint8_t *aos, uint64_t nb01, int64_t row_begin, int64_t rows, ggml_hip_weight *w, hipStream_t st);
-hipError_t launch_planar_to_q6k(const ggml_hip_weight *w, uint8_t *aos, hipStream_t st);
-hipError_t launch_dequantize_q6k(const void *blocks, int64_t nrows, int64_t k, float *y, hipStream_t st);
-hipError_t launch_quantize_q6k(const float *x, int64_t nrows, int64_t k, void *blocks, hipStream_t st);
-// (Q3_K: the same resident form as Q6_K, byte for byte; its own converters)
-hipError_t launch_q3k_to_planar(const uint8_t *aos, uint64_t nb01, int64_t row_begin, int64_t rows, ggml_hip_weight *w, hipStream_t st);
-hipError_t launch_planar_to_q3k(const ggml_hip_weight *w, uint8_t *aos, hipStream_t st);
-hipError_t launch_dequantize_q3k(const void *blocks, int64_t nrows, int64_t k, float *y, hipStream_t st);
-hipError_t launch_quantize_q3k(const float *x, int64_t nrows, int64_t k, void *blocks, hipStream_t st);
-// (Q2_K: the block term in Q6_K's resident form, scales[16] + d + dmin in the 32-byte header slot; its own converters)
-hipError_t launch_q2k_to_planar(const uint8_t *aos, uint64_t nb01, int64_t row_begin, int64_t rows, ggml_hip_weight *w, hipStream_t st);
-hipError_t launch_planar_to_q2k(const ggml_hip_weight *w, uint8_t *aos, hipStream_t st);
-hipError_t launch_dequantize_q2k(const void *blocks, int64_t nrows, int64_t k, float *y, hipStream_t st);
-hipError_t launch_quantize_q2k(const float *x, int64_t nrows, int64_t k, void *blocks, hipStream_t st);
+// ---- the weight types: ONE row per type id the library accepts anywhere -- the reference's thirteen and the extension ids of
+// include/ggml_hip_ext.h.  wtypes.cpp holds the table; everything that used to ask "is this a k-quant / IQ4_NL / BF16" reads a row.
+// DESIGN.md "Adding a weight type" says what a new type has to supply.
+typedef hipError_t (*wt_to_planar_fn)(int type, const uint8_t *aos, uint64_t nb01, int64_t row_begin, int64_t rows, ggml_hip_weight *w, hipStream_t st);
+typedef hipError_t (*wt_from_planar_fn)(const ggml_hip_weight *w, uint8_t *aos, hipStream_t st);
+typedef hipError_t (*wt_quantize_fn)(int type, const float *x, int64_t nrows, int64_t k, void *blocks, hipStream_t st);
+typedef hipError_t (*wt_dequantize_fn)(int type, const void *blocks, int64_t nrows, int64_t k, float *y, hipStream_t st);
+enum { WT_ORIGIN_NONE, WT_ORIGIN_EXT, WT_ORIGIN_UP };
+struct wtype {
+    int    id;
+    int    blck;       // the file format: elements ...
+    size_t bytes;      //   ... and bytes of a block
+    int    resident;   // the type whose planar form and kernels a weight of this type lives in (ggml_hip_weight::type); itself for native types
+    int    origin;     // how the weight remembers `id`: not at all (type == id), in ext_type (the plan sees it), in up_type (the plan does not)
+    bool   q8k;        // INIT quantizes the activations by the Q8_K rule (one scale per 256)
+    bool   min_pass;   // the product runs on the block term alone; kquants.hip's min pass subtracts the min term behind it (plan flag MM_FLAG_MIN_PASS)
+    int    hdr_slot;   // bytes per super-block in the weight's khdr plane (the header bytes a byte-exact download needs back); 0: no such plane
+    bool   own_i8;     // the two-scale form: to_planar writes the int8 planes itself (launch_q5_to_i8 is skipped, the nibble plane is a stub)
+    int    x_align;    // quantize: the alignment its source rows need (float4 loads), 0: none
+    wt_to_planar_fn   to_planar;     // file-format rows (device memory, nb01 apart, from row_begin on) -> the resident planes; null: not a weight type
+    wt_from_planar_fn from_planar;   // the exact inverse, rows packed
+    wt_quantize_fn    quantize;      // contiguous f32 rows -> blocks; null: no quantizer
+    wt_dequantize_fn  dequantize;    // blocks -> f32 rows; null: no dequantizer
+};
+const wtype *wtype_of(int id);                     // nullptr: not a type id
+static inline int wtype_ext(const wtype *r) { return r->origin == WT_ORIGIN_EXT ? r->id : 0; }      // the ext_type a weight of the row carries
+static inline bool kquant_min_pass(int ext_type) { const wtype *r = wtype_of(ext_type); return r && r->min_pass; }
+// kquants.hip: Q5_K / Q4_K on the planar Q5_1 form, Q6_K / Q3_K / Q2_K in the two-scale int8 form (two_scale.h); unpinned extras -- the
+// published upstream formats, no oracle in the reference.  x: contiguous rows, 16-byte aligned
+hipError_t launch_kq_to_planar(int type, const uint8_t *aos, uint64_t nb01, int64_t row_begin, int64_t rows, ggml_hip_weight *w, hipStream_t st);
+hipError_t launch_planar_to_kq(const ggml_hip_weight *w, uint8_t *aos, hipStream_t st);
+hipError_t launch_dequantize_kq(int type, const void *blocks, int64_t nrows, int64_t k, float *y, hipStream_t st);
+hipError_t launch_quantize_kq(int type, const float *x, int64_t nrows, int64_t k, void *blocks, hipStream_t st);
 // dst[n][i] -= the min term of a Q2_K weight against K1's int8 image by the Q8_K rule (columns i < M, rows n < N; kquants.hip);
 // form 0: the launcher's choice, 1 / 2: one / two 32-column tiles per wave (the same bits; a test hook selects them)
 hipError_t launch_q2k_min_pass(const ggml_hip_weight *w, act_planes p, int64_t N, float *dst, int64_t ldd, hipStream_t st, int form = 0);
-// iq4.hip: IQ4_NL in Q8_0's planar form (its qs / d planes), IQ4_XS in Q6_K's resident form; dequantizer and quantizer for both (type =
-// GGML_HIP_TYPE_IQ4_NL or _IQ4_XS; x: contiguous rows, 16-byte aligned)
-hipError_t launch_iq4nl_to_planar(const uint8_t *aos, uint64_t nb01, int64_t row_begin, int64_t rows, ggml_hip_weight *w, hipStream_t st);
-hipError_t launch_planar_to_iq4nl(const ggml_hip_weight *w, uint8_t *aos, hipStream_t st);
-hipError_t launch_iq4xs_to_planar(const uint8_t *aos, uint64_t nb01, int64_t row_begin, int64_t rows, ggml_hip_weight *w, hipStream_t st);
-hipError_t launch_planar_to_iq4xs(const ggml_hip_weight *w, uint8_t *aos, hipStream_t st);
+// iq4.hip: IQ4_NL in Q8_0's planar form (its qs / d planes), IQ4_XS in the two-scale int8 form
+hipError_t launch_iq4_to_planar(int type, const uint8_t *aos, uint64_t nb01, int64_t row_begin, int64_t rows, ggml_hip_weight *w, hipStream_t st);
+hipError_t launch_planar_to_iq4(const ggml_hip_weight *w, uint8_t *aos, hipStream_t st);
 hipError_t launch_dequantize_iq4(int type, const void *blocks, int64_t nrows, int64_t k, float *y, hipStream_t st);
 hipError_t launch_quantize_iq4(int type, const float *x, int64_t nrows, int64_t k, void *blocks, hipStream_t st);
 hipError_t launch_q8_aos_to_planes(int q8type, const void *blocks, int64_t N, int64_t K, act_planes p, hipStream_t st);
@@ -371,7 +358,7 @@ hipError_t launch_dense32(const ggml_hip_weight *w, const void *work, int64_t N,
 // BF16 weights (GGML_HIP_TYPE_BF16, an extension type: w->type holds 130 itself, so no F16 branch can take it): the F16 resident form with
 // bf16 bits (row-major copy + k-panels, launch_f16_rows_to_panels moves 16-bit words whatever they mean) and bf16 twins of the F16 kernels
 static inline bool is_bf16(int t) { return t == GGML_HIP_TYPE_BF16; }
-static inline bool is_dense16(int t) { return t == GGML_TYPE_F16 || t == GGML_HIP_TYPE_BF16; }   // 2-byte dense weights: F16 or BF16
+static inline bool is_dense16(int t) { return t == GGML_TYPE_F16 || is_bf16(t); }   // 2-byte dense weights: F16 or BF16
 // f32 -> bf16, THE rule of every conversion (include/ggml_hip_ext.h GGML_HIP_TYPE_BF16): a NaN stays a quiet NaN with its sign and high
 // payload (the bare integer form would turn a NaN whose payload sits in the low bits into an infinity or carry it into the exponent: the
 // separate select); anything else rounds to nearest even, subnormals kept, overflow to +-inf.  The select is written as a mask: as a

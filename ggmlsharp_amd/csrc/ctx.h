@@ -37,6 +37,9 @@ bool weight_type_ok(int t);
 bool is_q(int t);
 int vec_dot_type(int t);                           // Ggml.cs:219-290
 inline size_t row_bytes_of(int t, int64_t k) { return TSIZE[t] * (size_t)(k / BLCK[t]); }
+// the K unit of a type's rows: a whole block of the file format, and for the quantized resident forms a whole 32-element Q8 block too (every dot
+// product runs against those).  ASSUMES a block of such a type divides 32 or is a multiple of it, as every row of the table does (16, 32, 256).
+inline int64_t k_unit(const wtype *r) { return is_q(r->resident) && r->blck < QK ? QK : r->blck; }
 inline int64_t nelem(const ggml_tensor *t) { return t->ne[0] * t->ne[1] * t->ne[2] * t->ne[3]; }
 bool contiguous_f32(const ggml_tensor *t);
 int act_image_kind(int type, int64_t K, int64_t N);              // by type, K and N alone (plan.cpp)

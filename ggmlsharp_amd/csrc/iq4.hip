@@ -21,7 +21,7 @@
 // GQ_TYPE_I8X2, gemm_q8s.hip Q42 and gemm_qmp.hip TWO (v_mfma_i32_32x32x16_i8 into int32 accumulators).  None offsets, packs or narrows
 // the weight bytes, and a 16-element sum is at most 16 * 127 * 128 < 2^24 in magnitude, so its conversion to f32 is exact as for Q6_K.
 // No form needed a change.
-#include "common.h"
+#include "two_scale.h"
 
 namespace {
 
@@ -55,13 +55,6 @@ __device__ __forceinline__ int iq4_best_index(float x) {
         if (x < (float)iq4_kv(mav)) mu = mav; else ml = mav;
     }
     return (x - (float)iq4_kv(mu - 1) < (float)iq4_kv(mu) - x) ? mu - 1 : mu;
-}
-
-__device__ __forceinline__ float h2f(uint16_t h) {          // IEEE binary16 -> binary32, exact (NaN payloads kept, nothing quieted)
-    const uint32_t sign = ((uint32_t)h & 0x8000u) << 16, exp = (h >> 10) & 0x1Fu, man = h & 0x3FFu;
-    if (exp == 0) return __uint_as_float(__float_as_uint((float)man * 5.9604644775390625e-08f) | sign);
-    if (exp == 31) return __uint_as_float(sign | 0x7F800000u | (man << 13));
-    return __uint_as_float(sign | ((exp + 112u) << 23) | (man << 13));
 }
 
 __device__ __forceinline__ uint16_t f2h_exact(float f) {    // the inverse of h2f on its image: every half bit pattern comes back
@@ -138,72 +131,29 @@ __global__ void planar_to_iq4nl_kernel(uint8_t *__restrict__ aos, uint64_t nb01,
     for (int t = 0; t < 16; ++t) blk[2 + t] = q[t];
 }
 
-// ---- IQ4_XS: Q6_K's resident form (the planar Q4_2 form on int8 planes, both scales of a k-block equal) ---------------------------------
-// one thread per (row, k-block)
-__global__ void iq4xs_to_planar_kernel(const uint8_t *__restrict__ aos, uint64_t nb01, int64_t row_begin, int64_t rows, int64_t Mpad,
-                                       uint8_t *__restrict__ i8p, float *__restrict__ d, float *__restrict__ mm, uint8_t *__restrict__ khdr) {
-    const int64_t m = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    const int64_t b = blockIdx.y;
-    if (m >= rows) return;
-    const int64_t sb = b >> 3;
-    const int ib = (int)(b & 7);
-    const uint8_t *blk = aos + (uint64_t)(row_begin + m) * nb01 + (uint64_t)sb * 136;
-    const float dl = h2f((uint16_t)(blk[0] | ((uint16_t)blk[1] << 8))) * (float)(iq4xs_code(blk, ib) - 32);   // exact: 11 + 6 significant bits
-    const int64_t pi = b * Mpad + m;
-    d[pi] = dl;
-    mm[pi] = dl;
-    uint8_t q[16];
-#pragma unroll
-    for (int t = 0; t < 16; ++t) q[t] = blk[8 + 16 * ib + t];
-    uint32_t ev[4], od[4];
-    iq4_planes(q, ev, od);
-    *(uint4 *)(i8p + ((b * 2 + 0) * Mpad + m) * 16) = make_uint4(ev[0], ev[1], ev[2], ev[3]);
-    *(uint4 *)(i8p + ((b * 2 + 1) * Mpad + m) * 16) = make_uint4(od[0], od[1], od[2], od[3]);
-    if (ib == 0) {
-        uint32_t h[2] = {0, 0};
-#pragma unroll
-        for (int i = 0; i < 8; ++i) h[i >> 2] |= (uint32_t)blk[i] << (8 * (i & 3));
-        *(uint4 *)(khdr + (sb * Mpad + m) * 16) = make_uint4(h[0], h[1], 0u, 0u);
+// ---- IQ4_XS: Q6_K's resident form (the planar Q4_2 form on int8 planes, both scales of a k-block equal); the converters are two_scale.h's ----
+struct iq4xs_codec {
+    static constexpr int BYTES = 136, QOFF = 8, QLEN = 128, HDR = 8, SLOT = 16;
+    static constexpr bool MINS = false;
+    static __device__ __forceinline__ int hdr_pos(int i) { return i; }                        // d, scales_h, scales_l[4]
+    static __device__ __forceinline__ void scales(const uint8_t *blk, int ib, float &d0, float &d1) {
+        d0 = d1 = h2f_at(blk) * (float)(iq4xs_code(blk, ib) - 32);                            // exact: 11 + 6 significant bits
     }
-}
-
-// exact inverse: one thread per (row, k-block)
-__global__ void planar_to_iq4xs_kernel(uint8_t *__restrict__ aos, uint64_t nb01, int64_t rows, int64_t Mpad, const uint8_t *__restrict__ i8p,
-                                       const uint8_t *__restrict__ khdr) {
-    const int64_t m = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    const int64_t b = blockIdx.y;
-    if (m >= rows) return;
-    const int64_t sb = b >> 3;
-    const int ib = (int)(b & 7);
-    uint8_t *blk = aos + (uint64_t)m * nb01 + (uint64_t)sb * 136;
-    uint8_t q[16];
-    iq4_nibbles(*(const uint4 *)(i8p + ((b * 2 + 0) * Mpad + m) * 16), *(const uint4 *)(i8p + ((b * 2 + 1) * Mpad + m) * 16), q);
-#pragma unroll
-    for (int t = 0; t < 16; ++t) blk[8 + 16 * ib + t] = q[t];
-    if (ib == 0) {
-        const uint8_t *h = khdr + (sb * Mpad + m) * 16;
-#pragma unroll
-        for (int i = 0; i < 8; ++i) blk[i] = h[i];
+    static __device__ __forceinline__ int value(const uint8_t *blk, int ib, int t) {          // IQ4_NL's nibble order
+        const uint8_t q = blk[8 + 16 * ib + (t & 15)];
+        return iq4_kv(t < 16 ? (q & 15) : (q >> 4));
     }
-}
+    static __device__ __forceinline__ void put(uint32_t *q, int ib, int t, int v) {
+        or_byte(q, 16 * ib + (t & 15), (uint32_t)iq4_index_of(v) << (4 * (t >> 4)));
+    }
+};
 
-// ---- dequantize_row_iq4_nl / _iq4_xs of the published formats: one thread per (row-major) 32-element block ----------------------------------
-template <bool XS>
-__global__ void dequantize_iq4_kernel(const uint8_t *__restrict__ in, int64_t nkb, float *__restrict__ y) {
+// ---- dequantize_row_iq4_nl of the published format: one thread per 32-element block ----------------------------------------------------------
+__global__ void dequantize_iq4nl_kernel(const uint8_t *__restrict__ in, int64_t nkb, float *__restrict__ y) {
     const int64_t k = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (k >= nkb) return;
-    float dl;
-    const uint8_t *q;
-    if constexpr (XS) {
-        const uint8_t *blk = in + (k >> 3) * 136;
-        const int ib = (int)(k & 7);
-        dl = h2f((uint16_t)(blk[0] | ((uint16_t)blk[1] << 8))) * (float)(iq4xs_code(blk, ib) - 32);
-        q = blk + 8 + 16 * ib;
-    } else {
-        const uint8_t *blk = in + k * 18;
-        dl = h2f((uint16_t)(blk[0] | ((uint16_t)blk[1] << 8)));
-        q = blk + 2;
-    }
+    const uint8_t *blk = in + k * 18, *q = blk + 2;
+    const float dl = h2f_at(blk);
     float *o = y + k * 32;
 #pragma unroll
     for (int t = 0; t < 16; ++t) {
@@ -311,40 +261,28 @@ __global__ __launch_bounds__(128) void quantize_iq4_kernel(const float *__restri
 
 }  // namespace
 
-hipError_t launch_iq4nl_to_planar(const uint8_t *aos, uint64_t nb01, int64_t row_begin, int64_t rows, ggml_hip_weight *w, hipStream_t st) {
+// ---- the four operations of the two types (wtypes.cpp's rows point here; type = GGML_HIP_TYPE_IQ4_NL or _IQ4_XS) ----
+hipError_t launch_iq4_to_planar(int type, const uint8_t *aos, uint64_t nb01, int64_t row_begin, int64_t rows, ggml_hip_weight *w, hipStream_t st) {
+    if (type == GGML_HIP_TYPE_IQ4_XS) return two_scale_to_planar<iq4xs_codec>(aos, nb01, row_begin, rows, w, st);
     if (rows <= 0 || w->nbk <= 0) return hipSuccess;
     dim3 grid((unsigned)((rows + 127) / 128), (unsigned)w->nbk);
     iq4nl_to_planar_kernel<<<grid, 128, 0, st>>>(aos, nb01, row_begin, rows, w->Mpad, w->qs, w->d);
     return hipGetLastError();
 }
 
-hipError_t launch_planar_to_iq4nl(const ggml_hip_weight *w, uint8_t *aos, hipStream_t st) {
+hipError_t launch_planar_to_iq4(const ggml_hip_weight *w, uint8_t *aos, hipStream_t st) {
+    if (w->ext_type == GGML_HIP_TYPE_IQ4_XS) return planar_to_two_scale<iq4xs_codec>(w, aos, st);
     if (w->M <= 0 || w->nbk <= 0) return hipSuccess;
     dim3 grid((unsigned)((w->M + 127) / 128), (unsigned)w->nbk);
     planar_to_iq4nl_kernel<<<grid, 128, 0, st>>>(aos, (uint64_t)w->nbk * 18, w->M, w->Mpad, w->qs, w->d);
     return hipGetLastError();
 }
 
-hipError_t launch_iq4xs_to_planar(const uint8_t *aos, uint64_t nb01, int64_t row_begin, int64_t rows, ggml_hip_weight *w, hipStream_t st) {
-    if (rows <= 0 || w->nbk <= 0) return hipSuccess;
-    dim3 grid((unsigned)((rows + 127) / 128), (unsigned)w->nbk);
-    iq4xs_to_planar_kernel<<<grid, 128, 0, st>>>(aos, nb01, row_begin, rows, w->Mpad, w->i8p, w->d, w->m, w->khdr);
-    return hipGetLastError();
-}
-
-hipError_t launch_planar_to_iq4xs(const ggml_hip_weight *w, uint8_t *aos, hipStream_t st) {
-    if (w->M <= 0 || w->nbk <= 0) return hipSuccess;
-    dim3 grid((unsigned)((w->M + 127) / 128), (unsigned)w->nbk);
-    planar_to_iq4xs_kernel<<<grid, 128, 0, st>>>(aos, (uint64_t)(w->nbk / 8) * 136, w->M, w->Mpad, w->i8p, w->khdr);
-    return hipGetLastError();
-}
-
 hipError_t launch_dequantize_iq4(int type, const void *blocks, int64_t nrows, int64_t k, float *y, hipStream_t st) {
+    if (type == GGML_HIP_TYPE_IQ4_XS) return dequantize_two_scale<iq4xs_codec>(blocks, nrows, k, y, st);
     const int64_t nkb = nrows * (k / 32);
     if (nkb <= 0) return hipSuccess;
-    const dim3 grid((unsigned)((nkb + 127) / 128));
-    if (type == GGML_HIP_TYPE_IQ4_XS) dequantize_iq4_kernel<true><<<grid, 128, 0, st>>>((const uint8_t *)blocks, nkb, y);
-    else dequantize_iq4_kernel<false><<<grid, 128, 0, st>>>((const uint8_t *)blocks, nkb, y);
+    dequantize_iq4nl_kernel<<<dim3((unsigned)((nkb + 127) / 128)), 128, 0, st>>>((const uint8_t *)blocks, nkb, y);
     return hipGetLastError();
 }
 

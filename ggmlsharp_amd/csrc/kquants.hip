@@ -26,16 +26,9 @@
 // Q6_K super-block it transcodes to (see the two sections below).  Q2_K's sub-blocks of 16 each carry a min as well, which no resident
 // form has (the min-term products of the Q5_1 form are built per 32 elements): its block term lives in Q6_K's form and runs Q6_K's kernels,
 // and its min term is subtracted behind the product by a pass of its own (the Q2_K section at the end).
-#include "common.h"
+#include "two_scale.h"
 
 namespace {
-
-__device__ __forceinline__ float h2f(uint16_t h) {          // IEEE binary16 -> binary32, exact
-    const uint32_t sign = ((uint32_t)h & 0x8000u) << 16, exp = (h >> 10) & 0x1Fu, man = h & 0x3FFu;
-    if (exp == 0) return __uint_as_float(__float_as_uint((float)man * 5.9604644775390625e-08f) | sign);
-    if (exp == 31) return __uint_as_float(sign | 0x7F800000u | (man << 13));
-    return __uint_as_float(sign | ((exp + 112u) << 23) | (man << 13));
-}
 
 // upstream get_scale_min_k4
 __device__ __forceinline__ void scale_min_k4(int j, const uint8_t *q, uint32_t &sc, uint32_t &m) {
@@ -264,85 +257,30 @@ __global__ void quantize_kq_kernel(const float *__restrict__ x, int64_t nsb, uin
 // layout of Q8_0's planes), the first sub-block's effective scale d * sc (exact in f32: 11 + 8 bits) in the d plane, the second's in the m
 // plane.  The int8 kernels that take two scales per k-block serve it (gemm_q8s.hip Q42, gemm_q.hip's int8-plane two-scale form); the
 // nibble plane of the Q4_2 form stays empty.  32 header bytes per super-block (scales[16], d) are kept for the byte-exact download.
-// one thread per (row, k-block)
-__global__ void q6k_to_planar_kernel(const uint8_t *__restrict__ aos, uint64_t nb01, int64_t row_begin, int64_t rows, int64_t Mpad,
-                                     uint8_t *__restrict__ i8p, float *__restrict__ d, float *__restrict__ mm, uint8_t *__restrict__ khdr) {
-    const int64_t m = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    const int64_t b = blockIdx.y;
-    if (m >= rows) return;
-    const int64_t sb = b >> 3;
-    const int bq = (int)(b & 7), n = bq >> 2, c = bq & 3;
-    const uint8_t *blk = aos + (uint64_t)(row_begin + m) * nb01 + (uint64_t)sb * 210;
-    const uint8_t *ql = blk + 64 * n + 32 * (c & 1), *qh = blk + 128 + 32 * n;
-    const int8_t *sc = (const int8_t *)(blk + 192);
-    const float dd = h2f((uint16_t)(blk[208] | ((uint16_t)blk[209] << 8)));
-    const int64_t pi = b * Mpad + m;
-    d[pi] = dd * (float)sc[2 * bq];                         // exact: 11 + 8 significant bits
-    mm[pi] = dd * (float)sc[2 * bq + 1];
-    uint32_t ev[4] = {0, 0, 0, 0}, od[4] = {0, 0, 0, 0};
-#pragma unroll
-    for (int t = 0; t < 32; ++t) {
-        const uint32_t nib = c < 2 ? (uint32_t)(ql[t] & 15u) : (uint32_t)(ql[t] >> 4);
-        const int v = (int)(nib | (((uint32_t)(qh[t] >> (2 * c)) & 3u) << 4)) - 32;
-        const uint32_t byte = (uint32_t)(uint8_t)(int8_t)v << (8 * ((t >> 1) & 3));
-        if (t & 1) od[t >> 3] |= byte; else ev[t >> 3] |= byte;      // plane h byte j = element 2 j + h
+// The converters are two_scale.h's, over this codec.
+struct q6k_codec {
+    static constexpr int BYTES = 210, QOFF = 0, QLEN = 192, HDR = 18, SLOT = 32;
+    static constexpr bool MINS = false;
+    static __device__ __forceinline__ int hdr_pos(int i) { return 192 + i; }                  // scales[16], d
+    static __device__ __forceinline__ void scales(const uint8_t *blk, int bq, float &d0, float &d1) {
+        const int8_t *sc = (const int8_t *)(blk + 192);
+        const float dd = h2f_at(blk + 208);
+        d0 = dd * (float)sc[2 * bq];                        // exact: 11 + 8 significant bits
+        d1 = dd * (float)sc[2 * bq + 1];
     }
-    *(uint4 *)(i8p + ((b * 2 + 0) * Mpad + m) * 16) = make_uint4(ev[0], ev[1], ev[2], ev[3]);
-    *(uint4 *)(i8p + ((b * 2 + 1) * Mpad + m) * 16) = make_uint4(od[0], od[1], od[2], od[3]);
-    if (bq == 0) {
-        uint32_t h[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-#pragma unroll
-        for (int i = 0; i < 18; ++i) h[i >> 2] |= (uint32_t)blk[192 + i] << (8 * (i & 3));
-        uint4 *o = (uint4 *)(khdr + (sb * Mpad + m) * 32);
-        o[0] = make_uint4(h[0], h[1], h[2], h[3]);
-        o[1] = make_uint4(h[4], h[5], h[6], h[7]);
-    }
-}
-
-// exact inverse: one thread per (row, super-block)
-__global__ void planar_to_q6k_kernel(uint8_t *__restrict__ aos, uint64_t nb01, int64_t rows, int64_t Mpad, const uint8_t *__restrict__ i8p,
-                                     const uint8_t *__restrict__ khdr) {
-    const int64_t m = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    const int64_t sb = blockIdx.y;
-    if (m >= rows) return;
-    uint8_t *blk = aos + (uint64_t)m * nb01 + (uint64_t)sb * 210;
-    for (int i = 0; i < 192; ++i) blk[i] = 0;
-    for (int bq = 0; bq < 8; ++bq) {
+    static __device__ __forceinline__ int value(const uint8_t *blk, int bq, int t) {
         const int n = bq >> 2, c = bq & 3;
-        uint8_t *ql = blk + 64 * n + 32 * (c & 1), *qh = blk + 128 + 32 * n;
-        const int64_t b = sb * 8 + bq;
-        for (int hsel = 0; hsel < 2; ++hsel) {
-            const uint4 w4 = *(const uint4 *)(i8p + ((b * 2 + hsel) * Mpad + m) * 16);
-            const uint32_t w[4] = {w4.x, w4.y, w4.z, w4.w};
-            for (int j = 0; j < 16; ++j) {
-                const int t = 2 * j + hsel;
-                const uint32_t q = (uint32_t)((int)(int8_t)((w[j >> 2] >> (8 * (j & 3))) & 0xFFu) + 32);
-                ql[t] |= (uint8_t)(c < 2 ? (q & 15u) : ((q & 15u) << 4));
-                qh[t] |= (uint8_t)((q >> 4) << (2 * c));
-            }
-        }
-    }
-    const uint8_t *h = khdr + (sb * Mpad + m) * 32;
-    for (int i = 0; i < 18; ++i) blk[192 + i] = h[i];
-}
-
-// dequantize_row_q6_K of the published format: one thread per (row-major) k-block of 32 outputs
-__global__ void dequantize_q6k_kernel(const uint8_t *__restrict__ in, int64_t nkb, float *__restrict__ y) {
-    const int64_t s = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (s >= nkb) return;
-    const uint8_t *blk = in + (s >> 3) * 210;
-    const int bq = (int)(s & 7), n = bq >> 2, c = bq & 3;
-    const uint8_t *ql = blk + 64 * n + 32 * (c & 1), *qh = blk + 128 + 32 * n;
-    const int8_t *sc = (const int8_t *)(blk + 192);
-    const float dd = h2f((uint16_t)(blk[208] | ((uint16_t)blk[209] << 8)));
-    const float d0 = dd * (float)sc[2 * bq], d1 = dd * (float)sc[2 * bq + 1];
-    float *o = y + s * 32;
-    for (int t = 0; t < 32; ++t) {
+        const uint8_t *ql = blk + 64 * n + 32 * (c & 1), *qh = blk + 128 + 32 * n;
         const uint32_t nib = c < 2 ? (uint32_t)(ql[t] & 15u) : (uint32_t)(ql[t] >> 4);
-        const int v = (int)(nib | (((uint32_t)(qh[t] >> (2 * c)) & 3u) << 4)) - 32;
-        o[t] = (t < 16 ? d0 : d1) * (float)v;               // upstream: d * sc[is] * q, left to right
+        return (int)(nib | (((uint32_t)(qh[t] >> (2 * c)) & 3u) << 4)) - 32;
     }
-}
+    static __device__ __forceinline__ void put(uint32_t *q, int bq, int t, int v) {
+        const int n = bq >> 2, c = bq & 3;
+        const uint32_t u = (uint32_t)(v + 32);
+        or_byte(q, 64 * n + 32 * (c & 1) + t, c < 2 ? (u & 15u) : ((u & 15u) << 4));
+        or_byte(q, 128 + 32 * n + t, (u >> 4) << (2 * c));
+    }
+};
 
 // quantize_row_q6_K_reference with make_qx_quants in its plain form (no least-squares refinement of the sub-block scales: a VALID encoder of
 // the published structure, stated as such in include/ggml_hip_ext.h; tests/np_kquants.py quantize_q6_K is the same steps): sixteen lanes per
@@ -443,79 +381,26 @@ __device__ __forceinline__ int q3k_scale(const uint8_t *scales, int j) {
     return (lo | (((scales[8 + (j & 3)] >> (2 * (j >> 2))) & 3) << 4)) - 32;
 }
 
-// one thread per (row, k-block); rows fastest so the plane stores coalesce
-__global__ void q3k_to_planar_kernel(const uint8_t *__restrict__ aos, uint64_t nb01, int64_t row_begin, int64_t rows, int64_t Mpad,
-                                     uint8_t *__restrict__ i8p, float *__restrict__ d, float *__restrict__ mm, uint8_t *__restrict__ khdr) {
-    const int64_t m = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    const int64_t b = blockIdx.y;
-    if (m >= rows) return;
-    const int64_t sb = b >> 3;
-    const int bq = (int)(b & 7), n = bq >> 2, s = bq & 3;
-    const uint8_t *blk = aos + (uint64_t)(row_begin + m) * nb01 + (uint64_t)sb * 110;
-    const uint8_t *hm = blk, *qs = blk + 32 + 32 * n;
-    const float dd = h2f((uint16_t)(blk[108] | ((uint16_t)blk[109] << 8)));
-    const int64_t pi = b * Mpad + m;
-    d[pi] = dd * (float)q3k_scale(blk + 96, 2 * bq);       // exact: 11 + 6 significant bits
-    mm[pi] = dd * (float)q3k_scale(blk + 96, 2 * bq + 1);
-    uint32_t ev[4] = {0, 0, 0, 0}, od[4] = {0, 0, 0, 0};
-#pragma unroll
-    for (int t = 0; t < 32; ++t) {
-        const int v = (int)((qs[t] >> (2 * s)) & 3u) + 4 * (int)((hm[t] >> bq) & 1u) - 4;
-        const uint32_t byte = (uint32_t)(uint8_t)(int8_t)v << (8 * ((t >> 1) & 3));
-        if (t & 1) od[t >> 3] |= byte; else ev[t >> 3] |= byte;      // plane h byte j = element 2 j + h
+struct q3k_codec {
+    static constexpr int BYTES = 110, QOFF = 0, QLEN = 96, HDR = 14, SLOT = 16;
+    static constexpr bool MINS = false;
+    static __device__ __forceinline__ int hdr_pos(int i) { return 96 + i; }                   // scales[12], d
+    static __device__ __forceinline__ void scales(const uint8_t *blk, int bq, float &d0, float &d1) {
+        const float dd = h2f_at(blk + 108);
+        d0 = dd * (float)q3k_scale(blk + 96, 2 * bq);       // exact: 11 + 6 significant bits
+        d1 = dd * (float)q3k_scale(blk + 96, 2 * bq + 1);
     }
-    *(uint4 *)(i8p + ((b * 2 + 0) * Mpad + m) * 16) = make_uint4(ev[0], ev[1], ev[2], ev[3]);
-    *(uint4 *)(i8p + ((b * 2 + 1) * Mpad + m) * 16) = make_uint4(od[0], od[1], od[2], od[3]);
-    if (bq == 0) {
-        uint32_t h[4] = {0, 0, 0, 0};
-#pragma unroll
-        for (int i = 0; i < 14; ++i) h[i >> 2] |= (uint32_t)blk[96 + i] << (8 * (i & 3));
-        *(uint4 *)(khdr + (sb * Mpad + m) * 16) = make_uint4(h[0], h[1], h[2], h[3]);
-    }
-}
-
-// exact inverse: one thread per (row, super-block)
-__global__ void planar_to_q3k_kernel(uint8_t *__restrict__ aos, uint64_t nb01, int64_t rows, int64_t Mpad, const uint8_t *__restrict__ i8p,
-                                     const uint8_t *__restrict__ khdr) {
-    const int64_t m = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    const int64_t sb = blockIdx.y;
-    if (m >= rows) return;
-    uint8_t *blk = aos + (uint64_t)m * nb01 + (uint64_t)sb * 110;
-    for (int i = 0; i < 96; ++i) blk[i] = 0;
-    for (int bq = 0; bq < 8; ++bq) {
+    static __device__ __forceinline__ int value(const uint8_t *blk, int bq, int t) {
         const int n = bq >> 2, s = bq & 3;
-        uint8_t *hm = blk, *qs = blk + 32 + 32 * n;
-        const int64_t b = sb * 8 + bq;
-        for (int hsel = 0; hsel < 2; ++hsel) {
-            const uint4 w4 = *(const uint4 *)(i8p + ((b * 2 + hsel) * Mpad + m) * 16);
-            const uint32_t w[4] = {w4.x, w4.y, w4.z, w4.w};
-            for (int j = 0; j < 16; ++j) {
-                const int t = 2 * j + hsel;
-                const uint32_t q = (uint32_t)((int)(int8_t)((w[j >> 2] >> (8 * (j & 3))) & 0xFFu) + 4);   // 0..7
-                qs[t] |= (uint8_t)((q & 3u) << (2 * s));
-                hm[t] |= (uint8_t)((q >> 2) << bq);
-            }
-        }
+        return (int)((blk[32 + 32 * n + t] >> (2 * s)) & 3u) + 4 * (int)((blk[t] >> bq) & 1u) - 4;
     }
-    const uint8_t *h = khdr + (sb * Mpad + m) * 16;
-    for (int i = 0; i < 14; ++i) blk[96 + i] = h[i];
-}
-
-// dequantize_row_q3_K of the published format: one thread per (row-major) k-block of 32 outputs
-__global__ void dequantize_q3k_kernel(const uint8_t *__restrict__ in, int64_t nkb, float *__restrict__ y) {
-    const int64_t k = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (k >= nkb) return;
-    const uint8_t *blk = in + (k >> 3) * 110;
-    const int bq = (int)(k & 7), n = bq >> 2, s = bq & 3;
-    const uint8_t *hm = blk, *qs = blk + 32 + 32 * n;
-    const float dd = h2f((uint16_t)(blk[108] | ((uint16_t)blk[109] << 8)));
-    const float d0 = dd * (float)q3k_scale(blk + 96, 2 * bq), d1 = dd * (float)q3k_scale(blk + 96, 2 * bq + 1);
-    float *o = y + k * 32;
-    for (int t = 0; t < 32; ++t) {
-        const int v = (int)((qs[t] >> (2 * s)) & 3u) + 4 * (int)((hm[t] >> bq) & 1u) - 4;
-        o[t] = (t < 16 ? d0 : d1) * (float)v;               // upstream: d_all * (sc - 32) first, then times the value
+    static __device__ __forceinline__ void put(uint32_t *q, int bq, int t, int v) {
+        const int n = bq >> 2, s = bq & 3;
+        const uint32_t u = (uint32_t)(v + 4);               // 0..7
+        or_byte(q, 32 + 32 * n + t, (u & 3u) << (2 * s));
+        or_byte(q, t, (u >> 2) << bq);
     }
-}
+};
 
 // quantize_row_q3_K_reference of the published format, restated (tests/np_q3k.py quantize_q3_K is the same steps): per sub-block of 16
 // make_q3_quants(16, 4, x, L, true) -- codes l = nearest(-4 / max * x) in -4..3, then up to five passes that move one code at a time to
@@ -654,81 +539,29 @@ __global__ void quantize_q3k_kernel(const float *__restrict__ x, int64_t nsb, ui
 // becomes the two int8 planes of q and the scales d * sc_{2 b}, d * sc_{2 b + 1} (exact in f32: 11 + 4 significant bits) -- Q6_K's planes,
 // and every Q6_K kernel computes the block term B unchanged.  The 32-byte header slot of a super-block holds scales[16], d and dmin (bytes
 // 0..15, 16..17, 18..19): the download's header and the min pass's weight operand.
-// one thread per (row, k-block); rows fastest so the plane stores coalesce
-__global__ void q2k_to_planar_kernel(const uint8_t *__restrict__ aos, uint64_t nb01, int64_t row_begin, int64_t rows, int64_t Mpad,
-                                     uint8_t *__restrict__ i8p, float *__restrict__ d, float *__restrict__ mm, uint8_t *__restrict__ khdr) {
-    const int64_t m = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    const int64_t b = blockIdx.y;
-    if (m >= rows) return;
-    const int64_t sb = b >> 3;
-    const int bq = (int)(b & 7), n = bq >> 2, s = bq & 3;
-    const uint8_t *blk = aos + (uint64_t)(row_begin + m) * nb01 + (uint64_t)sb * 84;
-    const uint8_t *qs = blk + 16 + 32 * n;
-    const float dd = h2f((uint16_t)(blk[80] | ((uint16_t)blk[81] << 8)));
-    const int64_t pi = b * Mpad + m;
-    d[pi] = dd * (float)(blk[2 * bq] & 15);                 // exact: 11 + 4 significant bits
-    mm[pi] = dd * (float)(blk[2 * bq + 1] & 15);
-    uint32_t ev[4] = {0, 0, 0, 0}, od[4] = {0, 0, 0, 0};
-#pragma unroll
-    for (int t = 0; t < 32; ++t) {
-        const uint32_t byte = ((uint32_t)(qs[t] >> (2 * s)) & 3u) << (8 * ((t >> 1) & 3));
-        if (t & 1) od[t >> 3] |= byte; else ev[t >> 3] |= byte;      // plane h byte j = element 2 j + h
+// The dequantizer subtracts the min as upstream does: dl * q - ml, one multiply then one subtract.
+struct q2k_codec {
+    static constexpr int BYTES = 84, QOFF = 16, QLEN = 64, HDR = 20, SLOT = 32;
+    static constexpr bool MINS = true;
+    static __device__ __forceinline__ int hdr_pos(int i) { return i < 16 ? i : 64 + i; }      // scales[16], then d and dmin (bytes 80..83)
+    static __device__ __forceinline__ void scales(const uint8_t *blk, int bq, float &d0, float &d1) {
+        const float dd = h2f_at(blk + 80);
+        d0 = dd * (float)(blk[2 * bq] & 15);                // exact: 11 + 4 significant bits
+        d1 = dd * (float)(blk[2 * bq + 1] & 15);
     }
-    *(uint4 *)(i8p + ((b * 2 + 0) * Mpad + m) * 16) = make_uint4(ev[0], ev[1], ev[2], ev[3]);
-    *(uint4 *)(i8p + ((b * 2 + 1) * Mpad + m) * 16) = make_uint4(od[0], od[1], od[2], od[3]);
-    if (bq == 0) {
-        uint32_t h[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-#pragma unroll
-        for (int i = 0; i < 16; ++i) h[i >> 2] |= (uint32_t)blk[i] << (8 * (i & 3));
-        h[4] = (uint32_t)blk[80] | ((uint32_t)blk[81] << 8) | ((uint32_t)blk[82] << 16) | ((uint32_t)blk[83] << 24);
-        uint4 *o = (uint4 *)(khdr + (sb * Mpad + m) * 32);
-        o[0] = make_uint4(h[0], h[1], h[2], h[3]);
-        o[1] = make_uint4(h[4], h[5], h[6], h[7]);
+    static __device__ __forceinline__ void mins(const uint8_t *blk, int bq, float &m0, float &m1) {
+        const float dmin = h2f_at(blk + 82);
+        m0 = dmin * (float)(blk[2 * bq] >> 4);
+        m1 = dmin * (float)(blk[2 * bq + 1] >> 4);
     }
-}
-
-// exact inverse: one thread per (row, super-block)
-__global__ void planar_to_q2k_kernel(uint8_t *__restrict__ aos, uint64_t nb01, int64_t rows, int64_t Mpad, const uint8_t *__restrict__ i8p,
-                                     const uint8_t *__restrict__ khdr) {
-    const int64_t m = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    const int64_t sb = blockIdx.y;
-    if (m >= rows) return;
-    uint8_t *blk = aos + (uint64_t)m * nb01 + (uint64_t)sb * 84;
-    for (int i = 16; i < 80; ++i) blk[i] = 0;
-    for (int bq = 0; bq < 8; ++bq) {
-        const int n = bq >> 2, s = bq & 3;
-        uint8_t *qs = blk + 16 + 32 * n;
-        const int64_t b = sb * 8 + bq;
-        for (int hsel = 0; hsel < 2; ++hsel) {
-            const uint4 w4 = *(const uint4 *)(i8p + ((b * 2 + hsel) * Mpad + m) * 16);
-            const uint32_t w[4] = {w4.x, w4.y, w4.z, w4.w};
-            for (int j = 0; j < 16; ++j) {
-                const int t = 2 * j + hsel;
-                qs[t] |= (uint8_t)(((w[j >> 2] >> (8 * (j & 3))) & 3u) << (2 * s));
-            }
-        }
+    static __device__ __forceinline__ int value(const uint8_t *blk, int bq, int t) {
+        const uint8_t *qs = blk + 16 + 32 * (bq >> 2);
+        return (int)((qs[t] >> (2 * (bq & 3))) & 3u);
     }
-    const uint8_t *h = khdr + (sb * Mpad + m) * 32;
-    for (int i = 0; i < 16; ++i) blk[i] = h[i];
-    for (int i = 0; i < 4; ++i) blk[80 + i] = h[16 + i];
-}
-
-// dequantize_row_q2_K of the published format: one thread per (row-major) k-block of 32 outputs
-__global__ void dequantize_q2k_kernel(const uint8_t *__restrict__ in, int64_t nkb, float *__restrict__ y) {
-    const int64_t k = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (k >= nkb) return;
-    const uint8_t *blk = in + (k >> 3) * 84;
-    const int bq = (int)(k & 7), n = bq >> 2, s = bq & 3;
-    const uint8_t *qs = blk + 16 + 32 * n;
-    const float dd = h2f((uint16_t)(blk[80] | ((uint16_t)blk[81] << 8))), dmin = h2f((uint16_t)(blk[82] | ((uint16_t)blk[83] << 8)));
-    float *o = y + k * 32;
-    for (int hf = 0; hf < 2; ++hf) {
-        const uint32_t sc = blk[2 * bq + hf];
-        const float dl = dd * (float)(sc & 15u), ml = dmin * (float)(sc >> 4);
-        for (int t = 16 * hf; t < 16 * hf + 16; ++t)
-            o[t] = dl * (float)((qs[t] >> (2 * s)) & 3) - ml;   // upstream: dl * q - ml, one multiply then one subtract
+    static __device__ __forceinline__ void put(uint32_t *q, int bq, int t, int v) {
+        or_byte(q, 32 * (bq >> 2) + t, ((uint32_t)v & 3u) << (2 * (bq & 3)));
     }
-}
+};
 
 // quantize_row_q2_K_reference of the published format, restated (tests/np_q2k.py quantize_q2_K is the same steps): per sub-block of 16
 // make_qkx1_quants(16, 3, x, L, &min, 5) (the steps of quantize_kq_kernel above over 16 elements); the sixteen scales and mins as 4-bit codes
@@ -975,15 +808,26 @@ __global__ __launch_bounds__(256) void q2k_min_pass_kernel(const uint8_t *__rest
 
 }  // namespace
 
-hipError_t launch_q5k_to_planar(int kq_type, const uint8_t *aos, uint64_t nb01, int64_t row_begin, int64_t rows, ggml_hip_weight *w, hipStream_t st) {
+// ---- the four operations of a k-quant type (wtypes.cpp's rows point here): Q5_K / Q4_K onto the planar Q5_1 form, the others through two_scale.h
+hipError_t launch_kq_to_planar(int type, const uint8_t *aos, uint64_t nb01, int64_t row_begin, int64_t rows, ggml_hip_weight *w, hipStream_t st) {
+    switch (type) {
+    case GGML_HIP_TYPE_Q6_K: return two_scale_to_planar<q6k_codec>(aos, nb01, row_begin, rows, w, st);
+    case GGML_HIP_TYPE_Q3_K: return two_scale_to_planar<q3k_codec>(aos, nb01, row_begin, rows, w, st);
+    case GGML_HIP_TYPE_Q2_K: return two_scale_to_planar<q2k_codec>(aos, nb01, row_begin, rows, w, st);
+    }
     if (rows <= 0) return hipSuccess;
     dim3 grid((unsigned)((rows + 127) / 128), (unsigned)w->nbk);
-    if (kq_type == GGML_HIP_TYPE_Q5_K) q5k_to_planar_kernel<true><<<grid, 128, 0, st>>>(aos, nb01, row_begin, rows, w->Mpad, w->qs, w->qh, w->d, w->m, w->khdr);
+    if (type == GGML_HIP_TYPE_Q5_K) q5k_to_planar_kernel<true><<<grid, 128, 0, st>>>(aos, nb01, row_begin, rows, w->Mpad, w->qs, w->qh, w->d, w->m, w->khdr);
     else q5k_to_planar_kernel<false><<<grid, 128, 0, st>>>(aos, nb01, row_begin, rows, w->Mpad, w->qs, w->qh, w->d, w->m, w->khdr);
     return hipGetLastError();
 }
 
-hipError_t launch_planar_to_q5k(const ggml_hip_weight *w, uint8_t *aos, hipStream_t st) {
+hipError_t launch_planar_to_kq(const ggml_hip_weight *w, uint8_t *aos, hipStream_t st) {
+    switch (w->ext_type) {
+    case GGML_HIP_TYPE_Q6_K: return planar_to_two_scale<q6k_codec>(w, aos, st);
+    case GGML_HIP_TYPE_Q3_K: return planar_to_two_scale<q3k_codec>(w, aos, st);
+    case GGML_HIP_TYPE_Q2_K: return planar_to_two_scale<q2k_codec>(w, aos, st);
+    }
     if (w->M <= 0) return hipSuccess;
     dim3 grid((unsigned)((w->M + 127) / 128), (unsigned)(w->nbk / 8));
     if (w->ext_type == GGML_HIP_TYPE_Q5_K) planar_to_q5k_kernel<true><<<grid, 128, 0, st>>>(aos, (uint64_t)(w->nbk / 8) * 176, w->M, w->Mpad, w->qs, w->qh, w->khdr);
@@ -991,105 +835,31 @@ hipError_t launch_planar_to_q5k(const ggml_hip_weight *w, uint8_t *aos, hipStrea
     return hipGetLastError();
 }
 
-hipError_t launch_dequantize_q5k(int kq_type, const void *blocks, int64_t nrows, int64_t k, float *y, hipStream_t st) {
+hipError_t launch_dequantize_kq(int type, const void *blocks, int64_t nrows, int64_t k, float *y, hipStream_t st) {
+    switch (type) {
+    case GGML_HIP_TYPE_Q6_K: return dequantize_two_scale<q6k_codec>(blocks, nrows, k, y, st);
+    case GGML_HIP_TYPE_Q3_K: return dequantize_two_scale<q3k_codec>(blocks, nrows, k, y, st);
+    case GGML_HIP_TYPE_Q2_K: return dequantize_two_scale<q2k_codec>(blocks, nrows, k, y, st);
+    }
     const int64_t nsub = nrows * (k / 32);
     if (nsub <= 0) return hipSuccess;
-    if (kq_type == GGML_HIP_TYPE_Q5_K) dequantize_q5k_kernel<true><<<dim3((unsigned)((nsub + 127) / 128)), 128, 0, st>>>((const uint8_t *)blocks, nsub, y);
+    if (type == GGML_HIP_TYPE_Q5_K) dequantize_q5k_kernel<true><<<dim3((unsigned)((nsub + 127) / 128)), 128, 0, st>>>((const uint8_t *)blocks, nsub, y);
     else dequantize_q5k_kernel<false><<<dim3((unsigned)((nsub + 127) / 128)), 128, 0, st>>>((const uint8_t *)blocks, nsub, y);
     return hipGetLastError();
 }
 
-hipError_t launch_quantize_kq(int kq_type, const float *x, int64_t nrows, int64_t k, void *blocks, hipStream_t st) {
+// x: contiguous rows, 16-byte aligned.  Q5_K / Q4_K: eight lanes per super-block, the others sixteen
+hipError_t launch_quantize_kq(int type, const float *x, int64_t nrows, int64_t k, void *blocks, hipStream_t st) {
     const int64_t nsb = nrows * (k / 256);
     if (nsb <= 0) return hipSuccess;
-    const unsigned grid = (unsigned)((nsb * 8 + 127) / 128);
-    if (kq_type == GGML_HIP_TYPE_Q5_K) quantize_kq_kernel<true><<<dim3(grid), 128, 0, st>>>(x, nsb, (uint8_t *)blocks);
-    else quantize_kq_kernel<false><<<dim3(grid), 128, 0, st>>>(x, nsb, (uint8_t *)blocks);
-    return hipGetLastError();
-}
-
-hipError_t launch_q6k_to_planar(const uint8_t *aos, uint64_t nb01, int64_t row_begin, int64_t rows, ggml_hip_weight *w, hipStream_t st) {
-    if (rows <= 0) return hipSuccess;
-    dim3 grid((unsigned)((rows + 127) / 128), (unsigned)w->nbk);
-    q6k_to_planar_kernel<<<grid, 128, 0, st>>>(aos, nb01, row_begin, rows, w->Mpad, w->i8p, w->d, w->m, w->khdr);
-    return hipGetLastError();
-}
-
-hipError_t launch_planar_to_q6k(const ggml_hip_weight *w, uint8_t *aos, hipStream_t st) {
-    if (w->M <= 0) return hipSuccess;
-    dim3 grid((unsigned)((w->M + 127) / 128), (unsigned)(w->nbk / 8));
-    planar_to_q6k_kernel<<<grid, 128, 0, st>>>(aos, (uint64_t)(w->nbk / 8) * 210, w->M, w->Mpad, w->i8p, w->khdr);
-    return hipGetLastError();
-}
-
-hipError_t launch_dequantize_q6k(const void *blocks, int64_t nrows, int64_t k, float *y, hipStream_t st) {
-    const int64_t nkb = nrows * (k / 32);
-    if (nkb <= 0) return hipSuccess;
-    dequantize_q6k_kernel<<<dim3((unsigned)((nkb + 127) / 128)), 128, 0, st>>>((const uint8_t *)blocks, nkb, y);
-    return hipGetLastError();
-}
-
-hipError_t launch_quantize_q6k(const float *x, int64_t nrows, int64_t k, void *blocks, hipStream_t st) {
-    const int64_t nsb = nrows * (k / 256);
-    if (nsb <= 0) return hipSuccess;
-    quantize_q6k_kernel<<<dim3((unsigned)((nsb * 16 + 127) / 128)), 128, 0, st>>>(x, nsb, (uint8_t *)blocks);
-    return hipGetLastError();
-}
-
-
-hipError_t launch_q3k_to_planar(const uint8_t *aos, uint64_t nb01, int64_t row_begin, int64_t rows, ggml_hip_weight *w, hipStream_t st) {
-    if (rows <= 0) return hipSuccess;
-    dim3 grid((unsigned)((rows + 127) / 128), (unsigned)w->nbk);
-    q3k_to_planar_kernel<<<grid, 128, 0, st>>>(aos, nb01, row_begin, rows, w->Mpad, w->i8p, w->d, w->m, w->khdr);
-    return hipGetLastError();
-}
-
-hipError_t launch_planar_to_q3k(const ggml_hip_weight *w, uint8_t *aos, hipStream_t st) {
-    if (w->M <= 0) return hipSuccess;
-    dim3 grid((unsigned)((w->M + 127) / 128), (unsigned)(w->nbk / 8));
-    planar_to_q3k_kernel<<<grid, 128, 0, st>>>(aos, (uint64_t)(w->nbk / 8) * 110, w->M, w->Mpad, w->i8p, w->khdr);
-    return hipGetLastError();
-}
-
-hipError_t launch_dequantize_q3k(const void *blocks, int64_t nrows, int64_t k, float *y, hipStream_t st) {
-    const int64_t nkb = nrows * (k / 32);
-    if (nkb <= 0) return hipSuccess;
-    dequantize_q3k_kernel<<<dim3((unsigned)((nkb + 127) / 128)), 128, 0, st>>>((const uint8_t *)blocks, nkb, y);
-    return hipGetLastError();
-}
-
-hipError_t launch_quantize_q3k(const float *x, int64_t nrows, int64_t k, void *blocks, hipStream_t st) {
-    const int64_t nsb = nrows * (k / 256);
-    if (nsb <= 0) return hipSuccess;
-    quantize_q3k_kernel<<<dim3((unsigned)((nsb * 16 + 127) / 128)), 128, 0, st>>>(x, nsb, (uint8_t *)blocks);
-    return hipGetLastError();
-}
-
-hipError_t launch_q2k_to_planar(const uint8_t *aos, uint64_t nb01, int64_t row_begin, int64_t rows, ggml_hip_weight *w, hipStream_t st) {
-    if (rows <= 0) return hipSuccess;
-    dim3 grid((unsigned)((rows + 127) / 128), (unsigned)w->nbk);
-    q2k_to_planar_kernel<<<grid, 128, 0, st>>>(aos, nb01, row_begin, rows, w->Mpad, w->i8p, w->d, w->m, w->khdr);
-    return hipGetLastError();
-}
-
-hipError_t launch_planar_to_q2k(const ggml_hip_weight *w, uint8_t *aos, hipStream_t st) {
-    if (w->M <= 0) return hipSuccess;
-    dim3 grid((unsigned)((w->M + 127) / 128), (unsigned)(w->nbk / 8));
-    planar_to_q2k_kernel<<<grid, 128, 0, st>>>(aos, (uint64_t)(w->nbk / 8) * 84, w->M, w->Mpad, w->i8p, w->khdr);
-    return hipGetLastError();
-}
-
-hipError_t launch_dequantize_q2k(const void *blocks, int64_t nrows, int64_t k, float *y, hipStream_t st) {
-    const int64_t nkb = nrows * (k / 32);
-    if (nkb <= 0) return hipSuccess;
-    dequantize_q2k_kernel<<<dim3((unsigned)((nkb + 127) / 128)), 128, 0, st>>>((const uint8_t *)blocks, nkb, y);
-    return hipGetLastError();
-}
-
-hipError_t launch_quantize_q2k(const float *x, int64_t nrows, int64_t k, void *blocks, hipStream_t st) {
-    const int64_t nsb = nrows * (k / 256);
-    if (nsb <= 0) return hipSuccess;
-    quantize_q2k_kernel<<<dim3((unsigned)((nsb * 16 + 127) / 128)), 128, 0, st>>>(x, nsb, (uint8_t *)blocks);
+    const dim3 g8((unsigned)((nsb * 8 + 127) / 128)), g16((unsigned)((nsb * 16 + 127) / 128));
+    switch (type) {
+    case GGML_HIP_TYPE_Q6_K: quantize_q6k_kernel<<<g16, 128, 0, st>>>(x, nsb, (uint8_t *)blocks); break;
+    case GGML_HIP_TYPE_Q3_K: quantize_q3k_kernel<<<g16, 128, 0, st>>>(x, nsb, (uint8_t *)blocks); break;
+    case GGML_HIP_TYPE_Q2_K: quantize_q2k_kernel<<<g16, 128, 0, st>>>(x, nsb, (uint8_t *)blocks); break;
+    case GGML_HIP_TYPE_Q5_K: quantize_kq_kernel<true><<<g8, 128, 0, st>>>(x, nsb, (uint8_t *)blocks); break;
+    default:                 quantize_kq_kernel<false><<<g8, 128, 0, st>>>(x, nsb, (uint8_t *)blocks); break;
+    }
     return hipGetLastError();
 }
 

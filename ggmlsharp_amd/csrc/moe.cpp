@@ -66,11 +66,11 @@ int check_shape(int64_t n_tokens, int n_used) {
 
 // a public type id -> the resident type and ext_type a weight of it carries (what ggml_hip_mm_plan does)
 int resolve_type(int type, int64_t M, int64_t K, int *t, int *ext) {
-    const bool kq = is_kquant(type);
-    *t = kq ? kquant_resident_type(type) : is_iq4nl(type) ? GGML_TYPE_Q8_0 : type;
-    *ext = kq ? type : 0;
-    if (!is_bf16(*t) && (*t < 0 || *t >= GGML_TYPE_COUNT || !weight_type_ok(*t))) return fail(GGML_HIP_ERR_TYPE, "type %d is not a supported weight type", type);
-    if (M <= 0 || K <= 0 || K % ggml_hip_blck_size(*t) != 0 || (is_q(*t) && K % QK != 0) || (kq && K % 256 != 0)) return fail(GGML_HIP_ERR_SHAPE, "bad shape");
+    const wtype *r = wtype_of(type);
+    if (!r || !r->to_planar) return fail(GGML_HIP_ERR_TYPE, "type %d is not a supported weight type", type);
+    *t = r->resident;
+    *ext = wtype_ext(r);
+    if (M <= 0 || K <= 0 || K % k_unit(r) != 0) return fail(GGML_HIP_ERR_SHAPE, "bad shape");
     return GGML_HIP_OK;
 }
 
@@ -292,10 +292,9 @@ int ggml_hip_mul_mat_id_dev(const ggml_hip_expert_set *s, const int32_t *d_ids, 
 }
 
 int ggml_hip_mul_mat_id_grouped_serves_for(int type, int64_t M, int64_t K) {
-    const bool kq = is_kquant(type);
-    const int t = kq ? kquant_resident_type(type) : is_iq4nl(type) ? GGML_TYPE_Q8_0 : type;   // (IQ4_NL: a plain Q8_0 weight; a k-quant: never served)
-    if (M <= 0 || K <= 0 || K % QK != 0 || (kq && K % 256 != 0)) return 0;
-    return plan_mul_mat_id_grouped_serves(t, kq ? type : 0, M, K) ? 1 : 0;
+    const wtype *r = wtype_of(type);                       // (IQ4_NL: a plain Q8_0 weight; a k-quant: never served)
+    if (M <= 0 || K <= 0 || K % QK != 0 || (r && K % r->blck != 0)) return 0;
+    return plan_mul_mat_id_grouped_serves(r ? r->resident : type, r ? wtype_ext(r) : 0, M, K) ? 1 : 0;
 }
 
 int ggml_hip_mul_mat_id_grouped_serves(const ggml_hip_expert_set *s) {
@@ -304,9 +303,9 @@ int ggml_hip_mul_mat_id_grouped_serves(const ggml_hip_expert_set *s) {
 }
 
 size_t ggml_hip_mul_mat_id_grouped_work_size_for(int type, int64_t M, int64_t K, int n_expert, int64_t n_tokens, int n_used) {
-    const bool kq = is_kquant(type);
-    if (M <= 0 || K <= 0 || K % QK != 0 || (kq && K % 256 != 0)) return 0;
-    return grouped_work_size(kq ? kquant_resident_type(type) : is_iq4nl(type) ? GGML_TYPE_Q8_0 : type, kq ? type : 0, M, K, n_expert, n_tokens, n_used);
+    const wtype *r = wtype_of(type);
+    if (M <= 0 || K <= 0 || K % QK != 0 || (r && K % r->blck != 0)) return 0;
+    return grouped_work_size(r ? r->resident : type, r ? wtype_ext(r) : 0, M, K, n_expert, n_tokens, n_used);
 }
 
 size_t ggml_hip_mul_mat_id_grouped_work_size(const ggml_hip_expert_set *s, int64_t n_tokens, int n_used) {

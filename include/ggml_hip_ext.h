@@ -6,9 +6,7 @@
  *   - neighbours of the path and their fused forms                      (ggml_hip_compute_forward_{cpy,add,mul,scale,rms_norm,silu,...})
  *   - device-level fused / grouped products                             (ggml_hip_norm_mul_mat_dev, _mul_mat_multi_dev, _mul_mat_epilogue_dev, ...)
  *   - several devices in one process, one process per device           (ggml_hip_split_weight_*, _mul_mat_split_dev, _ipc_*, _push_columns_dev, ...)
- *   - the k-quant extension types                                       (GGML_HIP_TYPE_Q5_K, _Q4_K, _Q6_K, _Q3_K, _Q2_K)
- *   - the IQ4 extension types                                           (GGML_HIP_TYPE_IQ4_NL, _IQ4_XS)
- *   - the BF16 extension type                                           (GGML_HIP_TYPE_BF16)
+ *   - the extension weight types: k-quants, IQ4, BF16                  (GGML_HIP_TYPE_* below; one row each in csrc/wtypes.cpp says what the library does with an id)
  *   - expert-routed products of a mixture-of-experts layer             (ggml_hip_expert_set_*, ggml_hip_mul_mat_id_*)
  *   - TEST HOOKS (ggml_hip_debug_*): inert unless called; ggml_hip_debug_force_gemm acts on the CALLING THREAD only.
  */
