@@ -86,6 +86,13 @@ class ggml_hip_attn_plan_t(C.Structure):
                 ("n_chunks", C.c_int64), ("workgroups", C.c_int64)]
 
 
+class ggml_hip_rope_params_t(C.Structure):
+    """include/ggml_hip_ext.h: the parameters of a rotary embedding (mode 0 NORMAL, 2 NEOX)"""
+    _fields_ = [("n_dims", C.c_int32), ("mode", C.c_int32), ("n_ctx_orig", C.c_int32),
+                ("freq_base", C.c_float), ("freq_scale", C.c_float), ("ext_factor", C.c_float), ("attn_factor", C.c_float),
+                ("beta_fast", C.c_float), ("beta_slow", C.c_float)]
+
+
 class ggml_hip_mm_plan_t(C.Structure):
     """include/ggml_hip_ext.h: the plan of one product (csrc/plan.cpp)"""
     _fields_ = [("family", C.c_int32), ("image_kind", C.c_int32), ("form", C.c_int32), ("tree_id", C.c_uint32),
@@ -217,6 +224,11 @@ HIP_SYMBOLS = {
     "ggml_hip_attn_work_size": (C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int64, C.c_int64]),
     "ggml_hip_attn_dev": (C.c_int, [C.c_int, _P, C.c_int64, C.c_int64, _P, _P, C.c_int64, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int64, C.c_int64, _P,
                                     C.c_int64, C.c_int, C.c_float, _P, C.c_float, C.c_float, _P, _P, C.c_int64, C.c_int64, _P, C.c_size_t, _P]),
+    # the rotary embedding of Q / K rows: the per-pair constants (host only), the rotation, the rotation fused with the store into a KV cache
+    "ggml_hip_rope_table": (C.c_int, [_P, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
+    "ggml_hip_rope_dev": (C.c_int, [_P, _P, C.c_int64, C.c_int64, C.c_int, C.c_int, C.c_int64, _P, C.c_int64, _P, _P, _P, C.c_int64, C.c_int64, _P]),
+    "ggml_hip_rope_kv_store_dev": (C.c_int, [_P, C.c_int, _P, C.c_int64, C.c_int64, C.c_int, C.c_int, C.c_int64, _P, _P, C.c_int64, C.c_int64, C.c_int64,
+                                             C.c_int64, _P, _P]),
 }
 SYMBOLS = HIP_SYMBOLS
 

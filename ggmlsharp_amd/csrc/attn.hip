@@ -8,7 +8,7 @@
 // VISIBLE positions of query row t:  j < vis(t),  vis(t) = causal ? clamp(n_kv - n_q + t + 1, 0, n_kv) : n_kv.
 // CHUNK: the positions are cut into chunks of ATTN_CHUNK = 128, chunk c = [128 c, 128 c + 128), for every (kv_type, D), both forms.
 //
-// ---- kv_store ----  one thread per 32 elements (Q8_0) or 4 elements (F16) of a source row.  Q8_0: quantize.hip's statement of
+// ---- kv_store ----  one thread per 32 elements (Q8_0) or 4 elements (F16) of a source row, packed by kv_pack.h.  Q8_0: quantize.hip's statement of
 // quantize_row_q8_0 (amax; d = amax / 127; id = d ? 1 / d : 0; q = rint(v * id); the library is built without contraction and with the
 // correctly rounded division), bit for bit ggml_hip_quantize_rows_dev.  F16: IEEE round to nearest even by integer arithmetic (subnormals
 // kept, overflow to inf, a NaN stays a NaN).  A row whose position is outside [0, n_pos_max) leaves before any address is formed.
@@ -47,6 +47,7 @@
 // independently, a / l is c only up to the accumulation error -- so that case is held to the tolerance, not to bits.
 #include "common.h"
 #include "plan.h"
+#include "kv_pack.h"     // f32_to_f16_bits, kv_pack_q8_0, kv_pack_f16: the bytes of a cache row (shared with rope.hip)
 
 namespace {
 
@@ -55,30 +56,6 @@ using f16x4 = __attribute__((ext_vector_type(4))) _Float16;
 using f32x16 = __attribute__((ext_vector_type(16))) float;
 
 constexpr int C = ATTN_CHUNK;
-
-__device__ __forceinline__ uint32_t f32_to_f16_bits(float f) {      // (Half)f, IEEE round to nearest even (quantize.hip's algorithm)
-    const uint32_t x = __float_as_uint(f);
-    const uint32_t sign = (x >> 16) & 0x8000u;
-    const uint32_t exp = (x >> 23) & 0xFFu;
-    uint32_t man = x & 0x7FFFFFu;
-    if (exp == 0xFF) return man == 0 ? (sign | 0x7C00u) : (sign | 0x7C00u | 0x0200u | (man >> 13));
-    const int e = (int)exp - 127 + 15;
-    if (e >= 31) return sign | 0x7C00u;
-    if (e <= 0) {
-        if (e < -10) return sign;
-        man |= 0x800000u;
-        const int shift = 14 - e;
-        uint32_t hm = man >> shift;
-        const uint32_t rem = man & ((1u << shift) - 1u);
-        const uint32_t halfway = 1u << (shift - 1);
-        if (rem > halfway || (rem == halfway && (hm & 1u))) hm++;
-        return sign | hm;
-    }
-    uint32_t half = ((uint32_t)e << 10) | (man >> 13);
-    const uint32_t rem = man & 0x1FFFu;
-    if (rem > 0x1000u || (rem == 0x1000u && (half & 1u))) half++;
-    return sign | half;
-}
 
 __device__ __forceinline__ float f16_bits_to_f32(uint32_t h) { return (float)__builtin_bit_cast(_Float16, (uint16_t)h); }   // exact
 
@@ -110,27 +87,10 @@ __global__ __launch_bounds__(256) void kv_store_kernel(const float *__restrict__
         float v[QK];
 #pragma unroll
         for (int k = 0; k < 8; ++k) { const float4 f = x[k]; v[4 * k] = f.x; v[4 * k + 1] = f.y; v[4 * k + 2] = f.z; v[4 * k + 3] = f.w; }
-        float amax = 0.0f;
-#pragma unroll
-        for (int l = 0; l < QK; ++l) amax = fmaxf(amax, fabsf(v[l]));
-        const float d = amax / 127.0f;
-        const float id = d != 0.0f ? 1.0f / d : 0.0f;
-        uint32_t w[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-#pragma unroll
-        for (int l = 0; l < QK; ++l) {
-            const int q = (int)rintf(v[l] * id);
-            w[l / 4] |= ((uint32_t)q & 0xFFu) << (8 * (l & 3));
-        }
-        uint32_t *o = (uint32_t *)(row + 36 * (int64_t)u);
-        o[0] = __float_as_uint(d);
-#pragma unroll
-        for (int k = 0; k < 8; ++k) o[1 + k] = w[k];
+        kv_pack_q8_0(v, (uint32_t *)(row + 36 * (int64_t)u));
     } else {
         const float4 f = *(const float4 *)(src + r * ld + 4 * u);
-        uint2 o;
-        o.x = f32_to_f16_bits(f.x) | (f32_to_f16_bits(f.y) << 16);
-        o.y = f32_to_f16_bits(f.z) | (f32_to_f16_bits(f.w) << 16);
-        *(uint2 *)(row + 8 * (int64_t)u) = o;
+        *(uint2 *)(row + 8 * (int64_t)u) = kv_pack_f16(f);
     }
 }
 

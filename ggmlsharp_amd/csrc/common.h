@@ -449,6 +449,20 @@ struct attn_args {
 hipError_t launch_kv_store(int kv_type, const float *src, int64_t ld, int64_t n_rows, int64_t row_elems, void *cache, int64_t nb_pos, int64_t n_pos_max,
                            int64_t pos0, const int32_t *d_pos0, hipStream_t st);
 hipError_t launch_attn(const attn_plan &pl, const attn_args &a, hipStream_t st);
+// rope.hip: the rotation of Q / K rows (ggml_hip_rope_dev) and the rotation fused with kv_store (ggml_hip_rope_kv_store_dev; rope.cpp).
+// The per-pair constants are the HOST's (ggml_hip_rope_table) and go to the kernels by value: eff[i] for pair i < n_dims / 2, and mscale
+#define ROPE_MAX_PAIRS 128
+struct rope_table { double eff[ROPE_MAX_PAIRS]; double mscale; };
+struct rope_args {
+    int mode, n_dims, n_head, D;                                     // mode: 0 NORMAL, 2 NEOX
+    const float *x; int64_t ldx_tok, ldx_head; int64_t n_tokens;
+    const int32_t *d_pos; int64_t pos0; const int32_t *d_pos0;       // token t sits at d_pos[t], or at (d_pos0 ? *d_pos0 : pos0) + t
+    const float *freq_factors;
+};
+hipError_t launch_rope(const rope_table &tab, const rope_args &a, float *dst, int64_t ldd_tok, int64_t ldd_head, hipStream_t st);
+// (a.d_pos is not read: the rope position is the cache position)
+hipError_t launch_rope_kv_store(const rope_table &tab, const rope_args &a, int kv_type, void *cache, int64_t nb_pos, int64_t nb_head, int64_t n_pos_max,
+                                hipStream_t st);
 // gemm_q8s.hip / gemm_qmx.hip: ONE K3s launch over the tile table -- workgroup -> (weight tile group, column tile t); t >= *n_tiles leaves at once;
 // the expert's planes come from tab[tiles[t].expert], the 32 sorted rows at 32 t of the image p (K1's image of `32 * max_tiles` rows); res [rows][ldr]
 hipError_t launch_gemm_q8_small_grouped(const mm_plan &g, int type, const moe_gexpert *tab, const moe_tile *tiles, const int32_t *n_tiles, int64_t max_tiles,

@@ -284,6 +284,55 @@ def attention(kv_type, q, k, v, nb_pos, nb_head, n_head_kv, n_kv, d_n_kv=None, n
     return out
 
 
+def rope_params(n_dims, mode=0, freq_base=10000.0, freq_scale=1.0, ext_factor=0.0, attn_factor=1.0, beta_fast=32.0, beta_slow=1.0, n_ctx_orig=0):
+    """a ggml_hip_rope_params_t: mode 0 NORMAL (pairs 2i, 2i+1), 2 NEOX (pairs i, i + n_dims/2); ext_factor != 0 turns YaRN on"""
+    return _lib.ggml_hip_rope_params_t(int(n_dims), int(mode), int(n_ctx_orig), float(freq_base), float(freq_scale), float(ext_factor), float(attn_factor),
+                                       float(beta_fast), float(beta_slow))
+
+
+def rope_table(rp):
+    """(eff float64 [n_dims/2], mscale): the per-pair constants every rope kernel uses, as include/ggml_hip_ext.h defines them; no device needed"""
+    eff = np.zeros(rp.n_dims // 2 if rp.n_dims > 0 else 0, dtype=np.float64)
+    mscale = C.c_double()
+    check(lib().ggml_hip_rope_table(C.byref(rp), eff.ctypes.data_as(C.POINTER(C.c_double)), C.byref(mscale)), "ggml_hip_rope_table")
+    return eff, mscale.value
+
+
+def _opt(t):
+    return C.c_void_p(t.data_ptr()) if t is not None else None
+
+
+def rope(rp, x, pos=None, pos0=0, d_pos0=None, freq_factors=None, out=None):
+    """rotate the rows of x f32 [n_tokens, n_head, D] (last stride 1) on the current stream.  Token t sits at pos[t] (an int32 tensor on the
+    device), else at p0 + t with p0 = *d_pos0 (an int32 tensor on the device, read by the kernel) or pos0.  freq_factors: f32 [n_dims/2] on the
+    device.  out may be x itself (in place); default a new tensor."""
+    assert x.is_cuda and x.dtype == torch.float32 and x.dim() == 3 and x.stride(2) == 1
+    assert pos is None or (pos.is_cuda and pos.dtype == torch.int32 and pos.is_contiguous() and pos.numel() == x.shape[0])
+    assert d_pos0 is None or (d_pos0.is_cuda and d_pos0.dtype == torch.int32)
+    assert freq_factors is None or (freq_factors.is_cuda and freq_factors.dtype == torch.float32 and freq_factors.is_contiguous())
+    n_tokens, n_head, D = x.shape
+    if out is None:
+        out = torch.empty((n_tokens, n_head, D), dtype=torch.float32, device=x.device)
+    assert out.dtype == torch.float32 and out.dim() == 3 and out.stride(2) == 1 and tuple(out.shape) == (n_tokens, n_head, D)
+    check(lib().ggml_hip_rope_dev(C.byref(rp), C.c_void_p(x.data_ptr()), x.stride(0), x.stride(1), n_head, D, n_tokens, _opt(pos), int(pos0), _opt(d_pos0),
+                                  _opt(freq_factors), C.c_void_p(out.data_ptr()), out.stride(0), out.stride(1), _stream()), "ggml_hip_rope_dev")
+    return out
+
+
+def rope_kv_store(rp, kv_type, x, cache, nb_pos, nb_head, n_pos_max, pos0=0, d_pos0=None, freq_factors=None):
+    """rotate the rows of x f32 [n_tokens, n_head_kv, D] and store them as rows of kv_type (F16 / Q8_0) at cache + (p0 + t) * nb_pos +
+    hk * nb_head bytes in one launch: bit for bit rope() into a temporary, then kv_store().  The rope position is the cache position p0 + t,
+    p0 = *d_pos0 or pos0; positions outside [0, n_pos_max) write nothing."""
+    assert x.is_cuda and x.dtype == torch.float32 and x.dim() == 3 and x.stride(2) == 1
+    assert cache.is_cuda and cache.dtype == torch.uint8
+    assert d_pos0 is None or (d_pos0.is_cuda and d_pos0.dtype == torch.int32)
+    assert freq_factors is None or (freq_factors.is_cuda and freq_factors.dtype == torch.float32 and freq_factors.is_contiguous())
+    n_tokens, n_head_kv, D = x.shape
+    check(lib().ggml_hip_rope_kv_store_dev(C.byref(rp), kv_type, C.c_void_p(x.data_ptr()), x.stride(0), x.stride(1), n_head_kv, D, n_tokens, _opt(freq_factors),
+                                           C.c_void_p(cache.data_ptr()), nb_pos, nb_head, n_pos_max, int(pos0), _opt(d_pos0), _stream()),
+          "ggml_hip_rope_kv_store_dev")
+
+
 def quantize_rows(type, x):
     """x f32 [nrows, k] on the device -> uint8 [nrows, k/32*type_size] reference-format blocks."""
     assert x.is_cuda and x.dtype == torch.float32 and x.is_contiguous()

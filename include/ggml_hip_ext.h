@@ -491,7 +491,7 @@ int ggml_hip_silu_mul_rows_dev(const float *d_a, const float *d_b, float *d_silu
  * Upstream's ggml_flash_attn_ext, an EXTENSION like mul_mat_id (the reference has the op's id and no dispatch): device-resident entries only.
  * With ggml_hip_rms_norm_mul_rows_dev, ggml_hip_mul_mat_multi_dev (q / k / v in one launch) and the add / scale epilogues these make a decoder
  * layer's attention half out of device entries: projections -> kv_store -> attention -> output projection.  Both entries are stream-ordered on
- * `stream` on the current device; they do not synchronize and do not allocate, and may be captured.  (Rope stays the host's.)
+ * `stream` on the current device; they do not synchronize and do not allocate, and may be captured.  (The rotation of Q and K between the projections and the cache is the ROPE section's, below.)
  *
  * THE CACHE.  kv_type is GGML_TYPE_F16 or GGML_TYPE_Q8_0, the same for K and V (anything else: GGML_HIP_ERR_TYPE).  A cache ROW is
  * (position j, kv head hk): D elements in reference block format -- F16: 2 D bytes of IEEE halves, what ggml_cpy f32 -> f16 writes; Q8_0:
@@ -550,6 +550,63 @@ int    ggml_hip_attn_dev(int kv_type, const float *d_q, int64_t ldq_tok, int64_t
                          int n_head, int n_head_kv, int D, int64_t n_q, int64_t n_kv, const int32_t *d_n_kv, int64_t n_kv_max,
                          int causal, float scale, const void *d_mask, float max_bias, float logit_softcap, const float *d_sinks,
                          float *d_dst, int64_t ldd_tok, int64_t ldd_head, void *d_work, size_t work_bytes, void *stream);
+
+/* ---------------- ROPE: the rotary position embedding of Q / K rows, and the rotation fused with the store into the KV cache ----------------
+ * Upstream's ggml_rope_ext, an EXTENSION like attention (the reference has the op's id and no dispatch): device-resident entries only, no
+ * seam, no host mirror.  With the ATTENTION entries a decode step is device entries alone: projections -> rope(q) -> rope_kv_store(k) ->
+ * kv_store(v) -> attention.  Both device entries are stream-ordered on `stream` on the current device; they do not synchronize, do not
+ * allocate, take no work buffer and may be captured.  n_tokens = 0 returns 0 and writes nothing.
+ *
+ * MODE 0 NORMAL rotates the pairs (2i, 2i+1), mode 2 NEOX the pairs (i, i + n_dims/2), i = 0 .. n_dims/2 - 1, of every row of D elements;
+ * elements n_dims .. D-1 are copied bit for bit.  mrope, vision and any other mode: GGML_HIP_ERR_ARG.
+ *
+ * POSITIONS.  With d_pos != NULL token t sits at d_pos[t] (an int32 array on the device, upstream's `pos` tensor; ggml_hip_rope_dev
+ * rotates by whatever int32 it reads).  Otherwise it sits at p0 + t, p0 = d_pos0 ? *d_pos0 (an int32 on the device, read by the kernel) :
+ * pos0 -- ggml_hip_kv_store_dev's convention, so ONE device integer drives the store and the rotation of a captured step.
+ *
+ * THE PER-PAIR CONSTANTS (upstream's rope_yarn and ggml_rope_yarn_corr_dims restated; this text is the definition, ggml_hip_rope_table
+ * returns exactly these, all binary64, and the device entries call the same function on the host and hand the kernels the result):
+ *     extrap_i = freq_base ^ (-2 i / n_dims)
+ *     corr(r)  = n_dims * ln(n_ctx_orig / (2 pi r)) / (2 ln freq_base)
+ *     low      = max(0, floor(corr(beta_fast))),   high = min(n_dims - 1, ceil(corr(beta_slow)))
+ *     ramp_i   = 1 - clamp((i - low) / max(0.001, high - low), 0, 1)
+ *     mix_i    = ramp_i * ext_factor               (ext_factor == 0: mix_i = 0, and n_ctx_orig and the betas are not read)
+ *     eff_i    = extrap_i * (freq_scale * (1 - mix_i) + mix_i)
+ *     mscale   = attn_factor, times (1 + 0.1 ln(1 / freq_scale)) when ext_factor != 0
+ * THE ROTATION of the pair (x0, x1) of pair index i at position pos:
+ *     theta = (double)pos * eff_i,  divided by (double)d_freq_factors[i] where d_freq_factors != NULL (device f32 [n_dims/2], llama-3's)
+ *     c = (float)(cos(theta) * mscale),  s = (float)(sin(theta) * mscale)          binary64 cos / sin, one rounding to binary32 each
+ *     y0 = x0 * c - x1 * s,  y1 = x0 * s + x1 * c                                  every f32 operation rounds once, no fused multiply-add
+ *   This is MORE EXACT than upstream's f32 chain (whose angle carries about 4e-3 rad of rounding at position 32768), not bit-equal to it:
+ *   the angle is good to about pos * 2^-48 rad, and an element is within 4 * 2^-24 * mscale * (|x0| + |x1|) of the exact rotation up to
+ *   position 2^20.  Position 0 returns the input as VALUES (mscale = 1): a zero's sign may change (x0 * 1 - x1 * 0).
+ *   A row's bits depend on (pos, the row, the parameters) alone: not on n_head, the strides, n_tokens, in place or not, or where pos came from.
+ *
+ * SHAPES.  D a multiple of 4, at most 256; n_dims even, in 2 .. D; n_head in 1 .. 65535; n_tokens <= 2^24; the strides (elements) multiples
+ * of 4 and at least D; d_x, d_dst, d_cache 16-byte aligned: else GGML_HIP_ERR_SHAPE.  mode 0 or 2, freq_base > 1, freq_scale > 0, every
+ * parameter finite (and, with ext_factor != 0, n_ctx_orig >= 1 and both betas > 0): else GGML_HIP_ERR_ARG, as is a null d_x / d_dst / d_cache.
+ * d_dst may EQUAL d_x with equal strides (in place: a thread owns whole pairs); any other overlap is the caller's error.
+ *
+ * ggml_hip_rope_kv_store_dev: rotate K rows and store them as cache rows in one launch; the rotated row never goes to memory.  kv_type F16
+ * or Q8_0 (else GGML_HIP_ERR_TYPE; Q8_0: D % 32 == 0).  Only the p0 form: the rope position IS the cache position.  Row (t, hk) goes to
+ * d_cache + (p0 + t) * nb_pos + hk * nb_head; nb_pos / nb_head follow ggml_hip_attn_dev's rules (multiples of 16, at least a row's bytes,
+ * either may be the larger) -- because it takes nb_head, one call serves every head of a D = 64 Q8_0 cache whose heads are 80 bytes apart,
+ * where ggml_hip_kv_store_dev needs a call per head.  A row whose position is < 0 or >= n_pos_max writes nothing, and no address is formed
+ * from it.  THE CONTRACT: bit for bit ggml_hip_rope_dev into a temporary followed by ggml_hip_kv_store_dev. */
+typedef struct ggml_hip_rope_params_t {
+    int32_t n_dims, mode, n_ctx_orig;      /* mode: 0 NORMAL (pairs 2i, 2i+1), 2 NEOX (pairs i, i + n_dims/2) */
+    float   freq_base, freq_scale, ext_factor, attn_factor, beta_fast, beta_slow;
+} ggml_hip_rope_params_t;
+/* host only, no device: the per-pair constants every kernel uses; eff: n_dims/2 doubles */
+int ggml_hip_rope_table(const ggml_hip_rope_params_t *rp, double *eff, double *mscale);
+int ggml_hip_rope_dev(const ggml_hip_rope_params_t *rp, const float *d_x, int64_t ldx_tok, int64_t ldx_head,
+                      int n_head, int D, int64_t n_tokens,
+                      const int32_t *d_pos, int64_t pos0, const int32_t *d_pos0, const float *d_freq_factors,
+                      float *d_dst, int64_t ldd_tok, int64_t ldd_head, void *stream);
+int ggml_hip_rope_kv_store_dev(const ggml_hip_rope_params_t *rp, int kv_type, const float *d_x, int64_t ldx_tok, int64_t ldx_head,
+                               int n_head_kv, int D, int64_t n_tokens, const float *d_freq_factors,
+                               void *d_cache, int64_t nb_pos, int64_t nb_head, int64_t n_pos_max,
+                               int64_t pos0, const int32_t *d_pos0, void *stream);
 
 #if defined(__GNUC__)
 #pragma GCC visibility pop

@@ -92,6 +92,21 @@ internal static unsafe partial class GgmlHip
     [DllImport(Lib)] public static extern int ggml_hip_attn_dev(int kvType, float* dQ, long ldqTok, long ldqHead, void* dK, void* dV, long nbPos, long nbHead,
         int nHead, int nHeadKv, int d, long nQ, long nKv, int* dNKv, long nKvMax, int causal, float scale, void* dMask, float maxBias, float logitSoftcap, float* dSinks,
         float* dDst, long lddTok, long lddHead, void* dWork, nuint workBytes, void* stream);
+    // ... the rotary embedding of Q / K rows between the projections and the cache (device entries, capturable): token t sits at dPos[t] (int32 on the
+    // device) or at p0 + t, p0 = *dPos0 (int32 on the device) or pos0 -- kv_store's convention; mode 0 NORMAL, 2 NEOX; dFreqFactors (llama-3's) may be
+    // null; dDst may be dX (in place).  rope_kv_store: rotate K rows and store them as F16 / Q8_0 cache rows at (p0 + t) * nbPos + hk * nbHead in one
+    // launch, bit for bit rope then kv_store.  rope_table: the per-pair constants (eff: nDims / 2 doubles), host only
+    [StructLayout(LayoutKind.Sequential)]
+    public struct ggml_hip_rope_params_t
+    {
+        public int n_dims, mode, n_ctx_orig;
+        public float freq_base, freq_scale, ext_factor, attn_factor, beta_fast, beta_slow;
+    }
+    [DllImport(Lib)] public static extern int ggml_hip_rope_table(ggml_hip_rope_params_t* rp, double* eff, double* mscale);
+    [DllImport(Lib)] public static extern int ggml_hip_rope_dev(ggml_hip_rope_params_t* rp, float* dX, long ldxTok, long ldxHead, int nHead, int d, long nTokens,
+        int* dPos, long pos0, int* dPos0, float* dFreqFactors, float* dDst, long lddTok, long lddHead, void* stream);
+    [DllImport(Lib)] public static extern int ggml_hip_rope_kv_store_dev(ggml_hip_rope_params_t* rp, int kvType, float* dX, long ldxTok, long ldxHead, int nHeadKv, int d,
+        long nTokens, float* dFreqFactors, void* dCache, long nbPos, long nbHead, long nPosMax, long pos0, int* dPos0, void* stream);
 
     // Seam 2: the quantize_fns_t slots (TypeDefinitions.cs:334-342), type-indexed
     [DllImport(Lib)] public static extern int ggml_hip_quantize_row(int type, float* x, void* y, int k);
