@@ -229,6 +229,13 @@ HIP_SYMBOLS = {
     "ggml_hip_rope_dev": (C.c_int, [_P, _P, C.c_int64, C.c_int64, C.c_int, C.c_int, C.c_int64, _P, C.c_int64, _P, _P, _P, C.c_int64, C.c_int64, _P]),
     "ggml_hip_rope_kv_store_dev": (C.c_int, [_P, C.c_int, _P, C.c_int64, C.c_int64, C.c_int, C.c_int, C.c_int64, _P, _P, C.c_int64, C.c_int64, C.c_int64,
                                              C.c_int64, _P, _P]),
+    # the ends of a decode step: rows of a resident weight by device ids; top-k over a vocabulary, probabilities, top-p and the pick
+    "ggml_hip_get_rows_serves_for": (C.c_int, [C.c_int]),
+    "ggml_hip_get_rows_dev": (C.c_int, [_P, _P, C.c_int64, _P, C.c_int64, _P]),
+    "ggml_hip_topk_chunk": (C.c_int64, []),
+    "ggml_hip_topk_work_size": (C.c_size_t, [C.c_int64, C.c_int64, C.c_int]),
+    "ggml_hip_argmax_rows_dev": (C.c_int, [_P, C.c_int64, C.c_int64, C.c_int64, _P, _P, C.c_size_t, _P]),
+    "ggml_hip_sample_topk_dev": (C.c_int, [_P, C.c_int64, C.c_int64, C.c_int64, C.c_int, C.c_float, C.c_float, _P, _P, _P, _P, _P, C.c_size_t, _P]),
 }
 SYMBOLS = HIP_SYMBOLS
 

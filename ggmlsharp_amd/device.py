@@ -333,6 +333,61 @@ def rope_kv_store(rp, kv_type, x, cache, nb_pos, nb_head, n_pos_max, pos0=0, d_p
           "ggml_hip_rope_kv_store_dev")
 
 
+def get_rows(w, ids, out=None):
+    """out[i, :K] = dequantize(w[ids[i]]) on the current stream: ids an int32 tensor on the device; bit for bit download + dequantize, a row of
+    +0.0 for an id outside [0, M).  out f32 [n_ids, >= K] with last stride 1 (default a new [n_ids, K] tensor)."""
+    assert ids.is_cuda and ids.dtype == torch.int32 and ids.is_contiguous()
+    n = ids.numel()
+    if out is None:
+        out = torch.empty((n, w.K), dtype=torch.float32, device=ids.device)
+    assert out.is_cuda and out.dtype == torch.float32 and out.dim() == 2 and out.stride(1) == 1 and out.shape[0] >= n
+    check(lib().ggml_hip_get_rows_dev(w.handle, C.c_void_p(ids.data_ptr()), n, C.c_void_p(out.data_ptr()), out.stride(0), _stream()), "ggml_hip_get_rows_dev")
+    return out
+
+
+def topk_work(n_rows, n_vocab, k, device=None):
+    """the work buffer ggml_hip_argmax_rows_dev (k = 1) / ggml_hip_sample_topk_dev need for a shape"""
+    return torch.empty(max(int(lib().ggml_hip_topk_work_size(n_rows, n_vocab, k)), 8), dtype=torch.uint8, device=device or "cuda")
+
+
+def argmax_rows(logits, ids=None, work=None):
+    """ids[r] = the index of the largest logit of row r (ties: the smaller index; a NaN below every number): logits f32 [n_rows, n_vocab], last
+    stride 1.  ids: an int32 tensor on the device (default new) -- the one get_rows() reads on the next step."""
+    assert logits.is_cuda and logits.dtype == torch.float32 and logits.dim() == 2 and logits.stride(1) == 1
+    n_rows, n_vocab = logits.shape
+    if ids is None:
+        ids = torch.empty(n_rows, dtype=torch.int32, device=logits.device)
+    if work is None:
+        work = topk_work(n_rows, n_vocab, 1, logits.device)
+    assert ids.dtype == torch.int32 and ids.is_contiguous() and ids.numel() >= n_rows
+    check(lib().ggml_hip_argmax_rows_dev(C.c_void_p(logits.data_ptr()), logits.stride(0), n_rows, n_vocab, C.c_void_p(ids.data_ptr()), C.c_void_p(work.data_ptr()),
+                                         work.numel(), _stream()), "ggml_hip_argmax_rows_dev")
+    return ids
+
+
+def sample_topk(logits, k, inv_temp=1.0, top_p=1.0, u=None, ids=None, probs=None, token=None, work=None, want_probs=True):
+    """the k best logits of every row (ids [n_rows, k], rank order), p = softmax((l - l_0) * inv_temp) over them (probs [n_rows, k]) and, with
+    u (f32 [n_rows] uniforms in [0, 1) on the device), the pick among the top_p mass (token int32 [n_rows]).  -> (ids, probs, token); probs is
+    None with want_probs = False (then no pick), token is None without u."""
+    assert logits.is_cuda and logits.dtype == torch.float32 and logits.dim() == 2 and logits.stride(1) == 1
+    n_rows, n_vocab = logits.shape
+    dev = logits.device
+    if ids is None:
+        ids = torch.empty((n_rows, k), dtype=torch.int32, device=dev)
+    if probs is None and want_probs:
+        probs = torch.empty((n_rows, k), dtype=torch.float32, device=dev)
+    if u is not None and token is None:
+        token = torch.empty(n_rows, dtype=torch.int32, device=dev)
+    if work is None:
+        work = topk_work(n_rows, n_vocab, k, dev)
+    assert ids.dtype == torch.int32 and ids.is_contiguous() and (probs is None or (probs.dtype == torch.float32 and probs.is_contiguous()))
+    assert u is None or (u.is_cuda and u.dtype == torch.float32 and u.is_contiguous() and token.dtype == torch.int32)
+    check(lib().ggml_hip_sample_topk_dev(C.c_void_p(logits.data_ptr()), logits.stride(0), n_rows, n_vocab, int(k), float(inv_temp), float(top_p), _opt(u),
+                                         C.c_void_p(ids.data_ptr()), _opt(probs), _opt(token if u is not None else None), C.c_void_p(work.data_ptr()),
+                                         work.numel(), _stream()), "ggml_hip_sample_topk_dev")
+    return ids, probs, (token if u is not None else None)
+
+
 def quantize_rows(type, x):
     """x f32 [nrows, k] on the device -> uint8 [nrows, k/32*type_size] reference-format blocks."""
     assert x.is_cuda and x.dtype == torch.float32 and x.is_contiguous()

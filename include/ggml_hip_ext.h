@@ -608,6 +608,65 @@ int ggml_hip_rope_kv_store_dev(const ggml_hip_rope_params_t *rp, int kv_type, co
                                void *d_cache, int64_t nb_pos, int64_t nb_head, int64_t n_pos_max,
                                int64_t pos0, const int32_t *d_pos0, void *stream);
 
+/* ---------------- THE ENDS OF A DECODE STEP: a token id -> its embedding row; the LM head's logits -> the next token id ----------------
+ * Upstream's ggml_get_rows over the token-embedding matrix and its ggml_argmax / top-k -> temperature -> softmax -> top-p -> pick sampler
+ * chain, EXTENSIONS like rope (the reference lists get_rows and never dispatches it): device entries only.  With them a captured decode step
+ * is a closed loop, d_token -> get_rows -> the layers -> logits -> sample -> d_token: the int32 the sampler writes is the one get_rows reads
+ * on the next replay, and with tied embeddings the matrix get_rows reads is the LM head's own resident weight.  Every entry is stream-ordered
+ * on `stream`; none synchronizes or allocates, scratch is the caller's, all may be captured; no atomics, results independent of scheduling.
+ * Every refusal below is decided before a device is touched.
+ *
+ * ggml_hip_get_rows_dev:  d_dst[i * ldd + k] = dequantize(W[d_ids[i]])[k], k < K, i < n_ids; d_ids an int32 array on the device.
+ *   THE CONTRACT: a gathered row is bit for bit ggml_hip_weight_download of that row followed by the type's dequantize row function
+ *   (ggml_hip_dequantize_rows_dev); F32: the row itself; F16 / BF16: the exact widening.  The planes a weight is resident in hold the block
+ *   fields of its file format or values its dequantizer computes first and exactly, so nothing is added to a weight for this and nothing is
+ *   copied: every type that can be a resident weight is served (ggml_hip_get_rows_serves_for: 1; any other id 0, and the entry returns
+ *   GGML_HIP_ERR_TYPE) -- Q4_0, Q4_1, Q4_2, Q5_0, Q5_1, Q8_0, F16, F32, BF16, IQ4_NL, IQ4_XS, Q2_K, Q3_K, Q4_K, Q5_K, Q6_K.
+ *   An id outside [0, M) writes a row of +0.0f and no address is formed from it (upstream asserts; a device-side id cannot be asserted on
+ *   without a synchronize).  Repeated ids are fine.  Columns K .. ldd-1 of d_dst and rows past n_ids are not written.  d_dst may not overlap
+ *   the weight.  16-byte stores where d_dst is 16-byte aligned and ldd % 4 == 0, one element at a time otherwise: the same bits.
+ *   n_ids = 0: returns 0 and writes nothing.  n_ids < 0, or a null w / d_ids / d_dst: GGML_HIP_ERR_ARG.  n_ids > 2^20 or ldd < K:
+ *   GGML_HIP_ERR_SHAPE.  d_ids and d_dst must be 4-byte aligned (GGML_HIP_ERR_ARG).  Out of scope: rows of anything but a resident weight, a
+ *   backward pass, i32 / f16 outputs. */
+int ggml_hip_get_rows_serves_for(int type);                       /* host only: 1 / 0 */
+int ggml_hip_get_rows_dev(const ggml_hip_weight *w, const int32_t *d_ids, int64_t n_ids, float *d_dst, int64_t ldd, void *stream);
+/* THE SAMPLER.  d_logits: f32, [n_rows] rows of n_vocab, ld >= n_vocab elements apart (the dst of ggml_hip_mul_mat_dev for the LM head).
+ *   SELECTION is ggml_hip_moe_route_dev's rule, so a row's ids are defined bit for bit:
+ *     - d_ids[r * k + s] is the index of rank s under "larger logit first; equal logits: smaller index first";
+ *     - -0.0 and +0.0 compare equal;
+ *     - a NaN ranks below every non-NaN value, -inf included; NaNs rank among themselves by index;
+ *     - so a row's k ids are distinct and inside [0, n_vocab) whatever the logits hold.
+ *   ggml_hip_argmax_rows_dev is k = 1 with no probabilities (d_ids[r]): upstream's ggml_argmax with the tie and NaN cases defined.
+ *   PROBABILITIES (d_probs[r * k + s]), every operation one binary32 rounding, expf the correctly-specified library function, l_s the rank-s
+ *   logit (a zero taken as +0.0):
+ *       e_s = expf((l_s - l_0) * inv_temp);   S = e_0 + e_1 + ... + e_(k-1), summed sequentially in rank order;   p_s = e_s / S
+ *   -- upstream's top-k, then temperature, then softmax.
+ *   TOP-P AND THE PICK are defined on the p_s the entry wrote, by sequential f32 sums, so given d_probs they are bit-defined:
+ *       n_keep = the smallest n >= 1 with p_0 + .. + p_(n-1) >= top_p, or k if there is none; top_p >= 1: k, without summing
+ *       C      = p_0 + .. + p_(n_keep-1);   target = d_u[r] * C
+ *       d_token[r] = the id of the first s < n_keep whose running sum p_0 + .. + p_s exceeds target, or of rank n_keep - 1 if none does
+ *   d_u: the caller's uniforms in [0, 1), one per row, on the device -- the host refreshes them between replays; the library has no RNG.
+ *   d_u == NULL or d_token == NULL: no pick.  d_probs == NULL is allowed only when there is no pick.  A row whose rank-0 logit is NaN or
+ *   +-inf has UNSPECIFIED d_probs and d_token, but d_token is still one of the row's k ids and the ids still follow the rule.
+ *   A row's outputs depend on its logits and the parameters alone: not on n_rows, ld or the alignment of d_logits (16-byte loads where
+ *   d_logits is 16-byte aligned and ld % 4 == 0).
+ *   TWO LAUNCHES whatever the shape: every (row, chunk of ggml_hip_topk_chunk() logits) gives its best min(k, chunk length) keys to the work
+ *   buffer, then one workgroup per row merges them and its first wave does the arithmetic above.  The chunk length is a constant of the
+ *   library, a multiple of 256.
+ *   d_work / work_bytes: ggml_hip_topk_work_size(n_rows, n_vocab, k) bytes, 8-byte aligned (argmax_rows: k = 1); monotone in all three, 0
+ *   only for a refused shape.  Missing, misaligned or short: GGML_HIP_ERR_ARG.
+ *   1 <= n_vocab <= 2^20, 1 <= k <= min(n_vocab, 64), 1 <= n_rows <= 4096, ld >= n_vocab: else GGML_HIP_ERR_SHAPE.  A null d_logits or
+ *   d_ids, inv_temp not finite or <= 0, or a d_logits, d_ids, d_u, d_probs or d_token that is not 4-byte aligned: GGML_HIP_ERR_ARG.
+ *   n_rows = 0: returns 0 and writes nothing. */
+int64_t ggml_hip_topk_chunk(void);                                 /* host only: the chunk length stage 1 gives a workgroup */
+size_t  ggml_hip_topk_work_size(int64_t n_rows, int64_t n_vocab, int k);
+int ggml_hip_argmax_rows_dev(const float *d_logits, int64_t ld, int64_t n_rows, int64_t n_vocab,
+                             int32_t *d_ids, void *d_work, size_t work_bytes, void *stream);
+int ggml_hip_sample_topk_dev(const float *d_logits, int64_t ld, int64_t n_rows, int64_t n_vocab, int k,
+                             float inv_temp, float top_p, const float *d_u,
+                             int32_t *d_ids, float *d_probs, int32_t *d_token,
+                             void *d_work, size_t work_bytes, void *stream);
+
 #if defined(__GNUC__)
 #pragma GCC visibility pop
 #endif

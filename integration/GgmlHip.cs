@@ -107,6 +107,17 @@ internal static unsafe partial class GgmlHip
         int* dPos, long pos0, int* dPos0, float* dFreqFactors, float* dDst, long lddTok, long lddHead, void* stream);
     [DllImport(Lib)] public static extern int ggml_hip_rope_kv_store_dev(ggml_hip_rope_params_t* rp, int kvType, float* dX, long ldxTok, long ldxHead, int nHeadKv, int d,
         long nTokens, float* dFreqFactors, void* dCache, long nbPos, long nbHead, long nPosMax, long pos0, int* dPos0, void* stream);
+    // ... the ends of a decode step (device entries, capturable, scratch from the caller): rows of a resident weight by int32 ids on the device, bit
+    // for bit download + dequantize, an id outside [0, M) a row of +0; the k best logits of every row (larger first, ties to the smaller index, NaN
+    // last), p = softmax((l - l0) * invTemp) over them, top-p and the pick by the caller's uniforms dU (null: no pick) -- the int32 written to dToken
+    // is the one get_rows reads on the next replay.  The chunk length, the work size and serves_for need no device
+    [DllImport(Lib)] public static extern int ggml_hip_get_rows_serves_for(int type);
+    [DllImport(Lib)] public static extern int ggml_hip_get_rows_dev(void* weight, int* dIds, long nIds, float* dDst, long ldd, void* stream);
+    [DllImport(Lib)] public static extern long ggml_hip_topk_chunk();
+    [DllImport(Lib)] public static extern nuint ggml_hip_topk_work_size(long nRows, long nVocab, int k);
+    [DllImport(Lib)] public static extern int ggml_hip_argmax_rows_dev(float* dLogits, long ld, long nRows, long nVocab, int* dIds, void* dWork, nuint workBytes, void* stream);
+    [DllImport(Lib)] public static extern int ggml_hip_sample_topk_dev(float* dLogits, long ld, long nRows, long nVocab, int k, float invTemp, float topP, float* dU,
+        int* dIds, float* dProbs, int* dToken, void* dWork, nuint workBytes, void* stream);
 
     // Seam 2: the quantize_fns_t slots (TypeDefinitions.cs:334-342), type-indexed
     [DllImport(Lib)] public static extern int ggml_hip_quantize_row(int type, float* x, void* y, int k);
