@@ -229,6 +229,16 @@ HIP_SYMBOLS = {
     "ggml_hip_rope_dev": (C.c_int, [_P, _P, C.c_int64, C.c_int64, C.c_int, C.c_int, C.c_int64, _P, C.c_int64, _P, _P, _P, C.c_int64, C.c_int64, _P]),
     "ggml_hip_rope_kv_store_dev": (C.c_int, [_P, C.c_int, _P, C.c_int64, C.c_int64, C.c_int, C.c_int, C.c_int64, _P, _P, C.c_int64, C.c_int64, C.c_int64,
                                              C.c_int64, _P, _P]),
+    # paged attention: a batch of sequences over one pool of KV pages (page table and lengths on the device): the two stores, the plan, the work size, the call
+    "ggml_hip_kv_store_paged_dev": (C.c_int, [C.c_int, _P, C.c_int64, C.c_int64, C.c_int, C.c_int, C.c_int64, C.c_int64, _P, C.c_int64, C.c_int64, C.c_int64,
+                                              C.c_int, _P, C.c_int64, _P, C.c_int64, _P]),
+    "ggml_hip_rope_kv_store_paged_dev": (C.c_int, [_P, C.c_int, _P, C.c_int64, C.c_int64, C.c_int, C.c_int, C.c_int64, C.c_int64, _P, _P, C.c_int64, C.c_int64,
+                                                   C.c_int64, C.c_int, _P, C.c_int64, _P, C.c_int64, _P]),
+    "ggml_hip_attn_paged_plan": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int64, C.c_int64, C.c_int64, _P]),
+    "ggml_hip_attn_paged_work_size": (C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int64, C.c_int64, C.c_int64]),
+    "ggml_hip_attn_paged_dev": (C.c_int, [C.c_int, _P, C.c_int64, C.c_int64, _P, _P, C.c_int64, C.c_int64, C.c_int64, C.c_int, _P, C.c_int64, _P, C.c_int,
+                                          C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int64, C.c_int64, C.c_int, C.c_float, _P, C.c_float, C.c_float, _P, _P,
+                                          C.c_int64, C.c_int64, _P, C.c_size_t, _P]),
     # the ends of a decode step: rows of a resident weight by device ids; top-k over a vocabulary, probabilities, top-p and the pick
     "ggml_hip_get_rows_serves_for": (C.c_int, [C.c_int]),
     "ggml_hip_get_rows_dev": (C.c_int, [_P, _P, C.c_int64, _P, C.c_int64, _P]),

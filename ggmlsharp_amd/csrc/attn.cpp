@@ -23,7 +23,44 @@ int check_attn_shape(int kv_type, int D, int n_head, int n_head_kv, int64_t n_q,
     return GGML_HIP_OK;
 }
 
+// the shape rules of q / dst rows [rows][n_head][D]
+int check_attn_rows(int D, int64_t rows, int64_t ldq_tok, int64_t ldq_head, int64_t ldd_tok, int64_t ldd_head) {
+    if (ldq_tok % 4 != 0 || ldq_head % 4 != 0 || ldd_tok % 4 != 0 || ldd_head % 4 != 0 || ldq_head < D || ldd_head < D || ldq_tok < 0 || ldd_tok < 0 ||
+        (rows > 1 && (ldq_tok < D || ldd_tok < D)))
+        return fail(GGML_HIP_ERR_SHAPE, "the strides of q and dst are multiples of 4 elements, at least D");
+    return GGML_HIP_OK;
+}
+
 }  // namespace
+
+namespace ghip {
+
+int check_kv_pages(int kv_type, int D, int n_head_kv, int64_t nb_page, int64_t nb_pos, int64_t nb_head, int n_pages, const int32_t *d_pages, int64_t ld_pages,
+                   const int32_t *d_len, int64_t n_seq, int64_t n_kv_max, kv_pages *pg) {
+    if (!kv_type_ok(kv_type)) return fail(GGML_HIP_ERR_TYPE, "kv_type %d: the cache is F16 or Q8_0", kv_type);
+    if (D < 4 || D % (kv_type == GGML_TYPE_Q8_0 ? QK : 4) != 0 || D > 256) return fail(GGML_HIP_ERR_SHAPE, "head size %d", D);
+    if (n_head_kv < 1 || n_head_kv > 65535) return fail(GGML_HIP_ERR_SHAPE, "n_head_kv %d (1 .. 65535)", n_head_kv);
+    if (n_seq < 1 || n_seq > ATTN_PAGED_MAX_SEQ) return fail(GGML_HIP_ERR_SHAPE, "n_seq %lld (1 .. %lld)", (long long)n_seq, (long long)ATTN_PAGED_MAX_SEQ);
+    if (n_kv_max < 0) return fail(GGML_HIP_ERR_ARG, "n_kv_max %lld", (long long)n_kv_max);
+    if (n_kv_max > (1 << 24)) return fail(GGML_HIP_ERR_SHAPE, "n_kv_max %lld (<= 2^24)", (long long)n_kv_max);
+    const int64_t row_bytes = kv_type == GGML_TYPE_Q8_0 ? D / QK * (int64_t)sizeof(block_q8_0) : D * 2;
+    if (nb_pos % 16 != 0 || nb_head % 16 != 0 || nb_pos < row_bytes || nb_head < row_bytes)
+        return fail(GGML_HIP_ERR_SHAPE, "nb_pos %lld, nb_head %lld: multiples of 16 bytes, at least the %lld bytes of a row", (long long)nb_pos, (long long)nb_head,
+                    (long long)row_bytes);
+    if (nb_pos > ((int64_t)1 << 40) || nb_head > ((int64_t)1 << 40)) return fail(GGML_HIP_ERR_SHAPE, "nb_pos %lld, nb_head %lld", (long long)nb_pos, (long long)nb_head);
+    const int64_t span = (ATTN_CHUNK - 1) * nb_pos + (n_head_kv - 1) * nb_head + row_bytes;      // the bytes the rows of one page span
+    if (nb_page % 16 != 0 || nb_page < span)
+        return fail(GGML_HIP_ERR_SHAPE, "nb_page %lld: a multiple of 16 bytes, at least the %lld bytes a page's rows span", (long long)nb_page, (long long)span);
+    if (n_pages <= 0) return fail(GGML_HIP_ERR_ARG, "n_pages %d", n_pages);
+    if (ld_pages < (n_kv_max + ATTN_CHUNK - 1) / ATTN_CHUNK)
+        return fail(GGML_HIP_ERR_SHAPE, "ld_pages %lld below ceil(n_kv_max %lld / %d)", (long long)ld_pages, (long long)n_kv_max, ATTN_CHUNK);
+    if (!d_pages || !d_len) return fail(GGML_HIP_ERR_ARG, "d_pages and d_len must not be null");
+    if ((((uintptr_t)d_pages | (uintptr_t)d_len) & 3) != 0) return fail(GGML_HIP_ERR_SHAPE, "d_pages and d_len must be 4-byte aligned");
+    pg->pages = d_pages; pg->ld_pages = ld_pages; pg->len = d_len; pg->nb_page = nb_page; pg->n_pages = n_pages; pg->n_kv_max = (int)n_kv_max;
+    return GGML_HIP_OK;
+}
+
+}  // namespace ghip
 
 extern "C" {
 
@@ -96,6 +133,79 @@ int ggml_hip_attn_dev(int kv_type, const float *d_q, int64_t ldq_tok, int64_t ld
     a.dst = d_dst; a.ldd_tok = ldd_tok; a.ldd_head = ldd_head;
     a.work = need ? (void *)(((uintptr_t)d_work + ATTN_ALIGN - 1) / ATTN_ALIGN * ATTN_ALIGN) : nullptr;
     HIP_TRY(launch_attn(p, a, (hipStream_t)stream));
+    return GGML_HIP_OK;
+}
+
+int ggml_hip_kv_store_paged_dev(int kv_type, const float *d_src, int64_t ldx_tok, int64_t ldx_head, int n_head_kv, int D, int64_t n_seq, int64_t n_q,
+                                void *d_pool, int64_t nb_page, int64_t nb_pos, int64_t nb_head, int n_pages, const int32_t *d_pages, int64_t ld_pages,
+                                const int32_t *d_len, int64_t n_kv_max, void *stream) {
+    kv_pages pg;
+    const int rc = check_kv_pages(kv_type, D, n_head_kv, nb_page, nb_pos, nb_head, n_pages, d_pages, ld_pages, d_len, n_seq, n_kv_max, &pg);
+    if (rc) return rc;
+    if (n_q < 0) return fail(GGML_HIP_ERR_ARG, "n_q %lld", (long long)n_q);
+    if (n_seq * n_q > ATTN_PAGED_MAX_ROWS) return fail(GGML_HIP_ERR_SHAPE, "n_seq * n_q %lld (<= %lld)", (long long)(n_seq * n_q), (long long)ATTN_PAGED_MAX_ROWS);
+    if (ldx_tok % 4 != 0 || ldx_head % 4 != 0 || ldx_head < D || ldx_tok < 0 || (n_seq * n_q > 1 && ldx_tok < D))
+        return fail(GGML_HIP_ERR_SHAPE, "the strides of the rows are multiples of 4 elements, at least D");
+    if (n_q == 0) return GGML_HIP_OK;
+    if (!d_src || !d_pool) return fail(GGML_HIP_ERR_ARG, "null argument");
+    if ((((uintptr_t)d_src | (uintptr_t)d_pool) & 15) != 0) return fail(GGML_HIP_ERR_SHAPE, "d_src and d_pool must be 16-byte aligned");
+    HIP_TRY(launch_kv_store_paged(kv_type, d_src, ldx_tok, ldx_head, n_head_kv, D, n_seq, n_q, d_pool, nb_pos, nb_head, pg, (hipStream_t)stream));
+    return GGML_HIP_OK;
+}
+
+int ggml_hip_attn_paged_plan(int kv_type, int D, int n_head, int n_head_kv, int64_t n_seq, int64_t n_q, int64_t n_kv_max, ggml_hip_attn_plan_t *out) {
+    if (!out) return fail(GGML_HIP_ERR_ARG, "out is null");
+    const int rc = check_attn_shape(kv_type, D, n_head, n_head_kv, n_q, n_kv_max);
+    if (rc) return rc;
+    if (n_seq < 1 || n_seq > ATTN_PAGED_MAX_SEQ) return fail(GGML_HIP_ERR_SHAPE, "n_seq %lld (1 .. %lld)", (long long)n_seq, (long long)ATTN_PAGED_MAX_SEQ);
+    if (n_q == 0) { *out = ggml_hip_attn_plan_t{}; out->chunk = ATTN_CHUNK; return GGML_HIP_OK; }
+    const attn_plan p = plan_attn_paged(kv_type, D, n_head, n_head_kv, n_seq, n_q, n_kv_max);
+    if (p.form == ATTN_FORM_NONE)
+        return fail(GGML_HIP_ERR_SHAPE, "the shape is not served: n_seq * n_q %lld (<= %lld), times n_head below 2^31", (long long)(n_seq * n_q), (long long)ATTN_PAGED_MAX_ROWS);
+    out->form = p.form; out->chunk = p.chunk; out->q_tile = p.q_tile; out->launches = p.launches;
+    out->n_chunks = p.n_chunks; out->workgroups = p.wgs;
+    return GGML_HIP_OK;
+}
+
+size_t ggml_hip_attn_paged_work_size(int kv_type, int D, int n_head, int n_head_kv, int64_t n_seq, int64_t n_q, int64_t n_kv_max) {
+    if (!kv_type_ok(kv_type) || n_q <= 0 || n_seq <= 0) return 0;
+    const attn_plan p = plan_attn_paged(kv_type, D, n_head, n_head_kv, n_seq, n_q, n_kv_max);
+    if (p.form == ATTN_FORM_NONE || p.work_bytes == 0) return 0;
+    return (p.work_bytes + ATTN_ALIGN - 1) / ATTN_ALIGN * ATTN_ALIGN + ATTN_ALIGN;   // (the base is rounded up to a 256-byte boundary)
+}
+
+int ggml_hip_attn_paged_dev(int kv_type, const float *d_q, int64_t ldq_tok, int64_t ldq_head, const void *d_k, const void *d_v, int64_t nb_page, int64_t nb_pos,
+                            int64_t nb_head, int n_pages, const int32_t *d_pages, int64_t ld_pages, const int32_t *d_len, int len_bias, int64_t n_seq,
+                            int n_head, int n_head_kv, int D, int64_t n_q, int64_t n_kv_max, int causal, float scale, const void *d_mask, float max_bias,
+                            float logit_softcap, const float *d_sinks, float *d_dst, int64_t ldd_tok, int64_t ldd_head, void *d_work, size_t work_bytes,
+                            void *stream) {
+    if (d_mask || d_sinks || max_bias != 0.0f || logit_softcap != 0.0f)
+        return fail(GGML_HIP_ERR_ARG, "a mask tensor, ALiBi (max_bias), a soft-cap and sinks are not served: pass NULL / 0");
+    int rc = check_attn_shape(kv_type, D, n_head, n_head_kv, n_q, n_kv_max);
+    if (rc) return rc;
+    kv_pages pg;
+    rc = check_kv_pages(kv_type, D, n_head_kv, nb_page, nb_pos, nb_head, n_pages, d_pages, ld_pages, d_len, n_seq, n_kv_max, &pg);
+    if (rc) return rc;
+    if (n_seq * n_q > ATTN_PAGED_MAX_ROWS || n_seq * n_q * n_head > 0x7FFFFFFF)
+        return fail(GGML_HIP_ERR_SHAPE, "n_seq * n_q %lld (<= %lld, times n_head below 2^31)", (long long)(n_seq * n_q), (long long)ATTN_PAGED_MAX_ROWS);
+    rc = check_attn_rows(D, n_seq * n_q, ldq_tok, ldq_head, ldd_tok, ldd_head);
+    if (rc) return rc;
+    if (n_q == 0) return GGML_HIP_OK;
+    if (!d_q || !d_dst || !d_k || !d_v) return fail(GGML_HIP_ERR_ARG, "null argument");
+    if ((((uintptr_t)d_q | (uintptr_t)d_dst | (uintptr_t)d_k | (uintptr_t)d_v) & 15) != 0) return fail(GGML_HIP_ERR_SHAPE, "q, dst, K and V must be 16-byte aligned");
+    const attn_plan p = plan_attn_paged(kv_type, D, n_head, n_head_kv, n_seq, n_q, n_kv_max);
+    if (p.form == ATTN_FORM_NONE) return fail(GGML_HIP_ERR_SHAPE, "the shape is not served");
+    const size_t need = ggml_hip_attn_paged_work_size(kv_type, D, n_head, n_head_kv, n_seq, n_q, n_kv_max);
+    if (need && (!d_work || work_bytes < need)) return fail(GGML_HIP_ERR_ARG, "work buffer too small: need %zu (ggml_hip_attn_paged_work_size)", need);
+    attn_args a;
+    a.kv_type = kv_type; a.D = D; a.n_head = n_head; a.n_head_kv = n_head_kv; a.causal = causal != 0;
+    a.q = d_q; a.ldq_tok = ldq_tok; a.ldq_head = ldq_head;
+    a.k = d_k; a.v = d_v; a.nb_pos = nb_pos; a.nb_head = nb_head;
+    a.n_q = n_q; a.n_kv = 0; a.d_n_kv = nullptr; a.n_kv_max = n_kv_max;
+    a.scale = scale;
+    a.dst = d_dst; a.ldd_tok = ldd_tok; a.ldd_head = ldd_head;
+    a.work = need ? (void *)(((uintptr_t)d_work + ATTN_ALIGN - 1) / ATTN_ALIGN * ATTN_ALIGN) : nullptr;
+    HIP_TRY(launch_attn_paged(p, a, n_seq, pg, len_bias, (hipStream_t)stream));
     return GGML_HIP_OK;
 }
 

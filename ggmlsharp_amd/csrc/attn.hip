@@ -45,6 +45,15 @@
 //
 // V CONSTANT over the positions: neither form returns the constant exactly in general -- a[d] = sum of fl(p_j * c) and l = sum of p_j round
 // independently, a / l is c only up to the accumulation error -- so that case is held to the tolerance, not to bits.
+//
+// ---- PAGED (ggml_hip_kv_store_paged_dev, ggml_hip_attn_paged_dev; common.h kv_pages) ----
+// A pool of pages of ATTN_CHUNK = 128 positions, page p at pool + p * nb_page, row (jj, hk) inside it at jj * nb_pos + hk * nb_head; sequence b's
+// positions [128 c, 128 c + 128) lie in page pages[b][c], and n_kv[b] = clamp(len[b] + len_bias, 0, n_kv_max).  A page IS a chunk, and neither
+// form's arithmetic knows where a chunk lies: the chunk bodies below (attn_decode_chunk, attn_merge_row, attn_prompt_tile) are shared by a
+// contiguous and a paged kernel each, so a sequence's rows are bit for bit the contiguous call on the same row bytes.  The paged kernels carry
+// the sequence in grid z (the merge: in its row index).  A workgroup whose chunk lies at or beyond n_kv[b] leaves at once; a page id outside
+// [0, n_pages) among a sequence's first ceil(n_kv[b] / 128) entries makes ALL its rows +0.0f (DECODE: the merge scans the ids; PROMPT: the
+// workgroup does before its first stage) and no address is ever formed from such an id.
 #include "common.h"
 #include "plan.h"
 #include "kv_pack.h"     // f32_to_f16_bits, kv_pack_q8_0, kv_pack_f16: the bytes of a cache row (shared with rope.hip)
@@ -94,6 +103,42 @@ __global__ __launch_bounds__(256) void kv_store_kernel(const float *__restrict__
     }
 }
 
+// n_kv of sequence b of a paged call: clamp(len[b] + len_bias, 0, n_kv_max)
+__device__ __forceinline__ int paged_count(const kv_pages &pg, int b, int len_bias) {
+    const int64_t n = (int64_t)pg.len[b] + len_bias;
+    return (int)(n < 0 ? 0 : n > pg.n_kv_max ? pg.n_kv_max : n);
+}
+
+// the paged store: row (b, t, hk) of [n_seq * n_q][n_head_kv][D] -> page row (len[b] + t, hk); the kv_pack.h statement of kv_store_kernel
+// behind the paged address.  Every guard stands in front of the address it protects: the table is read only for a position inside
+// [0, n_kv_max) (whose chunk index is below ld_pages, the entry's rule), the pool is addressed only with a page id inside [0, n_pages).
+template <bool Q8>
+__global__ __launch_bounds__(256) void kv_store_paged_kernel(const float *__restrict__ src, int64_t ldx_tok, int64_t ldx_head, int n_head_kv, int units_per_head,
+                                                             int64_t n_tokens, int n_q, uint8_t *__restrict__ pool, int64_t nb_pos, int64_t nb_head, const kv_pages pg) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    const int64_t per_tok = (int64_t)n_head_kv * units_per_head;
+    if (i >= n_tokens * per_tok) return;
+    const int64_t tok = i / per_tok;
+    const int r = (int)(i - tok * per_tok), hk = r / units_per_head, u = r - hk * units_per_head;
+    const int64_t b = tok / n_q;
+    const int64_t pos = (int64_t)pg.len[b] + (tok - b * n_q);
+    if (pos < 0 || pos >= pg.n_kv_max) return;                      // (before the table is read)
+    const int page = pg.pages[b * pg.ld_pages + pos / C];
+    if (page < 0 || page >= pg.n_pages) return;                     // (before any address is formed from it)
+    uint8_t *row = pool + (int64_t)page * pg.nb_page + (pos % C) * nb_pos + (int64_t)hk * nb_head;
+    const float *x = src + tok * ldx_tok + (int64_t)hk * ldx_head;
+    if constexpr (Q8) {
+        const float4 *x4 = (const float4 *)(x + 32 * u);
+        float v[QK];
+#pragma unroll
+        for (int k = 0; k < 8; ++k) { const float4 f = x4[k]; v[4 * k] = f.x; v[4 * k + 1] = f.y; v[4 * k + 2] = f.z; v[4 * k + 3] = f.w; }
+        kv_pack_q8_0(v, (uint32_t *)(row + 36 * (int64_t)u));
+    } else {
+        const float4 f = *(const float4 *)(x + 4 * u);
+        *(uint2 *)(row + 8 * (int64_t)u) = kv_pack_f16(f);
+    }
+}
+
 // ------------------------------------------------------------------------------------------------ DECODE form
 // bytes of a cache row, and its stride in the LDS stage (F16: + 8, rows of 8-byte reads spread over all banks; Q8_0: + 4, an odd word count)
 template <bool Q8> __host__ __device__ constexpr int row_bytes_of(int D) { return Q8 ? D / 32 * 36 : 2 * D; }
@@ -133,26 +178,22 @@ __device__ __forceinline__ void load4(const uint8_t *row, int d4, float (&v)[4])
 }
 
 // the work buffer: partial (row gr = t * n_head + h, chunk c) at ((gr * n_chunks_max) + c) * (D + 4) floats: m, l, two spare, a[D]
+// THE CHUNK BODY of the DECODE form, shared by the contiguous and the paged kernel: chunk c (j0 = 128 c < n_kv) of kv head hk, its rows at
+// kb / vb + j * nb_pos -- where the chunk lies in memory is the caller's, the arithmetic does not know.  q and work are the sequence's own.
 template <bool Q8, int D>
-__global__ __launch_bounds__(256) void attn_decode_kernel(const float *__restrict__ q, int64_t ldq_tok, int64_t ldq_head, const uint8_t *__restrict__ kc,
-                                                          const uint8_t *__restrict__ vc, int64_t nb_pos, int64_t nb_head, int n_head, int G, int n_q,
-                                                          int n_kv_host, const int32_t *__restrict__ d_n_kv, int n_kv_max, int causal, float scale,
-                                                          float *__restrict__ work, int n_chunks_max) {
+__device__ __forceinline__ void attn_decode_chunk(uint8_t *lds, const float *__restrict__ q, int64_t ldq_tok, int64_t ldq_head, const uint8_t *__restrict__ kb,
+                                                  const uint8_t *__restrict__ vb, int64_t nb_pos, int n_head, int G, int n_q, int n_kv, int c, int hk, int causal,
+                                                  float scale, float *__restrict__ work, int n_chunks_max) {
     constexpr int RB = row_bytes_of<Q8>(D), ST = stage_stride<Q8>(D), PPR = RB / 8;
-    extern __shared__ __attribute__((aligned(16))) uint8_t lds[];
     uint8_t *kst = lds, *vst = lds + C * ST;
     float *qt = (float *)(lds + 2 * C * ST);                         // [DEC_RT][D]
     float *sc = qt + DEC_RT * D;                                     // [DEC_RT][C]
     static_assert((2 * C * ST) % 16 == 0, "the query tile is read as float4");
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int c = blockIdx.x, hk = blockIdx.y;
-    const int n_kv = device_count(d_n_kv, n_kv_host, n_kv_max);
     const int j0 = c * C;
-    if (j0 >= n_kv) return;                                          // (the whole workgroup: no barrier was reached)
     const int cnt = min(C, n_kv - j0);                               // rows of this chunk the cache holds: all below n_kv <= n_kv_max
     // ---- the chunk's K and V rows into LDS, as they are: 8-byte pieces, each read once ----
     {
-        const uint8_t *kb = kc + (int64_t)j0 * nb_pos + (int64_t)hk * nb_head, *vb = vc + (int64_t)j0 * nb_pos + (int64_t)hk * nb_head;
         const int per = cnt * PPR;
         constexpr int UN = 8;                                        // loads in flight per thread: all issued before the first is stored
         for (int i0 = tid; i0 < 2 * per; i0 += 256 * UN) {
@@ -267,18 +308,48 @@ __global__ __launch_bounds__(256) void attn_decode_kernel(const float *__restric
     }
 }
 
-// the merge: one workgroup of D threads per query row (t, h); thread d owns column d, every thread the row's (M, L)
-template <int D>
-__global__ __launch_bounds__(D) void attn_merge_kernel(const float *__restrict__ work, int n_chunks_max, int n_head, int n_q, int n_kv_host,
-                                                       const int32_t *__restrict__ d_n_kv, int n_kv_max, int causal, float *__restrict__ dst, int64_t ldd_tok,
-                                                       int64_t ldd_head) {
-    const int t = blockIdx.x / n_head, h = blockIdx.x - t * n_head, d = threadIdx.x;
+template <bool Q8, int D>
+__global__ __launch_bounds__(256) void attn_decode_kernel(const float *__restrict__ q, int64_t ldq_tok, int64_t ldq_head, const uint8_t *__restrict__ kc,
+                                                          const uint8_t *__restrict__ vc, int64_t nb_pos, int64_t nb_head, int n_head, int G, int n_q,
+                                                          int n_kv_host, const int32_t *__restrict__ d_n_kv, int n_kv_max, int causal, float scale,
+                                                          float *__restrict__ work, int n_chunks_max) {
+    extern __shared__ __attribute__((aligned(16))) uint8_t lds[];
+    const int c = blockIdx.x, hk = blockIdx.y;
     const int n_kv = device_count(d_n_kv, n_kv_host, n_kv_max);
+    const int j0 = c * C;
+    if (j0 >= n_kv) return;                                          // (the whole workgroup: no barrier was reached)
+    const int64_t off = (int64_t)j0 * nb_pos + (int64_t)hk * nb_head;
+    attn_decode_chunk<Q8, D>(lds, q, ldq_tok, ldq_head, kc + off, vc + off, nb_pos, n_head, G, n_q, n_kv, c, hk, causal, scale, work, n_chunks_max);
+}
+
+// the paged DECODE kernel: grid (chunks of n_kv_max) x (kv heads) x (sequences).  The sequence's length and the chunk's page id are
+// wave-uniform scalars; a workgroup whose chunk lies at or beyond n_kv[b], or whose page id is outside [0, n_pages), leaves before any
+// address is formed (the table entry itself is read only for c < ceil(n_kv[b] / 128) <= ld_pages).  Otherwise the chunk body above on
+// pool + page * nb_page, with the sequence's own rows of q and of the work buffer.
+template <bool Q8, int D>
+__global__ __launch_bounds__(256) void attn_decode_paged_kernel(const float *__restrict__ q, int64_t ldq_tok, int64_t ldq_head, const uint8_t *__restrict__ kc,
+                                                                const uint8_t *__restrict__ vc, int64_t nb_pos, int64_t nb_head, int n_head, int G, int n_q,
+                                                                const kv_pages pg, int len_bias, int causal, float scale, float *__restrict__ work,
+                                                                int n_chunks_max) {
+    extern __shared__ __attribute__((aligned(16))) uint8_t lds[];
+    const int c = blockIdx.x, hk = blockIdx.y, b = blockIdx.z;
+    const int n_kv = paged_count(pg, b, len_bias);
+    if (c * C >= n_kv) return;                                       // (the whole workgroup: no barrier was reached)
+    const int page = pg.pages[(int64_t)b * pg.ld_pages + c];
+    if (page < 0 || page >= pg.n_pages) return;                      // (the merge writes this sequence's rows as zeros)
+    const int64_t off = (int64_t)page * pg.nb_page + (int64_t)hk * nb_head;
+    const int64_t row0 = (int64_t)b * n_q;                           // the sequence's first row of q and of the work buffer
+    attn_decode_chunk<Q8, D>(lds, q + row0 * ldq_tok, ldq_tok, ldq_head, kc + off, vc + off, nb_pos, n_head, G, n_q, n_kv, c, hk, causal, scale,
+                             work + row0 * n_head * n_chunks_max * (D + 4), n_chunks_max);
+}
+
+// the merge of one query row (t, h) whose partials start at `part`; thread d owns column d, every thread the row's (M, L)
+template <int D>
+__device__ __forceinline__ void attn_merge_row(const float *__restrict__ part, int t, int n_q, int n_kv, int causal, float *__restrict__ out) {
+    const int d = threadIdx.x;
     const int vis = visible(t, n_kv, n_q, causal);
-    float *out = dst + (int64_t)t * ldd_tok + (int64_t)h * ldd_head + d;
     if (vis <= 0) { *out = 0.0f; return; }
     const int nc = (vis + C - 1) / C;                                // <= n_chunks_max: vis <= n_kv <= n_kv_max
-    const float *part = work + (int64_t)blockIdx.x * n_chunks_max * (D + 4);
     float M = part[0];
     for (int c = 1; c < nc; ++c) M = fmaxf(M, part[(int64_t)c * (D + 4)]);
     float L, A;
@@ -293,6 +364,43 @@ __global__ __launch_bounds__(D) void attn_merge_kernel(const float *__restrict__
         L = fmaf(p[1], b, L); A = fmaf(p[4 + d], b, A);
     }
     *out = A / L;
+}
+
+// the merge: one workgroup of D threads per query row (t, h)
+template <int D>
+__global__ __launch_bounds__(D) void attn_merge_kernel(const float *__restrict__ work, int n_chunks_max, int n_head, int n_q, int n_kv_host,
+                                                       const int32_t *__restrict__ d_n_kv, int n_kv_max, int causal, float *__restrict__ dst, int64_t ldd_tok,
+                                                       int64_t ldd_head) {
+    const int t = blockIdx.x / n_head, h = blockIdx.x - t * n_head;
+    const int n_kv = device_count(d_n_kv, n_kv_host, n_kv_max);
+    attn_merge_row<D>(work + (int64_t)blockIdx.x * n_chunks_max * (D + 4), t, n_q, n_kv, causal,
+                      dst + (int64_t)t * ldd_tok + (int64_t)h * ldd_head + threadIdx.x);
+}
+
+// 1 where one of the first ceil(n_kv / 128) entries of a sequence's table row lies outside [0, n_pages), the same answer in every thread
+// of the workgroup (NT threads; one barrier); no address is formed from an entry
+template <int NT>
+__device__ __forceinline__ int paged_any_invalid(const int32_t *__restrict__ row, int n_kv, int n_pages) {
+    const int needed = (n_kv + C - 1) / C;
+    int bad = 0;
+    for (int c = threadIdx.x; c < needed; c += NT) {
+        const int id = row[c];
+        bad |= (id < 0 || id >= n_pages) ? 1 : 0;
+    }
+    return __syncthreads_or(bad);
+}
+
+// the paged merge: one workgroup per row of all sequences, blockIdx.x = (b * n_q + t) * n_head + h.  It scans the sequence's needed page
+// ids first: one invalid id and the row is +0.0f (the partials of that sequence are then not read: some were never written).
+template <int D>
+__global__ __launch_bounds__(D) void attn_merge_paged_kernel(const float *__restrict__ work, int n_chunks_max, int n_head, int n_q, const kv_pages pg,
+                                                             int len_bias, int causal, float *__restrict__ dst, int64_t ldd_tok, int64_t ldd_head) {
+    const int bt = blockIdx.x / n_head, h = blockIdx.x - bt * n_head;
+    const int b = bt / n_q, t = bt - b * n_q;
+    const int n_kv = paged_count(pg, b, len_bias);
+    float *out = dst + (int64_t)bt * ldd_tok + (int64_t)h * ldd_head + threadIdx.x;
+    if (paged_any_invalid<D>(pg.pages + (int64_t)b * pg.ld_pages, n_kv, pg.n_pages)) { *out = 0.0f; return; }
+    attn_merge_row<D>(work + (int64_t)blockIdx.x * n_chunks_max * (D + 4), t, n_q, n_kv, causal, out);
 }
 
 // ------------------------------------------------------------------------------------------------ PROMPT form
@@ -319,18 +427,19 @@ __device__ __forceinline__ f16x8 stage_load8(const uint8_t *row, int d8) {      
     }
 }
 
-template <bool Q8, int D>
-__global__ __launch_bounds__(256) void attn_prompt_kernel(const float *__restrict__ q, int64_t ldq_tok, int64_t ldq_head, const uint8_t *__restrict__ kc,
-                                                          const uint8_t *__restrict__ vc, int64_t nb_pos, int64_t nb_head, int G, int n_q, int n_kv_host,
-                                                          const int32_t *__restrict__ d_n_kv, int n_kv_max, int causal, float scale, float *__restrict__ dst,
-                                                          int64_t ldd_tok, int64_t ldd_head) {
+// THE BODY of the PROMPT form, shared by the contiguous and the paged kernel: 128 query rows of head h of one sequence (q and dst are the
+// sequence's own) over n_kv positions.  PAGED: chunk c lies at pool + pages[c] * nb_page (pages: the sequence's table row, its first
+// ceil(n_kv / 128) entries checked by the caller); otherwise at cache + 128 c * nb_pos.  Nothing else knows where a chunk lies.
+template <bool Q8, int D, bool PAGED>
+__device__ __forceinline__ void attn_prompt_tile(uint8_t *lds, const float *__restrict__ q, int64_t ldq_tok, int64_t ldq_head, const uint8_t *__restrict__ kc,
+                                                 const uint8_t *__restrict__ vc, int64_t nb_pos, int64_t nb_head, const int32_t *__restrict__ pages,
+                                                 int64_t nb_page, int G, int n_q, int n_kv, int causal, float scale, float *__restrict__ dst, int64_t ldd_tok,
+                                                 int64_t ldd_head) {
     constexpr int KS = prompt_k_stride<D>(), VS = PROMPT_VT_STRIDE, NKS = D / 16, NDT = D / 32, NCT = C / 32;
-    extern __shared__ __attribute__((aligned(16))) uint8_t lds[];
     uint8_t *kst = lds, *vt = lds + C * KS;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, r = lane & 31, hh = lane >> 5;
     const int h = blockIdx.y, hk = h / G;
     const int q0 = blockIdx.x * 128, qw = q0 + 32 * wave;             // the workgroup's and the wave's first query row
-    const int n_kv = device_count(d_n_kv, n_kv_host, n_kv_max);
     const int tq = min(qw + r, n_q - 1);                             // this lane's query (a lane past n_q computes a copy and stores nothing)
     const int vis = visible(tq, n_kv, n_q, causal);
     const int wg_vis = visible(min(q0 + 127, n_q - 1), n_kv, n_q, causal);         // vis is monotone in t: the workgroup's largest
@@ -359,7 +468,8 @@ __global__ __launch_bounds__(256) void attn_prompt_kernel(const float *__restric
         if (c > 0) __syncthreads();                                  // (every wave is done with the previous stage)
         // ---- stage: K rows as they lie, V transposed; 16 bytes of f16 per item, consecutive lanes along a row ----
         {
-            const uint8_t *kb = kc + (int64_t)j0 * nb_pos + (int64_t)hk * nb_head, *vb = vc + (int64_t)j0 * nb_pos + (int64_t)hk * nb_head;
+            const int64_t off = (PAGED ? (int64_t)pages[c] * nb_page : (int64_t)j0 * nb_pos) + (int64_t)hk * nb_head;
+            const uint8_t *kb = kc + off, *vb = vc + off;
             for (int i = tid; i < C * (D / 8); i += 256) {
                 const int j = i / (D / 8), d8 = i - j * (D / 8);
                 f16x8 kv, vv;
@@ -450,6 +560,42 @@ __global__ __launch_bounds__(256) void attn_prompt_kernel(const float *__restric
     }
 }
 
+template <bool Q8, int D>
+__global__ __launch_bounds__(256) void attn_prompt_kernel(const float *__restrict__ q, int64_t ldq_tok, int64_t ldq_head, const uint8_t *__restrict__ kc,
+                                                          const uint8_t *__restrict__ vc, int64_t nb_pos, int64_t nb_head, int G, int n_q, int n_kv_host,
+                                                          const int32_t *__restrict__ d_n_kv, int n_kv_max, int causal, float scale, float *__restrict__ dst,
+                                                          int64_t ldd_tok, int64_t ldd_head) {
+    extern __shared__ __attribute__((aligned(16))) uint8_t lds[];
+    const int n_kv = device_count(d_n_kv, n_kv_host, n_kv_max);
+    attn_prompt_tile<Q8, D, false>(lds, q, ldq_tok, ldq_head, kc, vc, nb_pos, nb_head, nullptr, 0, G, n_q, n_kv, causal, scale, dst, ldd_tok, ldd_head);
+}
+
+// the paged PROMPT kernel: grid (query tiles) x (heads) x (sequences).  The workgroup scans its sequence's needed page ids before its first
+// stage; one invalid id and its rows are +0.0f, with no address formed from any entry.  Otherwise the body above, the chunk bases from the table.
+template <bool Q8, int D>
+__global__ __launch_bounds__(256) void attn_prompt_paged_kernel(const float *__restrict__ q, int64_t ldq_tok, int64_t ldq_head, const uint8_t *__restrict__ kc,
+                                                                const uint8_t *__restrict__ vc, int64_t nb_pos, int64_t nb_head, int G, int n_q,
+                                                                const kv_pages pg, int len_bias, int causal, float scale, float *__restrict__ dst,
+                                                                int64_t ldd_tok, int64_t ldd_head) {
+    extern __shared__ __attribute__((aligned(16))) uint8_t lds[];
+    const int b = blockIdx.z;
+    const int n_kv = paged_count(pg, b, len_bias);
+    const int32_t *pages = pg.pages + (int64_t)b * pg.ld_pages;
+    const int64_t row0 = (int64_t)b * n_q;
+    float *dst_b = dst + row0 * ldd_tok;
+    if (paged_any_invalid<256>(pages, n_kv, pg.n_pages)) {
+        const int lane = threadIdx.x & 63, tq = blockIdx.x * 128 + 32 * (threadIdx.x >> 6) + (lane & 31), hh = lane >> 5;
+        if (tq < n_q) {
+            float *out = dst_b + (int64_t)tq * ldd_tok + (int64_t)blockIdx.y * ldd_head;
+#pragma unroll
+            for (int i = 0; i < D / 8; ++i) *(float4 *)(out + 8 * i + 4 * hh) = make_float4(0.f, 0.f, 0.f, 0.f);
+        }
+        return;
+    }
+    attn_prompt_tile<Q8, D, true>(lds, q + row0 * ldq_tok, ldq_tok, ldq_head, kc, vc, nb_pos, nb_head, pages, pg.nb_page, G, n_q, n_kv, causal, scale, dst_b,
+                                  ldd_tok, ldd_head);
+}
+
 template <bool Q8, int D> constexpr int decode_lds() { return 2 * C * stage_stride<Q8>(D) + DEC_RT * D * 4 + DEC_RT * C * 4; }
 
 }  // namespace
@@ -464,6 +610,56 @@ hipError_t launch_kv_store(int kv_type, const float *src, int64_t ld, int64_t n_
     if (q8) kv_store_kernel<true><<<grid, 256, 0, st>>>(src, ld, n_rows, (int)upr, (uint8_t *)cache, nb_pos, n_pos_max, pos0, d_pos0);
     else kv_store_kernel<false><<<grid, 256, 0, st>>>(src, ld, n_rows, (int)upr, (uint8_t *)cache, nb_pos, n_pos_max, pos0, d_pos0);
     return hipGetLastError();
+}
+
+hipError_t launch_kv_store_paged(int kv_type, const float *src, int64_t ldx_tok, int64_t ldx_head, int n_head_kv, int D, int64_t n_seq, int64_t n_q, void *pool,
+                                 int64_t nb_pos, int64_t nb_head, const kv_pages &pg, hipStream_t st) {
+    const int64_t n_tokens = n_seq * n_q;
+    if (n_tokens <= 0) return hipSuccess;
+    const bool q8 = kv_type == GGML_TYPE_Q8_0;
+    const int64_t uph = D / (q8 ? 32 : 4), total = n_tokens * n_head_kv * uph;
+    if (uph <= 0 || n_q > 0x7FFFFFFF || total > (int64_t)0x7FFFFFFF * 256) return hipErrorInvalidValue;
+    const dim3 grid((unsigned)((total + 255) / 256));
+    if (q8) kv_store_paged_kernel<true><<<grid, 256, 0, st>>>(src, ldx_tok, ldx_head, n_head_kv, (int)uph, n_tokens, (int)n_q, (uint8_t *)pool, nb_pos, nb_head, pg);
+    else kv_store_paged_kernel<false><<<grid, 256, 0, st>>>(src, ldx_tok, ldx_head, n_head_kv, (int)uph, n_tokens, (int)n_q, (uint8_t *)pool, nb_pos, nb_head, pg);
+    return hipGetLastError();
+}
+
+// the grids are the plan's: DECODE pl.n_chunks x kv heads x sequences and one merge workgroup per row; PROMPT query tiles x heads x sequences
+hipError_t launch_attn_paged(const attn_plan &pl, const attn_args &a, int64_t n_seq, const kv_pages &pg, int len_bias, hipStream_t st) {
+    const bool q8 = a.kv_type == GGML_TYPE_Q8_0;
+    const int G = a.n_head / a.n_head_kv;
+    const uint8_t *kc = (const uint8_t *)a.k, *vc = (const uint8_t *)a.v;
+    if (pl.form == ATTN_FORM_DECODE) {
+        const dim3 grid((unsigned)pl.n_chunks, (unsigned)a.n_head_kv, (unsigned)n_seq);
+        float *work = (float *)a.work;
+#define DECODE(Q, DD)                                                                                                                                 \
+    do {                                                                                                                                              \
+        if (pl.n_chunks > 0) {                                                                                                                        \
+            hipError_t e = launch_lds(kfn<attn_decode_paged_kernel<Q, DD>>, grid, dim3(256), (size_t)decode_lds<Q, DD>(), decode_lds<Q, DD>(), st, a.q,  \
+                                      a.ldq_tok, a.ldq_head, kc, vc, a.nb_pos, a.nb_head, a.n_head, G, (int)a.n_q, pg, len_bias, a.causal, a.scale, work, \
+                                      (int)pl.n_chunks);                                                                                              \
+            if (e != hipSuccess) return e;                                                                                                            \
+        }                                                                                                                                             \
+        attn_merge_paged_kernel<DD><<<dim3((unsigned)(n_seq * a.n_q * a.n_head)), DD, 0, st>>>(work, (int)pl.n_chunks, a.n_head, (int)a.n_q, pg, len_bias, \
+                                                                                              a.causal, a.dst, a.ldd_tok, a.ldd_head);                \
+    } while (0)
+        if (q8 && a.D == 64) DECODE(true, 64);
+        else if (q8) DECODE(true, 128);
+        else if (a.D == 64) DECODE(false, 64);
+        else DECODE(false, 128);
+#undef DECODE
+        return hipGetLastError();
+    }
+    const dim3 grid((unsigned)((a.n_q + 127) / 128), (unsigned)a.n_head, (unsigned)n_seq);
+#define PROMPT(Q, DD)                                                                                                                                  \
+    return launch_lds(kfn<attn_prompt_paged_kernel<Q, DD>>, grid, dim3(256), (size_t)prompt_lds<DD>(), prompt_lds<DD>(), st, a.q, a.ldq_tok, a.ldq_head, kc, \
+                      vc, a.nb_pos, a.nb_head, G, (int)a.n_q, pg, len_bias, a.causal, a.scale, a.dst, a.ldd_tok, a.ldd_head)
+    if (q8 && a.D == 64) PROMPT(true, 64);
+    else if (q8) PROMPT(true, 128);
+    else if (a.D == 64) PROMPT(false, 64);
+    else PROMPT(false, 128);
+#undef PROMPT
 }
 
 hipError_t launch_attn(const attn_plan &pl, const attn_args &a, hipStream_t st) {

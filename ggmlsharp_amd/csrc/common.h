@@ -449,6 +449,21 @@ struct attn_args {
 hipError_t launch_kv_store(int kv_type, const float *src, int64_t ld, int64_t n_rows, int64_t row_elems, void *cache, int64_t nb_pos, int64_t n_pos_max,
                            int64_t pos0, const int32_t *d_pos0, hipStream_t st);
 hipError_t launch_attn(const attn_plan &pl, const attn_args &a, hipStream_t st);
+// The PAGED cache of the paged entries (ggml_hip_kv_store_paged_dev, ggml_hip_rope_kv_store_paged_dev, ggml_hip_attn_paged_dev): a pool of
+// n_pages pages of ATTN_CHUNK positions, nb_page bytes apart; entry c of sequence b's table row (ld_pages int32 apart) names the page of its
+// positions [128 c, 128 c + 128); len[b] is the positions it held before this step.  Goes to the kernels by value.
+struct kv_pages {
+    const int32_t *pages; int64_t ld_pages;
+    const int32_t *len;
+    int64_t nb_page; int n_pages; int n_kv_max;
+};
+// rows [n_seq * n_q][n_head_kv][D] -> row (b, t, hk) at page row (len[b] + t); a position outside [0, n_kv_max) or a page id outside
+// [0, n_pages) writes nothing
+hipError_t launch_kv_store_paged(int kv_type, const float *src, int64_t ldx_tok, int64_t ldx_head, int n_head_kv, int D, int64_t n_seq, int64_t n_q, void *pool,
+                                 int64_t nb_pos, int64_t nb_head, const kv_pages &pg, hipStream_t st);
+// a: k / v are the pools, n_q the rows PER SEQUENCE, q / dst [n_seq * n_q][n_head][D]; n_kv / d_n_kv are not read: n_kv[b] = clamp(len[b] + len_bias, 0, n_kv_max);
+// pl: plan_attn_paged's
+hipError_t launch_attn_paged(const attn_plan &pl, const attn_args &a, int64_t n_seq, const kv_pages &pg, int len_bias, hipStream_t st);
 // rope.hip: the rotation of Q / K rows (ggml_hip_rope_dev) and the rotation fused with kv_store (ggml_hip_rope_kv_store_dev; rope.cpp).
 // The per-pair constants are the HOST's (ggml_hip_rope_table) and go to the kernels by value: eff[i] for pair i < n_dims / 2, and mscale
 #define ROPE_MAX_PAIRS 128
@@ -463,6 +478,9 @@ hipError_t launch_rope(const rope_table &tab, const rope_args &a, float *dst, in
 // (a.d_pos is not read: the rope position is the cache position)
 hipError_t launch_rope_kv_store(const rope_table &tab, const rope_args &a, int kv_type, void *cache, int64_t nb_pos, int64_t nb_head, int64_t n_pos_max,
                                 hipStream_t st);
+// the same into a paged cache: a.n_tokens = n_seq * n_q rows, token (b, t) at position pg.len[b] + t (a.d_pos, a.pos0 and a.d_pos0 are not read)
+hipError_t launch_rope_kv_store_paged(const rope_table &tab, const rope_args &a, int kv_type, int64_t n_q, void *pool, int64_t nb_pos, int64_t nb_head,
+                                      const kv_pages &pg, hipStream_t st);
 // gemm_q8s.hip / gemm_qmx.hip: ONE K3s launch over the tile table -- workgroup -> (weight tile group, column tile t); t >= *n_tiles leaves at once;
 // the expert's planes come from tab[tiles[t].expert], the 32 sorted rows at 32 t of the image p (K1's image of `32 * max_tiles` rows); res [rows][ldr]
 hipError_t launch_gemm_q8_small_grouped(const mm_plan &g, int type, const moe_gexpert *tab, const moe_tile *tiles, const int32_t *n_tiles, int64_t max_tiles,

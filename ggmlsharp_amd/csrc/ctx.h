@@ -45,6 +45,10 @@ bool contiguous_f32(const ggml_tensor *t);
 int act_image_kind(int type, int64_t K, int64_t N);              // by type, K and N alone (plan.cpp)
 int weight_image_kind(const ggml_hip_weight *w, int64_t N);         // ... for one weight (kind 0 when its planes exceed 32-bit offsets)
 mm_plan weight_plan(const ggml_hip_weight *w, int64_t N, bool one_call);   // plan.h: the one decision per product
+// the rules of a PAGED cache shared by the three paged entries (attn.cpp): kv_type, the strides of a page, the pool, the table, the lengths,
+// 1 <= n_seq <= 4096 and 0 <= n_kv_max <= 2^24; fills *pg and returns 0, or an error code before a device is touched
+int check_kv_pages(int kv_type, int D, int n_head_kv, int64_t nb_page, int64_t nb_pos, int64_t nb_head, int n_pages, const int32_t *d_pages, int64_t ld_pages,
+                   const int32_t *d_len, int64_t n_seq, int64_t n_kv_max, kv_pages *pg);
 
 struct Scratch {
     void *p = nullptr;

@@ -634,3 +634,14 @@ attn_plan plan_attn(int kv_type, int D, int n_head, int n_head_kv, int64_t n_q, 
     }
     return p;
 }
+
+// The paged call: plan_attn's decision per sequence, every grid n_seq deep (DECODE: chunks x kv heads x sequences, its merge one workgroup
+// per row of all sequences; PROMPT: query tiles x heads x sequences).
+attn_plan plan_attn_paged(int kv_type, int D, int n_head, int n_head_kv, int64_t n_seq, int64_t n_q, int64_t n_kv_max) {
+    attn_plan p = plan_attn(kv_type, D, n_head, n_head_kv, n_q, n_kv_max);
+    if (p.form == ATTN_FORM_NONE) return p;
+    if (n_seq < 1 || n_seq > ATTN_PAGED_MAX_SEQ || n_seq * n_q > ATTN_PAGED_MAX_ROWS || n_seq * n_q * n_head > 0x7FFFFFFF) return attn_plan{};
+    p.wgs *= n_seq;
+    p.work_bytes *= (size_t)n_seq;
+    return p;
+}

@@ -129,6 +129,13 @@ struct attn_plan {
     size_t work_bytes;    // DECODE: the partials, n_q * n_head * n_chunks * (D + 4) floats; PROMPT 0
 };
 attn_plan plan_attn(int kv_type, int D, int n_head, int n_head_kv, int64_t n_q, int64_t n_kv_max);
+// ---- the same over a paged cache, n_seq independent sequences of n_q rows each in one call (ggml_hip_attn_paged_dev) ----
+// plan_attn(.., n_q, ..) with a sequence dimension on every grid: the form, the chunk, q_tile, launches and n_chunks are plan_attn's (page =
+// chunk), wgs and work_bytes are n_seq times its.  NONE where plan_attn says so, for n_seq outside 1 .. ATTN_PAGED_MAX_SEQ (the grids' z),
+// and for n_seq * n_q above ATTN_PAGED_MAX_ROWS or n_seq * n_q * n_head above 2^31 - 1 (the merge's grid is one workgroup per row and head).
+constexpr int64_t ATTN_PAGED_MAX_SEQ = 4096;
+constexpr int64_t ATTN_PAGED_MAX_ROWS = 1 << 20;
+attn_plan plan_attn_paged(int kv_type, int D, int n_head, int n_head_kv, int64_t n_seq, int64_t n_q, int64_t n_kv_max);
 // the K1 image for (type, K, N) with no weight at hand (no M: the exception cannot apply)
 int plan_image_kind(int type, int64_t K, int64_t N);
 // thread-local test switch (ggml_hip_debug_force_gemm): 0 auto, 1 int8, 2 f16, 3 MX

@@ -122,4 +122,30 @@ int ggml_hip_rope_kv_store_dev(const ggml_hip_rope_params_t *rp, int kv_type, co
     return GGML_HIP_OK;
 }
 
+int ggml_hip_rope_kv_store_paged_dev(const ggml_hip_rope_params_t *rp, int kv_type, const float *d_x, int64_t ldx_tok, int64_t ldx_head, int n_head_kv, int D,
+                                     int64_t n_seq, int64_t n_q, const float *d_freq_factors, void *d_pool, int64_t nb_page, int64_t nb_pos, int64_t nb_head,
+                                     int n_pages, const int32_t *d_pages, int64_t ld_pages, const int32_t *d_len, int64_t n_kv_max, void *stream) {
+    int rc = check_rope_params(rp);
+    if (rc) return rc;
+    kv_pages pg;
+    rc = check_kv_pages(kv_type, D, n_head_kv, nb_page, nb_pos, nb_head, n_pages, d_pages, ld_pages, d_len, n_seq, n_kv_max, &pg);
+    if (rc) return rc;
+    if (n_q < 0) return fail(GGML_HIP_ERR_ARG, "n_q %lld", (long long)n_q);
+    if (n_seq * n_q > ATTN_PAGED_MAX_ROWS) return fail(GGML_HIP_ERR_SHAPE, "n_seq * n_q %lld (<= %lld)", (long long)(n_seq * n_q), (long long)ATTN_PAGED_MAX_ROWS);
+    rc = check_rope_rows(rp, n_head_kv, D, n_seq * n_q, ldx_tok, ldx_head);
+    if (rc) return rc;
+    if (n_q == 0) return GGML_HIP_OK;
+    if (!d_x || !d_pool) return fail(GGML_HIP_ERR_ARG, "null argument");
+    if ((((uintptr_t)d_x | (uintptr_t)d_pool) & 15) != 0) return fail(GGML_HIP_ERR_SHAPE, "d_x and d_pool must be 16-byte aligned");
+    if (((uintptr_t)d_freq_factors & 3) != 0) return fail(GGML_HIP_ERR_SHAPE, "d_freq_factors must be 4-byte aligned");
+    rope_table tab;
+    rope_table_of(rp, tab.eff, &tab.mscale);
+    rope_args a;
+    a.mode = rp->mode; a.n_dims = rp->n_dims; a.n_head = n_head_kv; a.D = D;
+    a.x = d_x; a.ldx_tok = ldx_tok; a.ldx_head = ldx_head; a.n_tokens = n_seq * n_q;
+    a.d_pos = nullptr; a.pos0 = 0; a.d_pos0 = nullptr; a.freq_factors = d_freq_factors;
+    HIP_TRY(launch_rope_kv_store_paged(tab, a, kv_type, n_q, d_pool, nb_pos, nb_head, pg, (hipStream_t)stream));
+    return GGML_HIP_OK;
+}
+
 }  // extern "C"

@@ -23,27 +23,34 @@
 // never written, so no thread waits for another) and packs them with kv_pack.h -- bit for bit rope_kernel into a temporary, then
 // kv_store_kernel.  The rope position IS the cache position p0 + t; a row whose position is outside [0, n_pos_max) leaves before any
 // address is formed from it.
+//
+// rope_kv_store_paged_kernel<Q8, MODE>: the same into a PAGED cache (common.h kv_pages; ggml_hip_rope_kv_store_paged_dev): token (b, t) of
+// n_seq * n_q rows sits at len[b] + t, its rope position and, through the sequence's table row, its page row.  rope_store_unit is the
+// rotate-and-pack both store kernels share, so the bytes are rope_kernel's then kv_store_paged_kernel's.  A position outside [0, n_kv_max)
+// leaves before the table is read, a page id outside [0, n_pages) before any address is formed from it.
 // No scratch, no atomics; LDS: 8 tokens x 128 pairs x 8 bytes.
 #include "common.h"
+#include "plan.h"        // ATTN_CHUNK: a page of the paged cache
 #include "kv_pack.h"
 
 namespace {
 
 constexpr int ROPE_TPB_MAX = 8;
+constexpr int ROPE_PAGE = ATTN_CHUNK;                               // positions per page of a paged cache: attention's chunk
 
 __device__ __forceinline__ void rope_rot(float x0, float x1, float2 cs, float &y0, float &y1) {
     y0 = x0 * cs.x - x1 * cs.y;
     y1 = x0 * cs.y + x1 * cs.x;
 }
 
-// (c, s) of every pair of the workgroup's tokens -> cs[token in the workgroup][pair]; ends in the barrier
-__device__ __forceinline__ void rope_stage_cs(float2 *cs, const rope_table &tab, int half, int tpb, int64_t t0, int64_t n_tokens, const int32_t *d_pos,
-                                              int64_t p0, const float *ff) {
+// (c, s) of every pair of the workgroup's tokens -> cs[token in the workgroup][pair]; ends in the barrier.  pos_of(t): the position of token t
+template <class POS>
+__device__ __forceinline__ void rope_stage_cs(float2 *cs, const rope_table &tab, int half, int tpb, int64_t t0, int64_t n_tokens, POS pos_of, const float *ff) {
     for (int idx = threadIdx.x; idx < tpb * half; idx += 256) {
         const int tt = idx / half, i = idx - tt * half;
         const int64_t t = t0 + tt;
         if (t >= n_tokens) break;
-        const int64_t pos = d_pos ? (int64_t)d_pos[t] : p0 + t;
+        const int64_t pos = pos_of(t);
         double theta = (double)pos * tab.eff[i];
         if (ff) theta = theta / (double)ff[i];
         cs[idx] = make_float2((float)(cos(theta) * tab.mscale), (float)(sin(theta) * tab.mscale));
@@ -59,7 +66,8 @@ __global__ __launch_bounds__(256) void rope_kernel(const rope_table tab, const f
     __shared__ __align__(16) float2 cs[ROPE_TPB_MAX * ROPE_MAX_PAIRS];
     const int half = n_dims / 2;
     const int64_t t0 = (int64_t)blockIdx.x * tpb;
-    rope_stage_cs(cs, tab, half, tpb, t0, n_tokens, d_pos, d_pos0 ? (int64_t)*d_pos0 : pos0, ff);
+    const int64_t p0 = d_pos0 ? (int64_t)*d_pos0 : pos0;
+    rope_stage_cs(cs, tab, half, tpb, t0, n_tokens, [=](int64_t t) { return d_pos ? (int64_t)d_pos[t] : p0 + t; }, ff);
     const int rot = VEC ? half / 4 : half;
     const int per_head = rot + (copy_tail ? (VEC ? (D - n_dims) / 4 : D - n_dims) : 0);
     const int per_tok = n_head * per_head;
@@ -146,6 +154,22 @@ __device__ __forceinline__ float4 rope_rotated4(const float *__restrict__ xr, in
     return y;
 }
 
+// unit u (32 elements of a Q8_0 row, 4 of an F16 row) of the rotated row xr -> its bytes in the cache row `row`
+template <bool Q8, int MODE>
+__device__ __forceinline__ void rope_store_unit(const float *__restrict__ xr, uint8_t *__restrict__ row, int u, int n_dims, const float2 *c, bool vec) {
+    if constexpr (Q8) {
+        float v[QK];
+#pragma unroll
+        for (int k = 0; k < 8; ++k) {
+            const float4 f = rope_rotated4<MODE>(xr, QK * u + 4 * k, n_dims, c, vec);
+            v[4 * k] = f.x; v[4 * k + 1] = f.y; v[4 * k + 2] = f.z; v[4 * k + 3] = f.w;
+        }
+        kv_pack_q8_0(v, (uint32_t *)(row + 36 * (int64_t)u));
+    } else {
+        *(uint2 *)(row + 8 * (int64_t)u) = kv_pack_f16(rope_rotated4<MODE>(xr, 4 * u, n_dims, c, vec));
+    }
+}
+
 template <bool Q8, int MODE>
 __global__ __launch_bounds__(256) void rope_kv_store_kernel(const rope_table tab, const float *__restrict__ x, int64_t ldx_tok, int64_t ldx_head, int n_head_kv,
                                                             int D, int n_dims, int64_t n_tokens, int tpb, int64_t pos0, const int32_t *__restrict__ d_pos0,
@@ -155,7 +179,7 @@ __global__ __launch_bounds__(256) void rope_kv_store_kernel(const rope_table tab
     const int half = n_dims / 2;
     const int64_t t0 = (int64_t)blockIdx.x * tpb;
     const int64_t p0 = d_pos0 ? (int64_t)*d_pos0 : pos0;
-    rope_stage_cs(cs, tab, half, tpb, t0, n_tokens, nullptr, p0, ff);
+    rope_stage_cs(cs, tab, half, tpb, t0, n_tokens, [=](int64_t t) { return p0 + t; }, ff);
     const bool vec = n_dims % 8 == 0;
     const int per_head = D / (Q8 ? QK : 4);
     const int per_tok = n_head_kv * per_head;
@@ -166,20 +190,37 @@ __global__ __launch_bounds__(256) void rope_kv_store_kernel(const rope_table tab
         if (t >= n_tokens) break;
         const int64_t pos = p0 + t;
         if (pos < 0 || pos >= n_pos_max) continue;                  // (before any address is formed from it)
-        const float *xr = x + t * ldx_tok + (int64_t)h * ldx_head;
-        uint8_t *row = cache + pos * nb_pos + (int64_t)h * nb_head;
-        const float2 *c = cs + tt * half;
-        if constexpr (Q8) {
-            float v[QK];
-#pragma unroll
-            for (int k = 0; k < 8; ++k) {
-                const float4 f = rope_rotated4<MODE>(xr, QK * u + 4 * k, n_dims, c, vec);
-                v[4 * k] = f.x; v[4 * k + 1] = f.y; v[4 * k + 2] = f.z; v[4 * k + 3] = f.w;
-            }
-            kv_pack_q8_0(v, (uint32_t *)(row + 36 * (int64_t)u));
-        } else {
-            *(uint2 *)(row + 8 * (int64_t)u) = kv_pack_f16(rope_rotated4<MODE>(xr, 4 * u, n_dims, c, vec));
-        }
+        rope_store_unit<Q8, MODE>(x + t * ldx_tok + (int64_t)h * ldx_head, cache + pos * nb_pos + (int64_t)h * nb_head, u, n_dims, cs + tt * half, vec);
+    }
+}
+
+// The same into a PAGED cache (common.h kv_pages): token (b, t') = (t / n_q, t % n_q) of the n_seq * n_q rows sits at position
+// len[b] + t', which is its rope position and, through the sequence's table row, its page row.  Every guard stands in front of the address
+// it protects: the table is read only for a position inside [0, n_kv_max), the pool addressed only with a page id inside [0, n_pages).
+template <bool Q8, int MODE>
+__global__ __launch_bounds__(256) void rope_kv_store_paged_kernel(const rope_table tab, const float *__restrict__ x, int64_t ldx_tok, int64_t ldx_head,
+                                                                  int n_head_kv, int D, int n_dims, int64_t n_tokens, int tpb, int n_q,
+                                                                  const float *__restrict__ ff, uint8_t *__restrict__ pool, int64_t nb_pos, int64_t nb_head,
+                                                                  const kv_pages pg) {
+    __shared__ __align__(16) float2 cs[ROPE_TPB_MAX * ROPE_MAX_PAIRS];
+    const int half = n_dims / 2;
+    const int64_t t0 = (int64_t)blockIdx.x * tpb;
+    const auto pos_of = [=](int64_t t) { const int64_t b = t / n_q; return (int64_t)pg.len[b] + (t - b * n_q); };
+    rope_stage_cs(cs, tab, half, tpb, t0, n_tokens, pos_of, ff);
+    const bool vec = n_dims % 8 == 0;
+    const int per_head = D / (Q8 ? QK : 4);
+    const int per_tok = n_head_kv * per_head;
+    for (int idx = threadIdx.x; idx < tpb * per_tok; idx += 256) {
+        const int tt = idx / per_tok, r = idx - tt * per_tok;
+        const int h = r / per_head, u = r - h * per_head;
+        const int64_t t = t0 + tt;
+        if (t >= n_tokens) break;
+        const int64_t pos = pos_of(t);
+        if (pos < 0 || pos >= pg.n_kv_max) continue;                // (before the table is read)
+        const int page = pg.pages[(t / n_q) * pg.ld_pages + pos / ROPE_PAGE];
+        if (page < 0 || page >= pg.n_pages) continue;               // (before any address is formed from it)
+        uint8_t *row = pool + (int64_t)page * pg.nb_page + (pos % ROPE_PAGE) * nb_pos + (int64_t)h * nb_head;
+        rope_store_unit<Q8, MODE>(x + t * ldx_tok + (int64_t)h * ldx_head, row, u, n_dims, cs + tt * half, vec);
     }
 }
 
@@ -221,6 +262,24 @@ hipError_t launch_rope_kv_store(const rope_table &tab, const rope_args &a, int k
 #define ROPE_KV(Q, M)                                                                                                                                  \
     rope_kv_store_kernel<Q, M><<<dim3((unsigned)blocks), 256, 0, st>>>(tab, a.x, a.ldx_tok, a.ldx_head, a.n_head, a.D, a.n_dims, a.n_tokens, tpb, a.pos0,  \
                                                                       a.d_pos0, a.freq_factors, (uint8_t *)cache, nb_pos, nb_head, n_pos_max)
+    if (q8 && a.mode == 0) ROPE_KV(true, 0);
+    else if (q8) ROPE_KV(true, 2);
+    else if (a.mode == 0) ROPE_KV(false, 0);
+    else ROPE_KV(false, 2);
+#undef ROPE_KV
+    return hipGetLastError();
+}
+
+hipError_t launch_rope_kv_store_paged(const rope_table &tab, const rope_args &a, int kv_type, int64_t n_q, void *pool, int64_t nb_pos, int64_t nb_head,
+                                      const kv_pages &pg, hipStream_t st) {
+    if (a.n_tokens <= 0) return hipSuccess;
+    const bool q8 = kv_type == GGML_TYPE_Q8_0;
+    const int tpb = rope_tpb((int64_t)a.n_head * (a.D / (q8 ? QK : 4)), a.n_tokens);
+    const int64_t blocks = (a.n_tokens + tpb - 1) / tpb;
+    if (blocks > 0x7FFFFFFF || a.n_dims / 2 > ROPE_MAX_PAIRS || n_q < 1 || n_q > 0x7FFFFFFF) return hipErrorInvalidValue;
+#define ROPE_KV(Q, M)                                                                                                                                  \
+    rope_kv_store_paged_kernel<Q, M><<<dim3((unsigned)blocks), 256, 0, st>>>(tab, a.x, a.ldx_tok, a.ldx_head, a.n_head, a.D, a.n_dims, a.n_tokens, tpb,   \
+                                                                            (int)n_q, a.freq_factors, (uint8_t *)pool, nb_pos, nb_head, pg)
     if (q8 && a.mode == 0) ROPE_KV(true, 0);
     else if (q8) ROPE_KV(true, 2);
     else if (a.mode == 0) ROPE_KV(false, 0);

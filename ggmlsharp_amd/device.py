@@ -333,6 +333,88 @@ def rope_kv_store(rp, kv_type, x, cache, nb_pos, nb_head, n_pos_max, pos0=0, d_p
           "ggml_hip_rope_kv_store_dev")
 
 
+class PagedCache:
+    """how a paged KV cache is addressed (include/ggml_hip_ext.h, PAGED ATTENTION): pools k / v (uint8 tensors of n_pages pages of 128 positions,
+    nb_page bytes apart; row (jj, hk) of a page at jj * nb_pos + hk * nb_head), the page table pages int32 [n_seq, ld_pages] and the lengths
+    d_len int32 [n_seq] on the device, and n_kv_max, which sizes the launches (size it to the step).  The host owns the table."""
+
+    def __init__(self, kv_type, k, v, nb_page, nb_pos, nb_head, n_pages, pages, d_len, n_kv_max):
+        assert k.is_cuda and v.is_cuda and k.dtype == torch.uint8 and v.dtype == torch.uint8
+        assert pages.is_cuda and pages.dtype == torch.int32 and pages.dim() == 2 and pages.stride(1) == 1
+        assert d_len.is_cuda and d_len.dtype == torch.int32 and d_len.is_contiguous() and d_len.numel() == pages.shape[0]
+        self.kv_type, self.k, self.v, self.nb_page, self.nb_pos, self.nb_head = kv_type, k, v, int(nb_page), int(nb_pos), int(nb_head)
+        self.n_pages, self.pages, self.d_len, self.n_kv_max = int(n_pages), pages, d_len, int(n_kv_max)
+
+    @property
+    def n_seq(self):
+        return self.pages.shape[0]
+
+    def _args(self):
+        """(nb_page, nb_pos, nb_head, n_pages, d_pages, ld_pages, d_len) as the entries take them"""
+        return (self.nb_page, self.nb_pos, self.nb_head, self.n_pages, C.c_void_p(self.pages.data_ptr()), self.pages.stride(0), C.c_void_p(self.d_len.data_ptr()))
+
+
+def _paged_rows(pc, x):
+    assert x.is_cuda and x.dtype == torch.float32 and x.dim() == 3 and x.stride(2) == 1
+    n_rows, n_head_kv, D = x.shape
+    assert n_rows % pc.n_seq == 0, "n_seq * n_q rows"
+    return n_rows // pc.n_seq, n_head_kv, D
+
+
+def kv_store_paged(pc, x, pool):
+    """x f32 [n_seq * n_q, n_head_kv, D] -> row (b, t, hk) to its page row of pool (pc.k or pc.v) at position d_len[b] + t, bit for bit
+    kv_store's bytes; a position outside [0, n_kv_max) or a page id outside [0, n_pages) writes nothing"""
+    n_q, n_head_kv, D = _paged_rows(pc, x)
+    nbp, nbo, nbh, n_pages, d_pages, ld_pages, d_len = pc._args()
+    check(lib().ggml_hip_kv_store_paged_dev(pc.kv_type, C.c_void_p(x.data_ptr()), x.stride(0), x.stride(1), n_head_kv, D, pc.n_seq, n_q, C.c_void_p(pool.data_ptr()),
+                                            nbp, nbo, nbh, n_pages, d_pages, ld_pages, d_len, pc.n_kv_max, _stream()), "ggml_hip_kv_store_paged_dev")
+
+
+def rope_kv_store_paged(rp, pc, x, pool, freq_factors=None):
+    """rotate the rows of x f32 [n_seq * n_q, n_head_kv, D] at their cache positions d_len[b] + t and store them as page rows of pool in one
+    launch: bit for bit rope(pos = d_len[b] + t) into a temporary, then kv_store_paged()"""
+    assert freq_factors is None or (freq_factors.is_cuda and freq_factors.dtype == torch.float32 and freq_factors.is_contiguous())
+    n_q, n_head_kv, D = _paged_rows(pc, x)
+    nbp, nbo, nbh, n_pages, d_pages, ld_pages, d_len = pc._args()
+    check(lib().ggml_hip_rope_kv_store_paged_dev(C.byref(rp), pc.kv_type, C.c_void_p(x.data_ptr()), x.stride(0), x.stride(1), n_head_kv, D, pc.n_seq, n_q,
+                                                 _opt(freq_factors), C.c_void_p(pool.data_ptr()), nbp, nbo, nbh, n_pages, d_pages, ld_pages, d_len, pc.n_kv_max,
+                                                 _stream()), "ggml_hip_rope_kv_store_paged_dev")
+
+
+def attn_paged_plan(kv_type, D, n_head, n_head_kv, n_seq, n_q, n_kv_max):
+    """the ggml_hip_attn_plan_t of one paged call: attn_plan's form and chunk for n_q, the workgroups of all n_seq sequences; no device needed"""
+    out = _lib.ggml_hip_attn_plan_t()
+    check(lib().ggml_hip_attn_paged_plan(kv_type, D, n_head, n_head_kv, n_seq, n_q, n_kv_max, C.byref(out)), "ggml_hip_attn_paged_plan")
+    return out
+
+
+def attn_paged_work_size(kv_type, D, n_head, n_head_kv, n_seq, n_q, n_kv_max):
+    return int(lib().ggml_hip_attn_paged_work_size(kv_type, D, n_head, n_head_kv, n_seq, n_q, n_kv_max))
+
+
+def attn_paged(pc, q, n_head_kv, len_bias=0, causal=True, scale=None, out=None, work=None):
+    """attention of n_seq independent sequences over the paged cache pc in one call: q f32 [n_seq * n_q, n_head, D] (last stride 1), sequence b
+    over its n_kv[b] = clamp(d_len[b] + len_bias, 0, n_kv_max) positions; its rows are bit for bit attention() on a contiguous copy of its cache.
+    len_bias = n_q behind a store of this step's tokens.  A sequence with n_kv 0 or an invalid needed page id returns +0.0 rows."""
+    assert q.is_cuda and q.dtype == torch.float32 and q.dim() == 3 and q.stride(2) == 1
+    n_rows, n_head, D = q.shape
+    assert n_rows % pc.n_seq == 0, "n_seq * n_q rows"
+    n_q = n_rows // pc.n_seq
+    if scale is None:
+        scale = 1.0 / float(np.sqrt(np.float64(D)))
+    if out is None:
+        out = torch.empty((n_rows, n_head, D), dtype=torch.float32, device=q.device)
+    assert out.dtype == torch.float32 and out.dim() == 3 and out.stride(2) == 1 and tuple(out.shape) == (n_rows, n_head, D)
+    if work is None:
+        work = torch.empty(max(attn_paged_work_size(pc.kv_type, D, n_head, n_head_kv, pc.n_seq, n_q, pc.n_kv_max), 16), dtype=torch.uint8, device=q.device)
+    nbp, nbo, nbh, n_pages, d_pages, ld_pages, d_len = pc._args()
+    check(lib().ggml_hip_attn_paged_dev(pc.kv_type, C.c_void_p(q.data_ptr()), q.stride(0), q.stride(1), C.c_void_p(pc.k.data_ptr()), C.c_void_p(pc.v.data_ptr()),
+                                        nbp, nbo, nbh, n_pages, d_pages, ld_pages, d_len, int(len_bias), pc.n_seq, n_head, n_head_kv, D, n_q, pc.n_kv_max,
+                                        int(bool(causal)), float(scale), None, 0.0, 0.0, None, C.c_void_p(out.data_ptr()), out.stride(0), out.stride(1),
+                                        C.c_void_p(work.data_ptr()), work.numel(), _stream()), "ggml_hip_attn_paged_dev")
+    return out
+
+
 def get_rows(w, ids, out=None):
     """out[i, :K] = dequantize(w[ids[i]]) on the current stream: ids an int32 tensor on the device; bit for bit download + dequantize, a row of
     +0.0 for an id outside [0, M).  out f32 [n_ids, >= K] with last stride 1 (default a new [n_ids, K] tensor)."""

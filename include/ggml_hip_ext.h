@@ -608,6 +608,75 @@ int ggml_hip_rope_kv_store_dev(const ggml_hip_rope_params_t *rp, int kv_type, co
                                void *d_cache, int64_t nb_pos, int64_t nb_head, int64_t n_pos_max,
                                int64_t pos0, const int32_t *d_pos0, void *stream);
 
+/* ---------------- PAGED ATTENTION: a batch of independent sequences over one pool of KV pages, in one call per entry ----------------
+ * An EXTENSION like the two sections above (upstream serves a batch of sequences through its mask tensor; here the cache itself is cut into
+ * pages).  ggml_hip_attn_dev and ggml_hip_kv_store_dev know ONE cache, one n_kv and one pos0; a step that decodes 32 sequences would make 32
+ * attention calls and 64 stores, each sequence on a contiguous cache reserved at its maximum length.  These entries take the whole batch:
+ *     projections at n_seq * n_q rows -> rope(q, d_pos) -> rope_kv_store_paged(k) -> kv_store_paged(v) -> attn_paged
+ * All are stream-ordered on `stream` on the current device; none synchronizes or allocates; all may be captured; no atomics.  Every refusal
+ * below is decided before a device is touched.  The entries of the sections above keep their bits and their signatures.
+ *
+ * THE PAGED CACHE (shared by all entries).
+ *   POOL.   d_k / d_v (d_pool for a store) hold n_pages PAGES of 128 positions each -- a page is a CHUNK of ggml_hip_attn_dev, for every
+ *           kv_type and D.  kv_type is F16 or Q8_0 as above (else GGML_HIP_ERR_TYPE).
+ *   ROWS.   Row (position-in-page jj, kv head hk) of page p lies at byte offset  p * nb_page + jj * nb_pos + hk * nb_head,  in the reference
+ *           block format ggml_hip_kv_store_dev writes.
+ *   STRIDES. nb_pos and nb_head follow ggml_hip_attn_dev's rules (multiples of 16, at least a row's bytes, either may be the larger).
+ *           nb_page is a multiple of 16 and at least the bytes a page's rows span, 127 * nb_pos + (n_head_kv - 1) * nb_head + a row's bytes:
+ *           else GGML_HIP_ERR_SHAPE.
+ *   TABLE.  d_pages: int32 [n_seq][ld_pages] on the device, ld_pages >= ceil(n_kv_max / 128) (else GGML_HIP_ERR_SHAPE).  Entry c of
+ *           sequence b is the page that holds its positions [128 c, 128 c + 128).  Two sequences may name the same page (a shared prefix).
+ *           Entries at or beyond ceil(n_kv[b] / 128) are never read by attention and may hold anything.
+ *   LENGTHS. d_len: int32 [n_seq] on the device, never NULL: the positions sequence b held BEFORE this step.  The stores put token t of
+ *           sequence b at position d_len[b] + t.  Attention uses n_kv[b] = clamp(d_len[b] + len_bias, 0, n_kv_max), len_bias a host
+ *           integer: behind a store the caller passes len_bias = n_q, so ONE device array drives the rotation (d_pos = d_len for n_q = 1),
+ *           the stores and the attention of a captured step, and the host adds n_q to it between replays.
+ *   NULL d_pages / d_len, n_pages <= 0: GGML_HIP_ERR_ARG.  1 <= n_seq <= 4096, n_seq * n_q <= 2^20 and (attention) n_seq * n_q * n_head
+ *   < 2^31 -- the grids carry the sequences in their z dimension and the merge is one workgroup per row and head: above, GGML_HIP_ERR_SHAPE.
+ *   n_kv_max (0 .. 2^24) sizes the launches and bounds every position.  SIZE IT TO THE STEP, not to the model's context: the DECODE grid has
+ *   ceil(n_kv_max / 128) workgroups per kv head and sequence, and those beyond a sequence's length are launched to leave at once.
+ *   THE LIBRARY HAS NO ALLOCATOR: the host owns the table; page allocation, copy-on-write and defragmentation are the caller's.
+ *
+ * ggml_hip_kv_store_paged_dev: f32 rows [n_seq * n_q][n_head_kv][D] with element strides (ldx_tok, ldx_head) (multiples of 4, at least D;
+ *   d_src and d_pool 16-byte aligned; D a multiple of 4, for Q8_0 of 32, at most 256) -> row (b, t, hk) to its page row.
+ *   THE CONTRACT: the bytes written are bit for bit what ggml_hip_kv_store_dev writes for that f32 row.  A token writes nothing, and no
+ *   address is formed from it, when its position is < 0 or >= n_kv_max, or when its page id is outside [0, n_pages).
+ * ggml_hip_rope_kv_store_paged_dev: the same with the rotation in front; the rope position IS the cache position d_len[b] + t.
+ *   THE CONTRACT: bit for bit ggml_hip_rope_dev (d_pos[b * n_q + t] = d_len[b] + t) into a temporary, then ggml_hip_kv_store_paged_dev.
+ * ggml_hip_attn_paged_dev: q, dst f32 [n_seq * n_q][n_head][D] (rows of sequence b at b * n_q ..; strides as ggml_hip_attn_dev); n_q is
+ *   uniform over the sequences.  The form follows n_q alone exactly as ggml_hip_attn_plan decides it (DECODE up to 8 rows per sequence,
+ *   PROMPT above; the chunk is 128); ggml_hip_attn_paged_plan shows it, with the workgroups of all sequences.
+ *   THE CONTRACT: for every sequence b its n_q rows of dst are BIT FOR BIT ggml_hip_attn_dev with the same n_q, n_kv = n_kv[b], causal,
+ *   scale, heads and D on a contiguous cache holding the same row bytes -- in both forms: a paged call runs the same chunk body on
+ *   pool + page * nb_page, and neither form's arithmetic knows where a chunk lies.  So a sequence's bits do not depend on the page
+ *   assignment, n_pages, ld_pages, nb_page, n_kv_max, n_seq or its slot.
+ *   A sequence with n_kv[b] = 0 writes +0.0f rows: that is how a captured graph of fixed n_seq carries idle slots.
+ *   A sequence with a page id outside [0, n_pages) among its first ceil(n_kv[b] / 128) entries writes +0.0f for ALL its rows; no address is
+ *   formed from that id and the other sequences are unaffected.
+ *   A mask, ALiBi, a soft-cap and sinks are refused as by ggml_hip_attn_dev.
+ *   d_work / work_bytes: ggml_hip_attn_paged_work_size bytes -- DECODE: n_seq * n_q * n_head * ceil(n_kv_max / 128) * (D + 4) floats plus
+ *   alignment; 0 for n_seq * n_q = 0 and for PROMPT; monotone in n_seq, n_q (within DECODE) and n_kv_max.  Missing or short: GGML_HIP_ERR_ARG.
+ *   n_q = 0 returns 0 and writes nothing.
+ * KERNELS.  DECODE: grid (chunks of n_kv_max) x (kv heads) x (sequences); a workgroup reads its sequence's length and its chunk's page id as
+ *   scalars and leaves at once if the chunk lies at or beyond n_kv[b] or the id is invalid; the merge (one workgroup per row) scans the
+ *   sequence's needed ids first and writes zeros if one is invalid.  PROMPT: grid (query tiles) x (heads) x (sequences); a workgroup scans
+ *   the needed ids before its first stage, then takes each chunk's base from the table. */
+int    ggml_hip_kv_store_paged_dev(int kv_type, const float *d_src, int64_t ldx_tok, int64_t ldx_head, int n_head_kv, int D,
+                                   int64_t n_seq, int64_t n_q, void *d_pool, int64_t nb_page, int64_t nb_pos, int64_t nb_head, int n_pages,
+                                   const int32_t *d_pages, int64_t ld_pages, const int32_t *d_len, int64_t n_kv_max, void *stream);
+int    ggml_hip_rope_kv_store_paged_dev(const ggml_hip_rope_params_t *rp, int kv_type, const float *d_x, int64_t ldx_tok, int64_t ldx_head,
+                                        int n_head_kv, int D, int64_t n_seq, int64_t n_q, const float *d_freq_factors,
+                                        void *d_pool, int64_t nb_page, int64_t nb_pos, int64_t nb_head, int n_pages,
+                                        const int32_t *d_pages, int64_t ld_pages, const int32_t *d_len, int64_t n_kv_max, void *stream);
+int    ggml_hip_attn_paged_plan(int kv_type, int D, int n_head, int n_head_kv, int64_t n_seq, int64_t n_q, int64_t n_kv_max, ggml_hip_attn_plan_t *out);
+size_t ggml_hip_attn_paged_work_size(int kv_type, int D, int n_head, int n_head_kv, int64_t n_seq, int64_t n_q, int64_t n_kv_max);
+int    ggml_hip_attn_paged_dev(int kv_type, const float *d_q, int64_t ldq_tok, int64_t ldq_head,
+                               const void *d_k, const void *d_v, int64_t nb_page, int64_t nb_pos, int64_t nb_head, int n_pages,
+                               const int32_t *d_pages, int64_t ld_pages, const int32_t *d_len, int len_bias, int64_t n_seq,
+                               int n_head, int n_head_kv, int D, int64_t n_q, int64_t n_kv_max,
+                               int causal, float scale, const void *d_mask, float max_bias, float logit_softcap, const float *d_sinks,
+                               float *d_dst, int64_t ldd_tok, int64_t ldd_head, void *d_work, size_t work_bytes, void *stream);
+
 /* ---------------- THE ENDS OF A DECODE STEP: a token id -> its embedding row; the LM head's logits -> the next token id ----------------
  * Upstream's ggml_get_rows over the token-embedding matrix and its ggml_argmax / top-k -> temperature -> softmax -> top-p -> pick sampler
  * chain, EXTENSIONS like rope (the reference lists get_rows and never dispatches it): device entries only.  With them a captured decode step

@@ -107,6 +107,21 @@ internal static unsafe partial class GgmlHip
         int* dPos, long pos0, int* dPos0, float* dFreqFactors, float* dDst, long lddTok, long lddHead, void* stream);
     [DllImport(Lib)] public static extern int ggml_hip_rope_kv_store_dev(ggml_hip_rope_params_t* rp, int kvType, float* dX, long ldxTok, long ldxHead, int nHeadKv, int d,
         long nTokens, float* dFreqFactors, void* dCache, long nbPos, long nbHead, long nPosMax, long pos0, int* dPos0, void* stream);
+    // ... paged attention: a batch of nSeq independent sequences over one pool of KV pages of 128 positions (page p at p * nbPage; row (jj, hk) at
+    // jj * nbPos + hk * nbHead inside it), addressed by the int32 table dPages [nSeq][ldPages] and the int32 lengths dLen [nSeq] on the device: the
+    // stores put token t of sequence b at dLen[b] + t, attention uses n_kv[b] = clamp(dLen[b] + lenBias, 0, nKvMax); per sequence bit for bit the
+    // contiguous entries above; a position or page id out of range writes nothing, a sequence with an invalid needed id returns +0 rows
+    [DllImport(Lib)] public static extern int ggml_hip_kv_store_paged_dev(int kvType, float* dSrc, long ldxTok, long ldxHead, int nHeadKv, int d, long nSeq, long nQ,
+        void* dPool, long nbPage, long nbPos, long nbHead, int nPages, int* dPages, long ldPages, int* dLen, long nKvMax, void* stream);
+    [DllImport(Lib)] public static extern int ggml_hip_rope_kv_store_paged_dev(ggml_hip_rope_params_t* rp, int kvType, float* dX, long ldxTok, long ldxHead, int nHeadKv,
+        int d, long nSeq, long nQ, float* dFreqFactors, void* dPool, long nbPage, long nbPos, long nbHead, int nPages, int* dPages, long ldPages, int* dLen,
+        long nKvMax, void* stream);
+    [DllImport(Lib)] public static extern int ggml_hip_attn_paged_plan(int kvType, int d, int nHead, int nHeadKv, long nSeq, long nQ, long nKvMax, void* plan);
+    [DllImport(Lib)] public static extern nuint ggml_hip_attn_paged_work_size(int kvType, int d, int nHead, int nHeadKv, long nSeq, long nQ, long nKvMax);
+    [DllImport(Lib)] public static extern int ggml_hip_attn_paged_dev(int kvType, float* dQ, long ldqTok, long ldqHead, void* dK, void* dV, long nbPage, long nbPos,
+        long nbHead, int nPages, int* dPages, long ldPages, int* dLen, int lenBias, long nSeq, int nHead, int nHeadKv, int d, long nQ, long nKvMax, int causal,
+        float scale, void* dMask, float maxBias, float logitSoftcap, float* dSinks, float* dDst, long lddTok, long lddHead, void* dWork, nuint workBytes,
+        void* stream);
     // ... the ends of a decode step (device entries, capturable, scratch from the caller): rows of a resident weight by int32 ids on the device, bit
     // for bit download + dequantize, an id outside [0, M) a row of +0; the k best logits of every row (larger first, ties to the smaller index, NaN
     // last), p = softmax((l - l0) * invTemp) over them, top-p and the pick by the caller's uniforms dU (null: no pick) -- the int32 written to dToken
