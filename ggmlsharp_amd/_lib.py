@@ -86,6 +86,14 @@ class ggml_hip_attn_plan_t(C.Structure):
                 ("n_chunks", C.c_int64), ("workgroups", C.c_int64)]
 
 
+class ggml_hip_attn_opts_t(C.Structure):
+    """include/ggml_hip_ext.h: the options of the _ex attention entries (sinks f32 [n_head] on the device, window, soft-cap; reserved 0)"""
+    _fields_ = [("d_sinks", C.c_void_p), ("window", C.c_int64), ("logit_softcap", C.c_float), ("reserved", C.c_int32)]
+
+
+assert C.sizeof(ggml_hip_attn_opts_t) == 24
+
+
 class ggml_hip_rope_params_t(C.Structure):
     """include/ggml_hip_ext.h: the parameters of a rotary embedding (mode 0 NORMAL, 2 NEOX)"""
     _fields_ = [("n_dims", C.c_int32), ("mode", C.c_int32), ("n_ctx_orig", C.c_int32),
@@ -239,6 +247,14 @@ HIP_SYMBOLS = {
     "ggml_hip_attn_paged_dev": (C.c_int, [C.c_int, _P, C.c_int64, C.c_int64, _P, _P, C.c_int64, C.c_int64, C.c_int64, C.c_int, _P, C.c_int64, _P, C.c_int,
                                           C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int64, C.c_int64, C.c_int, C.c_float, _P, C.c_float, C.c_float, _P, _P,
                                           C.c_int64, C.c_int64, _P, C.c_size_t, _P]),
+    # the attention options (sliding window, sinks, soft-cap) over either cache: the plans and the calls; opts is a ggml_hip_attn_opts_t * or null
+    "ggml_hip_attn_ex_plan": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int64, C.c_int64, _P, _P]),
+    "ggml_hip_attn_ex_dev": (C.c_int, [C.c_int, _P, C.c_int64, C.c_int64, _P, _P, C.c_int64, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int64, C.c_int64, _P,
+                                       C.c_int64, C.c_int, C.c_float, _P, _P, C.c_int64, C.c_int64, _P, C.c_size_t, _P]),
+    "ggml_hip_attn_paged_ex_plan": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int64, C.c_int64, C.c_int64, _P, _P]),
+    "ggml_hip_attn_paged_ex_dev": (C.c_int, [C.c_int, _P, C.c_int64, C.c_int64, _P, _P, C.c_int64, C.c_int64, C.c_int64, C.c_int, _P, C.c_int64, _P, C.c_int,
+                                             C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int64, C.c_int64, C.c_int, C.c_float, _P, _P, C.c_int64, C.c_int64, _P,
+                                             C.c_size_t, _P]),
     # the ends of a decode step: rows of a resident weight by device ids; top-k over a vocabulary, probabilities, top-p and the pick
     "ggml_hip_get_rows_serves_for": (C.c_int, [C.c_int]),
     "ggml_hip_get_rows_dev": (C.c_int, [_P, _P, C.c_int64, _P, C.c_int64, _P]),

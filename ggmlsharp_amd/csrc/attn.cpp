@@ -1,7 +1,9 @@
 // attn.cpp -- the C-ABI of include/ggml_hip_ext.h, attention over a KV cache: rows into the cache (ggml_hip_kv_store_dev), the attention
-// itself (ggml_hip_attn_dev), its plan and work size.  The kernels and their arithmetic are attn.hip's, the form is plan.cpp's (plan_attn).
+// itself (ggml_hip_attn_dev), its plan and work size, the paged entries, and the _ex entries with a sliding window, sinks and a soft-cap
+// (one checked path serves an entry and its _ex twin).  The kernels and their arithmetic are attn.hip's, the form is plan.cpp's (plan_attn).
 // No set, no handle: stream-ordered launches on the current device, no synchronize, no allocation; capturable.
 #include "ctx.h"
+#include <cfloat>
 
 using namespace ghip;
 
@@ -29,6 +31,98 @@ int check_attn_rows(int D, int64_t rows, int64_t ldq_tok, int64_t ldq_head, int6
         (rows > 1 && (ldq_tok < D || ldd_tok < D)))
         return fail(GGML_HIP_ERR_SHAPE, "the strides of q and dst are multiples of 4 elements, at least D");
     return GGML_HIP_OK;
+}
+
+// the rules of a ggml_hip_attn_opts_t; 0 or an error code.  *on: one of the three options is set (else the base kernels run); vo: the kernels' form
+int check_attn_opts(const ggml_hip_attn_opts_t *opts, int causal, float scale, bool *on, attn_var *vo) {
+    *on = false;
+    *vo = attn_var{};
+    if (!opts) return GGML_HIP_OK;
+    if (opts->reserved != 0) return fail(GGML_HIP_ERR_ARG, "opts->reserved %d must be 0", (int)opts->reserved);
+    if (opts->window < 0) return fail(GGML_HIP_ERR_ARG, "window %lld (0: none, or >= 1)", (long long)opts->window);
+    if (opts->window > 0 && !causal) return fail(GGML_HIP_ERR_ARG, "a window needs causal != 0");
+    if (!(opts->logit_softcap >= 0.0f) || opts->logit_softcap > FLT_MAX) return fail(GGML_HIP_ERR_ARG, "logit_softcap must be 0 or a finite positive number");
+    if (((uintptr_t)opts->d_sinks & 3) != 0) return fail(GGML_HIP_ERR_ARG, "d_sinks must be 4-byte aligned");
+    vo->sinks = opts->d_sinks;
+    vo->window = (int)(opts->window > ((int64_t)1 << 30) ? ((int64_t)1 << 30) : opts->window);      // (n_kv_max <= 2^24: beyond it every window is "none")
+    vo->cap = opts->logit_softcap;
+    vo->sc = vo->cap != 0.0f ? scale / vo->cap : 0.0f;               // ONE binary32 division (the header's sc')
+    *on = vo->sinks || vo->window > 0 || vo->cap != 0.0f;
+    return GGML_HIP_OK;
+}
+
+// ggml_hip_attn_dev behind its refusal of upstream's extras, and ggml_hip_attn_ex_dev behind check_attn_opts: on / vo are its answer (off from the base entry)
+int attn_run(int kv_type, const float *d_q, int64_t ldq_tok, int64_t ldq_head, const void *d_k, const void *d_v, int64_t nb_pos, int64_t nb_head, int n_head,
+             int n_head_kv, int D, int64_t n_q, int64_t n_kv, const int32_t *d_n_kv, int64_t n_kv_max, int causal, float scale, bool on, const attn_var &vo,
+             float *d_dst, int64_t ldd_tok, int64_t ldd_head, void *d_work, size_t work_bytes, void *stream) {
+    int rc = check_attn_shape(kv_type, D, n_head, n_head_kv, n_q, n_kv_max);
+    if (rc) return rc;
+    if (!d_n_kv && (n_kv < 0 || n_kv > n_kv_max)) return fail(GGML_HIP_ERR_ARG, "n_kv %lld outside [0, n_kv_max %lld]", (long long)n_kv, (long long)n_kv_max);
+    const int64_t row_bytes = kv_type == GGML_TYPE_Q8_0 ? D / QK * (int64_t)sizeof(block_q8_0) : D * 2;
+    if (ldq_tok % 4 != 0 || ldq_head % 4 != 0 || ldd_tok % 4 != 0 || ldd_head % 4 != 0 || ldq_head < D || ldd_head < D || ldq_tok < 0 || ldd_tok < 0 ||
+        (n_q > 1 && (ldq_tok < D || ldd_tok < D)))
+        return fail(GGML_HIP_ERR_SHAPE, "the strides of q and dst are multiples of 4 elements, at least D");
+    if (nb_pos % 16 != 0 || nb_head % 16 != 0 || nb_pos < row_bytes || nb_head < row_bytes)
+        return fail(GGML_HIP_ERR_SHAPE, "nb_pos %lld, nb_head %lld: multiples of 16 bytes, at least the %lld bytes of a row", (long long)nb_pos, (long long)nb_head,
+                    (long long)row_bytes);
+    if (n_q == 0) return GGML_HIP_OK;
+    if (!d_q || !d_dst || (n_kv_max > 0 && (!d_k || !d_v))) return fail(GGML_HIP_ERR_ARG, "null argument");
+    if ((((uintptr_t)d_q | (uintptr_t)d_dst | (uintptr_t)d_k | (uintptr_t)d_v) & 15) != 0) return fail(GGML_HIP_ERR_SHAPE, "q, dst, K and V must be 16-byte aligned");
+    const attn_plan p = on ? plan_attn_ex(kv_type, D, n_head, n_head_kv, n_q, n_kv_max, vo.window) : plan_attn(kv_type, D, n_head, n_head_kv, n_q, n_kv_max);
+    if (p.form == ATTN_FORM_NONE) return fail(GGML_HIP_ERR_SHAPE, "the shape is not served");
+    const size_t need = ggml_hip_attn_work_size(kv_type, D, n_head, n_head_kv, n_q, n_kv_max);
+    if (need && (!d_work || work_bytes < need)) return fail(GGML_HIP_ERR_ARG, "work buffer too small: need %zu (ggml_hip_attn_work_size)", need);
+    attn_args a;
+    a.kv_type = kv_type; a.D = D; a.n_head = n_head; a.n_head_kv = n_head_kv; a.causal = causal != 0;
+    a.q = d_q; a.ldq_tok = ldq_tok; a.ldq_head = ldq_head;
+    a.k = d_k; a.v = d_v; a.nb_pos = nb_pos; a.nb_head = nb_head;
+    a.n_q = n_q; a.n_kv = d_n_kv ? 0 : n_kv; a.d_n_kv = d_n_kv; a.n_kv_max = n_kv_max;
+    a.scale = scale;
+    a.dst = d_dst; a.ldd_tok = ldd_tok; a.ldd_head = ldd_head;
+    a.work = need ? (void *)(((uintptr_t)d_work + ATTN_ALIGN - 1) / ATTN_ALIGN * ATTN_ALIGN) : nullptr;
+    if (on) HIP_TRY(launch_attn_ex(p, a, vo, (hipStream_t)stream));
+    else HIP_TRY(launch_attn(p, a, (hipStream_t)stream));
+    return GGML_HIP_OK;
+}
+
+int attn_paged_run(int kv_type, const float *d_q, int64_t ldq_tok, int64_t ldq_head, const void *d_k, const void *d_v, int64_t nb_page, int64_t nb_pos,
+                   int64_t nb_head, int n_pages, const int32_t *d_pages, int64_t ld_pages, const int32_t *d_len, int len_bias, int64_t n_seq, int n_head,
+                   int n_head_kv, int D, int64_t n_q, int64_t n_kv_max, int causal, float scale, bool on, const attn_var &vo, float *d_dst, int64_t ldd_tok,
+                   int64_t ldd_head, void *d_work, size_t work_bytes, void *stream) {
+    int rc = check_attn_shape(kv_type, D, n_head, n_head_kv, n_q, n_kv_max);
+    if (rc) return rc;
+    kv_pages pg;
+    rc = check_kv_pages(kv_type, D, n_head_kv, nb_page, nb_pos, nb_head, n_pages, d_pages, ld_pages, d_len, n_seq, n_kv_max, &pg);
+    if (rc) return rc;
+    if (n_seq * n_q > ATTN_PAGED_MAX_ROWS || n_seq * n_q * n_head > 0x7FFFFFFF)
+        return fail(GGML_HIP_ERR_SHAPE, "n_seq * n_q %lld (<= %lld, times n_head below 2^31)", (long long)(n_seq * n_q), (long long)ATTN_PAGED_MAX_ROWS);
+    rc = check_attn_rows(D, n_seq * n_q, ldq_tok, ldq_head, ldd_tok, ldd_head);
+    if (rc) return rc;
+    if (n_q == 0) return GGML_HIP_OK;
+    if (!d_q || !d_dst || !d_k || !d_v) return fail(GGML_HIP_ERR_ARG, "null argument");
+    if ((((uintptr_t)d_q | (uintptr_t)d_dst | (uintptr_t)d_k | (uintptr_t)d_v) & 15) != 0) return fail(GGML_HIP_ERR_SHAPE, "q, dst, K and V must be 16-byte aligned");
+    const attn_plan p = on ? plan_attn_paged_ex(kv_type, D, n_head, n_head_kv, n_seq, n_q, n_kv_max, vo.window)
+                           : plan_attn_paged(kv_type, D, n_head, n_head_kv, n_seq, n_q, n_kv_max);
+    if (p.form == ATTN_FORM_NONE) return fail(GGML_HIP_ERR_SHAPE, "the shape is not served");
+    const size_t need = ggml_hip_attn_paged_work_size(kv_type, D, n_head, n_head_kv, n_seq, n_q, n_kv_max);
+    if (need && (!d_work || work_bytes < need)) return fail(GGML_HIP_ERR_ARG, "work buffer too small: need %zu (ggml_hip_attn_paged_work_size)", need);
+    attn_args a;
+    a.kv_type = kv_type; a.D = D; a.n_head = n_head; a.n_head_kv = n_head_kv; a.causal = causal != 0;
+    a.q = d_q; a.ldq_tok = ldq_tok; a.ldq_head = ldq_head;
+    a.k = d_k; a.v = d_v; a.nb_pos = nb_pos; a.nb_head = nb_head;
+    a.n_q = n_q; a.n_kv = 0; a.d_n_kv = nullptr; a.n_kv_max = n_kv_max;
+    a.scale = scale;
+    a.dst = d_dst; a.ldd_tok = ldd_tok; a.ldd_head = ldd_head;
+    a.work = need ? (void *)(((uintptr_t)d_work + ATTN_ALIGN - 1) / ATTN_ALIGN * ATTN_ALIGN) : nullptr;
+    if (on) HIP_TRY(launch_attn_paged_ex(p, a, n_seq, pg, len_bias, vo, (hipStream_t)stream));
+    else HIP_TRY(launch_attn_paged(p, a, n_seq, pg, len_bias, (hipStream_t)stream));
+    return GGML_HIP_OK;
+}
+
+// the plan of the public struct
+void put_plan(const attn_plan &p, ggml_hip_attn_plan_t *out) {
+    out->form = p.form; out->chunk = p.chunk; out->q_tile = p.q_tile; out->launches = p.launches;
+    out->n_chunks = p.n_chunks; out->workgroups = p.wgs;
 }
 
 }  // namespace
@@ -107,33 +201,33 @@ int ggml_hip_attn_dev(int kv_type, const float *d_q, int64_t ldq_tok, int64_t ld
                       void *d_work, size_t work_bytes, void *stream) {
     if (d_mask || d_sinks || max_bias != 0.0f || logit_softcap != 0.0f)
         return fail(GGML_HIP_ERR_ARG, "a mask tensor, ALiBi (max_bias), a soft-cap and sinks are not served: pass NULL / 0");
-    int rc = check_attn_shape(kv_type, D, n_head, n_head_kv, n_q, n_kv_max);
+    return attn_run(kv_type, d_q, ldq_tok, ldq_head, d_k, d_v, nb_pos, nb_head, n_head, n_head_kv, D, n_q, n_kv, d_n_kv, n_kv_max, causal, scale, false, attn_var{},
+                    d_dst, ldd_tok, ldd_head, d_work, work_bytes, stream);
+}
+
+int ggml_hip_attn_ex_plan(int kv_type, int D, int n_head, int n_head_kv, int64_t n_q, int64_t n_kv_max, const ggml_hip_attn_opts_t *opts,
+                          ggml_hip_attn_plan_t *out) {
+    if (!out) return fail(GGML_HIP_ERR_ARG, "out is null");
+    bool on; attn_var vo;
+    int rc = check_attn_opts(opts, 1, 1.0f, &on, &vo);               // (a plan has no causal flag: the entry refuses a window without it)
     if (rc) return rc;
-    if (!d_n_kv && (n_kv < 0 || n_kv > n_kv_max)) return fail(GGML_HIP_ERR_ARG, "n_kv %lld outside [0, n_kv_max %lld]", (long long)n_kv, (long long)n_kv_max);
-    const int64_t row_bytes = kv_type == GGML_TYPE_Q8_0 ? D / QK * (int64_t)sizeof(block_q8_0) : D * 2;
-    if (ldq_tok % 4 != 0 || ldq_head % 4 != 0 || ldd_tok % 4 != 0 || ldd_head % 4 != 0 || ldq_head < D || ldd_head < D || ldq_tok < 0 || ldd_tok < 0 ||
-        (n_q > 1 && (ldq_tok < D || ldd_tok < D)))
-        return fail(GGML_HIP_ERR_SHAPE, "the strides of q and dst are multiples of 4 elements, at least D");
-    if (nb_pos % 16 != 0 || nb_head % 16 != 0 || nb_pos < row_bytes || nb_head < row_bytes)
-        return fail(GGML_HIP_ERR_SHAPE, "nb_pos %lld, nb_head %lld: multiples of 16 bytes, at least the %lld bytes of a row", (long long)nb_pos, (long long)nb_head,
-                    (long long)row_bytes);
-    if (n_q == 0) return GGML_HIP_OK;
-    if (!d_q || !d_dst || (n_kv_max > 0 && (!d_k || !d_v))) return fail(GGML_HIP_ERR_ARG, "null argument");
-    if ((((uintptr_t)d_q | (uintptr_t)d_dst | (uintptr_t)d_k | (uintptr_t)d_v) & 15) != 0) return fail(GGML_HIP_ERR_SHAPE, "q, dst, K and V must be 16-byte aligned");
-    const attn_plan p = plan_attn(kv_type, D, n_head, n_head_kv, n_q, n_kv_max);
+    rc = check_attn_shape(kv_type, D, n_head, n_head_kv, n_q, n_kv_max);
+    if (rc) return rc;
+    if (n_q == 0) { *out = ggml_hip_attn_plan_t{}; out->chunk = ATTN_CHUNK; return GGML_HIP_OK; }
+    const attn_plan p = plan_attn_ex(kv_type, D, n_head, n_head_kv, n_q, n_kv_max, vo.window);
     if (p.form == ATTN_FORM_NONE) return fail(GGML_HIP_ERR_SHAPE, "the shape is not served");
-    const size_t need = ggml_hip_attn_work_size(kv_type, D, n_head, n_head_kv, n_q, n_kv_max);
-    if (need && (!d_work || work_bytes < need)) return fail(GGML_HIP_ERR_ARG, "work buffer too small: need %zu (ggml_hip_attn_work_size)", need);
-    attn_args a;
-    a.kv_type = kv_type; a.D = D; a.n_head = n_head; a.n_head_kv = n_head_kv; a.causal = causal != 0;
-    a.q = d_q; a.ldq_tok = ldq_tok; a.ldq_head = ldq_head;
-    a.k = d_k; a.v = d_v; a.nb_pos = nb_pos; a.nb_head = nb_head;
-    a.n_q = n_q; a.n_kv = d_n_kv ? 0 : n_kv; a.d_n_kv = d_n_kv; a.n_kv_max = n_kv_max;
-    a.scale = scale;
-    a.dst = d_dst; a.ldd_tok = ldd_tok; a.ldd_head = ldd_head;
-    a.work = need ? (void *)(((uintptr_t)d_work + ATTN_ALIGN - 1) / ATTN_ALIGN * ATTN_ALIGN) : nullptr;
-    HIP_TRY(launch_attn(p, a, (hipStream_t)stream));
+    put_plan(p, out);
     return GGML_HIP_OK;
+}
+
+int ggml_hip_attn_ex_dev(int kv_type, const float *d_q, int64_t ldq_tok, int64_t ldq_head, const void *d_k, const void *d_v, int64_t nb_pos, int64_t nb_head,
+                         int n_head, int n_head_kv, int D, int64_t n_q, int64_t n_kv, const int32_t *d_n_kv, int64_t n_kv_max, int causal, float scale,
+                         const ggml_hip_attn_opts_t *opts, float *d_dst, int64_t ldd_tok, int64_t ldd_head, void *d_work, size_t work_bytes, void *stream) {
+    bool on; attn_var vo;
+    const int rc = check_attn_opts(opts, causal, scale, &on, &vo);
+    if (rc) return rc;
+    return attn_run(kv_type, d_q, ldq_tok, ldq_head, d_k, d_v, nb_pos, nb_head, n_head, n_head_kv, D, n_q, n_kv, d_n_kv, n_kv_max, causal, scale, on, vo, d_dst,
+                    ldd_tok, ldd_head, d_work, work_bytes, stream);
 }
 
 int ggml_hip_kv_store_paged_dev(int kv_type, const float *d_src, int64_t ldx_tok, int64_t ldx_head, int n_head_kv, int D, int64_t n_seq, int64_t n_q,
@@ -181,32 +275,36 @@ int ggml_hip_attn_paged_dev(int kv_type, const float *d_q, int64_t ldq_tok, int6
                             void *stream) {
     if (d_mask || d_sinks || max_bias != 0.0f || logit_softcap != 0.0f)
         return fail(GGML_HIP_ERR_ARG, "a mask tensor, ALiBi (max_bias), a soft-cap and sinks are not served: pass NULL / 0");
-    int rc = check_attn_shape(kv_type, D, n_head, n_head_kv, n_q, n_kv_max);
+    return attn_paged_run(kv_type, d_q, ldq_tok, ldq_head, d_k, d_v, nb_page, nb_pos, nb_head, n_pages, d_pages, ld_pages, d_len, len_bias, n_seq, n_head,
+                          n_head_kv, D, n_q, n_kv_max, causal, scale, false, attn_var{}, d_dst, ldd_tok, ldd_head, d_work, work_bytes, stream);
+}
+
+int ggml_hip_attn_paged_ex_plan(int kv_type, int D, int n_head, int n_head_kv, int64_t n_seq, int64_t n_q, int64_t n_kv_max, const ggml_hip_attn_opts_t *opts,
+                                ggml_hip_attn_plan_t *out) {
+    if (!out) return fail(GGML_HIP_ERR_ARG, "out is null");
+    bool on; attn_var vo;
+    int rc = check_attn_opts(opts, 1, 1.0f, &on, &vo);
     if (rc) return rc;
-    kv_pages pg;
-    rc = check_kv_pages(kv_type, D, n_head_kv, nb_page, nb_pos, nb_head, n_pages, d_pages, ld_pages, d_len, n_seq, n_kv_max, &pg);
+    rc = check_attn_shape(kv_type, D, n_head, n_head_kv, n_q, n_kv_max);
     if (rc) return rc;
-    if (n_seq * n_q > ATTN_PAGED_MAX_ROWS || n_seq * n_q * n_head > 0x7FFFFFFF)
-        return fail(GGML_HIP_ERR_SHAPE, "n_seq * n_q %lld (<= %lld, times n_head below 2^31)", (long long)(n_seq * n_q), (long long)ATTN_PAGED_MAX_ROWS);
-    rc = check_attn_rows(D, n_seq * n_q, ldq_tok, ldq_head, ldd_tok, ldd_head);
-    if (rc) return rc;
-    if (n_q == 0) return GGML_HIP_OK;
-    if (!d_q || !d_dst || !d_k || !d_v) return fail(GGML_HIP_ERR_ARG, "null argument");
-    if ((((uintptr_t)d_q | (uintptr_t)d_dst | (uintptr_t)d_k | (uintptr_t)d_v) & 15) != 0) return fail(GGML_HIP_ERR_SHAPE, "q, dst, K and V must be 16-byte aligned");
-    const attn_plan p = plan_attn_paged(kv_type, D, n_head, n_head_kv, n_seq, n_q, n_kv_max);
-    if (p.form == ATTN_FORM_NONE) return fail(GGML_HIP_ERR_SHAPE, "the shape is not served");
-    const size_t need = ggml_hip_attn_paged_work_size(kv_type, D, n_head, n_head_kv, n_seq, n_q, n_kv_max);
-    if (need && (!d_work || work_bytes < need)) return fail(GGML_HIP_ERR_ARG, "work buffer too small: need %zu (ggml_hip_attn_paged_work_size)", need);
-    attn_args a;
-    a.kv_type = kv_type; a.D = D; a.n_head = n_head; a.n_head_kv = n_head_kv; a.causal = causal != 0;
-    a.q = d_q; a.ldq_tok = ldq_tok; a.ldq_head = ldq_head;
-    a.k = d_k; a.v = d_v; a.nb_pos = nb_pos; a.nb_head = nb_head;
-    a.n_q = n_q; a.n_kv = 0; a.d_n_kv = nullptr; a.n_kv_max = n_kv_max;
-    a.scale = scale;
-    a.dst = d_dst; a.ldd_tok = ldd_tok; a.ldd_head = ldd_head;
-    a.work = need ? (void *)(((uintptr_t)d_work + ATTN_ALIGN - 1) / ATTN_ALIGN * ATTN_ALIGN) : nullptr;
-    HIP_TRY(launch_attn_paged(p, a, n_seq, pg, len_bias, (hipStream_t)stream));
+    if (n_seq < 1 || n_seq > ATTN_PAGED_MAX_SEQ) return fail(GGML_HIP_ERR_SHAPE, "n_seq %lld (1 .. %lld)", (long long)n_seq, (long long)ATTN_PAGED_MAX_SEQ);
+    if (n_q == 0) { *out = ggml_hip_attn_plan_t{}; out->chunk = ATTN_CHUNK; return GGML_HIP_OK; }
+    const attn_plan p = plan_attn_paged_ex(kv_type, D, n_head, n_head_kv, n_seq, n_q, n_kv_max, vo.window);
+    if (p.form == ATTN_FORM_NONE)
+        return fail(GGML_HIP_ERR_SHAPE, "the shape is not served: n_seq * n_q %lld (<= %lld), times n_head below 2^31", (long long)(n_seq * n_q), (long long)ATTN_PAGED_MAX_ROWS);
+    put_plan(p, out);
     return GGML_HIP_OK;
+}
+
+int ggml_hip_attn_paged_ex_dev(int kv_type, const float *d_q, int64_t ldq_tok, int64_t ldq_head, const void *d_k, const void *d_v, int64_t nb_page, int64_t nb_pos,
+                               int64_t nb_head, int n_pages, const int32_t *d_pages, int64_t ld_pages, const int32_t *d_len, int len_bias, int64_t n_seq,
+                               int n_head, int n_head_kv, int D, int64_t n_q, int64_t n_kv_max, int causal, float scale, const ggml_hip_attn_opts_t *opts,
+                               float *d_dst, int64_t ldd_tok, int64_t ldd_head, void *d_work, size_t work_bytes, void *stream) {
+    bool on; attn_var vo;
+    const int rc = check_attn_opts(opts, causal, scale, &on, &vo);
+    if (rc) return rc;
+    return attn_paged_run(kv_type, d_q, ldq_tok, ldq_head, d_k, d_v, nb_page, nb_pos, nb_head, n_pages, d_pages, ld_pages, d_len, len_bias, n_seq, n_head,
+                          n_head_kv, D, n_q, n_kv_max, causal, scale, on, vo, d_dst, ldd_tok, ldd_head, d_work, work_bytes, stream);
 }
 
 }  // extern "C"

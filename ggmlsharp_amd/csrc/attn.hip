@@ -1,6 +1,7 @@
 // attn.hip -- attention over an F16 or Q8_0 KV cache on the device (include/ggml_hip_ext.h ggml_hip_kv_store_dev, ggml_hip_attn_dev;
-// attn.cpp has the C-ABI, plan.cpp plan_attn chooses the form from n_q alone).  Upstream's ggml_flash_attn_ext without mask tensor, ALiBi,
-// soft-cap and sinks; an EXTENSION like mul_mat_id (the reference has the op's id and no dispatch).
+// attn.cpp has the C-ABI, plan.cpp plan_attn chooses the form from n_q alone).  Upstream's ggml_flash_attn_ext without mask tensor and ALiBi;
+// a sliding window, sinks and a soft-cap are the _ex entries' (the OPTIONS block below); an EXTENSION like mul_mat_id (the reference has the
+// op's id and no dispatch).
 //
 // A cache row is (position j, kv head hk): D elements in reference block format at  base + j * nb_pos + hk * nb_head  (F16: 2 D bytes of IEEE
 // halves; Q8_0: D / 32 blocks {f32 d; int8 qs[32]} of 36 bytes).  deq(row)[i] is the half widened (exact), or (float)qs[i] * d in ONE binary32
@@ -54,6 +55,16 @@
 // the sequence in grid z (the merge: in its row index).  A workgroup whose chunk lies at or beyond n_kv[b] leaves at once; a page id outside
 // [0, n_pages) among a sequence's first ceil(n_kv[b] / 128) entries makes ALL its rows +0.0f (DECODE: the merge scans the ids; PROMPT: the
 // workgroup does before its first stage) and no address is ever formed from such an id.
+//
+// ---- OPTIONS (ggml_hip_attn_ex_dev, ggml_hip_attn_paged_ex_dev; common.h attn_var; the header's ATTENTION OPTIONS section is the statement) ----
+// The chunk bodies carry a template <bool VAR>; VAR = false IS the kernels above (every use of attn_var sits under if constexpr (VAR)), VAR = true
+// serves the six _ex kernels.  WINDOW W: row t sees lo_t <= j < hi_t, hi_t = vis(t), lo_t = max(0, hi_t - W) (window_lo); a position outside takes
+// part in nothing, a (row, chunk) without a visible position has no partial.  DECODE: the a[d] chain starts at the row's first visible position of
+// the chunk; workgroup x serves chunk c_lo + x, c_lo = lo_0 / 128 from the n_kv the kernel reads anyway, and writes work-buffer chunk x; the merge
+// walks the row's chunks lo_t / 128 .. (hi_t - 1) / 128 ascending, the first term the product.  PROMPT: the workgroup starts at the chunk of its
+// first row's lo, a wave skips the chunks wholly below its first row's lo, the element mask gains j >= lo.  SOFT-CAP: s = cap * tanhf(sc' * dot),
+// sc' = scale / cap from the host.  SINKS: sink_h joins M and the denominator only (DECODE: in the merge; PROMPT: one more online-softmax step
+// after the last chunk).  PAGED: no table entry below c_lo[b] is read; the id scans start there.
 #include "common.h"
 #include "plan.h"
 #include "kv_pack.h"     // f32_to_f16_bits, kv_pack_q8_0, kv_pack_f16: the bytes of a cache row (shared with rope.hip)
@@ -79,6 +90,9 @@ __device__ __forceinline__ int device_count(const int32_t *d_n, int host_n, int 
     n = n < 0 ? 0 : n;
     return n > n_max ? n_max : n;
 }
+
+// the first visible position of a row whose visible range ends at hi, under a window of W positions (0: none): max(0, hi - W)
+__device__ __forceinline__ int window_lo(int hi, int window) { return window > 0 && hi > window ? hi - window : 0; }
 
 // ------------------------------------------------------------------------------------------------ kv_store
 template <bool Q8>
@@ -180,10 +194,12 @@ __device__ __forceinline__ void load4(const uint8_t *row, int d4, float (&v)[4])
 // the work buffer: partial (row gr = t * n_head + h, chunk c) at ((gr * n_chunks_max) + c) * (D + 4) floats: m, l, two spare, a[D]
 // THE CHUNK BODY of the DECODE form, shared by the contiguous and the paged kernel: chunk c (j0 = 128 c < n_kv) of kv head hk, its rows at
 // kb / vb + j * nb_pos -- where the chunk lies in memory is the caller's, the arithmetic does not know.  q and work are the sequence's own.
-template <bool Q8, int D>
+// VAR (the _ex kernels): the partial goes to work-buffer chunk index wc = c - c_lo, the score may be soft-capped, and a row's visible range
+// inside the chunk is [f, n) instead of [0, n): its a[d] chain starts at f, and a chunk with no visible position writes no partial.
+template <bool Q8, int D, bool VAR>
 __device__ __forceinline__ void attn_decode_chunk(uint8_t *lds, const float *__restrict__ q, int64_t ldq_tok, int64_t ldq_head, const uint8_t *__restrict__ kb,
-                                                  const uint8_t *__restrict__ vb, int64_t nb_pos, int n_head, int G, int n_q, int n_kv, int c, int hk, int causal,
-                                                  float scale, float *__restrict__ work, int n_chunks_max) {
+                                                  const uint8_t *__restrict__ vb, int64_t nb_pos, int n_head, int G, int n_q, int n_kv, int c, int wc, int hk,
+                                                  int causal, float scale, float *__restrict__ work, int n_chunks_max, const attn_var &vo) {
     constexpr int RB = row_bytes_of<Q8>(D), ST = stage_stride<Q8>(D), PPR = RB / 8;
     uint8_t *kst = lds, *vst = lds + C * ST;
     float *qt = (float *)(lds + 2 * C * ST);                         // [DEC_RT][D]
@@ -250,7 +266,12 @@ __device__ __forceinline__ void attn_decode_chunk(uint8_t *lds, const float *__r
                 }
             }
 #pragma unroll
-            for (int i = 0; i < 4; ++i) sc[(4 * hs + i) * C + j] = scale * acc[i];
+            for (int i = 0; i < 4; ++i) {
+                float s;
+                if constexpr (VAR) s = vo.cap != 0.0f ? vo.cap * tanhf(vo.sc * acc[i]) : scale * acc[i];
+                else s = scale * acc[i];
+                sc[(4 * hs + i) * C + j] = s;
+            }
         }
         __syncthreads();
         // ---- the chunk's softmax pieces: wave w takes rows w and w + 4 of the pass ----
@@ -258,22 +279,28 @@ __device__ __forceinline__ void attn_decode_chunk(uint8_t *lds, const float *__r
         for (int k = 0; k < 2; ++k) {
             const int ri = wave + 4 * k, r = r0 + ri;
             if (r >= R) continue;                                    // (wave-uniform)
-            const int vis = visible(r / G, n_kv, n_q, causal) - j0;
+            const int hi = visible(r / G, n_kv, n_q, causal), vis = hi - j0;
             if (vis <= 0) continue;
             const int n = min(vis, C);
+            int f = 0;                                               // the row's first visible position of the chunk (wave-uniform)
+            if constexpr (VAR) {
+                f = max(window_lo(hi, vo.window) - j0, 0);
+                if (f >= n) continue;
+            }
+            const bool in0 = lane >= f && lane < n, in1 = lane + 64 >= f && lane + 64 < n;
             const float ninf = -__builtin_inff();
-            const float s0 = lane < n ? sc[ri * C + lane] : ninf, s1 = lane + 64 < n ? sc[ri * C + lane + 64] : ninf;
+            const float s0 = in0 ? sc[ri * C + lane] : ninf, s1 = in1 ? sc[ri * C + lane + 64] : ninf;
             float m = fmaxf(s0, s1);
 #pragma unroll
             for (int dd = 32; dd >= 1; dd >>= 1) m = fmaxf(m, __shfl_xor(m, dd));
-            const float p0 = lane < n ? (s0 == m ? 1.0f : expf(s0 - m)) : 0.0f, p1 = lane + 64 < n ? (s1 == m ? 1.0f : expf(s1 - m)) : 0.0f;
+            const float p0 = in0 ? (s0 == m ? 1.0f : expf(s0 - m)) : 0.0f, p1 = in1 ? (s1 == m ? 1.0f : expf(s1 - m)) : 0.0f;
             sc[ri * C + lane] = p0; sc[ri * C + lane + 64] = p1;
             float l = p0 + p1;
 #pragma unroll
             for (int dd = 32; dd >= 1; dd >>= 1) l = l + __shfl_xor(l, dd);
             if (lane == 0) {
                 const int64_t gr = (int64_t)(r / G) * n_head + hk * G + r % G;
-                float *part = work + (gr * n_chunks_max + c) * (D + 4);
+                float *part = work + (gr * n_chunks_max + wc) * (D + 4);
                 part[0] = m; part[1] = l;
             }
         }
@@ -285,23 +312,28 @@ __device__ __forceinline__ void attn_decode_chunk(uint8_t *lds, const float *__r
             for (int ri = g; ri < DEC_RT; ri += NG) {
                 const int r = r0 + ri;
                 if (r >= R) break;
-                const int vis = visible(r / G, n_kv, n_q, causal) - j0;
+                const int hi = visible(r / G, n_kv, n_q, causal), vis = hi - j0;
                 if (vis <= 0) continue;
                 const int n = min(vis, C);
+                int f = 0;
+                if constexpr (VAR) {
+                    f = max(window_lo(hi, vo.window) - j0, 0);
+                    if (f >= n) continue;
+                }
                 float v[4], a[4];
-                load4<Q8>(vst, d4, v);
-                const float pf = sc[ri * C];
+                load4<Q8>(vst + f * ST, d4, v);
+                const float pf = sc[ri * C + f];
 #pragma unroll
                 for (int i = 0; i < 4; ++i) a[i] = pf * v[i];
 #pragma unroll 4
-                for (int j = 1; j < n; ++j) {
+                for (int j = f + 1; j < n; ++j) {
                     load4<Q8>(vst + j * ST, d4, v);
                     const float p = sc[ri * C + j];
 #pragma unroll
                     for (int i = 0; i < 4; ++i) a[i] = fmaf(p, v[i], a[i]);
                 }
                 const int64_t gr = (int64_t)(r / G) * n_head + hk * G + r % G;
-                *(float4 *)(work + (gr * n_chunks_max + c) * (D + 4) + 4 + 4 * d4) = make_float4(a[0], a[1], a[2], a[3]);
+                *(float4 *)(work + (gr * n_chunks_max + wc) * (D + 4) + 4 + 4 * d4) = make_float4(a[0], a[1], a[2], a[3]);
             }
         }
         __syncthreads();                                             // (the next pass rewrites the query tile and the scores)
@@ -319,7 +351,25 @@ __global__ __launch_bounds__(256) void attn_decode_kernel(const float *__restric
     const int j0 = c * C;
     if (j0 >= n_kv) return;                                          // (the whole workgroup: no barrier was reached)
     const int64_t off = (int64_t)j0 * nb_pos + (int64_t)hk * nb_head;
-    attn_decode_chunk<Q8, D>(lds, q, ldq_tok, ldq_head, kc + off, vc + off, nb_pos, n_head, G, n_q, n_kv, c, hk, causal, scale, work, n_chunks_max);
+    attn_decode_chunk<Q8, D, false>(lds, q, ldq_tok, ldq_head, kc + off, vc + off, nb_pos, n_head, G, n_q, n_kv, c, c, hk, causal, scale, work, n_chunks_max,
+                                    attn_var{});
+}
+
+// the _ex DECODE kernel: workgroup x serves chunk c_lo + x, c_lo the chunk of row 0's first visible position, from the same clamped n_kv
+template <bool Q8, int D>
+__global__ __launch_bounds__(256) void attn_decode_ex_kernel(const float *__restrict__ q, int64_t ldq_tok, int64_t ldq_head, const uint8_t *__restrict__ kc,
+                                                             const uint8_t *__restrict__ vc, int64_t nb_pos, int64_t nb_head, int n_head, int G, int n_q,
+                                                             int n_kv_host, const int32_t *__restrict__ d_n_kv, int n_kv_max, int causal, float scale,
+                                                             float *__restrict__ work, int n_chunks_max, const attn_var vo) {
+    extern __shared__ __attribute__((aligned(16))) uint8_t lds[];
+    const int hk = blockIdx.y;
+    const int n_kv = device_count(d_n_kv, n_kv_host, n_kv_max);
+    const int c = window_lo(visible(0, n_kv, n_q, causal), vo.window) / C + (int)blockIdx.x;
+    const int j0 = c * C;
+    if (j0 >= n_kv) return;                                          // (the whole workgroup: no barrier was reached)
+    const int64_t off = (int64_t)j0 * nb_pos + (int64_t)hk * nb_head;
+    attn_decode_chunk<Q8, D, true>(lds, q, ldq_tok, ldq_head, kc + off, vc + off, nb_pos, n_head, G, n_q, n_kv, c, (int)blockIdx.x, hk, causal, scale, work,
+                                   n_chunks_max, vo);
 }
 
 // the paged DECODE kernel: grid (chunks of n_kv_max) x (kv heads) x (sequences).  The sequence's length and the chunk's page id are
@@ -339,19 +389,48 @@ __global__ __launch_bounds__(256) void attn_decode_paged_kernel(const float *__r
     if (page < 0 || page >= pg.n_pages) return;                      // (the merge writes this sequence's rows as zeros)
     const int64_t off = (int64_t)page * pg.nb_page + (int64_t)hk * nb_head;
     const int64_t row0 = (int64_t)b * n_q;                           // the sequence's first row of q and of the work buffer
-    attn_decode_chunk<Q8, D>(lds, q + row0 * ldq_tok, ldq_tok, ldq_head, kc + off, vc + off, nb_pos, n_head, G, n_q, n_kv, c, hk, causal, scale,
-                             work + row0 * n_head * n_chunks_max * (D + 4), n_chunks_max);
+    attn_decode_chunk<Q8, D, false>(lds, q + row0 * ldq_tok, ldq_tok, ldq_head, kc + off, vc + off, nb_pos, n_head, G, n_q, n_kv, c, c, hk, causal, scale,
+                                    work + row0 * n_head * n_chunks_max * (D + 4), n_chunks_max, attn_var{});
+}
+
+// the _ex paged DECODE kernel: chunk c_lo[b] + x of sequence b; table entries below c_lo[b] are never read
+template <bool Q8, int D>
+__global__ __launch_bounds__(256) void attn_decode_paged_ex_kernel(const float *__restrict__ q, int64_t ldq_tok, int64_t ldq_head, const uint8_t *__restrict__ kc,
+                                                                   const uint8_t *__restrict__ vc, int64_t nb_pos, int64_t nb_head, int n_head, int G, int n_q,
+                                                                   const kv_pages pg, int len_bias, int causal, float scale, float *__restrict__ work,
+                                                                   int n_chunks_max, const attn_var vo) {
+    extern __shared__ __attribute__((aligned(16))) uint8_t lds[];
+    const int hk = blockIdx.y, b = blockIdx.z;
+    const int n_kv = paged_count(pg, b, len_bias);
+    const int c = window_lo(visible(0, n_kv, n_q, causal), vo.window) / C + (int)blockIdx.x;
+    if (c * C >= n_kv) return;                                       // (the whole workgroup: no barrier was reached)
+    const int page = pg.pages[(int64_t)b * pg.ld_pages + c];         // (c < ceil(n_kv[b] / 128) <= ld_pages)
+    if (page < 0 || page >= pg.n_pages) return;                      // (before any address is formed from it; the merge writes zeros)
+    const int64_t off = (int64_t)page * pg.nb_page + (int64_t)hk * nb_head;
+    const int64_t row0 = (int64_t)b * n_q;
+    attn_decode_chunk<Q8, D, true>(lds, q + row0 * ldq_tok, ldq_tok, ldq_head, kc + off, vc + off, nb_pos, n_head, G, n_q, n_kv, c, (int)blockIdx.x, hk, causal,
+                                   scale, work + row0 * n_head * n_chunks_max * (D + 4), n_chunks_max, vo);
 }
 
 // the merge of one query row (t, h) whose partials start at `part`; thread d owns column d, every thread the row's (M, L)
-template <int D>
-__device__ __forceinline__ void attn_merge_row(const float *__restrict__ part, int t, int n_q, int n_kv, int causal, float *__restrict__ out) {
+// VAR: the row's chunks are lo / 128 .. (vis - 1) / 128, at work-buffer index c - c_lo (part points at index 0); head h's sink joins M and L
+template <int D, bool VAR>
+__device__ __forceinline__ void attn_merge_row(const float *__restrict__ part, int t, int n_q, int n_kv, int causal, float *__restrict__ out, int h,
+                                               const attn_var &vo) {
     const int d = threadIdx.x;
     const int vis = visible(t, n_kv, n_q, causal);
     if (vis <= 0) { *out = 0.0f; return; }
-    const int nc = (vis + C - 1) / C;                                // <= n_chunks_max: vis <= n_kv <= n_kv_max
+    int nc = (vis + C - 1) / C;                                      // <= n_chunks_max: vis <= n_kv <= n_kv_max
+    float sink = -__builtin_inff();
+    if constexpr (VAR) {
+        const int c0 = window_lo(vis, vo.window) / C, c_lo = window_lo(visible(0, n_kv, n_q, causal), vo.window) / C;
+        part += (int64_t)(c0 - c_lo) * (D + 4);                      // (c_lo <= c0: the bounds are monotone in t)
+        nc -= c0;
+        if (vo.sinks) sink = vo.sinks[h];
+    }
     float M = part[0];
     for (int c = 1; c < nc; ++c) M = fmaxf(M, part[(int64_t)c * (D + 4)]);
+    if constexpr (VAR) if (vo.sinks) M = fmaxf(M, sink);
     float L, A;
     {
         const float m = part[0], b = m == M ? 1.0f : expf(m - M);
@@ -363,6 +442,7 @@ __device__ __forceinline__ void attn_merge_row(const float *__restrict__ part, i
         const float m = p[0], b = m == M ? 1.0f : expf(m - M);
         L = fmaf(p[1], b, L); A = fmaf(p[4 + d], b, A);
     }
+    if constexpr (VAR) if (vo.sinks) L = L + (sink == M ? 1.0f : expf(sink - M));
     *out = A / L;
 }
 
@@ -373,17 +453,27 @@ __global__ __launch_bounds__(D) void attn_merge_kernel(const float *__restrict__
                                                        int64_t ldd_head) {
     const int t = blockIdx.x / n_head, h = blockIdx.x - t * n_head;
     const int n_kv = device_count(d_n_kv, n_kv_host, n_kv_max);
-    attn_merge_row<D>(work + (int64_t)blockIdx.x * n_chunks_max * (D + 4), t, n_q, n_kv, causal,
-                      dst + (int64_t)t * ldd_tok + (int64_t)h * ldd_head + threadIdx.x);
+    attn_merge_row<D, false>(work + (int64_t)blockIdx.x * n_chunks_max * (D + 4), t, n_q, n_kv, causal,
+                             dst + (int64_t)t * ldd_tok + (int64_t)h * ldd_head + threadIdx.x, h, attn_var{});
 }
 
-// 1 where one of the first ceil(n_kv / 128) entries of a sequence's table row lies outside [0, n_pages), the same answer in every thread
-// of the workgroup (NT threads; one barrier); no address is formed from an entry
+template <int D>
+__global__ __launch_bounds__(D) void attn_merge_ex_kernel(const float *__restrict__ work, int n_chunks_max, int n_head, int n_q, int n_kv_host,
+                                                          const int32_t *__restrict__ d_n_kv, int n_kv_max, int causal, float *__restrict__ dst, int64_t ldd_tok,
+                                                          int64_t ldd_head, const attn_var vo) {
+    const int t = blockIdx.x / n_head, h = blockIdx.x - t * n_head;
+    const int n_kv = device_count(d_n_kv, n_kv_host, n_kv_max);
+    attn_merge_row<D, true>(work + (int64_t)blockIdx.x * n_chunks_max * (D + 4), t, n_q, n_kv, causal,
+                            dst + (int64_t)t * ldd_tok + (int64_t)h * ldd_head + threadIdx.x, h, vo);
+}
+
+// 1 where one of the entries [first, ceil(n_kv / 128)) of a sequence's table row lies outside [0, n_pages), the same answer in every thread
+// of the workgroup (NT threads; one barrier); no address is formed from an entry.  first: 0, or the _ex kernels' c_lo (entries below it are not read)
 template <int NT>
-__device__ __forceinline__ int paged_any_invalid(const int32_t *__restrict__ row, int n_kv, int n_pages) {
+__device__ __forceinline__ int paged_any_invalid(const int32_t *__restrict__ row, int first, int n_kv, int n_pages) {
     const int needed = (n_kv + C - 1) / C;
     int bad = 0;
-    for (int c = threadIdx.x; c < needed; c += NT) {
+    for (int c = first + threadIdx.x; c < needed; c += NT) {
         const int id = row[c];
         bad |= (id < 0 || id >= n_pages) ? 1 : 0;
     }
@@ -399,8 +489,21 @@ __global__ __launch_bounds__(D) void attn_merge_paged_kernel(const float *__rest
     const int b = bt / n_q, t = bt - b * n_q;
     const int n_kv = paged_count(pg, b, len_bias);
     float *out = dst + (int64_t)bt * ldd_tok + (int64_t)h * ldd_head + threadIdx.x;
-    if (paged_any_invalid<D>(pg.pages + (int64_t)b * pg.ld_pages, n_kv, pg.n_pages)) { *out = 0.0f; return; }
-    attn_merge_row<D>(work + (int64_t)blockIdx.x * n_chunks_max * (D + 4), t, n_q, n_kv, causal, out);
+    if (paged_any_invalid<D>(pg.pages + (int64_t)b * pg.ld_pages, 0, n_kv, pg.n_pages)) { *out = 0.0f; return; }
+    attn_merge_row<D, false>(work + (int64_t)blockIdx.x * n_chunks_max * (D + 4), t, n_q, n_kv, causal, out, h, attn_var{});
+}
+
+template <int D>
+__global__ __launch_bounds__(D) void attn_merge_paged_ex_kernel(const float *__restrict__ work, int n_chunks_max, int n_head, int n_q, const kv_pages pg,
+                                                                int len_bias, int causal, float *__restrict__ dst, int64_t ldd_tok, int64_t ldd_head,
+                                                                const attn_var vo) {
+    const int bt = blockIdx.x / n_head, h = blockIdx.x - bt * n_head;
+    const int b = bt / n_q, t = bt - b * n_q;
+    const int n_kv = paged_count(pg, b, len_bias);
+    float *out = dst + (int64_t)bt * ldd_tok + (int64_t)h * ldd_head + threadIdx.x;
+    const int c_lo = window_lo(visible(0, n_kv, n_q, causal), vo.window) / C;
+    if (paged_any_invalid<D>(pg.pages + (int64_t)b * pg.ld_pages, c_lo, n_kv, pg.n_pages)) { *out = 0.0f; return; }
+    attn_merge_row<D, true>(work + (int64_t)blockIdx.x * n_chunks_max * (D + 4), t, n_q, n_kv, causal, out, h, vo);
 }
 
 // ------------------------------------------------------------------------------------------------ PROMPT form
@@ -430,11 +533,13 @@ __device__ __forceinline__ f16x8 stage_load8(const uint8_t *row, int d8) {      
 // THE BODY of the PROMPT form, shared by the contiguous and the paged kernel: 128 query rows of head h of one sequence (q and dst are the
 // sequence's own) over n_kv positions.  PAGED: chunk c lies at pool + pages[c] * nb_page (pages: the sequence's table row, its first
 // ceil(n_kv / 128) entries checked by the caller); otherwise at cache + 128 c * nb_pos.  Nothing else knows where a chunk lies.
-template <bool Q8, int D, bool PAGED>
+// VAR (the _ex kernels): a lane's visible range is [lo, vis), the workgroup starts at the chunk of its first row's lo and a wave skips the
+// chunks wholly below its first row's lo; the score may be soft-capped; head h's sink joins the denominator after the last chunk.
+template <bool Q8, int D, bool PAGED, bool VAR>
 __device__ __forceinline__ void attn_prompt_tile(uint8_t *lds, const float *__restrict__ q, int64_t ldq_tok, int64_t ldq_head, const uint8_t *__restrict__ kc,
                                                  const uint8_t *__restrict__ vc, int64_t nb_pos, int64_t nb_head, const int32_t *__restrict__ pages,
                                                  int64_t nb_page, int G, int n_q, int n_kv, int causal, float scale, float *__restrict__ dst, int64_t ldd_tok,
-                                                 int64_t ldd_head) {
+                                                 int64_t ldd_head, const attn_var &vo) {
     constexpr int KS = prompt_k_stride<D>(), VS = PROMPT_VT_STRIDE, NKS = D / 16, NDT = D / 32, NCT = C / 32;
     uint8_t *kst = lds, *vt = lds + C * KS;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, r = lane & 31, hh = lane >> 5;
@@ -444,6 +549,12 @@ __device__ __forceinline__ void attn_prompt_tile(uint8_t *lds, const float *__re
     const int vis = visible(tq, n_kv, n_q, causal);
     const int wg_vis = visible(min(q0 + 127, n_q - 1), n_kv, n_q, causal);         // vis is monotone in t: the workgroup's largest
     const int wave_vis = qw < n_q ? visible(min(qw + 31, n_q - 1), n_kv, n_q, causal) : 0;
+    int lo = 0, wave_lo = 0, c_first = 0;                            // lo is monotone in t as vis is: the first row's is the smallest
+    if constexpr (VAR) {
+        lo = window_lo(vis, vo.window);
+        wave_lo = qw < n_q ? window_lo(visible(qw, n_kv, n_q, causal), vo.window) : 0;
+        c_first = window_lo(visible(q0, n_kv, n_q, causal), vo.window) / C;
+    }
     // Q^T as the B operand: lane (query r, half hh) holds Q[tq][16 ks + 8 hh + i], rounded to f16
     f16x8 qf[NKS];
     {
@@ -463,9 +574,9 @@ __device__ __forceinline__ void attn_prompt_tile(uint8_t *lds, const float *__re
     const float ninf = -__builtin_inff();
     float m = ninf, l = 0.0f;
     const int nc = (wg_vis + C - 1) / C;
-    for (int c = 0; c < nc; ++c) {
+    for (int c = c_first; c < nc; ++c) {
         const int j0 = c * C, cnt = min(C, n_kv - j0);               // (j0 < wg_vis <= n_kv: cnt >= 1)
-        if (c > 0) __syncthreads();                                  // (every wave is done with the previous stage)
+        if (c > c_first) __syncthreads();                                  // (every wave is done with the previous stage)
         // ---- stage: K rows as they lie, V transposed; 16 bytes of f16 per item, consecutive lanes along a row ----
         {
             const int64_t off = (PAGED ? (int64_t)pages[c] * nb_page : (int64_t)j0 * nb_pos) + (int64_t)hk * nb_head;
@@ -487,6 +598,7 @@ __device__ __forceinline__ void attn_prompt_tile(uint8_t *lds, const float *__re
         }
         __syncthreads();
         if (j0 >= wave_vis) continue;                                // (wave-uniform: nothing of this chunk is visible to the wave's rows)
+        if constexpr (VAR) if (j0 + C <= wave_lo) continue;          // (the same below the window of the wave's first row)
         // ---- S^T = K Q^T: tile ct holds positions j0 + 32 ct + row(i, hh) of this lane's query ----
         f32x16 s[NCT];
 #pragma unroll
@@ -506,7 +618,9 @@ __device__ __forceinline__ void attn_prompt_tile(uint8_t *lds, const float *__re
 #pragma unroll
             for (int i = 0; i < 16; ++i) {
                 const int j = j0 + 32 * ct + (i & 3) + 8 * (i >> 2) + 4 * hh;
-                const float v = j < vis ? scale * s[ct][i] : ninf;
+                float v;
+                if constexpr (VAR) v = (j < vis && j >= lo) ? (vo.cap != 0.0f ? vo.cap * tanhf(vo.sc * s[ct][i]) : scale * s[ct][i]) : ninf;
+                else v = j < vis ? scale * s[ct][i] : ninf;
                 s[ct][i] = v;
                 cm = fmaxf(cm, v);
             }
@@ -546,6 +660,16 @@ __device__ __forceinline__ void attn_prompt_tile(uint8_t *lds, const float *__re
                 }
         }
     }
+    if constexpr (VAR) {
+        if (vo.sinks && m != ninf) {                                 // (a row with no visible position keeps l = 0 and writes +0.0f)
+            const float sink = vo.sinks[h], mn = fmaxf(m, sink), alpha = expf(m - mn);
+            l = l * alpha + expf(sink - mn);
+#pragma unroll
+            for (int dt = 0; dt < NDT; ++dt)
+#pragma unroll
+                for (int i = 0; i < 16; ++i) o[dt][i] = o[dt][i] * alpha;
+        }
+    }
     // ---- dst[tq][h][d] = O^T[d][query] / l: register i of tile dt is d = 32 dt + (i & 3) + 8 (i >> 2) + 4 hh ----
     if (qw + r < n_q) {
         float *out = dst + (int64_t)tq * ldd_tok + (int64_t)h * ldd_head;
@@ -567,23 +691,36 @@ __global__ __launch_bounds__(256) void attn_prompt_kernel(const float *__restric
                                                           int64_t ldd_tok, int64_t ldd_head) {
     extern __shared__ __attribute__((aligned(16))) uint8_t lds[];
     const int n_kv = device_count(d_n_kv, n_kv_host, n_kv_max);
-    attn_prompt_tile<Q8, D, false>(lds, q, ldq_tok, ldq_head, kc, vc, nb_pos, nb_head, nullptr, 0, G, n_q, n_kv, causal, scale, dst, ldd_tok, ldd_head);
+    attn_prompt_tile<Q8, D, false, false>(lds, q, ldq_tok, ldq_head, kc, vc, nb_pos, nb_head, nullptr, 0, G, n_q, n_kv, causal, scale, dst, ldd_tok, ldd_head,
+                                          attn_var{});
+}
+
+template <bool Q8, int D>
+__global__ __launch_bounds__(256) void attn_prompt_ex_kernel(const float *__restrict__ q, int64_t ldq_tok, int64_t ldq_head, const uint8_t *__restrict__ kc,
+                                                             const uint8_t *__restrict__ vc, int64_t nb_pos, int64_t nb_head, int G, int n_q, int n_kv_host,
+                                                             const int32_t *__restrict__ d_n_kv, int n_kv_max, int causal, float scale, float *__restrict__ dst,
+                                                             int64_t ldd_tok, int64_t ldd_head, const attn_var vo) {
+    extern __shared__ __attribute__((aligned(16))) uint8_t lds[];
+    const int n_kv = device_count(d_n_kv, n_kv_host, n_kv_max);
+    attn_prompt_tile<Q8, D, false, true>(lds, q, ldq_tok, ldq_head, kc, vc, nb_pos, nb_head, nullptr, 0, G, n_q, n_kv, causal, scale, dst, ldd_tok, ldd_head, vo);
 }
 
 // the paged PROMPT kernel: grid (query tiles) x (heads) x (sequences).  The workgroup scans its sequence's needed page ids before its first
 // stage; one invalid id and its rows are +0.0f, with no address formed from any entry.  Otherwise the body above, the chunk bases from the table.
-template <bool Q8, int D>
-__global__ __launch_bounds__(256) void attn_prompt_paged_kernel(const float *__restrict__ q, int64_t ldq_tok, int64_t ldq_head, const uint8_t *__restrict__ kc,
-                                                                const uint8_t *__restrict__ vc, int64_t nb_pos, int64_t nb_head, int G, int n_q,
-                                                                const kv_pages pg, int len_bias, int causal, float scale, float *__restrict__ dst,
-                                                                int64_t ldd_tok, int64_t ldd_head) {
-    extern __shared__ __attribute__((aligned(16))) uint8_t lds[];
+// VAR (the _ex kernel): the scan starts at c_lo[b], the chunk of the sequence's row 0's first visible position; the body reads no entry below it
+template <bool Q8, int D, bool VAR>
+__device__ __forceinline__ void attn_prompt_paged_body(uint8_t *lds, const float *__restrict__ q, int64_t ldq_tok, int64_t ldq_head, const uint8_t *__restrict__ kc,
+                                                       const uint8_t *__restrict__ vc, int64_t nb_pos, int64_t nb_head, int G, int n_q, const kv_pages &pg,
+                                                       int len_bias, int causal, float scale, float *__restrict__ dst, int64_t ldd_tok, int64_t ldd_head,
+                                                       const attn_var &vo) {
     const int b = blockIdx.z;
     const int n_kv = paged_count(pg, b, len_bias);
     const int32_t *pages = pg.pages + (int64_t)b * pg.ld_pages;
     const int64_t row0 = (int64_t)b * n_q;
     float *dst_b = dst + row0 * ldd_tok;
-    if (paged_any_invalid<256>(pages, n_kv, pg.n_pages)) {
+    int c_lo = 0;
+    if constexpr (VAR) c_lo = window_lo(visible(0, n_kv, n_q, causal), vo.window) / C;
+    if (paged_any_invalid<256>(pages, c_lo, n_kv, pg.n_pages)) {
         const int lane = threadIdx.x & 63, tq = blockIdx.x * 128 + 32 * (threadIdx.x >> 6) + (lane & 31), hh = lane >> 5;
         if (tq < n_q) {
             float *out = dst_b + (int64_t)tq * ldd_tok + (int64_t)blockIdx.y * ldd_head;
@@ -592,8 +729,26 @@ __global__ __launch_bounds__(256) void attn_prompt_paged_kernel(const float *__r
         }
         return;
     }
-    attn_prompt_tile<Q8, D, true>(lds, q + row0 * ldq_tok, ldq_tok, ldq_head, kc, vc, nb_pos, nb_head, pages, pg.nb_page, G, n_q, n_kv, causal, scale, dst_b,
-                                  ldd_tok, ldd_head);
+    attn_prompt_tile<Q8, D, true, VAR>(lds, q + row0 * ldq_tok, ldq_tok, ldq_head, kc, vc, nb_pos, nb_head, pages, pg.nb_page, G, n_q, n_kv, causal, scale, dst_b,
+                                       ldd_tok, ldd_head, vo);
+}
+
+template <bool Q8, int D>
+__global__ __launch_bounds__(256) void attn_prompt_paged_kernel(const float *__restrict__ q, int64_t ldq_tok, int64_t ldq_head, const uint8_t *__restrict__ kc,
+                                                                const uint8_t *__restrict__ vc, int64_t nb_pos, int64_t nb_head, int G, int n_q,
+                                                                const kv_pages pg, int len_bias, int causal, float scale, float *__restrict__ dst,
+                                                                int64_t ldd_tok, int64_t ldd_head) {
+    extern __shared__ __attribute__((aligned(16))) uint8_t lds[];
+    attn_prompt_paged_body<Q8, D, false>(lds, q, ldq_tok, ldq_head, kc, vc, nb_pos, nb_head, G, n_q, pg, len_bias, causal, scale, dst, ldd_tok, ldd_head, attn_var{});
+}
+
+template <bool Q8, int D>
+__global__ __launch_bounds__(256) void attn_prompt_paged_ex_kernel(const float *__restrict__ q, int64_t ldq_tok, int64_t ldq_head, const uint8_t *__restrict__ kc,
+                                                                   const uint8_t *__restrict__ vc, int64_t nb_pos, int64_t nb_head, int G, int n_q,
+                                                                   const kv_pages pg, int len_bias, int causal, float scale, float *__restrict__ dst,
+                                                                   int64_t ldd_tok, int64_t ldd_head, const attn_var vo) {
+    extern __shared__ __attribute__((aligned(16))) uint8_t lds[];
+    attn_prompt_paged_body<Q8, D, true>(lds, q, ldq_tok, ldq_head, kc, vc, nb_pos, nb_head, G, n_q, pg, len_bias, causal, scale, dst, ldd_tok, ldd_head, vo);
 }
 
 template <bool Q8, int D> constexpr int decode_lds() { return 2 * C * stage_stride<Q8>(D) + DEC_RT * D * 4 + DEC_RT * C * 4; }
@@ -626,6 +781,79 @@ hipError_t launch_kv_store_paged(int kv_type, const float *src, int64_t ldx_tok,
 }
 
 // the grids are the plan's: DECODE pl.n_chunks x kv heads x sequences and one merge workgroup per row; PROMPT query tiles x heads x sequences
+// the _ex launches: the same grids from plan_attn_ex / plan_attn_paged_ex (a windowed DECODE grid follows the window), the _ex kernels, vo by value
+hipError_t launch_attn_paged_ex(const attn_plan &pl, const attn_args &a, int64_t n_seq, const kv_pages &pg, int len_bias, const attn_var &vo, hipStream_t st) {
+    const bool q8 = a.kv_type == GGML_TYPE_Q8_0;
+    const int G = a.n_head / a.n_head_kv;
+    const uint8_t *kc = (const uint8_t *)a.k, *vc = (const uint8_t *)a.v;
+    if (pl.form == ATTN_FORM_DECODE) {
+        const dim3 grid((unsigned)pl.n_chunks, (unsigned)a.n_head_kv, (unsigned)n_seq);
+        float *work = (float *)a.work;
+#define DECODE(Q, DD)                                                                                                                                 \
+    do {                                                                                                                                              \
+        if (pl.n_chunks > 0) {                                                                                                                        \
+            hipError_t e = launch_lds(kfn<attn_decode_paged_ex_kernel<Q, DD>>, grid, dim3(256), (size_t)decode_lds<Q, DD>(), decode_lds<Q, DD>(), st, a.q, \
+                                      a.ldq_tok, a.ldq_head, kc, vc, a.nb_pos, a.nb_head, a.n_head, G, (int)a.n_q, pg, len_bias, a.causal, a.scale, work, \
+                                      (int)pl.n_chunks, vo);                                                                                          \
+            if (e != hipSuccess) return e;                                                                                                            \
+        }                                                                                                                                             \
+        attn_merge_paged_ex_kernel<DD><<<dim3((unsigned)(n_seq * a.n_q * a.n_head)), DD, 0, st>>>(work, (int)pl.n_chunks, a.n_head, (int)a.n_q, pg, len_bias, \
+                                                                                                 a.causal, a.dst, a.ldd_tok, a.ldd_head, vo);         \
+    } while (0)
+        if (q8 && a.D == 64) DECODE(true, 64);
+        else if (q8) DECODE(true, 128);
+        else if (a.D == 64) DECODE(false, 64);
+        else DECODE(false, 128);
+#undef DECODE
+        return hipGetLastError();
+    }
+    const dim3 grid((unsigned)((a.n_q + 127) / 128), (unsigned)a.n_head, (unsigned)n_seq);
+#define PROMPT(Q, DD)                                                                                                                                  \
+    return launch_lds(kfn<attn_prompt_paged_ex_kernel<Q, DD>>, grid, dim3(256), (size_t)prompt_lds<DD>(), prompt_lds<DD>(), st, a.q, a.ldq_tok, a.ldq_head, \
+                      kc, vc, a.nb_pos, a.nb_head, G, (int)a.n_q, pg, len_bias, a.causal, a.scale, a.dst, a.ldd_tok, a.ldd_head, vo)
+    if (q8 && a.D == 64) PROMPT(true, 64);
+    else if (q8) PROMPT(true, 128);
+    else if (a.D == 64) PROMPT(false, 64);
+    else PROMPT(false, 128);
+#undef PROMPT
+}
+
+hipError_t launch_attn_ex(const attn_plan &pl, const attn_args &a, const attn_var &vo, hipStream_t st) {
+    const bool q8 = a.kv_type == GGML_TYPE_Q8_0;
+    const int G = a.n_head / a.n_head_kv;
+    const uint8_t *kc = (const uint8_t *)a.k, *vc = (const uint8_t *)a.v;
+    if (pl.form == ATTN_FORM_DECODE) {
+        const dim3 grid((unsigned)pl.n_chunks, (unsigned)a.n_head_kv);
+        float *work = (float *)a.work;
+#define DECODE(Q, DD)                                                                                                                                 \
+    do {                                                                                                                                              \
+        if (pl.n_chunks > 0) {                                                                                                                        \
+            hipError_t e = launch_lds(kfn<attn_decode_ex_kernel<Q, DD>>, grid, dim3(256), (size_t)decode_lds<Q, DD>(), decode_lds<Q, DD>(), st, a.q,   \
+                                      a.ldq_tok, a.ldq_head, kc, vc, a.nb_pos, a.nb_head, a.n_head, G, (int)a.n_q, (int)a.n_kv, a.d_n_kv, (int)a.n_kv_max, \
+                                      a.causal, a.scale, work, (int)pl.n_chunks, vo);                                                                 \
+            if (e != hipSuccess) return e;                                                                                                            \
+        }                                                                                                                                             \
+        attn_merge_ex_kernel<DD><<<dim3((unsigned)(a.n_q * a.n_head)), DD, 0, st>>>(work, (int)pl.n_chunks, a.n_head, (int)a.n_q, (int)a.n_kv, a.d_n_kv, \
+                                                                                   (int)a.n_kv_max, a.causal, a.dst, a.ldd_tok, a.ldd_head, vo);      \
+    } while (0)
+        if (q8 && a.D == 64) DECODE(true, 64);
+        else if (q8) DECODE(true, 128);
+        else if (a.D == 64) DECODE(false, 64);
+        else DECODE(false, 128);
+#undef DECODE
+        return hipGetLastError();
+    }
+    const dim3 grid((unsigned)((a.n_q + 127) / 128), (unsigned)a.n_head);
+#define PROMPT(Q, DD)                                                                                                                                  \
+    return launch_lds(kfn<attn_prompt_ex_kernel<Q, DD>>, grid, dim3(256), (size_t)prompt_lds<DD>(), prompt_lds<DD>(), st, a.q, a.ldq_tok, a.ldq_head, kc, vc, \
+                      a.nb_pos, a.nb_head, G, (int)a.n_q, (int)a.n_kv, a.d_n_kv, (int)a.n_kv_max, a.causal, a.scale, a.dst, a.ldd_tok, a.ldd_head, vo)
+    if (q8 && a.D == 64) PROMPT(true, 64);
+    else if (q8) PROMPT(true, 128);
+    else if (a.D == 64) PROMPT(false, 64);
+    else PROMPT(false, 128);
+#undef PROMPT
+}
+
 hipError_t launch_attn_paged(const attn_plan &pl, const attn_args &a, int64_t n_seq, const kv_pages &pg, int len_bias, hipStream_t st) {
     const bool q8 = a.kv_type == GGML_TYPE_Q8_0;
     const int G = a.n_head / a.n_head_kv;

@@ -449,6 +449,11 @@ struct attn_args {
 hipError_t launch_kv_store(int kv_type, const float *src, int64_t ld, int64_t n_rows, int64_t row_elems, void *cache, int64_t nb_pos, int64_t n_pos_max,
                            int64_t pos0, const int32_t *d_pos0, hipStream_t st);
 hipError_t launch_attn(const attn_plan &pl, const attn_args &a, hipStream_t st);
+// The options of the _ex entries (ggml_hip_attn_ex_dev, ggml_hip_attn_paged_ex_dev), by value to the _ex kernels: sinks f32 [n_head] or null;
+// window 0 (none) or W >= 1 (row at position P sees j with P - j < W; clamped to 2^30 by the entry); cap 0 (none) or > 0 with sc = scale / cap
+struct attn_var { const float *sinks; int window; float cap, sc; };
+// pl: plan_attn_ex's (a windowed DECODE grid holds the chunks the window can touch, workgroup x serves chunk c_lo + x)
+hipError_t launch_attn_ex(const attn_plan &pl, const attn_args &a, const attn_var &vo, hipStream_t st);
 // The PAGED cache of the paged entries (ggml_hip_kv_store_paged_dev, ggml_hip_rope_kv_store_paged_dev, ggml_hip_attn_paged_dev): a pool of
 // n_pages pages of ATTN_CHUNK positions, nb_page bytes apart; entry c of sequence b's table row (ld_pages int32 apart) names the page of its
 // positions [128 c, 128 c + 128); len[b] is the positions it held before this step.  Goes to the kernels by value.
@@ -464,6 +469,8 @@ hipError_t launch_kv_store_paged(int kv_type, const float *src, int64_t ldx_tok,
 // a: k / v are the pools, n_q the rows PER SEQUENCE, q / dst [n_seq * n_q][n_head][D]; n_kv / d_n_kv are not read: n_kv[b] = clamp(len[b] + len_bias, 0, n_kv_max);
 // pl: plan_attn_paged's
 hipError_t launch_attn_paged(const attn_plan &pl, const attn_args &a, int64_t n_seq, const kv_pages &pg, int len_bias, hipStream_t st);
+// pl: plan_attn_paged_ex's; table entries below a sequence's c_lo are never read
+hipError_t launch_attn_paged_ex(const attn_plan &pl, const attn_args &a, int64_t n_seq, const kv_pages &pg, int len_bias, const attn_var &vo, hipStream_t st);
 // rope.hip: the rotation of Q / K rows (ggml_hip_rope_dev) and the rotation fused with kv_store (ggml_hip_rope_kv_store_dev; rope.cpp).
 // The per-pair constants are the HOST's (ggml_hip_rope_table) and go to the kernels by value: eff[i] for pair i < n_dims / 2, and mscale
 #define ROPE_MAX_PAIRS 128

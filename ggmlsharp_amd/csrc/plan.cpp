@@ -645,3 +645,20 @@ attn_plan plan_attn_paged(int kv_type, int D, int n_head, int n_head_kv, int64_t
     p.work_bytes *= (size_t)n_seq;
     return p;
 }
+
+// The _ex calls: the base decision; a windowed DECODE grid follows the window instead of n_kv_max (plan.h has the bound).
+attn_plan plan_attn_ex(int kv_type, int D, int n_head, int n_head_kv, int64_t n_q, int64_t n_kv_max, int64_t window) {
+    attn_plan p = plan_attn(kv_type, D, n_head, n_head_kv, n_q, n_kv_max);
+    if (p.form != ATTN_FORM_DECODE || window <= 0 || window >= n_kv_max) return p;
+    const int64_t n = cdiv(window + n_q - 1, ATTN_CHUNK) + 1;
+    if (n < p.n_chunks) { p.n_chunks = n; p.wgs = n * n_head_kv; }
+    return p;
+}
+
+attn_plan plan_attn_paged_ex(int kv_type, int D, int n_head, int n_head_kv, int64_t n_seq, int64_t n_q, int64_t n_kv_max, int64_t window) {
+    attn_plan p = plan_attn_paged(kv_type, D, n_head, n_head_kv, n_seq, n_q, n_kv_max);
+    if (p.form == ATTN_FORM_NONE) return p;
+    const attn_plan one = plan_attn_ex(kv_type, D, n_head, n_head_kv, n_q, n_kv_max, window);
+    p.n_chunks = one.n_chunks; p.wgs = one.wgs * n_seq;
+    return p;
+}

@@ -136,6 +136,12 @@ attn_plan plan_attn(int kv_type, int D, int n_head, int n_head_kv, int64_t n_q, 
 constexpr int64_t ATTN_PAGED_MAX_SEQ = 4096;
 constexpr int64_t ATTN_PAGED_MAX_ROWS = 1 << 20;
 attn_plan plan_attn_paged(int kv_type, int D, int n_head, int n_head_kv, int64_t n_seq, int64_t n_q, int64_t n_kv_max);
+// ---- the _ex entries (sliding window, sinks, soft-cap; ggml_hip_attn_ex_dev / ggml_hip_attn_paged_ex_dev) ----
+// plan_attn / plan_attn_paged unchanged but for ONE thing: a DECODE call with a window 0 < W < n_kv_max has
+// n_chunks = min(ceil(n_kv_max / 128), ceil((W + n_q - 1) / 128) + 1), the chunks the union of its rows' visible ranges can touch (the union is
+// W + n_q - 1 positions long and may start anywhere in a chunk), and wgs follows.  work_bytes stays the base plan's: the base work size serves.
+attn_plan plan_attn_ex(int kv_type, int D, int n_head, int n_head_kv, int64_t n_q, int64_t n_kv_max, int64_t window);
+attn_plan plan_attn_paged_ex(int kv_type, int D, int n_head, int n_head_kv, int64_t n_seq, int64_t n_q, int64_t n_kv_max, int64_t window);
 // the K1 image for (type, K, N) with no weight at hand (no M: the exception cannot apply)
 int plan_image_kind(int type, int64_t K, int64_t N);
 // thread-local test switch (ggml_hip_debug_force_gemm): 0 auto, 1 int8, 2 f16, 3 MX

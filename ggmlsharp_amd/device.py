@@ -259,11 +259,30 @@ def attn_work_size(kv_type, D, n_head, n_head_kv, n_q, n_kv_max):
     return int(lib().ggml_hip_attn_work_size(kv_type, D, n_head, n_head_kv, n_q, n_kv_max))
 
 
-def attention(kv_type, q, k, v, nb_pos, nb_head, n_head_kv, n_kv, d_n_kv=None, n_kv_max=None, causal=True, scale=None, out=None, work=None):
+def attn_opts(window=0, softcap=0.0, sinks=None):
+    """a ggml_hip_attn_opts_t (sinks: an f32 tensor [n_head] on the device, kept alive by the caller), or None when every option is off"""
+    if not window and not softcap and sinks is None:
+        return None
+    assert sinks is None or (sinks.is_cuda and sinks.dtype == torch.float32 and sinks.is_contiguous())
+    return _lib.ggml_hip_attn_opts_t(sinks.data_ptr() if sinks is not None else None, int(window), float(softcap), 0)
+
+
+def attn_ex_plan(kv_type, D, n_head, n_head_kv, n_q, n_kv_max, window=0, softcap=0.0):
+    """attn_plan under the options: a windowed DECODE call has min(ceil(n_kv_max / 128), ceil((window + n_q - 1) / 128) + 1) chunks; no device needed"""
+    out = _lib.ggml_hip_attn_plan_t()
+    opts = _lib.ggml_hip_attn_opts_t(None, int(window), float(softcap), 0)
+    check(lib().ggml_hip_attn_ex_plan(kv_type, D, n_head, n_head_kv, n_q, n_kv_max, C.byref(opts), C.byref(out)), "ggml_hip_attn_ex_plan")
+    return out
+
+
+def attention(kv_type, q, k, v, nb_pos, nb_head, n_head_kv, n_kv, d_n_kv=None, n_kv_max=None, causal=True, scale=None, out=None, work=None, window=0,
+              softcap=0.0, sinks=None):
     """out[t, h] = softmax_j(scale * q[t, h] . K[j, h / G]) V[j, h / G] over the visible j of an F16 / Q8_0 cache, on the current stream.
     q f32 [n_q, n_head, D] (last stride 1); k, v: uint8 tensors whose first byte is row (position 0, kv head 0), rows nb_pos / nb_head bytes
     apart; causal: the batch is the last n_q of the n_kv positions.  d_n_kv: an int32 tensor on the device read instead of n_kv (clamped to
-    n_kv_max, which sizes the launch; default n_kv).  scale defaults to 1 / sqrt(D)."""
+    n_kv_max, which sizes the launch; default n_kv).  scale defaults to 1 / sqrt(D).
+    window (0: none; W: a row at position P sees j with P - j < W), softcap (0: none) and sinks (f32 [n_head] on the device) go through
+    ggml_hip_attn_ex_dev; with all three off the call is ggml_hip_attn_dev as before."""
     assert q.is_cuda and q.dtype == torch.float32 and q.dim() == 3 and q.stride(2) == 1
     assert k.is_cuda and v.is_cuda and k.dtype == torch.uint8 and v.dtype == torch.uint8
     assert d_n_kv is None or (d_n_kv.is_cuda and d_n_kv.dtype == torch.int32)
@@ -277,6 +296,13 @@ def attention(kv_type, q, k, v, nb_pos, nb_head, n_head_kv, n_kv, d_n_kv=None, n
     assert out.dtype == torch.float32 and out.dim() == 3 and out.stride(2) == 1 and tuple(out.shape) == (n_q, n_head, D)
     if work is None:
         work = torch.empty(max(attn_work_size(kv_type, D, n_head, n_head_kv, n_q, n_kv_max), 16), dtype=torch.uint8, device=q.device)
+    opts = attn_opts(window, softcap, sinks)
+    if opts is not None:
+        check(lib().ggml_hip_attn_ex_dev(kv_type, C.c_void_p(q.data_ptr()), q.stride(0), q.stride(1), C.c_void_p(k.data_ptr()), C.c_void_p(v.data_ptr()), nb_pos,
+                                         nb_head, n_head, n_head_kv, D, n_q, int(n_kv), C.c_void_p(d_n_kv.data_ptr()) if d_n_kv is not None else None, n_kv_max,
+                                         int(bool(causal)), float(scale), C.byref(opts), C.c_void_p(out.data_ptr()), out.stride(0), out.stride(1),
+                                         C.c_void_p(work.data_ptr()), work.numel(), _stream()), "ggml_hip_attn_ex_dev")
+        return out
     check(lib().ggml_hip_attn_dev(kv_type, C.c_void_p(q.data_ptr()), q.stride(0), q.stride(1), C.c_void_p(k.data_ptr()), C.c_void_p(v.data_ptr()), nb_pos, nb_head,
                                   n_head, n_head_kv, D, n_q, int(n_kv), C.c_void_p(d_n_kv.data_ptr()) if d_n_kv is not None else None, n_kv_max,
                                   int(bool(causal)), float(scale), None, 0.0, 0.0, None, C.c_void_p(out.data_ptr()), out.stride(0), out.stride(1),
@@ -392,10 +418,20 @@ def attn_paged_work_size(kv_type, D, n_head, n_head_kv, n_seq, n_q, n_kv_max):
     return int(lib().ggml_hip_attn_paged_work_size(kv_type, D, n_head, n_head_kv, n_seq, n_q, n_kv_max))
 
 
-def attn_paged(pc, q, n_head_kv, len_bias=0, causal=True, scale=None, out=None, work=None):
+def attn_paged_ex_plan(kv_type, D, n_head, n_head_kv, n_seq, n_q, n_kv_max, window=0, softcap=0.0):
+    """attn_paged_plan under the options: attn_ex_plan's chunk count, the workgroups of all n_seq sequences; no device needed"""
+    out = _lib.ggml_hip_attn_plan_t()
+    opts = _lib.ggml_hip_attn_opts_t(None, int(window), float(softcap), 0)
+    check(lib().ggml_hip_attn_paged_ex_plan(kv_type, D, n_head, n_head_kv, n_seq, n_q, n_kv_max, C.byref(opts), C.byref(out)), "ggml_hip_attn_paged_ex_plan")
+    return out
+
+
+def attn_paged(pc, q, n_head_kv, len_bias=0, causal=True, scale=None, out=None, work=None, window=0, softcap=0.0, sinks=None):
     """attention of n_seq independent sequences over the paged cache pc in one call: q f32 [n_seq * n_q, n_head, D] (last stride 1), sequence b
     over its n_kv[b] = clamp(d_len[b] + len_bias, 0, n_kv_max) positions; its rows are bit for bit attention() on a contiguous copy of its cache.
-    len_bias = n_q behind a store of this step's tokens.  A sequence with n_kv 0 or an invalid needed page id returns +0.0 rows."""
+    len_bias = n_q behind a store of this step's tokens.  A sequence with n_kv 0 or an invalid needed page id returns +0.0 rows.
+    window, softcap, sinks: as attention(), through ggml_hip_attn_paged_ex_dev; under a window the table entries below a sequence's first
+    needed chunk are never read (the host may recycle those pages)."""
     assert q.is_cuda and q.dtype == torch.float32 and q.dim() == 3 and q.stride(2) == 1
     n_rows, n_head, D = q.shape
     assert n_rows % pc.n_seq == 0, "n_seq * n_q rows"
@@ -408,6 +444,13 @@ def attn_paged(pc, q, n_head_kv, len_bias=0, causal=True, scale=None, out=None, 
     if work is None:
         work = torch.empty(max(attn_paged_work_size(pc.kv_type, D, n_head, n_head_kv, pc.n_seq, n_q, pc.n_kv_max), 16), dtype=torch.uint8, device=q.device)
     nbp, nbo, nbh, n_pages, d_pages, ld_pages, d_len = pc._args()
+    opts = attn_opts(window, softcap, sinks)
+    if opts is not None:
+        check(lib().ggml_hip_attn_paged_ex_dev(pc.kv_type, C.c_void_p(q.data_ptr()), q.stride(0), q.stride(1), C.c_void_p(pc.k.data_ptr()),
+                                               C.c_void_p(pc.v.data_ptr()), nbp, nbo, nbh, n_pages, d_pages, ld_pages, d_len, int(len_bias), pc.n_seq, n_head,
+                                               n_head_kv, D, n_q, pc.n_kv_max, int(bool(causal)), float(scale), C.byref(opts), C.c_void_p(out.data_ptr()),
+                                               out.stride(0), out.stride(1), C.c_void_p(work.data_ptr()), work.numel(), _stream()), "ggml_hip_attn_paged_ex_dev")
+        return out
     check(lib().ggml_hip_attn_paged_dev(pc.kv_type, C.c_void_p(q.data_ptr()), q.stride(0), q.stride(1), C.c_void_p(pc.k.data_ptr()), C.c_void_p(pc.v.data_ptr()),
                                         nbp, nbo, nbh, n_pages, d_pages, ld_pages, d_len, int(len_bias), pc.n_seq, n_head, n_head_kv, D, n_q, pc.n_kv_max,
                                         int(bool(causal)), float(scale), None, 0.0, 0.0, None, C.c_void_p(out.data_ptr()), out.stride(0), out.stride(1),

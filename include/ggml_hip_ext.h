@@ -8,6 +8,7 @@
  *   - several devices in one process, one process per device           (ggml_hip_split_weight_*, _mul_mat_split_dev, _ipc_*, _push_columns_dev, ...)
  *   - the extension weight types: k-quants, IQ4, BF16                  (GGML_HIP_TYPE_* below; one row each in csrc/wtypes.cpp says what the library does with an id)
  *   - expert-routed products of a mixture-of-experts layer             (ggml_hip_expert_set_*, ggml_hip_mul_mat_id_*)
+ *   - attention over a KV cache, contiguous and paged, and its options  (ggml_hip_attn_dev, _attn_paged_dev; sliding window, sinks, soft-cap: _attn_ex_dev, _attn_paged_ex_dev)
  *   - TEST HOOKS (ggml_hip_debug_*): inert unless called; ggml_hip_debug_force_gemm acts on the CALLING THREAD only.
  */
 #ifndef GGML_HIP_EXT_H
@@ -676,6 +677,78 @@ int    ggml_hip_attn_paged_dev(int kv_type, const float *d_q, int64_t ldq_tok, i
                                int n_head, int n_head_kv, int D, int64_t n_q, int64_t n_kv_max,
                                int causal, float scale, const void *d_mask, float max_bias, float logit_softcap, const float *d_sinks,
                                float *d_dst, int64_t ldd_tok, int64_t ldd_head, void *d_work, size_t work_bytes, void *stream);
+
+/* ---------------- ATTENTION OPTIONS: a sliding window, attention sinks and a logit soft-cap over either cache ----------------
+ * ggml_hip_attn_dev and ggml_hip_attn_paged_dev compute softmax(scale Q K^T + causal mask) V and refuse upstream's other parameters.  The
+ * four entries below serve three of them -- what Mistral / Gemma 2, 3 / Phi-3 / gpt-oss layers need -- with NO mask tensor: the window is a
+ * number, the sinks a vector per head, the cap a number.  A mask tensor and ALiBi stay unserved everywhere: these entries have no parameter
+ * for them.  The base entries keep their signatures, their refusals and their bits.
+ *
+ * ggml_hip_attn_opts_t:  d_sinks: device f32 [n_head], 4-byte aligned, or NULL (none).  window: 0 (none), or W >= 1: the row at position P
+ * sees position j only if P - j < W (upstream's pos_q - pos_k < n_swa); needs causal != 0.  logit_softcap: 0 (none) or a finite cap > 0.
+ * reserved: 0.  REFUSED with GGML_HIP_ERR_ARG before a device is touched: window < 0; window > 0 with causal == 0; a cap that is negative
+ * or not finite; a misaligned d_sinks; reserved != 0.  A window of n_kv_max or more is accepted.
+ * EVERY RULE of the base entry holds unchanged: shapes, strides, alignment, null pointers, n_q = 0, the clamped device n_kv, the paged cache's
+ * rules, no synchronize, no allocation, capturable, no atomics.  The form follows n_q alone as ggml_hip_attn_plan decides it.  The work buffer
+ * is the BASE entry's (ggml_hip_attn_work_size / ggml_hip_attn_paged_work_size): always enough, there is no new size function.
+ * opts == NULL, or an opts with everything off, runs the base kernels and returns the base entry's bits.
+ *
+ * THE ARITHMETIC.  Everything not named here is the two forms' statement above, unchanged.
+ *   WINDOW.  With hi_t = the base entry's visible count of row t, row t sees lo_t <= j < hi_t, lo_t = max(0, hi_t - W).  A position outside
+ *     that range takes part in nothing.  A chunk with no visible position for a row writes no partial for it and the merge reads none.
+ *     DECODE: inside a chunk the a[d] chain starts at the row's first visible position (a[d] = p_f deq(V_f)[d], then fma for j ascending); the
+ *     merge runs the row's chunks lo_t / 128 .. (hi_t - 1) / 128 in ascending order with the base statement (the first chunk's term is the
+ *     product, the rest are fma).  PROMPT: a workgroup starts at the chunk of its FIRST row's lo; a wave skips the chunks wholly outside its
+ *     rows' ranges, as it skips those above the diagonal; the element mask gains j >= lo.
+ *   SOFT-CAP.  s_j = cap * tanhf(sc' * dot_j), sc' = scale / cap in ONE binary32 division on the host, tanhf the library function; it stands
+ *     where scale * acc (DECODE) / scale * S_j (PROMPT) stands in the base statement.
+ *   SINKS.  sink_h is read for the row's head and joins the DENOMINATOR only; it is neither scaled nor capped.
+ *     DECODE merge: M = max(max_c m_c, sink_h); the base chain over the chunks against that M; then L = L + (sink_h == M ? 1.0f :
+ *     expf(sink_h - M)); dst = A / L.  PROMPT, after the last chunk: mn = max(m, sink); alpha = expf(m - mn); l = l alpha + expf(sink - mn);
+ *     O = O alpha; dst = O / l.  A row with no visible position still writes +0.0f.  A sink of -inf is legal and means "none"; NaN or +inf
+ *     gives unspecified values in that head's rows and nothing else.
+ * CONSEQUENCES (the tests hold the kernels to them bit for bit, in both forms, contiguous and paged):
+ *   1. Everything off gives the base entry's bits.
+ *   2. window >= n_kv gives the bits of window = 0.
+ *   3. Every sink -inf gives the bits of d_sinks = NULL.
+ *   4. TRANSLATION BY WHOLE CHUNKS: for k <= lo_0 / 128 the windowed call over (cache, n_kv) equals the windowed call over (the cache advanced
+ *      by 128 k positions, n_kv - 128 k).  So for n_q = 1 with n_kv - W a multiple of 128 it equals the BASE entry on the advanced cache with
+ *      n_kv' = W.
+ *   5. The base entries' invariances hold: n_head, the strides, n_kv_max, where n_kv comes from, n_q within DECODE, the page assignment,
+ *      n_pages, ld_pages, nb_page, n_seq, the slot.
+ *   With q = 0, sink_h = 0 and one visible position, DECODE returns deq(V_0) / 2 bit for bit.
+ *
+ * THE GRID AND THE PAGE TABLE FOLLOW THE WINDOW (DECODE).  The chunk count of a windowed DECODE call is
+ *     min(ceil(n_kv_max / 128), ceil((W + n_q - 1) / 128) + 1)
+ * -- the chunks the union of the rows' ranges can touch; the _ex plan entries report it and the workgroups, which past the window do not grow
+ * with n_kv_max (the base entries' "size n_kv_max to the step" does not bind a windowed layer).  Workgroup x serves chunk c_lo + x,
+ * c_lo = lo_0 / 128, computed ON THE DEVICE from the same clamped n_kv (contiguous) or d_len[b] + len_bias (paged) the kernel reads anyway: a
+ * captured step keeps working while c_lo moves between replays.  The work buffer's chunk index is x and the merge walks it in the same
+ * ascending order: the bits do not change.
+ * PAGED: table entries BELOW c_lo[b] are never read and may hold anything, invalid ids included; the merge's and the PROMPT kernel's id scan
+ * covers [c_lo[b], ceil(n_kv[b] / 128)) only.  THIS IS WHAT LETS A HOST RECYCLE THE PAGES THAT SLID OUT OF A WINDOWED LAYER.  An invalid id
+ * inside that range still zeroes that sequence's rows alone; every id is checked before an address is formed from it. */
+typedef struct ggml_hip_attn_opts_t {
+    const float *d_sinks;        /* device f32 [n_head], or NULL: none */
+    int64_t      window;         /* 0: none; W >= 1: row at position P sees j with P - j < W */
+    float        logit_softcap;  /* 0: none; cap > 0 */
+    int32_t      reserved;       /* must be 0 */
+} ggml_hip_attn_opts_t;
+int    ggml_hip_attn_ex_plan(int kv_type, int D, int n_head, int n_head_kv, int64_t n_q, int64_t n_kv_max,
+                             const ggml_hip_attn_opts_t *opts, ggml_hip_attn_plan_t *out);
+int    ggml_hip_attn_ex_dev(int kv_type, const float *d_q, int64_t ldq_tok, int64_t ldq_head,
+                            const void *d_k, const void *d_v, int64_t nb_pos, int64_t nb_head,
+                            int n_head, int n_head_kv, int D, int64_t n_q, int64_t n_kv, const int32_t *d_n_kv, int64_t n_kv_max,
+                            int causal, float scale, const ggml_hip_attn_opts_t *opts,
+                            float *d_dst, int64_t ldd_tok, int64_t ldd_head, void *d_work, size_t work_bytes, void *stream);
+int    ggml_hip_attn_paged_ex_plan(int kv_type, int D, int n_head, int n_head_kv, int64_t n_seq, int64_t n_q, int64_t n_kv_max,
+                                   const ggml_hip_attn_opts_t *opts, ggml_hip_attn_plan_t *out);
+int    ggml_hip_attn_paged_ex_dev(int kv_type, const float *d_q, int64_t ldq_tok, int64_t ldq_head,
+                                  const void *d_k, const void *d_v, int64_t nb_page, int64_t nb_pos, int64_t nb_head, int n_pages,
+                                  const int32_t *d_pages, int64_t ld_pages, const int32_t *d_len, int len_bias, int64_t n_seq,
+                                  int n_head, int n_head_kv, int D, int64_t n_q, int64_t n_kv_max,
+                                  int causal, float scale, const ggml_hip_attn_opts_t *opts,
+                                  float *d_dst, int64_t ldd_tok, int64_t ldd_head, void *d_work, size_t work_bytes, void *stream);
 
 /* ---------------- THE ENDS OF A DECODE STEP: a token id -> its embedding row; the LM head's logits -> the next token id ----------------
  * Upstream's ggml_get_rows over the token-embedding matrix and its ggml_argmax / top-k -> temperature -> softmax -> top-p -> pick sampler

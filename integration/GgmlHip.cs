@@ -122,6 +122,26 @@ internal static unsafe partial class GgmlHip
         long nbHead, int nPages, int* dPages, long ldPages, int* dLen, int lenBias, long nSeq, int nHead, int nHeadKv, int d, long nQ, long nKvMax, int causal,
         float scale, void* dMask, float maxBias, float logitSoftcap, float* dSinks, float* dDst, long lddTok, long lddHead, void* dWork, nuint workBytes,
         void* stream);
+    // ... the attention OPTIONS of both caches: a sliding window (row at position P sees j with P - j < window; needs causal), attention sinks (f32
+    // [nHead] on the device, in the softmax denominator only) and a logit soft-cap (cap * tanh(scale / cap * s)); opts null or all off: the base
+    // entries' bits; the base entries' work sizes serve; a windowed decode grid follows the window, and paged table entries below it are never read
+    [StructLayout(LayoutKind.Sequential)]
+    public struct ggml_hip_attn_opts_t
+    {
+        public float* d_sinks;
+        public long window;
+        public float logit_softcap;
+        public int reserved;
+    }
+    [DllImport(Lib)] public static extern int ggml_hip_attn_ex_plan(int kvType, int d, int nHead, int nHeadKv, long nQ, long nKvMax, ggml_hip_attn_opts_t* opts, void* plan);
+    [DllImport(Lib)] public static extern int ggml_hip_attn_ex_dev(int kvType, float* dQ, long ldqTok, long ldqHead, void* dK, void* dV, long nbPos, long nbHead,
+        int nHead, int nHeadKv, int d, long nQ, long nKv, int* dNKv, long nKvMax, int causal, float scale, ggml_hip_attn_opts_t* opts,
+        float* dDst, long lddTok, long lddHead, void* dWork, nuint workBytes, void* stream);
+    [DllImport(Lib)] public static extern int ggml_hip_attn_paged_ex_plan(int kvType, int d, int nHead, int nHeadKv, long nSeq, long nQ, long nKvMax,
+        ggml_hip_attn_opts_t* opts, void* plan);
+    [DllImport(Lib)] public static extern int ggml_hip_attn_paged_ex_dev(int kvType, float* dQ, long ldqTok, long ldqHead, void* dK, void* dV, long nbPage, long nbPos,
+        long nbHead, int nPages, int* dPages, long ldPages, int* dLen, int lenBias, long nSeq, int nHead, int nHeadKv, int d, long nQ, long nKvMax, int causal,
+        float scale, ggml_hip_attn_opts_t* opts, float* dDst, long lddTok, long lddHead, void* dWork, nuint workBytes, void* stream);
     // ... the ends of a decode step (device entries, capturable, scratch from the caller): rows of a resident weight by int32 ids on the device, bit
     // for bit download + dequantize, an id outside [0, M) a row of +0; the k best logits of every row (larger first, ties to the smaller index, NaN
     // last), p = softmax((l - l0) * invTemp) over them, top-p and the pick by the caller's uniforms dU (null: no pick) -- the int32 written to dToken
