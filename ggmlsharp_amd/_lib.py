@@ -94,6 +94,12 @@ class ggml_hip_attn_opts_t(C.Structure):
 assert C.sizeof(ggml_hip_attn_opts_t) == 24
 
 
+class ggml_hip_attn_ragged_plan_t(C.Structure):
+    """include/ggml_hip_ext.h: the plan of one ragged paged attention call (csrc/plan.cpp plan_attn_ragged)"""
+    _fields_ = [("chunk", C.c_int32), ("launches", C.c_int32), ("n_chunks", C.c_int64), ("max_tiles", C.c_int64),
+                ("decode_workgroups", C.c_int64), ("merge_workgroups", C.c_int64), ("prompt_workgroups", C.c_int64), ("index_bytes", C.c_int64)]
+
+
 class ggml_hip_rope_params_t(C.Structure):
     """include/ggml_hip_ext.h: the parameters of a rotary embedding (mode 0 NORMAL, 2 NEOX)"""
     _fields_ = [("n_dims", C.c_int32), ("mode", C.c_int32), ("n_ctx_orig", C.c_int32),
@@ -255,6 +261,18 @@ HIP_SYMBOLS = {
     "ggml_hip_attn_paged_ex_dev": (C.c_int, [C.c_int, _P, C.c_int64, C.c_int64, _P, _P, C.c_int64, C.c_int64, C.c_int64, C.c_int, _P, C.c_int64, _P, C.c_int,
                                              C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int64, C.c_int64, C.c_int, C.c_float, _P, _P, C.c_int64, C.c_int64, _P,
                                              C.c_size_t, _P]),
+    # ragged paged attention: a query count per sequence on the device (d_q_start int32 [n_seq + 1], prefix sums over packed rows): the positions, the two
+    # stores, the plan, the work size, the call
+    "ggml_hip_ragged_positions_dev": (C.c_int, [_P, _P, C.c_int64, C.c_int64, _P, _P]),
+    "ggml_hip_kv_store_paged_ragged_dev": (C.c_int, [C.c_int, _P, C.c_int64, C.c_int64, C.c_int, C.c_int, C.c_int64, _P, C.c_int64, _P, C.c_int64, C.c_int64,
+                                                     C.c_int64, C.c_int, _P, C.c_int64, _P, C.c_int64, _P]),
+    "ggml_hip_rope_kv_store_paged_ragged_dev": (C.c_int, [_P, C.c_int, _P, C.c_int64, C.c_int64, C.c_int, C.c_int, C.c_int64, _P, C.c_int64, _P, _P, C.c_int64,
+                                                          C.c_int64, C.c_int64, C.c_int, _P, C.c_int64, _P, C.c_int64, _P]),
+    "ggml_hip_attn_paged_ragged_plan": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int64, C.c_int64, C.c_int64, C.c_int64, _P, _P]),
+    "ggml_hip_attn_paged_ragged_work_size": (C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int64, C.c_int64, C.c_int64, C.c_int64]),
+    "ggml_hip_attn_paged_ragged_dev": (C.c_int, [C.c_int, _P, C.c_int64, C.c_int64, _P, _P, C.c_int64, C.c_int64, C.c_int64, C.c_int, _P, C.c_int64, _P, C.c_int,
+                                                 C.c_int, C.c_int64, _P, C.c_int64, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int64, C.c_int, C.c_float, _P, _P,
+                                                 C.c_int64, C.c_int64, _P, C.c_size_t, _P]),
     # the ends of a decode step: rows of a resident weight by device ids; top-k over a vocabulary, probabilities, top-p and the pick
     "ggml_hip_get_rows_serves_for": (C.c_int, [C.c_int]),
     "ggml_hip_get_rows_dev": (C.c_int, [_P, _P, C.c_int64, _P, C.c_int64, _P]),

@@ -1,5 +1,5 @@
 // attn.cpp -- the C-ABI of include/ggml_hip_ext.h, attention over a KV cache: rows into the cache (ggml_hip_kv_store_dev), the attention
-// itself (ggml_hip_attn_dev), its plan and work size, the paged entries, and the _ex entries with a sliding window, sinks and a soft-cap
+// itself (ggml_hip_attn_dev), its plan and work size, the paged entries, the ragged entries (a query count per sequence on the device), and the _ex entries with a sliding window, sinks and a soft-cap
 // (one checked path serves an entry and its _ex twin).  The kernels and their arithmetic are attn.hip's, the form is plan.cpp's (plan_attn).
 // No set, no handle: stream-ordered launches on the current device, no synchronize, no allocation; capturable.
 #include "ctx.h"
@@ -119,6 +119,17 @@ int attn_paged_run(int kv_type, const float *d_q, int64_t ldq_tok, int64_t ldq_h
     return GGML_HIP_OK;
 }
 
+// the shape of a RAGGED call's plan and work size: plan_attn_ragged's refusals as codes
+int check_attn_ragged_shape(int kv_type, int D, int n_head, int n_head_kv, int64_t n_seq, int64_t n_tokens_max, int64_t n_dec_rows_max, int64_t n_kv_max) {
+    const int rc = check_attn_shape(kv_type, D, n_head, n_head_kv, n_tokens_max < 0 ? 0 : n_tokens_max, n_kv_max);     // (n_tokens_max <= 2^20, times n_head below 2^31)
+    if (rc) return rc;
+    if (n_seq < 1 || n_seq > ATTN_PAGED_MAX_SEQ) return fail(GGML_HIP_ERR_SHAPE, "n_seq %lld (1 .. %lld)", (long long)n_seq, (long long)ATTN_PAGED_MAX_SEQ);
+    if (n_tokens_max < 0) return fail(GGML_HIP_ERR_ARG, "n_tokens_max %lld", (long long)n_tokens_max);
+    if (n_dec_rows_max < 0 || n_dec_rows_max > n_tokens_max)
+        return fail(GGML_HIP_ERR_ARG, "n_dec_rows_max %lld outside [0, n_tokens_max %lld]", (long long)n_dec_rows_max, (long long)n_tokens_max);
+    return GGML_HIP_OK;
+}
+
 // the plan of the public struct
 void put_plan(const attn_plan &p, ggml_hip_attn_plan_t *out) {
     out->form = p.form; out->chunk = p.chunk; out->q_tile = p.q_tile; out->launches = p.launches;
@@ -151,6 +162,16 @@ int check_kv_pages(int kv_type, int D, int n_head_kv, int64_t nb_page, int64_t n
     if (!d_pages || !d_len) return fail(GGML_HIP_ERR_ARG, "d_pages and d_len must not be null");
     if ((((uintptr_t)d_pages | (uintptr_t)d_len) & 3) != 0) return fail(GGML_HIP_ERR_SHAPE, "d_pages and d_len must be 4-byte aligned");
     pg->pages = d_pages; pg->ld_pages = ld_pages; pg->len = d_len; pg->nb_page = nb_page; pg->n_pages = n_pages; pg->n_kv_max = (int)n_kv_max;
+    return GGML_HIP_OK;
+}
+
+
+int check_kv_ragged(const int32_t *d_q_start, int64_t n_seq, int64_t n_tokens_max, kv_ragged *rg) {
+    if (!d_q_start) return fail(GGML_HIP_ERR_ARG, "d_q_start must not be null");
+    if (((uintptr_t)d_q_start & 3) != 0) return fail(GGML_HIP_ERR_SHAPE, "d_q_start must be 4-byte aligned");
+    if (n_tokens_max < 0) return fail(GGML_HIP_ERR_ARG, "n_tokens_max %lld", (long long)n_tokens_max);
+    if (n_tokens_max > ATTN_PAGED_MAX_ROWS) return fail(GGML_HIP_ERR_SHAPE, "n_tokens_max %lld (<= %lld)", (long long)n_tokens_max, (long long)ATTN_PAGED_MAX_ROWS);
+    rg->q_start = d_q_start; rg->n_seq = (int)n_seq; rg->n_tokens_max = (int)n_tokens_max;      // (n_seq: check_kv_pages')
     return GGML_HIP_OK;
 }
 
@@ -305,6 +326,101 @@ int ggml_hip_attn_paged_ex_dev(int kv_type, const float *d_q, int64_t ldq_tok, i
     if (rc) return rc;
     return attn_paged_run(kv_type, d_q, ldq_tok, ldq_head, d_k, d_v, nb_page, nb_pos, nb_head, n_pages, d_pages, ld_pages, d_len, len_bias, n_seq, n_head,
                           n_head_kv, D, n_q, n_kv_max, causal, scale, on, vo, d_dst, ldd_tok, ldd_head, d_work, work_bytes, stream);
+}
+
+int ggml_hip_ragged_positions_dev(const int32_t *d_q_start, const int32_t *d_len, int64_t n_seq, int64_t n_tokens_max, int32_t *d_pos, void *stream) {
+    if (n_seq < 1 || n_seq > ATTN_PAGED_MAX_SEQ) return fail(GGML_HIP_ERR_SHAPE, "n_seq %lld (1 .. %lld)", (long long)n_seq, (long long)ATTN_PAGED_MAX_SEQ);
+    kv_ragged rg;
+    const int rc = check_kv_ragged(d_q_start, n_seq, n_tokens_max, &rg);
+    if (rc) return rc;
+    if (!d_len) return fail(GGML_HIP_ERR_ARG, "d_len must not be null");
+    if (((uintptr_t)d_len & 3) != 0) return fail(GGML_HIP_ERR_SHAPE, "d_len must be 4-byte aligned");
+    if (n_tokens_max == 0) return GGML_HIP_OK;
+    if (!d_pos) return fail(GGML_HIP_ERR_ARG, "d_pos must not be null");
+    if (((uintptr_t)d_pos & 3) != 0) return fail(GGML_HIP_ERR_SHAPE, "d_pos must be 4-byte aligned");
+    HIP_TRY(launch_ragged_positions(rg, d_len, d_pos, (hipStream_t)stream));
+    return GGML_HIP_OK;
+}
+
+int ggml_hip_kv_store_paged_ragged_dev(int kv_type, const float *d_src, int64_t ldx_tok, int64_t ldx_head, int n_head_kv, int D, int64_t n_seq,
+                                       const int32_t *d_q_start, int64_t n_tokens_max, void *d_pool, int64_t nb_page, int64_t nb_pos, int64_t nb_head, int n_pages,
+                                       const int32_t *d_pages, int64_t ld_pages, const int32_t *d_len, int64_t n_kv_max, void *stream) {
+    kv_pages pg;
+    int rc = check_kv_pages(kv_type, D, n_head_kv, nb_page, nb_pos, nb_head, n_pages, d_pages, ld_pages, d_len, n_seq, n_kv_max, &pg);
+    if (rc) return rc;
+    kv_ragged rg;
+    rc = check_kv_ragged(d_q_start, n_seq, n_tokens_max, &rg);
+    if (rc) return rc;
+    if (ldx_tok % 4 != 0 || ldx_head % 4 != 0 || ldx_head < D || ldx_tok < 0 || (n_tokens_max > 1 && ldx_tok < D))
+        return fail(GGML_HIP_ERR_SHAPE, "the strides of the rows are multiples of 4 elements, at least D");
+    if (n_tokens_max == 0) return GGML_HIP_OK;
+    if (!d_src || !d_pool) return fail(GGML_HIP_ERR_ARG, "null argument");
+    if ((((uintptr_t)d_src | (uintptr_t)d_pool) & 15) != 0) return fail(GGML_HIP_ERR_SHAPE, "d_src and d_pool must be 16-byte aligned");
+    HIP_TRY(launch_kv_store_paged_ragged(kv_type, d_src, ldx_tok, ldx_head, n_head_kv, D, rg, d_pool, nb_pos, nb_head, pg, (hipStream_t)stream));
+    return GGML_HIP_OK;
+}
+
+int ggml_hip_attn_paged_ragged_plan(int kv_type, int D, int n_head, int n_head_kv, int64_t n_seq, int64_t n_tokens_max, int64_t n_dec_rows_max, int64_t n_kv_max,
+                                    const ggml_hip_attn_opts_t *opts, ggml_hip_attn_ragged_plan_t *out) {
+    if (!out) return fail(GGML_HIP_ERR_ARG, "out is null");
+    bool on; attn_var vo;
+    int rc = check_attn_opts(opts, 1, 1.0f, &on, &vo);               // (a plan has no causal flag: the entry refuses a window without it)
+    if (rc) return rc;
+    rc = check_attn_ragged_shape(kv_type, D, n_head, n_head_kv, n_seq, n_tokens_max, n_dec_rows_max, n_kv_max);
+    if (rc) return rc;
+    const attn_ragged_plan p = plan_attn_ragged(kv_type, D, n_head, n_head_kv, n_seq, n_tokens_max, n_dec_rows_max, n_kv_max, vo.window);
+    if (!p.ok) return fail(GGML_HIP_ERR_SHAPE, "the shape is not served");
+    *out = ggml_hip_attn_ragged_plan_t{};
+    out->chunk = p.chunk; out->launches = p.launches; out->n_chunks = p.n_chunks; out->max_tiles = p.max_tiles;
+    out->decode_workgroups = p.decode_wgs; out->merge_workgroups = p.merge_wgs; out->prompt_workgroups = p.prompt_wgs;
+    out->index_bytes = (int64_t)p.part_off;
+    return GGML_HIP_OK;
+}
+
+size_t ggml_hip_attn_paged_ragged_work_size(int kv_type, int D, int n_head, int n_head_kv, int64_t n_seq, int64_t n_tokens_max, int64_t n_dec_rows_max,
+                                            int64_t n_kv_max) {
+    const attn_ragged_plan p = plan_attn_ragged(kv_type, D, n_head, n_head_kv, n_seq, n_tokens_max, n_dec_rows_max, n_kv_max, 0);
+    if (!p.ok || p.work_bytes == 0) return 0;
+    return (p.work_bytes + ATTN_ALIGN - 1) / ATTN_ALIGN * ATTN_ALIGN + ATTN_ALIGN;   // (the base is rounded up to a 256-byte boundary)
+}
+
+int ggml_hip_attn_paged_ragged_dev(int kv_type, const float *d_q, int64_t ldq_tok, int64_t ldq_head, const void *d_k, const void *d_v, int64_t nb_page,
+                                   int64_t nb_pos, int64_t nb_head, int n_pages, const int32_t *d_pages, int64_t ld_pages, const int32_t *d_len, int add_q,
+                                   int len_bias, int64_t n_seq, const int32_t *d_q_start, int64_t n_tokens_max, int64_t n_dec_rows_max, int n_head, int n_head_kv,
+                                   int D, int64_t n_kv_max, int causal, float scale, const ggml_hip_attn_opts_t *opts, float *d_dst, int64_t ldd_tok,
+                                   int64_t ldd_head, void *d_work, size_t work_bytes, void *stream) {
+    bool on; attn_var vo;
+    int rc = check_attn_opts(opts, causal, scale, &on, &vo);
+    if (rc) return rc;
+    rc = check_attn_shape(kv_type, D, n_head, n_head_kv, 0, n_kv_max);
+    if (rc) return rc;
+    kv_pages pg;
+    rc = check_kv_pages(kv_type, D, n_head_kv, nb_page, nb_pos, nb_head, n_pages, d_pages, ld_pages, d_len, n_seq, n_kv_max, &pg);
+    if (rc) return rc;
+    kv_ragged rg;
+    rc = check_kv_ragged(d_q_start, n_seq, n_tokens_max, &rg);
+    if (rc) return rc;
+    rc = check_attn_ragged_shape(kv_type, D, n_head, n_head_kv, n_seq, n_tokens_max, n_dec_rows_max, n_kv_max);
+    if (rc) return rc;
+    rc = check_attn_rows(D, n_tokens_max, ldq_tok, ldq_head, ldd_tok, ldd_head);
+    if (rc) return rc;
+    if (n_tokens_max == 0) return GGML_HIP_OK;
+    if (!d_q || !d_dst || !d_k || !d_v) return fail(GGML_HIP_ERR_ARG, "null argument");
+    if ((((uintptr_t)d_q | (uintptr_t)d_dst | (uintptr_t)d_k | (uintptr_t)d_v) & 15) != 0) return fail(GGML_HIP_ERR_SHAPE, "q, dst, K and V must be 16-byte aligned");
+    const attn_ragged_plan p = plan_attn_ragged(kv_type, D, n_head, n_head_kv, n_seq, n_tokens_max, n_dec_rows_max, n_kv_max, on ? vo.window : 0);
+    if (!p.ok) return fail(GGML_HIP_ERR_SHAPE, "the shape is not served");
+    const size_t need = ggml_hip_attn_paged_ragged_work_size(kv_type, D, n_head, n_head_kv, n_seq, n_tokens_max, n_dec_rows_max, n_kv_max);
+    if (!d_work || work_bytes < need) return fail(GGML_HIP_ERR_ARG, "work buffer too small: need %zu (ggml_hip_attn_paged_ragged_work_size)", need);
+    attn_args a;
+    a.kv_type = kv_type; a.D = D; a.n_head = n_head; a.n_head_kv = n_head_kv; a.causal = causal != 0;
+    a.q = d_q; a.ldq_tok = ldq_tok; a.ldq_head = ldq_head;
+    a.k = d_k; a.v = d_v; a.nb_pos = nb_pos; a.nb_head = nb_head;
+    a.n_q = 0; a.n_kv = 0; a.d_n_kv = nullptr; a.n_kv_max = n_kv_max;
+    a.scale = scale;
+    a.dst = d_dst; a.ldd_tok = ldd_tok; a.ldd_head = ldd_head;
+    a.work = (void *)(((uintptr_t)d_work + ATTN_ALIGN - 1) / ATTN_ALIGN * ATTN_ALIGN);
+    HIP_TRY(launch_attn_paged_ragged(p, a, rg, pg, add_q != 0, len_bias, on, vo, (hipStream_t)stream));
+    return GGML_HIP_OK;
 }
 
 }  // extern "C"

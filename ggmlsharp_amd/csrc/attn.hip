@@ -65,6 +65,11 @@
 // first row's lo, a wave skips the chunks wholly below its first row's lo, the element mask gains j >= lo.  SOFT-CAP: s = cap * tanhf(sc' * dot),
 // sc' = scale / cap from the host.  SINKS: sink_h joins M and the denominator only (DECODE: in the merge; PROMPT: one more online-softmax step
 // after the last chunk).  PAGED: no table entry below c_lo[b] is read; the id scans start there.
+//
+// ---- RAGGED (ggml_hip_attn_paged_ragged_dev, ggml_hip_kv_store_paged_ragged_dev, ggml_hip_ragged_positions_dev; common.h kv_ragged) ----
+// The paged kernels with a query count PER SEQUENCE read on the device (q_start, prefix sums over packed rows): an index launch turns q_start into row slots
+// and a tile list, and the paged DECODE, merge and PROMPT kernels take (sequence, row base, n_q) from those tables -- the same chunk bodies, so the same bits.
+// The RAGGED block below has the statement.
 #include "common.h"
 #include "plan.h"
 #include "kv_pack.h"     // f32_to_f16_bits, kv_pack_q8_0, kv_pack_f16: the bytes of a cache row (shared with rope.hip)
@@ -126,16 +131,11 @@ __device__ __forceinline__ int paged_count(const kv_pages &pg, int b, int len_bi
 // the paged store: row (b, t, hk) of [n_seq * n_q][n_head_kv][D] -> page row (len[b] + t, hk); the kv_pack.h statement of kv_store_kernel
 // behind the paged address.  Every guard stands in front of the address it protects: the table is read only for a position inside
 // [0, n_kv_max) (whose chunk index is below ld_pages, the entry's rule), the pool is addressed only with a page id inside [0, n_pages).
+// unit u of row (tok, hk) of the source rows -> its bytes in the page row of position pos of sequence b: the guards and the packing both paged
+// stores share
 template <bool Q8>
-__global__ __launch_bounds__(256) void kv_store_paged_kernel(const float *__restrict__ src, int64_t ldx_tok, int64_t ldx_head, int n_head_kv, int units_per_head,
-                                                             int64_t n_tokens, int n_q, uint8_t *__restrict__ pool, int64_t nb_pos, int64_t nb_head, const kv_pages pg) {
-    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    const int64_t per_tok = (int64_t)n_head_kv * units_per_head;
-    if (i >= n_tokens * per_tok) return;
-    const int64_t tok = i / per_tok;
-    const int r = (int)(i - tok * per_tok), hk = r / units_per_head, u = r - hk * units_per_head;
-    const int64_t b = tok / n_q;
-    const int64_t pos = (int64_t)pg.len[b] + (tok - b * n_q);
+__device__ __forceinline__ void kv_store_paged_unit(const float *__restrict__ src, int64_t ldx_tok, int64_t ldx_head, int64_t tok, int hk, int u, int64_t b,
+                                                    int64_t pos, uint8_t *__restrict__ pool, int64_t nb_pos, int64_t nb_head, const kv_pages &pg) {
     if (pos < 0 || pos >= pg.n_kv_max) return;                      // (before the table is read)
     const int page = pg.pages[b * pg.ld_pages + pos / C];
     if (page < 0 || page >= pg.n_pages) return;                     // (before any address is formed from it)
@@ -151,6 +151,44 @@ __global__ __launch_bounds__(256) void kv_store_paged_kernel(const float *__rest
         const float4 f = *(const float4 *)(x + 4 * u);
         *(uint2 *)(row + 8 * (int64_t)u) = kv_pack_f16(f);
     }
+}
+
+template <bool Q8>
+__global__ __launch_bounds__(256) void kv_store_paged_kernel(const float *__restrict__ src, int64_t ldx_tok, int64_t ldx_head, int n_head_kv, int units_per_head,
+                                                             int64_t n_tokens, int n_q, uint8_t *__restrict__ pool, int64_t nb_pos, int64_t nb_head, const kv_pages pg) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    const int64_t per_tok = (int64_t)n_head_kv * units_per_head;
+    if (i >= n_tokens * per_tok) return;
+    const int64_t tok = i / per_tok;
+    const int r = (int)(i - tok * per_tok), hk = r / units_per_head, u = r - hk * units_per_head;
+    const int64_t b = tok / n_q;
+    kv_store_paged_unit<Q8>(src, ldx_tok, ldx_head, tok, hk, u, b, (int64_t)pg.len[b] + (tok - b * n_q), pool, nb_pos, nb_head, pg);
+}
+
+// the RAGGED paged store: packed rows [n_tokens_max][n_head_kv][D], one thread per unit as above; the thread finds its row's sequence by bisection of
+// q_start (common.h ragged_find: a present sequence, the row inside it -- else nothing is read or written for the row), then the unit above
+template <bool Q8>
+__global__ __launch_bounds__(256) void kv_store_paged_ragged_kernel(const float *__restrict__ src, int64_t ldx_tok, int64_t ldx_head, int n_head_kv,
+                                                                    int units_per_head, const kv_ragged rg, uint8_t *__restrict__ pool, int64_t nb_pos,
+                                                                    int64_t nb_head, const kv_pages pg) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    const int64_t per_tok = (int64_t)n_head_kv * units_per_head;
+    if (i >= rg.n_tokens_max * per_tok) return;
+    const int64_t tok = i / per_tok;
+    const int r = (int)(i - tok * per_tok), hk = r / units_per_head, u = r - hk * units_per_head;
+    int t;
+    const int b = ragged_find(rg, tok, &t);
+    if (b < 0) return;
+    kv_store_paged_unit<Q8>(src, ldx_tok, ldx_head, tok, hk, u, b, (int64_t)pg.len[b] + t, pool, nb_pos, nb_head, pg);
+}
+
+// d_pos of the packed rows: len[b] + t for row (b, t) of a present sequence, 0 for every other row below n_tokens_max
+__global__ __launch_bounds__(256) void ragged_positions_kernel(const kv_ragged rg, const int32_t *__restrict__ len, int32_t *__restrict__ pos) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= rg.n_tokens_max) return;
+    int t;
+    const int b = ragged_find(rg, i, &t);
+    pos[i] = b < 0 ? 0 : (int32_t)((uint32_t)len[b] + (uint32_t)t);
 }
 
 // ------------------------------------------------------------------------------------------------ DECODE form
@@ -530,21 +568,21 @@ __device__ __forceinline__ f16x8 stage_load8(const uint8_t *row, int d8) {      
     }
 }
 
-// THE BODY of the PROMPT form, shared by the contiguous and the paged kernel: 128 query rows of head h of one sequence (q and dst are the
-// sequence's own) over n_kv positions.  PAGED: chunk c lies at pool + pages[c] * nb_page (pages: the sequence's table row, its first
-// ceil(n_kv / 128) entries checked by the caller); otherwise at cache + 128 c * nb_pos.  Nothing else knows where a chunk lies.
+// THE BODY of the PROMPT form, shared by the contiguous, the paged and the ragged kernel: query rows 128 tile .. 128 tile + 127 of head h of one
+// sequence (q and dst are the sequence's own; tile and h are the caller's -- its blockIdx, or the ragged kernel's tile list) over n_kv positions.
+// PAGED: chunk c lies at pool + pages[c] * nb_page (pages: the sequence's table row, its first ceil(n_kv / 128) entries checked by the caller); otherwise at cache + 128 c * nb_pos.  Nothing else knows where a chunk lies.
 // VAR (the _ex kernels): a lane's visible range is [lo, vis), the workgroup starts at the chunk of its first row's lo and a wave skips the
 // chunks wholly below its first row's lo; the score may be soft-capped; head h's sink joins the denominator after the last chunk.
 template <bool Q8, int D, bool PAGED, bool VAR>
 __device__ __forceinline__ void attn_prompt_tile(uint8_t *lds, const float *__restrict__ q, int64_t ldq_tok, int64_t ldq_head, const uint8_t *__restrict__ kc,
                                                  const uint8_t *__restrict__ vc, int64_t nb_pos, int64_t nb_head, const int32_t *__restrict__ pages,
-                                                 int64_t nb_page, int G, int n_q, int n_kv, int causal, float scale, float *__restrict__ dst, int64_t ldd_tok,
-                                                 int64_t ldd_head, const attn_var &vo) {
+                                                 int64_t nb_page, int G, int n_q, int n_kv, int tile, int h, int causal, float scale, float *__restrict__ dst,
+                                                 int64_t ldd_tok, int64_t ldd_head, const attn_var &vo) {
     constexpr int KS = prompt_k_stride<D>(), VS = PROMPT_VT_STRIDE, NKS = D / 16, NDT = D / 32, NCT = C / 32;
     uint8_t *kst = lds, *vt = lds + C * KS;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, r = lane & 31, hh = lane >> 5;
-    const int h = blockIdx.y, hk = h / G;
-    const int q0 = blockIdx.x * 128, qw = q0 + 32 * wave;             // the workgroup's and the wave's first query row
+    const int hk = h / G;
+    const int q0 = tile * 128, qw = q0 + 32 * wave;                   // the workgroup's and the wave's first query row
     const int tq = min(qw + r, n_q - 1);                             // this lane's query (a lane past n_q computes a copy and stores nothing)
     const int vis = visible(tq, n_kv, n_q, causal);
     const int wg_vis = visible(min(q0 + 127, n_q - 1), n_kv, n_q, causal);         // vis is monotone in t: the workgroup's largest
@@ -691,8 +729,8 @@ __global__ __launch_bounds__(256) void attn_prompt_kernel(const float *__restric
                                                           int64_t ldd_tok, int64_t ldd_head) {
     extern __shared__ __attribute__((aligned(16))) uint8_t lds[];
     const int n_kv = device_count(d_n_kv, n_kv_host, n_kv_max);
-    attn_prompt_tile<Q8, D, false, false>(lds, q, ldq_tok, ldq_head, kc, vc, nb_pos, nb_head, nullptr, 0, G, n_q, n_kv, causal, scale, dst, ldd_tok, ldd_head,
-                                          attn_var{});
+    attn_prompt_tile<Q8, D, false, false>(lds, q, ldq_tok, ldq_head, kc, vc, nb_pos, nb_head, nullptr, 0, G, n_q, n_kv, (int)blockIdx.x, (int)blockIdx.y, causal, scale, dst,
+                                          ldd_tok, ldd_head, attn_var{});
 }
 
 template <bool Q8, int D>
@@ -702,35 +740,35 @@ __global__ __launch_bounds__(256) void attn_prompt_ex_kernel(const float *__rest
                                                              int64_t ldd_tok, int64_t ldd_head, const attn_var vo) {
     extern __shared__ __attribute__((aligned(16))) uint8_t lds[];
     const int n_kv = device_count(d_n_kv, n_kv_host, n_kv_max);
-    attn_prompt_tile<Q8, D, false, true>(lds, q, ldq_tok, ldq_head, kc, vc, nb_pos, nb_head, nullptr, 0, G, n_q, n_kv, causal, scale, dst, ldd_tok, ldd_head, vo);
+    attn_prompt_tile<Q8, D, false, true>(lds, q, ldq_tok, ldq_head, kc, vc, nb_pos, nb_head, nullptr, 0, G, n_q, n_kv, (int)blockIdx.x, (int)blockIdx.y, causal, scale, dst,
+                                         ldd_tok, ldd_head, vo);
 }
 
 // the paged PROMPT kernel: grid (query tiles) x (heads) x (sequences).  The workgroup scans its sequence's needed page ids before its first
 // stage; one invalid id and its rows are +0.0f, with no address formed from any entry.  Otherwise the body above, the chunk bases from the table.
 // VAR (the _ex kernel): the scan starts at c_lo[b], the chunk of the sequence's row 0's first visible position; the body reads no entry below it
+// b, row0, n_q, n_kv: the sequence, its first row of q / dst, its rows and its clamped length; tile, h: the workgroup's query tile and head -- all the
+// caller's (the paged kernels: blockIdx and b * n_q; the ragged kernel: its tile list and the index tables)
 template <bool Q8, int D, bool VAR>
 __device__ __forceinline__ void attn_prompt_paged_body(uint8_t *lds, const float *__restrict__ q, int64_t ldq_tok, int64_t ldq_head, const uint8_t *__restrict__ kc,
-                                                       const uint8_t *__restrict__ vc, int64_t nb_pos, int64_t nb_head, int G, int n_q, const kv_pages &pg,
-                                                       int len_bias, int causal, float scale, float *__restrict__ dst, int64_t ldd_tok, int64_t ldd_head,
-                                                       const attn_var &vo) {
-    const int b = blockIdx.z;
-    const int n_kv = paged_count(pg, b, len_bias);
+                                                       const uint8_t *__restrict__ vc, int64_t nb_pos, int64_t nb_head, int G, int n_q, const kv_pages &pg, int b,
+                                                       int64_t row0, int n_kv, int tile, int h, int causal, float scale, float *__restrict__ dst,
+                                                       int64_t ldd_tok, int64_t ldd_head, const attn_var &vo) {
     const int32_t *pages = pg.pages + (int64_t)b * pg.ld_pages;
-    const int64_t row0 = (int64_t)b * n_q;
     float *dst_b = dst + row0 * ldd_tok;
     int c_lo = 0;
     if constexpr (VAR) c_lo = window_lo(visible(0, n_kv, n_q, causal), vo.window) / C;
     if (paged_any_invalid<256>(pages, c_lo, n_kv, pg.n_pages)) {
-        const int lane = threadIdx.x & 63, tq = blockIdx.x * 128 + 32 * (threadIdx.x >> 6) + (lane & 31), hh = lane >> 5;
+        const int lane = threadIdx.x & 63, tq = tile * 128 + 32 * (threadIdx.x >> 6) + (lane & 31), hh = lane >> 5;
         if (tq < n_q) {
-            float *out = dst_b + (int64_t)tq * ldd_tok + (int64_t)blockIdx.y * ldd_head;
+            float *out = dst_b + (int64_t)tq * ldd_tok + (int64_t)h * ldd_head;
 #pragma unroll
             for (int i = 0; i < D / 8; ++i) *(float4 *)(out + 8 * i + 4 * hh) = make_float4(0.f, 0.f, 0.f, 0.f);
         }
         return;
     }
-    attn_prompt_tile<Q8, D, true, VAR>(lds, q + row0 * ldq_tok, ldq_tok, ldq_head, kc, vc, nb_pos, nb_head, pages, pg.nb_page, G, n_q, n_kv, causal, scale, dst_b,
-                                       ldd_tok, ldd_head, vo);
+    attn_prompt_tile<Q8, D, true, VAR>(lds, q + row0 * ldq_tok, ldq_tok, ldq_head, kc, vc, nb_pos, nb_head, pages, pg.nb_page, G, n_q, n_kv, tile, h, causal, scale,
+                                       dst_b, ldd_tok, ldd_head, vo);
 }
 
 template <bool Q8, int D>
@@ -739,7 +777,9 @@ __global__ __launch_bounds__(256) void attn_prompt_paged_kernel(const float *__r
                                                                 const kv_pages pg, int len_bias, int causal, float scale, float *__restrict__ dst,
                                                                 int64_t ldd_tok, int64_t ldd_head) {
     extern __shared__ __attribute__((aligned(16))) uint8_t lds[];
-    attn_prompt_paged_body<Q8, D, false>(lds, q, ldq_tok, ldq_head, kc, vc, nb_pos, nb_head, G, n_q, pg, len_bias, causal, scale, dst, ldd_tok, ldd_head, attn_var{});
+    const int b = blockIdx.z;
+    attn_prompt_paged_body<Q8, D, false>(lds, q, ldq_tok, ldq_head, kc, vc, nb_pos, nb_head, G, n_q, pg, b, (int64_t)b * n_q, paged_count(pg, b, len_bias),
+                                         (int)blockIdx.x, (int)blockIdx.y, causal, scale, dst, ldd_tok, ldd_head, attn_var{});
 }
 
 template <bool Q8, int D>
@@ -748,7 +788,165 @@ __global__ __launch_bounds__(256) void attn_prompt_paged_ex_kernel(const float *
                                                                    const kv_pages pg, int len_bias, int causal, float scale, float *__restrict__ dst,
                                                                    int64_t ldd_tok, int64_t ldd_head, const attn_var vo) {
     extern __shared__ __attribute__((aligned(16))) uint8_t lds[];
-    attn_prompt_paged_body<Q8, D, true>(lds, q, ldq_tok, ldq_head, kc, vc, nb_pos, nb_head, G, n_q, pg, len_bias, causal, scale, dst, ldd_tok, ldd_head, vo);
+    const int b = blockIdx.z;
+    attn_prompt_paged_body<Q8, D, true>(lds, q, ldq_tok, ldq_head, kc, vc, nb_pos, nb_head, G, n_q, pg, b, (int64_t)b * n_q, paged_count(pg, b, len_bias),
+                                        (int)blockIdx.x, (int)blockIdx.y, causal, scale, dst, ldd_tok, ldd_head, vo);
+}
+
+// ------------------------------------------------------------------------------------------------ RAGGED
+// (ggml_hip_attn_paged_ragged_dev; plan.h plan_attn_ragged has the grids and the layout of the index tables, the header's RAGGED section the statement)
+// The paged kernels with each sequence's query count read on the device: launch 1 below turns q_start into the index tables, launches 2 .. 4 are the
+// paged DECODE, merge and PROMPT kernels with (sequence, row base, n_q) taken from those tables instead of (blockIdx.z, b * n_q, a host n_q) -- the
+// chunk bodies above, called with the sequence's own n_q, so a sequence's rows are bit for bit the uniform paged call's.
+constexpr int RAG_NT = 1024, RAG_PER = (int)(ATTN_PAGED_MAX_SEQ / RAG_NT);      // the index workgroup; consecutive sequences per thread
+
+// n_kv of sequence b of a ragged call: clamp(len[b] + (add_q ? n_q : 0) + len_bias, 0, n_kv_max)
+__device__ __forceinline__ int ragged_count(const kv_pages &pg, int b, int n_q, int add_q, int len_bias) {
+    const int64_t n = (int64_t)pg.len[b] + (add_q ? n_q : 0) + len_bias;
+    return (int)(n < 0 ? 0 : n > pg.n_kv_max ? pg.n_kv_max : n);
+}
+
+// LAUNCH 1, one workgroup.  Thread e owns sequences 4 e .. 4 e + 3: it reads their bounds (a sequence that is not present counts as empty and its
+// bounds are dropped here: seq[b] = (-1, 0, 0, 0)), and two exclusive scans through LDS over the threads give each sequence its first DECODE row slot
+// and its first PROMPT tile, both in ascending b.
+//   seq[b]    = (first row slot or -1, first packed row, n_q, 0)
+//   slots[s]  = (b, t) of row slot s, (-1, -1) for a slot no row has
+//   tiles[i]  = (b, tile) in ascending (b, tile); *n_tiles their count (never above max_tiles: plan.h; the clamp costs nothing)
+// WHERE THE DECODE ROWS DO NOT ALL FIT under n_dec_rows_max (never with n_dec_rows_max >= min(n_tokens_max, 8 n_seq)) the slots are not a prefix sum:
+// thread 0 walks the sequences in ascending b and gives a slot to each one that still fits behind those served before it, so a later, shorter
+// sequence is still served.  A DECODE sequence without a slot is skipped by launches 2 and 3; ITS OWNER THREAD HERE writes its rows as +0.0f.
+__global__ __launch_bounds__(RAG_NT) void attn_ragged_index_kernel(const kv_ragged rg, int n_dec_rows_max, int max_tiles, int4 *__restrict__ seq,
+                                                                   int32_t *__restrict__ n_tiles, int2 *__restrict__ tiles, int2 *__restrict__ slots,
+                                                                   float *__restrict__ dst, int64_t ldd_tok, int64_t ldd_head, int n_head, int D) {
+    __shared__ int32_t s_dec[RAG_NT], s_til[RAG_NT];
+    __shared__ int32_t s_slot[RAG_NT * RAG_PER];                     // in: a sequence's DECODE rows (0: it is not DECODE); out: its first slot or -1
+    __shared__ int32_t s_used;
+    const int e = threadIdx.x;
+    int qs[RAG_PER], nq[RAG_PER];
+    int own_d = 0, own_t = 0;
+#pragma unroll
+    for (int k = 0; k < RAG_PER; ++k) {
+        const int b = RAG_PER * e + k;
+        qs[k] = 0; nq[k] = 0;
+        if (b < rg.n_seq) {
+            const int64_t a = rg.q_start[b], z = rg.q_start[b + 1];
+            if (a >= 0 && a <= z && z <= rg.n_tokens_max) { qs[k] = (int)a; nq[k] = (int)(z - a); }
+        }
+        const int dec = nq[k] <= ATTN_DECODE_MAX_Q ? nq[k] : 0;
+        s_slot[b] = dec;
+        own_d += dec;
+        own_t += nq[k] > ATTN_DECODE_MAX_Q ? (nq[k] + 127) / 128 : 0;
+    }
+    s_dec[e] = own_d; s_til[e] = own_t;
+    __syncthreads();
+    for (int d = 1; d < RAG_NT; d <<= 1) {
+        const int vd = e >= d ? s_dec[e - d] : 0, vt = e >= d ? s_til[e - d] : 0;
+        __syncthreads();
+        s_dec[e] += vd; s_til[e] += vt;
+        __syncthreads();
+    }
+    const int total_d = s_dec[RAG_NT - 1], total_t = s_til[RAG_NT - 1];
+    if (total_d <= n_dec_rows_max) {                                 // (the same answer in every thread) every DECODE sequence fits: the prefix sum
+        int d = s_dec[e] - own_d;
+#pragma unroll
+        for (int k = 0; k < RAG_PER; ++k) {
+            const int b = RAG_PER * e + k, dec = s_slot[b];
+            s_slot[b] = dec ? d : -1;
+            d += dec;
+        }
+        if (e == 0) s_used = total_d;
+    } else if (e == 0) {
+        int used = 0;
+        for (int b = 0; b < rg.n_seq; ++b) {
+            const int dec = s_slot[b];
+            const bool fits = dec > 0 && used + dec <= n_dec_rows_max;
+            s_slot[b] = fits ? used : -1;
+            used += fits ? dec : 0;
+        }
+        s_used = used;
+    }
+    __syncthreads();
+    int tt = s_til[e] - own_t;
+#pragma unroll
+    for (int k = 0; k < RAG_PER; ++k) {
+        const int b = RAG_PER * e + k, n = nq[k];
+        if (b >= rg.n_seq) break;
+        const int slot = s_slot[b];
+        seq[b] = make_int4(slot, qs[k], n, 0);
+        if (n > ATTN_DECODE_MAX_Q) {
+            for (int j = 0; j < (n + 127) / 128; ++j, ++tt)
+                if (tt < max_tiles) tiles[tt] = make_int2(b, j);
+        } else if (slot >= 0) {
+            for (int t = 0; t < n; ++t) slots[slot + t] = make_int2(b, t);          // (slot + n <= n_dec_rows_max: it fits)
+        } else {
+            for (int t = 0; t < n; ++t)                              // a DECODE sequence without a slot: its rows (inside [0, n_tokens_max): it is present) are +0.0f
+                for (int h = 0; h < n_head; ++h) {
+                    float *out = dst + (int64_t)(qs[k] + t) * ldd_tok + (int64_t)h * ldd_head;
+                    for (int d4 = 0; d4 < D / 4; ++d4) *(float4 *)(out + 4 * d4) = make_float4(0.f, 0.f, 0.f, 0.f);
+                }
+        }
+    }
+    for (int i = s_used + e; i < n_dec_rows_max; i += RAG_NT) slots[i] = make_int2(-1, -1);
+    if (e == RAG_NT - 1) *n_tiles = total_t < max_tiles ? total_t : max_tiles;
+}
+
+// LAUNCH 2, the grid of attn_decode_paged_kernel / attn_decode_paged_ex_kernel: (chunks) x (kv heads) x (sequences).  A workgroup whose sequence is
+// not DECODE or has no slot leaves before its first barrier; otherwise those kernels' guards and the chunk body with the sequence's own n_q, its
+// rows of q from its first packed row and its partials from its first row slot.
+template <bool Q8, int D, bool VAR>
+__global__ __launch_bounds__(256) void attn_decode_ragged_kernel(const float *__restrict__ q, int64_t ldq_tok, int64_t ldq_head, const uint8_t *__restrict__ kc,
+                                                                 const uint8_t *__restrict__ vc, int64_t nb_pos, int64_t nb_head, int n_head, int G,
+                                                                 const kv_pages pg, const int4 *__restrict__ seq, int add_q, int len_bias, int causal, float scale,
+                                                                 float *__restrict__ work, int n_chunks_max, const attn_var vo) {
+    extern __shared__ __attribute__((aligned(16))) uint8_t lds[];
+    const int hk = blockIdx.y, b = blockIdx.z;
+    const int4 sq = seq[b];
+    if (sq.x < 0) return;                                            // (the whole workgroup: no barrier was reached)
+    const int n_q = sq.z;
+    const int n_kv = ragged_count(pg, b, n_q, add_q, len_bias);
+    int c = blockIdx.x;
+    if constexpr (VAR) c += window_lo(visible(0, n_kv, n_q, causal), vo.window) / C;
+    if (c * C >= n_kv) return;
+    const int page = pg.pages[(int64_t)b * pg.ld_pages + c];         // (c < ceil(n_kv[b] / 128) <= ld_pages)
+    if (page < 0 || page >= pg.n_pages) return;                      // (before any address is formed from it; the merge writes zeros)
+    const int64_t off = (int64_t)page * pg.nb_page + (int64_t)hk * nb_head;
+    attn_decode_chunk<Q8, D, VAR>(lds, q + (int64_t)sq.y * ldq_tok, ldq_tok, ldq_head, kc + off, vc + off, nb_pos, n_head, G, n_q, n_kv, c, (int)blockIdx.x, hk,
+                                  causal, scale, work + (int64_t)sq.x * n_head * n_chunks_max * (D + 4), n_chunks_max, vo);
+}
+
+// LAUNCH 3, one workgroup per row slot and head, blockIdx.x = slot * n_head + h: the paged merge (its id scan, its zero row) for the slot's (b, t)
+template <int D, bool VAR>
+__global__ __launch_bounds__(D) void attn_merge_ragged_kernel(const float *__restrict__ work, int n_chunks_max, int n_head, const kv_pages pg,
+                                                              const int4 *__restrict__ seq, const int2 *__restrict__ slots, int add_q, int len_bias, int causal,
+                                                              float *__restrict__ dst, int64_t ldd_tok, int64_t ldd_head, const attn_var vo) {
+    const int slot = blockIdx.x / n_head, h = blockIdx.x - slot * n_head;
+    const int2 bt = slots[slot];
+    if (bt.x < 0) return;                                            // (the whole workgroup: the slot holds no row)
+    const int4 sq = seq[bt.x];
+    const int n_q = sq.z;
+    const int n_kv = ragged_count(pg, bt.x, n_q, add_q, len_bias);
+    float *out = dst + (int64_t)(sq.y + bt.y) * ldd_tok + (int64_t)h * ldd_head + threadIdx.x;
+    int c_lo = 0;
+    if constexpr (VAR) c_lo = window_lo(visible(0, n_kv, n_q, causal), vo.window) / C;
+    if (paged_any_invalid<D>(pg.pages + (int64_t)bt.x * pg.ld_pages, c_lo, n_kv, pg.n_pages)) { *out = 0.0f; return; }
+    attn_merge_row<D, VAR>(work + (int64_t)blockIdx.x * n_chunks_max * (D + 4), bt.y, n_q, n_kv, causal, out, h, vo);
+}
+
+// LAUNCH 4, grid (heads) x (tile bound): a workgroup past the list's length leaves at once, otherwise the paged PROMPT body for its (b, tile).  The heads
+// are the grid's x so that the list is walked in dispatch order: every entry past its length comes AFTER the last tile.  With the list on x the
+// empty workgroups of one head stood in front of the next head's tiles, each waiting for a whole CU's registers only to leave (measured: DESIGN.md 22).
+template <bool Q8, int D, bool VAR>
+__global__ __launch_bounds__(256) void attn_prompt_ragged_kernel(const float *__restrict__ q, int64_t ldq_tok, int64_t ldq_head, const uint8_t *__restrict__ kc,
+                                                                 const uint8_t *__restrict__ vc, int64_t nb_pos, int64_t nb_head, int G, const kv_pages pg,
+                                                                 const int4 *__restrict__ seq, const int2 *__restrict__ tiles, const int32_t *__restrict__ n_tiles,
+                                                                 int add_q, int len_bias, int causal, float scale, float *__restrict__ dst, int64_t ldd_tok,
+                                                                 int64_t ldd_head, const attn_var vo) {
+    extern __shared__ __attribute__((aligned(16))) uint8_t lds[];
+    if ((int)blockIdx.y >= *n_tiles) return;
+    const int2 bt = tiles[blockIdx.y];
+    const int4 sq = seq[bt.x];
+    attn_prompt_paged_body<Q8, D, VAR>(lds, q, ldq_tok, ldq_head, kc, vc, nb_pos, nb_head, G, sq.z, pg, bt.x, (int64_t)sq.y, ragged_count(pg, bt.x, sq.z, add_q, len_bias),
+                                       bt.y, (int)blockIdx.x, causal, scale, dst, ldd_tok, ldd_head, vo);
 }
 
 template <bool Q8, int D> constexpr int decode_lds() { return 2 * C * stage_stride<Q8>(D) + DEC_RT * D * 4 + DEC_RT * C * 4; }
@@ -777,6 +975,72 @@ hipError_t launch_kv_store_paged(int kv_type, const float *src, int64_t ldx_tok,
     const dim3 grid((unsigned)((total + 255) / 256));
     if (q8) kv_store_paged_kernel<true><<<grid, 256, 0, st>>>(src, ldx_tok, ldx_head, n_head_kv, (int)uph, n_tokens, (int)n_q, (uint8_t *)pool, nb_pos, nb_head, pg);
     else kv_store_paged_kernel<false><<<grid, 256, 0, st>>>(src, ldx_tok, ldx_head, n_head_kv, (int)uph, n_tokens, (int)n_q, (uint8_t *)pool, nb_pos, nb_head, pg);
+    return hipGetLastError();
+}
+
+hipError_t launch_ragged_positions(const kv_ragged &rg, const int32_t *len, int32_t *pos, hipStream_t st) {
+    if (rg.n_tokens_max <= 0) return hipSuccess;
+    ragged_positions_kernel<<<dim3((unsigned)((rg.n_tokens_max + 255) / 256)), 256, 0, st>>>(rg, len, pos);
+    return hipGetLastError();
+}
+
+hipError_t launch_kv_store_paged_ragged(int kv_type, const float *src, int64_t ldx_tok, int64_t ldx_head, int n_head_kv, int D, const kv_ragged &rg, void *pool,
+                                        int64_t nb_pos, int64_t nb_head, const kv_pages &pg, hipStream_t st) {
+    if (rg.n_tokens_max <= 0) return hipSuccess;
+    const bool q8 = kv_type == GGML_TYPE_Q8_0;
+    const int64_t uph = D / (q8 ? 32 : 4), total = (int64_t)rg.n_tokens_max * n_head_kv * uph;
+    if (uph <= 0 || total > (int64_t)0x7FFFFFFF * 256) return hipErrorInvalidValue;
+    const dim3 grid((unsigned)((total + 255) / 256));
+    if (q8) kv_store_paged_ragged_kernel<true><<<grid, 256, 0, st>>>(src, ldx_tok, ldx_head, n_head_kv, (int)uph, rg, (uint8_t *)pool, nb_pos, nb_head, pg);
+    else kv_store_paged_ragged_kernel<false><<<grid, 256, 0, st>>>(src, ldx_tok, ldx_head, n_head_kv, (int)uph, rg, (uint8_t *)pool, nb_pos, nb_head, pg);
+    return hipGetLastError();
+}
+
+// every grid and every offset into the work buffer is the plan's (plan_attn_ragged); a launch whose grid the bounds leave empty is not made
+hipError_t launch_attn_paged_ragged(const attn_ragged_plan &pl, const attn_args &a, const kv_ragged &rg, const kv_pages &pg, int add_q, int len_bias, bool var,
+                                    const attn_var &vo, hipStream_t st) {
+    if (pl.launches == 0) return hipSuccess;
+    const bool q8 = a.kv_type == GGML_TYPE_Q8_0;
+    const int G = a.n_head / a.n_head_kv;
+    const uint8_t *kc = (const uint8_t *)a.k, *vc = (const uint8_t *)a.v;
+    uint8_t *w = (uint8_t *)a.work;
+    int4 *seq = (int4 *)(w + pl.seq_off);
+    int32_t *n_tiles = (int32_t *)(w + pl.n_tiles_off);
+    int2 *tiles = (int2 *)(w + pl.tiles_off), *slots = (int2 *)(w + pl.slots_off);
+    float *part = (float *)(w + pl.part_off);
+    attn_ragged_index_kernel<<<dim3(1), RAG_NT, 0, st>>>(rg, (int)pl.dec_rows, (int)pl.max_tiles, seq, n_tiles, tiles, slots, a.dst, a.ldd_tok, a.ldd_head, a.n_head,
+                                                        a.D);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+#define RAGGED(Q, DD, V)                                                                                                                               \
+    do {                                                                                                                                              \
+        if (pl.decode_wgs > 0) {                                                                                                                      \
+            e = launch_lds(kfn<attn_decode_ragged_kernel<Q, DD, V>>, dim3((unsigned)pl.n_chunks, (unsigned)a.n_head_kv, (unsigned)rg.n_seq), dim3(256), \
+                           (size_t)decode_lds<Q, DD>(), decode_lds<Q, DD>(), st, a.q, a.ldq_tok, a.ldq_head, kc, vc, a.nb_pos, a.nb_head, a.n_head, G, pg, \
+                           (const int4 *)seq, add_q, len_bias, a.causal, a.scale, part, (int)pl.n_chunks, vo);                                        \
+            if (e != hipSuccess) return e;                                                                                                            \
+        }                                                                                                                                             \
+        if (pl.merge_wgs > 0)                                                                                                                         \
+            attn_merge_ragged_kernel<DD, V><<<dim3((unsigned)pl.merge_wgs), DD, 0, st>>>(part, (int)pl.n_chunks, a.n_head, pg, seq, slots, add_q, len_bias, \
+                                                                                        a.causal, a.dst, a.ldd_tok, a.ldd_head, vo);                  \
+        if (pl.prompt_wgs > 0) {                                                                                                                      \
+            e = launch_lds(kfn<attn_prompt_ragged_kernel<Q, DD, V>>, dim3((unsigned)a.n_head, (unsigned)pl.max_tiles), dim3(256), (size_t)prompt_lds<DD>(), \
+                           prompt_lds<DD>(), st, a.q, a.ldq_tok, a.ldq_head, kc, vc, a.nb_pos, a.nb_head, G, pg, (const int4 *)seq, (const int2 *)tiles, \
+                           (const int32_t *)n_tiles, add_q, len_bias, a.causal, a.scale, a.dst, a.ldd_tok, a.ldd_head, vo);                           \
+            if (e != hipSuccess) return e;                                                                                                            \
+        }                                                                                                                                             \
+    } while (0)
+#define RAGGED_V(Q, DD)                                                                                                                                \
+    do {                                                                                                                                              \
+        if (var) RAGGED(Q, DD, true);                                                                                                                 \
+        else RAGGED(Q, DD, false);                                                                                                                    \
+    } while (0)
+    if (q8 && a.D == 64) RAGGED_V(true, 64);
+    else if (q8) RAGGED_V(true, 128);
+    else if (a.D == 64) RAGGED_V(false, 64);
+    else RAGGED_V(false, 128);
+#undef RAGGED_V
+#undef RAGGED
     return hipGetLastError();
 }
 

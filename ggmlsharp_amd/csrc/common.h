@@ -471,6 +471,38 @@ hipError_t launch_kv_store_paged(int kv_type, const float *src, int64_t ldx_tok,
 hipError_t launch_attn_paged(const attn_plan &pl, const attn_args &a, int64_t n_seq, const kv_pages &pg, int len_bias, hipStream_t st);
 // pl: plan_attn_paged_ex's; table entries below a sequence's c_lo are never read
 hipError_t launch_attn_paged_ex(const attn_plan &pl, const attn_args &a, int64_t n_seq, const kv_pages &pg, int len_bias, const attn_var &vo, hipStream_t st);
+// The RAGGED batch of the ragged entries (ggml_hip_ragged_positions_dev, ggml_hip_kv_store_paged_ragged_dev, ggml_hip_rope_kv_store_paged_ragged_dev,
+// ggml_hip_attn_paged_ragged_dev): q_start int32 [n_seq + 1] on the device, prefix sums; sequence b owns the packed rows q_start[b] .. q_start[b+1] - 1 and
+// is PRESENT when 0 <= q_start[b] <= q_start[b+1] <= n_tokens_max.  Goes to the kernels by value.
+struct kv_ragged {
+    const int32_t *q_start; int n_seq; int n_tokens_max;
+};
+#ifdef __HIPCC__
+// The sequence of packed row `row` < n_tokens_max by bisection of q_start: the largest b < n_seq with q_start[b] <= row, then every guard in
+// front of what it protects -- the sequence is present and the row lies inside it.  Returns b and *t = the row's index in the sequence, or -1
+// (the row belongs to no present sequence the bisection finds: nothing is formed from its bounds).  Reads q_start[0 .. n_seq] only.
+__device__ __forceinline__ int ragged_find(const kv_ragged &rg, int64_t row, int *t) {
+    int lo = 0, hi = rg.n_seq;                                       // (q_start[lo] <= row or lo == 0; q_start[hi] > row or hi == n_seq)
+    while (hi - lo > 1) {
+        const int mid = (lo + hi) >> 1;
+        if ((int64_t)rg.q_start[mid] <= row) lo = mid; else hi = mid;
+    }
+    const int64_t qs = rg.q_start[lo], qe = rg.q_start[lo + 1];
+    if (qs < 0 || qs > qe || qe > rg.n_tokens_max || row < qs || row >= qe) return -1;
+    *t = (int)(row - qs);
+    return lo;
+}
+#endif
+// d_pos[i] = len[b] + t for row i = (b, t) of a present sequence, 0 for the other rows below n_tokens_max
+hipError_t launch_ragged_positions(const kv_ragged &rg, const int32_t *len, int32_t *pos, hipStream_t st);
+// launch_kv_store_paged over packed rows [n_tokens_max][n_head_kv][D]: the same bytes for a row of a present sequence, nothing for the others
+hipError_t launch_kv_store_paged_ragged(int kv_type, const float *src, int64_t ldx_tok, int64_t ldx_head, int n_head_kv, int D, const kv_ragged &rg, void *pool,
+                                        int64_t nb_pos, int64_t nb_head, const kv_pages &pg, hipStream_t st);
+// a: k / v are the pools, q / dst the packed rows (a.n_q, a.n_kv, a.d_n_kv are not read), a.work the 256-byte aligned work buffer with pl's index tables
+// in front; n_kv[b] = clamp(len[b] + (add_q ? n_q[b] : 0) + len_bias, 0, n_kv_max).  pl: plan_attn_ragged's, every grid and offset; var: the VAR bodies, vo theirs
+struct attn_ragged_plan;
+hipError_t launch_attn_paged_ragged(const attn_ragged_plan &pl, const attn_args &a, const kv_ragged &rg, const kv_pages &pg, int add_q, int len_bias, bool var,
+                                    const attn_var &vo, hipStream_t st);
 // rope.hip: the rotation of Q / K rows (ggml_hip_rope_dev) and the rotation fused with kv_store (ggml_hip_rope_kv_store_dev; rope.cpp).
 // The per-pair constants are the HOST's (ggml_hip_rope_table) and go to the kernels by value: eff[i] for pair i < n_dims / 2, and mscale
 #define ROPE_MAX_PAIRS 128
@@ -488,6 +520,9 @@ hipError_t launch_rope_kv_store(const rope_table &tab, const rope_args &a, int k
 // the same into a paged cache: a.n_tokens = n_seq * n_q rows, token (b, t) at position pg.len[b] + t (a.d_pos, a.pos0 and a.d_pos0 are not read)
 hipError_t launch_rope_kv_store_paged(const rope_table &tab, const rope_args &a, int kv_type, int64_t n_q, void *pool, int64_t nb_pos, int64_t nb_head,
                                       const kv_pages &pg, hipStream_t st);
+// the same over packed rows: a.n_tokens = rg.n_tokens_max, the row's sequence and position from ragged_find
+hipError_t launch_rope_kv_store_paged_ragged(const rope_table &tab, const rope_args &a, int kv_type, const kv_ragged &rg, void *pool, int64_t nb_pos,
+                                             int64_t nb_head, const kv_pages &pg, hipStream_t st);
 // gemm_q8s.hip / gemm_qmx.hip: ONE K3s launch over the tile table -- workgroup -> (weight tile group, column tile t); t >= *n_tiles leaves at once;
 // the expert's planes come from tab[tiles[t].expert], the 32 sorted rows at 32 t of the image p (K1's image of `32 * max_tiles` rows); res [rows][ldr]
 hipError_t launch_gemm_q8_small_grouped(const mm_plan &g, int type, const moe_gexpert *tab, const moe_tile *tiles, const int32_t *n_tiles, int64_t max_tiles,

@@ -49,6 +49,9 @@ mm_plan weight_plan(const ggml_hip_weight *w, int64_t N, bool one_call);   // pl
 // 1 <= n_seq <= 4096 and 0 <= n_kv_max <= 2^24; fills *pg and returns 0, or an error code before a device is touched
 int check_kv_pages(int kv_type, int D, int n_head_kv, int64_t nb_page, int64_t nb_pos, int64_t nb_head, int n_pages, const int32_t *d_pages, int64_t ld_pages,
                    const int32_t *d_len, int64_t n_seq, int64_t n_kv_max, kv_pages *pg);
+// the rules of a RAGGED batch shared by the ragged entries (attn.cpp): d_q_start not null and 4-byte aligned, 0 <= n_tokens_max <= 2^20; n_seq is
+// check_kv_pages'; fills *rg and returns 0, or an error code before a device is touched
+int check_kv_ragged(const int32_t *d_q_start, int64_t n_seq, int64_t n_tokens_max, kv_ragged *rg);
 
 struct Scratch {
     void *p = nullptr;

@@ -662,3 +662,36 @@ attn_plan plan_attn_paged_ex(int kv_type, int D, int n_head, int n_head_kv, int6
     p.n_chunks = one.n_chunks; p.wgs = one.wgs * n_seq;
     return p;
 }
+
+// The ragged paged call (plan.h has the statement): the bounds size everything, the batch nothing.
+int64_t attn_ragged_max_tiles(int64_t n_tokens_max, int64_t n_seq) {
+    if (n_tokens_max < 9 || n_seq < 1) return 0;
+    const int64_t P = n_seq < n_tokens_max / 9 ? n_seq : n_tokens_max / 9, L = n_tokens_max - 9 * P;
+    const int64_t k = P < L / 120 ? P : L / 120;
+    return P + k + (L - 120 * k) / 128;
+}
+
+attn_ragged_plan plan_attn_ragged(int kv_type, int D, int n_head, int n_head_kv, int64_t n_seq, int64_t n_tokens_max, int64_t n_dec_rows_max, int64_t n_kv_max,
+                                  int64_t window) {
+    attn_ragged_plan p = {};
+    if (n_seq < 1 || n_seq > ATTN_PAGED_MAX_SEQ || n_tokens_max < 0 || n_tokens_max > ATTN_PAGED_MAX_ROWS || n_dec_rows_max < 0 || n_dec_rows_max > n_tokens_max) return p;
+    const attn_plan one = plan_attn_ex(kv_type, D, n_head, n_head_kv, ATTN_DECODE_MAX_Q, n_kv_max, window);    // (the served types, D and heads; the chunks at 8 rows)
+    if (one.form == ATTN_FORM_NONE || n_tokens_max * n_head > 0x7FFFFFFF) return p;
+    p.ok = 1;
+    p.chunk = ATTN_CHUNK;
+    if (n_tokens_max == 0) return p;
+    p.dec_rows = n_dec_rows_max;
+    p.n_chunks = one.n_chunks;
+    p.max_tiles = attn_ragged_max_tiles(n_tokens_max, n_seq);
+    p.decode_wgs = n_dec_rows_max > 0 ? p.n_chunks * n_head_kv * n_seq : 0;      // (no row slot: every DECODE workgroup would leave)
+    p.merge_wgs = n_dec_rows_max * n_head;
+    p.prompt_wgs = p.max_tiles * n_head;
+    p.launches = 1 + (p.decode_wgs > 0) + (p.merge_wgs > 0) + (p.prompt_wgs > 0);
+    p.seq_off = 0;
+    p.n_tiles_off = 16 * (size_t)n_seq;
+    p.tiles_off = p.n_tiles_off + 16;
+    p.slots_off = p.tiles_off + 8 * (size_t)p.max_tiles;
+    p.part_off = (p.slots_off + 8 * (size_t)n_dec_rows_max + 255) / 256 * 256;
+    p.work_bytes = p.part_off + (size_t)n_dec_rows_max * (size_t)n_head * (size_t)cdiv(n_kv_max, ATTN_CHUNK) * (size_t)(D + 4) * 4;
+    return p;
+}

@@ -142,6 +142,32 @@ attn_plan plan_attn_paged(int kv_type, int D, int n_head, int n_head_kv, int64_t
 // W + n_q - 1 positions long and may start anywhere in a chunk), and wgs follows.  work_bytes stays the base plan's: the base work size serves.
 attn_plan plan_attn_ex(int kv_type, int D, int n_head, int n_head_kv, int64_t n_q, int64_t n_kv_max, int64_t window);
 attn_plan plan_attn_paged_ex(int kv_type, int D, int n_head, int n_head_kv, int64_t n_seq, int64_t n_q, int64_t n_kv_max, int64_t window);
+// ---- the RAGGED paged call: a query count per sequence, read on the device (ggml_hip_attn_paged_ragged_dev) ----
+// Nothing here follows the batch: every grid and size is a function of the host bounds (n_seq, n_tokens_max, n_dec_rows_max, n_kv_max, window).
+// FOUR launches: the index (one workgroup), DECODE (n_chunks x kv heads x sequences), the merge (one workgroup per row slot and head), PROMPT
+// (heads x max_tiles).  n_chunks is plan_attn's ceil(n_kv_max / 128), under a window 0 < W < n_kv_max plan_attn_ex's bound taken at 8 rows,
+// min(ceil(n_kv_max / 128), ceil((W + 7) / 128) + 1): a DECODE sequence has at most 8 rows, whatever the device says.
+// max_tiles = attn_ragged_max_tiles: the most PROMPT tiles any batch inside the bounds can hold.  A PROMPT sequence has n >= 9 rows and
+// ceil(n / 128) = 1 + (n - 1) / 128 tiles, so with P such sequences over N rows the tiles are P + sum of (n_i - 1) / 128: a sequence is worth a tile
+// for 9 rows, its second tile costs 120 more rows (n - 1 from 8 to 128), every further one 128.  Hence P = min(n_seq, N / 9), L = N - 9 P rows left,
+// k = min(P, L / 120) second tiles, and max_tiles = P + k + (L - 120 k) / 128.
+// THE WORK BUFFER, from its 256-byte aligned base: int32 x 4 [n_seq] (first row slot or -1, first packed row, n_q, 0) at seq_off = 0; the tile
+// count, one int32 in 16 bytes, at n_tiles_off; int32 x 2 [max_tiles] (b, tile) at tiles_off; int32 x 2 [n_dec_rows_max] (b, t) or (-1, -1) at
+// slots_off; then at part_off (a multiple of 256) the partials, n_dec_rows_max * n_head * ceil(n_kv_max / 128) * (D + 4) floats -- the UNWINDOWED
+// chunk count, as the _ex entries size theirs.  work_bytes is the whole; 0 for n_tokens_max = 0 (nothing is launched).
+struct attn_ragged_plan {
+    int ok;               // 0: not served (plan_attn's rules; n_seq outside 1 .. 4096; n_tokens_max outside 0 .. 2^20 or times n_head above 2^31 - 1;
+                          //    n_dec_rows_max outside 0 .. n_tokens_max)
+    int chunk, launches;  // 128; 4: the index and every launch below whose grid is not empty (0 for n_tokens_max = 0)
+    int64_t dec_rows;     // n_dec_rows_max: the row slots
+    int64_t n_chunks;     // DECODE's grid x and the partials' chunk stride
+    int64_t max_tiles;    // PROMPT's grid y (<= 4096 + 4096 + 2^20 / 128: inside a grid's y)
+    int64_t decode_wgs, merge_wgs, prompt_wgs;
+    size_t seq_off, n_tiles_off, tiles_off, slots_off, part_off, work_bytes;
+};
+int64_t attn_ragged_max_tiles(int64_t n_tokens_max, int64_t n_seq);
+attn_ragged_plan plan_attn_ragged(int kv_type, int D, int n_head, int n_head_kv, int64_t n_seq, int64_t n_tokens_max, int64_t n_dec_rows_max, int64_t n_kv_max,
+                                  int64_t window);
 // the K1 image for (type, K, N) with no weight at hand (no M: the exception cannot apply)
 int plan_image_kind(int type, int64_t K, int64_t N);
 // thread-local test switch (ggml_hip_debug_force_gemm): 0 auto, 1 int8, 2 f16, 3 MX

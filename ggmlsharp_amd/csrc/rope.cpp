@@ -1,5 +1,5 @@
 // rope.cpp -- the C-ABI of include/ggml_hip_ext.h, ROPE: the per-pair constants (ggml_hip_rope_table, host only), the rotation of Q / K rows
-// (ggml_hip_rope_dev) and the rotation fused with the store into a KV cache (ggml_hip_rope_kv_store_dev).  The kernels are rope.hip's; the
+// (ggml_hip_rope_dev) and the rotation fused with the store into a KV cache (ggml_hip_rope_kv_store_dev, its paged and its ragged form).  The kernels are rope.hip's; the
 // launchers get the table this file computes by value, so pow and log are the host's.  No set, no handle: stream-ordered launches on the
 // current device, no synchronize, no allocation; capturable.
 #include <cmath>
@@ -145,6 +145,34 @@ int ggml_hip_rope_kv_store_paged_dev(const ggml_hip_rope_params_t *rp, int kv_ty
     a.x = d_x; a.ldx_tok = ldx_tok; a.ldx_head = ldx_head; a.n_tokens = n_seq * n_q;
     a.d_pos = nullptr; a.pos0 = 0; a.d_pos0 = nullptr; a.freq_factors = d_freq_factors;
     HIP_TRY(launch_rope_kv_store_paged(tab, a, kv_type, n_q, d_pool, nb_pos, nb_head, pg, (hipStream_t)stream));
+    return GGML_HIP_OK;
+}
+
+int ggml_hip_rope_kv_store_paged_ragged_dev(const ggml_hip_rope_params_t *rp, int kv_type, const float *d_x, int64_t ldx_tok, int64_t ldx_head, int n_head_kv,
+                                            int D, int64_t n_seq, const int32_t *d_q_start, int64_t n_tokens_max, const float *d_freq_factors, void *d_pool,
+                                            int64_t nb_page, int64_t nb_pos, int64_t nb_head, int n_pages, const int32_t *d_pages, int64_t ld_pages,
+                                            const int32_t *d_len, int64_t n_kv_max, void *stream) {
+    int rc = check_rope_params(rp);
+    if (rc) return rc;
+    kv_pages pg;
+    rc = check_kv_pages(kv_type, D, n_head_kv, nb_page, nb_pos, nb_head, n_pages, d_pages, ld_pages, d_len, n_seq, n_kv_max, &pg);
+    if (rc) return rc;
+    kv_ragged rg;
+    rc = check_kv_ragged(d_q_start, n_seq, n_tokens_max, &rg);
+    if (rc) return rc;
+    rc = check_rope_rows(rp, n_head_kv, D, n_tokens_max, ldx_tok, ldx_head);
+    if (rc) return rc;
+    if (n_tokens_max == 0) return GGML_HIP_OK;
+    if (!d_x || !d_pool) return fail(GGML_HIP_ERR_ARG, "null argument");
+    if ((((uintptr_t)d_x | (uintptr_t)d_pool) & 15) != 0) return fail(GGML_HIP_ERR_SHAPE, "d_x and d_pool must be 16-byte aligned");
+    if (((uintptr_t)d_freq_factors & 3) != 0) return fail(GGML_HIP_ERR_SHAPE, "d_freq_factors must be 4-byte aligned");
+    rope_table tab;
+    rope_table_of(rp, tab.eff, &tab.mscale);
+    rope_args a;
+    a.mode = rp->mode; a.n_dims = rp->n_dims; a.n_head = n_head_kv; a.D = D;
+    a.x = d_x; a.ldx_tok = ldx_tok; a.ldx_head = ldx_head; a.n_tokens = n_tokens_max;
+    a.d_pos = nullptr; a.pos0 = 0; a.d_pos0 = nullptr; a.freq_factors = d_freq_factors;
+    HIP_TRY(launch_rope_kv_store_paged_ragged(tab, a, kv_type, rg, d_pool, nb_pos, nb_head, pg, (hipStream_t)stream));
     return GGML_HIP_OK;
 }
 

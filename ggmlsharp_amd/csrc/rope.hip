@@ -28,6 +28,9 @@
 // n_seq * n_q rows sits at len[b] + t, its rope position and, through the sequence's table row, its page row.  rope_store_unit is the
 // rotate-and-pack both store kernels share, so the bytes are rope_kernel's then kv_store_paged_kernel's.  A position outside [0, n_kv_max)
 // leaves before the table is read, a page id outside [0, n_pages) before any address is formed from it.
+// rope_kv_store_paged_ragged_kernel<Q8, MODE>: the same body (rope_kv_store_paged_body) over the packed rows of a RAGGED batch (common.h kv_ragged;
+// ggml_hip_rope_kv_store_paged_ragged_dev): the row's sequence and its index in it come from a bisection of q_start instead of t / n_q, t % n_q; a row of
+// no present sequence writes nothing.
 // No scratch, no atomics; LDS: 8 tokens x 128 pairs x 8 bytes.
 #include "common.h"
 #include "plan.h"        // ATTN_CHUNK: a page of the paged cache
@@ -197,16 +200,14 @@ __global__ __launch_bounds__(256) void rope_kv_store_kernel(const rope_table tab
 // The same into a PAGED cache (common.h kv_pages): token (b, t') = (t / n_q, t % n_q) of the n_seq * n_q rows sits at position
 // len[b] + t', which is its rope position and, through the sequence's table row, its page row.  Every guard stands in front of the address
 // it protects: the table is read only for a position inside [0, n_kv_max), the pool addressed only with a page id inside [0, n_pages).
-template <bool Q8, int MODE>
-__global__ __launch_bounds__(256) void rope_kv_store_paged_kernel(const rope_table tab, const float *__restrict__ x, int64_t ldx_tok, int64_t ldx_head,
-                                                                  int n_head_kv, int D, int n_dims, int64_t n_tokens, int tpb, int n_q,
-                                                                  const float *__restrict__ ff, uint8_t *__restrict__ pool, int64_t nb_pos, int64_t nb_head,
-                                                                  const kv_pages pg) {
-    __shared__ __align__(16) float2 cs[ROPE_TPB_MAX * ROPE_MAX_PAIRS];
+// where(t, &b): the position of packed row t and its sequence b (whose table row names its page); a negative position writes nothing
+template <bool Q8, int MODE, class WHERE>
+__device__ __forceinline__ void rope_kv_store_paged_body(float2 *cs, const rope_table &tab, const float *__restrict__ x, int64_t ldx_tok, int64_t ldx_head,
+                                                         int n_head_kv, int D, int n_dims, int64_t n_tokens, int tpb, WHERE where, const float *__restrict__ ff,
+                                                         uint8_t *__restrict__ pool, int64_t nb_pos, int64_t nb_head, const kv_pages &pg) {
     const int half = n_dims / 2;
     const int64_t t0 = (int64_t)blockIdx.x * tpb;
-    const auto pos_of = [=](int64_t t) { const int64_t b = t / n_q; return (int64_t)pg.len[b] + (t - b * n_q); };
-    rope_stage_cs(cs, tab, half, tpb, t0, n_tokens, pos_of, ff);
+    rope_stage_cs(cs, tab, half, tpb, t0, n_tokens, [=](int64_t t) { int64_t b; return where(t, &b); }, ff);
     const bool vec = n_dims % 8 == 0;
     const int per_head = D / (Q8 ? QK : 4);
     const int per_tok = n_head_kv * per_head;
@@ -215,13 +216,40 @@ __global__ __launch_bounds__(256) void rope_kv_store_paged_kernel(const rope_tab
         const int h = r / per_head, u = r - h * per_head;
         const int64_t t = t0 + tt;
         if (t >= n_tokens) break;
-        const int64_t pos = pos_of(t);
+        int64_t b;
+        const int64_t pos = where(t, &b);
         if (pos < 0 || pos >= pg.n_kv_max) continue;                // (before the table is read)
-        const int page = pg.pages[(t / n_q) * pg.ld_pages + pos / ROPE_PAGE];
+        const int page = pg.pages[b * pg.ld_pages + pos / ROPE_PAGE];
         if (page < 0 || page >= pg.n_pages) continue;               // (before any address is formed from it)
         uint8_t *row = pool + (int64_t)page * pg.nb_page + (pos % ROPE_PAGE) * nb_pos + (int64_t)h * nb_head;
         rope_store_unit<Q8, MODE>(x + t * ldx_tok + (int64_t)h * ldx_head, row, u, n_dims, cs + tt * half, vec);
     }
+}
+
+template <bool Q8, int MODE>
+__global__ __launch_bounds__(256) void rope_kv_store_paged_kernel(const rope_table tab, const float *__restrict__ x, int64_t ldx_tok, int64_t ldx_head,
+                                                                  int n_head_kv, int D, int n_dims, int64_t n_tokens, int tpb, int n_q,
+                                                                  const float *__restrict__ ff, uint8_t *__restrict__ pool, int64_t nb_pos, int64_t nb_head,
+                                                                  const kv_pages pg) {
+    __shared__ __align__(16) float2 cs[ROPE_TPB_MAX * ROPE_MAX_PAIRS];
+    const auto where = [=](int64_t t, int64_t *b) { *b = t / n_q; return (int64_t)pg.len[*b] + (t - *b * n_q); };
+    rope_kv_store_paged_body<Q8, MODE>(cs, tab, x, ldx_tok, ldx_head, n_head_kv, D, n_dims, n_tokens, tpb, where, ff, pool, nb_pos, nb_head, pg);
+}
+
+// The same over the packed rows of a RAGGED batch (common.h kv_ragged; ggml_hip_rope_kv_store_paged_ragged_dev): the row's sequence by bisection of
+// q_start (ragged_find); a row of no present sequence gets position -1 (its (c, s) are computed for that number and never used) and writes nothing.
+template <bool Q8, int MODE>
+__global__ __launch_bounds__(256) void rope_kv_store_paged_ragged_kernel(const rope_table tab, const float *__restrict__ x, int64_t ldx_tok, int64_t ldx_head,
+                                                                         int n_head_kv, int D, int n_dims, int tpb, const kv_ragged rg,
+                                                                         const float *__restrict__ ff, uint8_t *__restrict__ pool, int64_t nb_pos,
+                                                                         int64_t nb_head, const kv_pages pg) {
+    __shared__ __align__(16) float2 cs[ROPE_TPB_MAX * ROPE_MAX_PAIRS];
+    const auto where = [=](int64_t t, int64_t *b) {
+        int tq;
+        *b = ragged_find(rg, t, &tq);
+        return *b < 0 ? (int64_t)-1 : (int64_t)pg.len[*b] + tq;
+    };
+    rope_kv_store_paged_body<Q8, MODE>(cs, tab, x, ldx_tok, ldx_head, n_head_kv, D, n_dims, (int64_t)rg.n_tokens_max, tpb, where, ff, pool, nb_pos, nb_head, pg);
 }
 
 // tokens per workgroup: as many as keep its 256 threads busy, at most ROPE_TPB_MAX
@@ -280,6 +308,24 @@ hipError_t launch_rope_kv_store_paged(const rope_table &tab, const rope_args &a,
 #define ROPE_KV(Q, M)                                                                                                                                  \
     rope_kv_store_paged_kernel<Q, M><<<dim3((unsigned)blocks), 256, 0, st>>>(tab, a.x, a.ldx_tok, a.ldx_head, a.n_head, a.D, a.n_dims, a.n_tokens, tpb,   \
                                                                             (int)n_q, a.freq_factors, (uint8_t *)pool, nb_pos, nb_head, pg)
+    if (q8 && a.mode == 0) ROPE_KV(true, 0);
+    else if (q8) ROPE_KV(true, 2);
+    else if (a.mode == 0) ROPE_KV(false, 0);
+    else ROPE_KV(false, 2);
+#undef ROPE_KV
+    return hipGetLastError();
+}
+
+hipError_t launch_rope_kv_store_paged_ragged(const rope_table &tab, const rope_args &a, int kv_type, const kv_ragged &rg, void *pool, int64_t nb_pos,
+                                             int64_t nb_head, const kv_pages &pg, hipStream_t st) {
+    if (a.n_tokens <= 0) return hipSuccess;
+    const bool q8 = kv_type == GGML_TYPE_Q8_0;
+    const int tpb = rope_tpb((int64_t)a.n_head * (a.D / (q8 ? QK : 4)), a.n_tokens);
+    const int64_t blocks = (a.n_tokens + tpb - 1) / tpb;
+    if (blocks > 0x7FFFFFFF || a.n_dims / 2 > ROPE_MAX_PAIRS || a.n_tokens != rg.n_tokens_max) return hipErrorInvalidValue;
+#define ROPE_KV(Q, M)                                                                                                                                  \
+    rope_kv_store_paged_ragged_kernel<Q, M><<<dim3((unsigned)blocks), 256, 0, st>>>(tab, a.x, a.ldx_tok, a.ldx_head, a.n_head, a.D, a.n_dims, tpb, rg,     \
+                                                                                   a.freq_factors, (uint8_t *)pool, nb_pos, nb_head, pg)
     if (q8 && a.mode == 0) ROPE_KV(true, 0);
     else if (q8) ROPE_KV(true, 2);
     else if (a.mode == 0) ROPE_KV(false, 0);

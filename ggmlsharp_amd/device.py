@@ -458,6 +458,90 @@ def attn_paged(pc, q, n_head_kv, len_bias=0, causal=True, scale=None, out=None, 
     return out
 
 
+def _ragged(pc, q_start, x):
+    """(n_tokens_max, heads, D) of packed rows x [n_tokens_max, heads, D] under q_start int32 [n_seq + 1] on the device"""
+    assert x.is_cuda and x.dtype == torch.float32 and x.dim() == 3 and x.stride(2) == 1
+    assert q_start.is_cuda and q_start.dtype == torch.int32 and q_start.is_contiguous() and q_start.numel() == pc.n_seq + 1
+    return x.shape
+
+
+def ragged_positions(q_start, d_len, n_tokens_max, out=None):
+    """out[i] = d_len[b] + t for packed row i = (b, t) of a present sequence (0 <= q_start[b] <= q_start[b+1] <= n_tokens_max), 0 for the other rows:
+    the int32 position tensor rope() takes for Q, computed on the device so that a captured step follows q_start"""
+    assert q_start.is_cuda and q_start.dtype == torch.int32 and q_start.is_contiguous()
+    assert d_len.is_cuda and d_len.dtype == torch.int32 and d_len.is_contiguous() and d_len.numel() + 1 == q_start.numel()
+    if out is None:
+        out = torch.empty((n_tokens_max,), dtype=torch.int32, device=q_start.device)
+    assert out.dtype == torch.int32 and out.is_contiguous() and out.numel() == n_tokens_max
+    check(lib().ggml_hip_ragged_positions_dev(C.c_void_p(q_start.data_ptr()), C.c_void_p(d_len.data_ptr()), d_len.numel(), n_tokens_max,
+                                              C.c_void_p(out.data_ptr()), _stream()), "ggml_hip_ragged_positions_dev")
+    return out
+
+
+def kv_store_paged_ragged(pc, q_start, x, pool):
+    """kv_store_paged over packed rows: x f32 [n_tokens_max, n_head_kv, D], the rows of sequence b at q_start[b] .. q_start[b+1] - 1 (q_start int32
+    [n_seq + 1] on the device); the same bytes per row, nothing for a row of no present sequence"""
+    n_tokens_max, n_head_kv, D = _ragged(pc, q_start, x)
+    nbp, nbo, nbh, n_pages, d_pages, ld_pages, d_len = pc._args()
+    check(lib().ggml_hip_kv_store_paged_ragged_dev(pc.kv_type, C.c_void_p(x.data_ptr()), x.stride(0), x.stride(1), n_head_kv, D, pc.n_seq,
+                                                   C.c_void_p(q_start.data_ptr()), n_tokens_max, C.c_void_p(pool.data_ptr()), nbp, nbo, nbh, n_pages, d_pages,
+                                                   ld_pages, d_len, pc.n_kv_max, _stream()), "ggml_hip_kv_store_paged_ragged_dev")
+
+
+def rope_kv_store_paged_ragged(rp, pc, q_start, x, pool, freq_factors=None):
+    """rope_kv_store_paged over packed rows (see kv_store_paged_ragged): the same bytes per row"""
+    assert freq_factors is None or (freq_factors.is_cuda and freq_factors.dtype == torch.float32 and freq_factors.is_contiguous())
+    n_tokens_max, n_head_kv, D = _ragged(pc, q_start, x)
+    nbp, nbo, nbh, n_pages, d_pages, ld_pages, d_len = pc._args()
+    check(lib().ggml_hip_rope_kv_store_paged_ragged_dev(C.byref(rp), pc.kv_type, C.c_void_p(x.data_ptr()), x.stride(0), x.stride(1), n_head_kv, D, pc.n_seq,
+                                                        C.c_void_p(q_start.data_ptr()), n_tokens_max, _opt(freq_factors), C.c_void_p(pool.data_ptr()), nbp, nbo,
+                                                        nbh, n_pages, d_pages, ld_pages, d_len, pc.n_kv_max, _stream()), "ggml_hip_rope_kv_store_paged_ragged_dev")
+
+
+def attn_paged_ragged_plan(kv_type, D, n_head, n_head_kv, n_seq, n_tokens_max, n_dec_rows_max, n_kv_max, window=0, softcap=0.0):
+    """the ggml_hip_attn_ragged_plan_t of one ragged call: four launches sized by the bounds alone; no device needed"""
+    out = _lib.ggml_hip_attn_ragged_plan_t()
+    opts = _lib.ggml_hip_attn_opts_t(None, int(window), float(softcap), 0)
+    check(lib().ggml_hip_attn_paged_ragged_plan(kv_type, D, n_head, n_head_kv, n_seq, n_tokens_max, n_dec_rows_max, n_kv_max, C.byref(opts), C.byref(out)),
+          "ggml_hip_attn_paged_ragged_plan")
+    return out
+
+
+def attn_paged_ragged_work_size(kv_type, D, n_head, n_head_kv, n_seq, n_tokens_max, n_dec_rows_max, n_kv_max):
+    return int(lib().ggml_hip_attn_paged_ragged_work_size(kv_type, D, n_head, n_head_kv, n_seq, n_tokens_max, n_dec_rows_max, n_kv_max))
+
+
+def attn_paged_ragged(pc, q_start, q, n_head_kv, add_q=False, len_bias=0, n_dec_rows_max=None, causal=True, scale=None, out=None, work=None, window=0,
+                      softcap=0.0, sinks=None):
+    """attn_paged with a query count per sequence read on the device: q f32 [n_tokens_max, n_head, D] packed, the rows of sequence b at q_start[b] ..
+    q_start[b+1] - 1 (q_start int32 [n_seq + 1] on the device), over n_kv[b] = clamp(d_len[b] + (add_q ? n_q[b] : 0) + len_bias, 0, n_kv_max) positions.
+    A sequence's rows are bit for bit attn_paged for it alone; the form (DECODE up to 8 rows, PROMPT above) follows n_q[b] per sequence.
+    n_dec_rows_max (default min(n_tokens_max, 8 n_seq), which never overflows) bounds the DECODE rows of the work buffer: a DECODE sequence that does
+    not fit returns +0.0 rows.  out must be given for rows of no present sequence to keep what they held: they are not written."""
+    assert q_start.is_cuda and q_start.dtype == torch.int32 and q_start.is_contiguous() and q_start.numel() == pc.n_seq + 1
+    assert q.is_cuda and q.dtype == torch.float32 and q.dim() == 3 and q.stride(2) == 1
+    n_tokens_max, n_head, D = q.shape
+    if n_dec_rows_max is None:
+        n_dec_rows_max = min(n_tokens_max, 8 * pc.n_seq)
+    if scale is None:
+        scale = 1.0 / float(np.sqrt(np.float64(D)))
+    if out is None:
+        out = torch.zeros((n_tokens_max, n_head, D), dtype=torch.float32, device=q.device)
+    assert out.dtype == torch.float32 and out.dim() == 3 and out.stride(2) == 1 and tuple(out.shape) == (n_tokens_max, n_head, D)
+    if work is None:
+        work = torch.empty(max(attn_paged_ragged_work_size(pc.kv_type, D, n_head, n_head_kv, pc.n_seq, n_tokens_max, n_dec_rows_max, pc.n_kv_max), 16),
+                           dtype=torch.uint8, device=q.device)
+    nbp, nbo, nbh, n_pages, d_pages, ld_pages, d_len = pc._args()
+    opts = attn_opts(window, softcap, sinks)
+    check(lib().ggml_hip_attn_paged_ragged_dev(pc.kv_type, C.c_void_p(q.data_ptr()), q.stride(0), q.stride(1), C.c_void_p(pc.k.data_ptr()),
+                                               C.c_void_p(pc.v.data_ptr()), nbp, nbo, nbh, n_pages, d_pages, ld_pages, d_len, int(bool(add_q)), int(len_bias),
+                                               pc.n_seq, C.c_void_p(q_start.data_ptr()), n_tokens_max, int(n_dec_rows_max), n_head, n_head_kv, D, pc.n_kv_max,
+                                               int(bool(causal)), float(scale), C.byref(opts) if opts is not None else None, C.c_void_p(out.data_ptr()),
+                                               out.stride(0), out.stride(1), C.c_void_p(work.data_ptr()), work.numel(), _stream()),
+          "ggml_hip_attn_paged_ragged_dev")
+    return out
+
+
 def get_rows(w, ids, out=None):
     """out[i, :K] = dequantize(w[ids[i]]) on the current stream: ids an int32 tensor on the device; bit for bit download + dequantize, a row of
     +0.0 for an id outside [0, M).  out f32 [n_ids, >= K] with last stride 1 (default a new [n_ids, K] tensor)."""

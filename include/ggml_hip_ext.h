@@ -8,7 +8,8 @@
  *   - several devices in one process, one process per device           (ggml_hip_split_weight_*, _mul_mat_split_dev, _ipc_*, _push_columns_dev, ...)
  *   - the extension weight types: k-quants, IQ4, BF16                  (GGML_HIP_TYPE_* below; one row each in csrc/wtypes.cpp says what the library does with an id)
  *   - expert-routed products of a mixture-of-experts layer             (ggml_hip_expert_set_*, ggml_hip_mul_mat_id_*)
- *   - attention over a KV cache, contiguous and paged, and its options  (ggml_hip_attn_dev, _attn_paged_dev; sliding window, sinks, soft-cap: _attn_ex_dev, _attn_paged_ex_dev)
+ *   - attention over a KV cache, contiguous and paged, and its options  (ggml_hip_attn_dev, _attn_paged_dev; sliding window, sinks, soft-cap: _attn_ex_dev, _attn_paged_ex_dev;
+ *     a query count per sequence on the device: _attn_paged_ragged_dev and its stores)
  *   - TEST HOOKS (ggml_hip_debug_*): inert unless called; ggml_hip_debug_force_gemm acts on the CALLING THREAD only.
  */
 #ifndef GGML_HIP_EXT_H
@@ -749,6 +750,100 @@ int    ggml_hip_attn_paged_ex_dev(int kv_type, const float *d_q, int64_t ldq_tok
                                   int n_head, int n_head_kv, int D, int64_t n_q, int64_t n_kv_max,
                                   int causal, float scale, const ggml_hip_attn_opts_t *opts,
                                   float *d_dst, int64_t ldd_tok, int64_t ldd_head, void *d_work, size_t work_bytes, void *stream);
+
+/* ---------------- RAGGED PAGED ATTENTION: the paged entries with a query count PER SEQUENCE, read on the device ----------------
+ * ggml_hip_attn_paged_dev takes ONE n_q for all sequences.  A continuous-batching step holds sequences that decode one token, a few that
+ * verify 2 .. 8 draft tokens, one or two that prefill a chunk, and idle slots: the host would split it into one paged call per distinct n_q,
+ * and a captured graph would be frozen to that grouping.  The entries below take the whole step over the SAME paged cache:
+ *     ragged_positions -> rope(q, d_pos) -> rope_kv_store_paged_ragged(k) -> kv_store_paged_ragged(v) -> attn_paged_ragged
+ * All are stream-ordered on `stream` on the current device; none synchronizes or allocates; all may be captured; no atomics.  Every refusal
+ * below is decided before a device is touched.  The entries of the sections above keep their bits and their signatures.
+ *
+ * THE RAGGED BATCH (shared by all entries).
+ *   ROWS.   q, dst and the stores' source rows are PACKED: f32 [n_tokens_max][heads][D], the rows of sequence b one after the other.
+ *   d_q_start: int32 [n_seq + 1] on the device, never NULL (GGML_HIP_ERR_ARG), 4-byte aligned (else GGML_HIP_ERR_SHAPE): prefix sums.  The
+ *           rows of sequence b are rows d_q_start[b] .. d_q_start[b+1] - 1, and n_q[b] = d_q_start[b+1] - d_q_start[b].  n_q[b] = 0 is an
+ *           idle slot: nothing is written for it.
+ *   n_tokens_max: a host integer, 0 .. 2^20 (negative: GGML_HIP_ERR_ARG; above: GGML_HIP_ERR_SHAPE), for attention n_tokens_max * n_head
+ *           < 2^31 (else GGML_HIP_ERR_SHAPE).  It sizes the grids and bounds every row address.  n_tokens_max = 0 returns 0 and writes nothing.
+ *   PRESENT. Sequence b is PRESENT when 0 <= d_q_start[b] <= d_q_start[b+1] <= n_tokens_max.  A sequence that is not present writes nothing
+ *           and no address is formed from its bounds.  Rows that belong to no present sequence are not written (ragged_positions writes 0).
+ *           d_q_start is MEANT to ascend.  Attention looks at every sequence by itself, so a present sequence is served whatever the others'
+ *           bounds are.  The stores and ragged_positions find a row's sequence by bisection of d_q_start, which is exact for ascending
+ *           bounds; where the bounds do not ascend, a row is either written exactly as stated (for a present sequence that holds it) or not
+ *           written at all -- never anything else, and never from an address outside the stated bounds.  Present sequences that overlap
+ *           are the caller's error.
+ *   THE CACHE is the paged cache of the PAGED ATTENTION section, unchanged: pool, rows, strides, table, d_len, 1 <= n_seq <= 4096, n_kv_max,
+ *           and the rule that a page id outside [0, n_pages) gives zeros (a store: writes nothing) and is never turned into an address.
+ *           Every refusal of the paged entries carries over with its code.
+ *   POSITIONS. Token t of sequence b sits at position d_len[b] + t.  Attention uses
+ *               n_kv[b] = clamp(d_len[b] + (add_q ? n_q[b] : 0) + len_bias, 0, n_kv_max);
+ *           behind a store of this step's tokens the caller passes add_q = 1, len_bias = 0.
+ *
+ * ggml_hip_ragged_positions_dev: d_pos[i] = d_len[b] + t for every packed row i = (b, t) of a present sequence, 0 for the other rows below
+ *   n_tokens_max: the int32 position array ggml_hip_rope_dev takes for Q, so a captured step follows d_q_start.  d_pos: int32 [n_tokens_max],
+ *   4-byte aligned; NULL d_len / d_pos: GGML_HIP_ERR_ARG.
+ * ggml_hip_kv_store_paged_ragged_dev, ggml_hip_rope_kv_store_paged_ragged_dev: the paged stores over packed rows, one thread per 32 (Q8_0) or 4
+ *   (F16) elements as theirs.  The thread finds its row's sequence by bisection of d_q_start, and every guard comes before the address it
+ *   protects: a present sequence, the row inside it, the position inside [0, n_kv_max), the page id inside [0, n_pages).
+ *   THE CONTRACT: the bytes written for a row are bit for bit what ggml_hip_kv_store_paged_dev / ggml_hip_rope_kv_store_paged_dev write for
+ *   that row of that sequence (n_seq = 1, n_q = n_q[b], the same table row and d_len[b]).
+ * ggml_hip_attn_paged_ragged_dev: q, dst packed [n_tokens_max][n_head][D] (strides as ggml_hip_attn_dev).  opts as the _ex entries take it,
+ *   with their rules: NULL, or everything off, runs the base bodies, otherwise the option bodies.
+ *   THE FORM IS CHOSEN PER SEQUENCE from n_q[b] alone by ggml_hip_attn_plan's rule: DECODE for 1 .. 8 rows, PROMPT above; 0 writes nothing.
+ *   THE CONTRACT: for every present sequence b that has a slot or a tile (below), its n_q[b] rows of dst are BIT FOR BIT those of
+ *   ggml_hip_attn_paged_dev -- ggml_hip_attn_paged_ex_dev when an option is on -- called with n_seq = 1, n_q = n_q[b], the same table row,
+ *   d_len[b], len_bias = (add_q ? n_q[b] : 0) + len_bias, the same pool and the same parameters: the ragged kernels run the same chunk
+ *   bodies with the sequence's own n_q.  So a sequence's bits do not depend on the other sequences, its slot, the order of the batch,
+ *   n_tokens_max, n_dec_rows_max, n_kv_max or the page assignment; n_kv[b] = 0 and an invalid needed page id give +0.0f rows as there.
+ *   n_dec_rows_max: a host integer, 0 .. n_tokens_max (else GGML_HIP_ERR_ARG): the DECODE-form rows the work buffer can hold.
+ *   min(n_tokens_max, 8 * n_seq) can never overflow.  Below that, the DECODE sequences get their row SLOTS in ascending b, each one that
+ *   still fits behind those served before it; a DECODE sequence that does not fit gets no slot and ITS ROWS ARE WRITTEN AS +0.0f (by the
+ *   index launch); later sequences that fit are still served.  PROMPT sequences need no slot.
+ *   d_work / work_bytes: ggml_hip_attn_paged_ragged_work_size bytes: the index tables, then n_dec_rows_max * n_head * ceil(n_kv_max / 128) *
+ *   (D + 4) floats, plus alignment -- sized by the DECODE bound and never by n_tokens_max (a 2048-token prefill pays no partials).  0 for
+ *   n_tokens_max = 0; monotone in n_seq, n_tokens_max, n_dec_rows_max and n_kv_max; one size serves every opts.  Missing or short:
+ *   GGML_HIP_ERR_ARG.
+ * FOUR LAUNCHES whatever the batch holds (ggml_hip_attn_paged_ragged_plan shows them; host only, as is the work size):
+ *   1. INDEX, one workgroup: an exclusive scan through LDS over the sequences writes, to the front of d_work, for every sequence (first row
+ *      slot or -1, first packed row, n_q); for every row slot its (b, t), (-1, -1) for an unused one; the list of PROMPT tiles (b, tile) in
+ *      ascending (b, tile) order and its length.
+ *   2. DECODE, grid (n_chunks) x (kv heads) x (sequences), the paged DECODE grid.  n_chunks = ceil(n_kv_max / 128); under a window
+ *      0 < W < n_kv_max it is min(ceil(n_kv_max / 128), ceil((W + 7) / 128) + 1), the _ex entries' bound taken at 8 rows.  A workgroup whose
+ *      sequence is not DECODE or has no slot leaves before its first barrier.
+ *   3. MERGE, one workgroup per row slot and head, with the paged merge's id scan and zero row.
+ *   4. PROMPT, grid (heads) x (max_tiles), the list in dispatch order: a workgroup past the list's length leaves at once, after the last
+ *      tile.  max_tiles is the most tiles a batch inside the bounds can hold.  A PROMPT sequence has n >= 9 rows and 1 + (n - 1) / 128 tiles: it is worth a tile for 9 rows, a second one for 120
+ *      more, every further one for 128.  With P = min(n_seq, n_tokens_max / 9), L = n_tokens_max - 9 P, k = min(P, L / 120):
+ *          max_tiles = P + k + (L - 120 k) / 128          (integer divisions)
+ *   A launch whose grid the BOUNDS leave empty (n_dec_rows_max = 0, n_kv_max = 0, n_tokens_max < 9) is not made; `launches` counts the rest. */
+typedef struct ggml_hip_attn_ragged_plan_t {
+    int32_t chunk, launches;                 /* positions per chunk (128); launches of one call (4) */
+    int64_t n_chunks, max_tiles;             /* DECODE's chunks per sequence; the PROMPT tile bound */
+    int64_t decode_workgroups, merge_workgroups, prompt_workgroups;
+    int64_t index_bytes;                     /* the index tables in front of the partials, rounded up to 256 */
+} ggml_hip_attn_ragged_plan_t;
+int    ggml_hip_ragged_positions_dev(const int32_t *d_q_start, const int32_t *d_len, int64_t n_seq, int64_t n_tokens_max, int32_t *d_pos, void *stream);
+int    ggml_hip_kv_store_paged_ragged_dev(int kv_type, const float *d_src, int64_t ldx_tok, int64_t ldx_head, int n_head_kv, int D,
+                                          int64_t n_seq, const int32_t *d_q_start, int64_t n_tokens_max,
+                                          void *d_pool, int64_t nb_page, int64_t nb_pos, int64_t nb_head, int n_pages,
+                                          const int32_t *d_pages, int64_t ld_pages, const int32_t *d_len, int64_t n_kv_max, void *stream);
+int    ggml_hip_rope_kv_store_paged_ragged_dev(const ggml_hip_rope_params_t *rp, int kv_type, const float *d_x, int64_t ldx_tok, int64_t ldx_head,
+                                               int n_head_kv, int D, int64_t n_seq, const int32_t *d_q_start, int64_t n_tokens_max,
+                                               const float *d_freq_factors,
+                                               void *d_pool, int64_t nb_page, int64_t nb_pos, int64_t nb_head, int n_pages,
+                                               const int32_t *d_pages, int64_t ld_pages, const int32_t *d_len, int64_t n_kv_max, void *stream);
+int    ggml_hip_attn_paged_ragged_plan(int kv_type, int D, int n_head, int n_head_kv, int64_t n_seq, int64_t n_tokens_max, int64_t n_dec_rows_max,
+                                       int64_t n_kv_max, const ggml_hip_attn_opts_t *opts, ggml_hip_attn_ragged_plan_t *out);
+size_t ggml_hip_attn_paged_ragged_work_size(int kv_type, int D, int n_head, int n_head_kv, int64_t n_seq, int64_t n_tokens_max,
+                                            int64_t n_dec_rows_max, int64_t n_kv_max);
+int    ggml_hip_attn_paged_ragged_dev(int kv_type, const float *d_q, int64_t ldq_tok, int64_t ldq_head,
+                                      const void *d_k, const void *d_v, int64_t nb_page, int64_t nb_pos, int64_t nb_head, int n_pages,
+                                      const int32_t *d_pages, int64_t ld_pages, const int32_t *d_len, int add_q, int len_bias, int64_t n_seq,
+                                      const int32_t *d_q_start, int64_t n_tokens_max, int64_t n_dec_rows_max,
+                                      int n_head, int n_head_kv, int D, int64_t n_kv_max,
+                                      int causal, float scale, const ggml_hip_attn_opts_t *opts,
+                                      float *d_dst, int64_t ldd_tok, int64_t ldd_head, void *d_work, size_t work_bytes, void *stream);
 
 /* ---------------- THE ENDS OF A DECODE STEP: a token id -> its embedding row; the LM head's logits -> the next token id ----------------
  * Upstream's ggml_get_rows over the token-embedding matrix and its ggml_argmax / top-k -> temperature -> softmax -> top-p -> pick sampler

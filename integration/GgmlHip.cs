@@ -142,6 +142,30 @@ internal static unsafe partial class GgmlHip
     [DllImport(Lib)] public static extern int ggml_hip_attn_paged_ex_dev(int kvType, float* dQ, long ldqTok, long ldqHead, void* dK, void* dV, long nbPage, long nbPos,
         long nbHead, int nPages, int* dPages, long ldPages, int* dLen, int lenBias, long nSeq, int nHead, int nHeadKv, int d, long nQ, long nKvMax, int causal,
         float scale, ggml_hip_attn_opts_t* opts, float* dDst, long lddTok, long lddHead, void* dWork, nuint workBytes, void* stream);
+    // ... ragged paged attention: the paged entries with a query count per sequence read on the device.  q / dst / the stores' rows are packed
+    // [nTokensMax][heads][d]; dQStart int32 [nSeq + 1] holds prefix sums, sequence b owns rows dQStart[b] .. dQStart[b+1] - 1 and is present when
+    // 0 <= dQStart[b] <= dQStart[b+1] <= nTokensMax (else it writes nothing); n_kv[b] = clamp(dLen[b] + (addQ ? n_q[b] : 0) + lenBias, 0, nKvMax); the form
+    // follows n_q[b] per sequence; per sequence bit for bit the uniform paged entries; nDecRowsMax bounds the DECODE rows of the work buffer
+    [StructLayout(LayoutKind.Sequential)]
+    public struct ggml_hip_attn_ragged_plan_t
+    {
+        public int chunk, launches;
+        public long n_chunks, max_tiles, decode_workgroups, merge_workgroups, prompt_workgroups, index_bytes;
+    }
+    [DllImport(Lib)] public static extern int ggml_hip_ragged_positions_dev(int* dQStart, int* dLen, long nSeq, long nTokensMax, int* dPos, void* stream);
+    [DllImport(Lib)] public static extern int ggml_hip_kv_store_paged_ragged_dev(int kvType, float* dSrc, long ldxTok, long ldxHead, int nHeadKv, int d, long nSeq,
+        int* dQStart, long nTokensMax, void* dPool, long nbPage, long nbPos, long nbHead, int nPages, int* dPages, long ldPages, int* dLen, long nKvMax, void* stream);
+    [DllImport(Lib)] public static extern int ggml_hip_rope_kv_store_paged_ragged_dev(ggml_hip_rope_params_t* rp, int kvType, float* dX, long ldxTok, long ldxHead,
+        int nHeadKv, int d, long nSeq, int* dQStart, long nTokensMax, float* dFreqFactors, void* dPool, long nbPage, long nbPos, long nbHead, int nPages, int* dPages,
+        long ldPages, int* dLen, long nKvMax, void* stream);
+    [DllImport(Lib)] public static extern int ggml_hip_attn_paged_ragged_plan(int kvType, int d, int nHead, int nHeadKv, long nSeq, long nTokensMax, long nDecRowsMax,
+        long nKvMax, ggml_hip_attn_opts_t* opts, ggml_hip_attn_ragged_plan_t* plan);
+    [DllImport(Lib)] public static extern nuint ggml_hip_attn_paged_ragged_work_size(int kvType, int d, int nHead, int nHeadKv, long nSeq, long nTokensMax,
+        long nDecRowsMax, long nKvMax);
+    [DllImport(Lib)] public static extern int ggml_hip_attn_paged_ragged_dev(int kvType, float* dQ, long ldqTok, long ldqHead, void* dK, void* dV, long nbPage,
+        long nbPos, long nbHead, int nPages, int* dPages, long ldPages, int* dLen, int addQ, int lenBias, long nSeq, int* dQStart, long nTokensMax, long nDecRowsMax,
+        int nHead, int nHeadKv, int d, long nKvMax, int causal, float scale, ggml_hip_attn_opts_t* opts, float* dDst, long lddTok, long lddHead, void* dWork,
+        nuint workBytes, void* stream);
     // ... the ends of a decode step (device entries, capturable, scratch from the caller): rows of a resident weight by int32 ids on the device, bit
     // for bit download + dequantize, an id outside [0, M) a row of +0; the k best logits of every row (larger first, ties to the smaller index, NaN
     // last), p = softmax((l - l0) * invTemp) over them, top-p and the pick by the caller's uniforms dU (null: no pick) -- the int32 written to dToken
