@@ -94,6 +94,14 @@ class ggml_hip_attn_opts_t(C.Structure):
 assert C.sizeof(ggml_hip_attn_opts_t) == 24
 
 
+class ggml_hip_attn_bias_t(C.Structure):
+    """include/ggml_hip_ext.h: the mask (f16 [rows][ld_mask] on the device) and the ALiBi slopes (f32 [n_head] on the device) of the _bias attention entries"""
+    _fields_ = [("d_mask", C.c_void_p), ("ld_mask", C.c_int64), ("d_slopes", C.c_void_p)]
+
+
+assert C.sizeof(ggml_hip_attn_bias_t) == 24
+
+
 class ggml_hip_attn_ragged_plan_t(C.Structure):
     """include/ggml_hip_ext.h: the plan of one ragged paged attention call (csrc/plan.cpp plan_attn_ragged)"""
     _fields_ = [("chunk", C.c_int32), ("launches", C.c_int32), ("n_chunks", C.c_int64), ("max_tiles", C.c_int64),
@@ -273,6 +281,16 @@ HIP_SYMBOLS = {
     "ggml_hip_attn_paged_ragged_dev": (C.c_int, [C.c_int, _P, C.c_int64, C.c_int64, _P, _P, C.c_int64, C.c_int64, C.c_int64, C.c_int, _P, C.c_int64, _P, C.c_int,
                                                  C.c_int, C.c_int64, _P, C.c_int64, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int64, C.c_int, C.c_float, _P, _P,
                                                  C.c_int64, C.c_int64, _P, C.c_size_t, _P]),
+    # attention with a mask tensor and ALiBi slopes: the _ex / ragged entries with a ggml_hip_attn_bias_t * (or null) behind opts; the slopes are host only
+    "ggml_hip_alibi_slopes": (C.c_int, [C.c_int, C.c_float, _P]),
+    "ggml_hip_attn_bias_dev": (C.c_int, [C.c_int, _P, C.c_int64, C.c_int64, _P, _P, C.c_int64, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int64, C.c_int64, _P,
+                                         C.c_int64, C.c_int, C.c_float, _P, _P, _P, C.c_int64, C.c_int64, _P, C.c_size_t, _P]),
+    "ggml_hip_attn_paged_bias_dev": (C.c_int, [C.c_int, _P, C.c_int64, C.c_int64, _P, _P, C.c_int64, C.c_int64, C.c_int64, C.c_int, _P, C.c_int64, _P, C.c_int,
+                                               C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int64, C.c_int64, C.c_int, C.c_float, _P, _P, _P, C.c_int64, C.c_int64, _P,
+                                               C.c_size_t, _P]),
+    "ggml_hip_attn_paged_ragged_bias_dev": (C.c_int, [C.c_int, _P, C.c_int64, C.c_int64, _P, _P, C.c_int64, C.c_int64, C.c_int64, C.c_int, _P, C.c_int64, _P, C.c_int,
+                                                      C.c_int, C.c_int64, _P, C.c_int64, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int64, C.c_int, C.c_float, _P, _P, _P,
+                                                      C.c_int64, C.c_int64, _P, C.c_size_t, _P]),
     # the ends of a decode step: rows of a resident weight by device ids; top-k over a vocabulary, probabilities, top-p and the pick
     "ggml_hip_get_rows_serves_for": (C.c_int, [C.c_int]),
     "ggml_hip_get_rows_dev": (C.c_int, [_P, _P, C.c_int64, _P, C.c_int64, _P]),

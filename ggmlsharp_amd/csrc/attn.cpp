@@ -1,9 +1,11 @@
 // attn.cpp -- the C-ABI of include/ggml_hip_ext.h, attention over a KV cache: rows into the cache (ggml_hip_kv_store_dev), the attention
 // itself (ggml_hip_attn_dev), its plan and work size, the paged entries, the ragged entries (a query count per sequence on the device), and the _ex entries with a sliding window, sinks and a soft-cap
-// (one checked path serves an entry and its _ex twin).  The kernels and their arithmetic are attn.hip's, the form is plan.cpp's (plan_attn).
+// (one checked path serves an entry and its _ex twin), the _bias entries with a mask tensor and ALiBi slopes on top of those (the same paths once more), and
+// ggml_hip_alibi_slopes (host only).  The kernels and their arithmetic are attn.hip's, the form is plan.cpp's (plan_attn).
 // No set, no handle: stream-ordered launches on the current device, no synchronize, no allocation; capturable.
 #include "ctx.h"
 #include <cfloat>
+#include <cmath>
 
 using namespace ghip;
 
@@ -51,10 +53,24 @@ int check_attn_opts(const ggml_hip_attn_opts_t *opts, int causal, float scale, b
     return GGML_HIP_OK;
 }
 
+// the rules of a ggml_hip_attn_bias_t; 0 or an error code.  *on: a mask is given (else the _ex / ragged entry's own kernels run); bs: the kernels' form
+int check_attn_bias(const ggml_hip_attn_bias_t *bias, int64_t n_kv_max, bool *on, attn_bias *bs) {
+    *on = false;
+    *bs = attn_bias{};
+    if (!bias || (!bias->d_mask && !bias->d_slopes)) return GGML_HIP_OK;
+    if (((uintptr_t)bias->d_slopes & 3) != 0) return fail(GGML_HIP_ERR_ARG, "d_slopes must be 4-byte aligned");
+    if (!bias->d_mask) return fail(GGML_HIP_ERR_ARG, "d_slopes without d_mask: there is nothing to multiply");
+    if (bias->ld_mask < n_kv_max || bias->ld_mask % 8 != 0 || ((uintptr_t)bias->d_mask & 15) != 0)
+        return fail(GGML_HIP_ERR_SHAPE, "ld_mask %lld (>= n_kv_max %lld, a multiple of 8 halves), d_mask 16-byte aligned", (long long)bias->ld_mask, (long long)n_kv_max);
+    bs->mask = (const uint16_t *)bias->d_mask; bs->ld = bias->ld_mask; bs->slopes = bias->d_slopes;
+    *on = true;
+    return GGML_HIP_OK;
+}
+
 // ggml_hip_attn_dev behind its refusal of upstream's extras, and ggml_hip_attn_ex_dev behind check_attn_opts: on / vo are its answer (off from the base entry)
 int attn_run(int kv_type, const float *d_q, int64_t ldq_tok, int64_t ldq_head, const void *d_k, const void *d_v, int64_t nb_pos, int64_t nb_head, int n_head,
              int n_head_kv, int D, int64_t n_q, int64_t n_kv, const int32_t *d_n_kv, int64_t n_kv_max, int causal, float scale, bool on, const attn_var &vo,
-             float *d_dst, int64_t ldd_tok, int64_t ldd_head, void *d_work, size_t work_bytes, void *stream) {
+             float *d_dst, int64_t ldd_tok, int64_t ldd_head, void *d_work, size_t work_bytes, void *stream, const attn_bias *bs = nullptr) {
     int rc = check_attn_shape(kv_type, D, n_head, n_head_kv, n_q, n_kv_max);
     if (rc) return rc;
     if (!d_n_kv && (n_kv < 0 || n_kv > n_kv_max)) return fail(GGML_HIP_ERR_ARG, "n_kv %lld outside [0, n_kv_max %lld]", (long long)n_kv, (long long)n_kv_max);
@@ -68,6 +84,7 @@ int attn_run(int kv_type, const float *d_q, int64_t ldq_tok, int64_t ldq_head, c
     if (n_q == 0) return GGML_HIP_OK;
     if (!d_q || !d_dst || (n_kv_max > 0 && (!d_k || !d_v))) return fail(GGML_HIP_ERR_ARG, "null argument");
     if ((((uintptr_t)d_q | (uintptr_t)d_dst | (uintptr_t)d_k | (uintptr_t)d_v) & 15) != 0) return fail(GGML_HIP_ERR_SHAPE, "q, dst, K and V must be 16-byte aligned");
+    on = on || bs;                                                   // (a mask runs the option bodies, whatever vo holds; window 0 plans like the base entry)
     const attn_plan p = on ? plan_attn_ex(kv_type, D, n_head, n_head_kv, n_q, n_kv_max, vo.window) : plan_attn(kv_type, D, n_head, n_head_kv, n_q, n_kv_max);
     if (p.form == ATTN_FORM_NONE) return fail(GGML_HIP_ERR_SHAPE, "the shape is not served");
     const size_t need = ggml_hip_attn_work_size(kv_type, D, n_head, n_head_kv, n_q, n_kv_max);
@@ -80,7 +97,7 @@ int attn_run(int kv_type, const float *d_q, int64_t ldq_tok, int64_t ldq_head, c
     a.scale = scale;
     a.dst = d_dst; a.ldd_tok = ldd_tok; a.ldd_head = ldd_head;
     a.work = need ? (void *)(((uintptr_t)d_work + ATTN_ALIGN - 1) / ATTN_ALIGN * ATTN_ALIGN) : nullptr;
-    if (on) HIP_TRY(launch_attn_ex(p, a, vo, (hipStream_t)stream));
+    if (on) HIP_TRY(launch_attn_ex(p, a, vo, (hipStream_t)stream, bs));
     else HIP_TRY(launch_attn(p, a, (hipStream_t)stream));
     return GGML_HIP_OK;
 }
@@ -88,7 +105,7 @@ int attn_run(int kv_type, const float *d_q, int64_t ldq_tok, int64_t ldq_head, c
 int attn_paged_run(int kv_type, const float *d_q, int64_t ldq_tok, int64_t ldq_head, const void *d_k, const void *d_v, int64_t nb_page, int64_t nb_pos,
                    int64_t nb_head, int n_pages, const int32_t *d_pages, int64_t ld_pages, const int32_t *d_len, int len_bias, int64_t n_seq, int n_head,
                    int n_head_kv, int D, int64_t n_q, int64_t n_kv_max, int causal, float scale, bool on, const attn_var &vo, float *d_dst, int64_t ldd_tok,
-                   int64_t ldd_head, void *d_work, size_t work_bytes, void *stream) {
+                   int64_t ldd_head, void *d_work, size_t work_bytes, void *stream, const attn_bias *bs = nullptr) {
     int rc = check_attn_shape(kv_type, D, n_head, n_head_kv, n_q, n_kv_max);
     if (rc) return rc;
     kv_pages pg;
@@ -101,6 +118,7 @@ int attn_paged_run(int kv_type, const float *d_q, int64_t ldq_tok, int64_t ldq_h
     if (n_q == 0) return GGML_HIP_OK;
     if (!d_q || !d_dst || !d_k || !d_v) return fail(GGML_HIP_ERR_ARG, "null argument");
     if ((((uintptr_t)d_q | (uintptr_t)d_dst | (uintptr_t)d_k | (uintptr_t)d_v) & 15) != 0) return fail(GGML_HIP_ERR_SHAPE, "q, dst, K and V must be 16-byte aligned");
+    on = on || bs;
     const attn_plan p = on ? plan_attn_paged_ex(kv_type, D, n_head, n_head_kv, n_seq, n_q, n_kv_max, vo.window)
                            : plan_attn_paged(kv_type, D, n_head, n_head_kv, n_seq, n_q, n_kv_max);
     if (p.form == ATTN_FORM_NONE) return fail(GGML_HIP_ERR_SHAPE, "the shape is not served");
@@ -114,7 +132,7 @@ int attn_paged_run(int kv_type, const float *d_q, int64_t ldq_tok, int64_t ldq_h
     a.scale = scale;
     a.dst = d_dst; a.ldd_tok = ldd_tok; a.ldd_head = ldd_head;
     a.work = need ? (void *)(((uintptr_t)d_work + ATTN_ALIGN - 1) / ATTN_ALIGN * ATTN_ALIGN) : nullptr;
-    if (on) HIP_TRY(launch_attn_paged_ex(p, a, n_seq, pg, len_bias, vo, (hipStream_t)stream));
+    if (on) HIP_TRY(launch_attn_paged_ex(p, a, n_seq, pg, len_bias, vo, (hipStream_t)stream, bs));
     else HIP_TRY(launch_attn_paged(p, a, n_seq, pg, len_bias, (hipStream_t)stream));
     return GGML_HIP_OK;
 }
@@ -328,6 +346,46 @@ int ggml_hip_attn_paged_ex_dev(int kv_type, const float *d_q, int64_t ldq_tok, i
                           n_head_kv, D, n_q, n_kv_max, causal, scale, on, vo, d_dst, ldd_tok, ldd_head, d_work, work_bytes, stream);
 }
 
+int ggml_hip_alibi_slopes(int n_head, float max_bias, float *out) {
+    if (n_head < 1 || n_head > 65535) return fail(GGML_HIP_ERR_ARG, "n_head %d (1 .. 65535)", n_head);
+    if (!out) return fail(GGML_HIP_ERR_ARG, "out is null");
+    if (!(max_bias >= 0.0f) || max_bias > FLT_MAX) return fail(GGML_HIP_ERR_ARG, "max_bias must be 0 or a finite positive number");
+    int n2 = 1;
+    while (2 * n2 <= n_head) n2 *= 2;                                // 2^floor(log2 n_head)
+    const float m0 = powf(2.0f, -max_bias / (float)n2), m1 = powf(2.0f, -(max_bias / 2.0f) / (float)n2);
+    for (int h = 0; h < n_head; ++h)
+        out[h] = max_bias == 0.0f ? 1.0f : h < n2 ? powf(m0, (float)(h + 1)) : powf(m1, (float)(2 * (h - n2) + 1));
+    return GGML_HIP_OK;
+}
+
+int ggml_hip_attn_bias_dev(int kv_type, const float *d_q, int64_t ldq_tok, int64_t ldq_head, const void *d_k, const void *d_v, int64_t nb_pos, int64_t nb_head,
+                           int n_head, int n_head_kv, int D, int64_t n_q, int64_t n_kv, const int32_t *d_n_kv, int64_t n_kv_max, int causal, float scale,
+                           const ggml_hip_attn_opts_t *opts, const ggml_hip_attn_bias_t *bias, float *d_dst, int64_t ldd_tok, int64_t ldd_head, void *d_work,
+                           size_t work_bytes, void *stream) {
+    bool on; attn_var vo;
+    int rc = check_attn_opts(opts, causal, scale, &on, &vo);
+    if (rc) return rc;
+    bool mon; attn_bias bs;
+    rc = check_attn_bias(bias, n_kv_max, &mon, &bs);
+    if (rc) return rc;
+    return attn_run(kv_type, d_q, ldq_tok, ldq_head, d_k, d_v, nb_pos, nb_head, n_head, n_head_kv, D, n_q, n_kv, d_n_kv, n_kv_max, causal, scale, on, vo, d_dst,
+                    ldd_tok, ldd_head, d_work, work_bytes, stream, mon ? &bs : nullptr);
+}
+
+int ggml_hip_attn_paged_bias_dev(int kv_type, const float *d_q, int64_t ldq_tok, int64_t ldq_head, const void *d_k, const void *d_v, int64_t nb_page, int64_t nb_pos,
+                                 int64_t nb_head, int n_pages, const int32_t *d_pages, int64_t ld_pages, const int32_t *d_len, int len_bias, int64_t n_seq,
+                                 int n_head, int n_head_kv, int D, int64_t n_q, int64_t n_kv_max, int causal, float scale, const ggml_hip_attn_opts_t *opts,
+                                 const ggml_hip_attn_bias_t *bias, float *d_dst, int64_t ldd_tok, int64_t ldd_head, void *d_work, size_t work_bytes, void *stream) {
+    bool on; attn_var vo;
+    int rc = check_attn_opts(opts, causal, scale, &on, &vo);
+    if (rc) return rc;
+    bool mon; attn_bias bs;
+    rc = check_attn_bias(bias, n_kv_max, &mon, &bs);
+    if (rc) return rc;
+    return attn_paged_run(kv_type, d_q, ldq_tok, ldq_head, d_k, d_v, nb_page, nb_pos, nb_head, n_pages, d_pages, ld_pages, d_len, len_bias, n_seq, n_head,
+                          n_head_kv, D, n_q, n_kv_max, causal, scale, on, vo, d_dst, ldd_tok, ldd_head, d_work, work_bytes, stream, mon ? &bs : nullptr);
+}
+
 int ggml_hip_ragged_positions_dev(const int32_t *d_q_start, const int32_t *d_len, int64_t n_seq, int64_t n_tokens_max, int32_t *d_pos, void *stream) {
     if (n_seq < 1 || n_seq > ATTN_PAGED_MAX_SEQ) return fail(GGML_HIP_ERR_SHAPE, "n_seq %lld (1 .. %lld)", (long long)n_seq, (long long)ATTN_PAGED_MAX_SEQ);
     kv_ragged rg;
@@ -389,8 +447,22 @@ int ggml_hip_attn_paged_ragged_dev(int kv_type, const float *d_q, int64_t ldq_to
                                    int len_bias, int64_t n_seq, const int32_t *d_q_start, int64_t n_tokens_max, int64_t n_dec_rows_max, int n_head, int n_head_kv,
                                    int D, int64_t n_kv_max, int causal, float scale, const ggml_hip_attn_opts_t *opts, float *d_dst, int64_t ldd_tok,
                                    int64_t ldd_head, void *d_work, size_t work_bytes, void *stream) {
+    return ggml_hip_attn_paged_ragged_bias_dev(kv_type, d_q, ldq_tok, ldq_head, d_k, d_v, nb_page, nb_pos, nb_head, n_pages, d_pages, ld_pages, d_len, add_q, len_bias,
+                                               n_seq, d_q_start, n_tokens_max, n_dec_rows_max, n_head, n_head_kv, D, n_kv_max, causal, scale, opts, nullptr, d_dst,
+                                               ldd_tok, ldd_head, d_work, work_bytes, stream);
+}
+
+int ggml_hip_attn_paged_ragged_bias_dev(int kv_type, const float *d_q, int64_t ldq_tok, int64_t ldq_head, const void *d_k, const void *d_v, int64_t nb_page,
+                                        int64_t nb_pos, int64_t nb_head, int n_pages, const int32_t *d_pages, int64_t ld_pages, const int32_t *d_len, int add_q,
+                                        int len_bias, int64_t n_seq, const int32_t *d_q_start, int64_t n_tokens_max, int64_t n_dec_rows_max, int n_head,
+                                        int n_head_kv, int D, int64_t n_kv_max, int causal, float scale, const ggml_hip_attn_opts_t *opts,
+                                        const ggml_hip_attn_bias_t *bias, float *d_dst, int64_t ldd_tok, int64_t ldd_head, void *d_work, size_t work_bytes,
+                                        void *stream) {
     bool on; attn_var vo;
     int rc = check_attn_opts(opts, causal, scale, &on, &vo);
+    if (rc) return rc;
+    bool mon; attn_bias bs;
+    rc = check_attn_bias(bias, n_kv_max, &mon, &bs);
     if (rc) return rc;
     rc = check_attn_shape(kv_type, D, n_head, n_head_kv, 0, n_kv_max);
     if (rc) return rc;
@@ -408,6 +480,7 @@ int ggml_hip_attn_paged_ragged_dev(int kv_type, const float *d_q, int64_t ldq_to
     if (!d_q || !d_dst || !d_k || !d_v) return fail(GGML_HIP_ERR_ARG, "null argument");
     if ((((uintptr_t)d_q | (uintptr_t)d_dst | (uintptr_t)d_k | (uintptr_t)d_v) & 15) != 0) return fail(GGML_HIP_ERR_SHAPE, "q, dst, K and V must be 16-byte aligned");
     const attn_ragged_plan p = plan_attn_ragged(kv_type, D, n_head, n_head_kv, n_seq, n_tokens_max, n_dec_rows_max, n_kv_max, on ? vo.window : 0);
+    // (a mask with every option off: vo is all zero, the option bodies' arithmetic is then the base bodies')
     if (!p.ok) return fail(GGML_HIP_ERR_SHAPE, "the shape is not served");
     const size_t need = ggml_hip_attn_paged_ragged_work_size(kv_type, D, n_head, n_head_kv, n_seq, n_tokens_max, n_dec_rows_max, n_kv_max);
     if (!d_work || work_bytes < need) return fail(GGML_HIP_ERR_ARG, "work buffer too small: need %zu (ggml_hip_attn_paged_ragged_work_size)", need);
@@ -419,7 +492,7 @@ int ggml_hip_attn_paged_ragged_dev(int kv_type, const float *d_q, int64_t ldq_to
     a.scale = scale;
     a.dst = d_dst; a.ldd_tok = ldd_tok; a.ldd_head = ldd_head;
     a.work = (void *)(((uintptr_t)d_work + ATTN_ALIGN - 1) / ATTN_ALIGN * ATTN_ALIGN);
-    HIP_TRY(launch_attn_paged_ragged(p, a, rg, pg, add_q != 0, len_bias, on, vo, (hipStream_t)stream));
+    HIP_TRY(launch_attn_paged_ragged(p, a, rg, pg, add_q != 0, len_bias, on, vo, (hipStream_t)stream, mon ? &bs : nullptr));
     return GGML_HIP_OK;
 }
 

@@ -1,6 +1,6 @@
 // attn.hip -- attention over an F16 or Q8_0 KV cache on the device (include/ggml_hip_ext.h ggml_hip_kv_store_dev, ggml_hip_attn_dev;
 // attn.cpp has the C-ABI, plan.cpp plan_attn chooses the form from n_q alone).  Upstream's ggml_flash_attn_ext without mask tensor and ALiBi;
-// a sliding window, sinks and a soft-cap are the _ex entries' (the OPTIONS block below); an EXTENSION like mul_mat_id (the reference has the
+// a sliding window, sinks and a soft-cap are the _ex entries' (the OPTIONS block below), the mask tensor and ALiBi slopes the _bias entries' (MASK AND SLOPES); an EXTENSION like mul_mat_id (the reference has the
 // op's id and no dispatch).
 //
 // A cache row is (position j, kv head hk): D elements in reference block format at  base + j * nb_pos + hk * nb_head  (F16: 2 D bytes of IEEE
@@ -65,6 +65,15 @@
 // first row's lo, a wave skips the chunks wholly below its first row's lo, the element mask gains j >= lo.  SOFT-CAP: s = cap * tanhf(sc' * dot),
 // sc' = scale / cap from the host.  SINKS: sink_h joins M and the denominator only (DECODE: in the merge; PROMPT: one more online-softmax step
 // after the last chunk).  PAGED: no table entry below c_lo[b] is read; the id scans start there.
+//
+// ---- MASK AND SLOPES (ggml_hip_attn_bias_dev, ggml_hip_attn_paged_bias_dev, ggml_hip_attn_paged_ragged_bias_dev; common.h attn_bias; the header's section
+// ATTENTION WITH A MASK TENSOR AND ALiBi SLOPES is the statement) ----
+// The bodies carry a second template <bool MSK>; MSK = false IS the kernels above (every use of attn_bias sits under if constexpr (MSK)), MSK = true (always
+// with VAR = true, vo possibly all off) serves the mask kernels: the _ex and the ragged kernels instantiated once more.  A mask value of -inf hides the position
+// from the row, any other value mk turns the score into fma(slope_h, mk, s).  DECODE: the score thread fetches its four rows' mask halves before its dot
+// products; the softmax pass finds the row's first and last mask-visible position of the chunk by ballots and hands them to the P V pass through LDS; a
+// chunk of the row's range with none writes the partial (-inf, 0, 0), and the merge returns +0.0f where M = -inf.  PROMPT: a lane fetches the 16 8-byte
+// pieces of its own mask row under the chunk before the chunk is staged; the online softmax needs nothing new (an empty chunk has alpha = 1 and every P = 0).
 //
 // ---- RAGGED (ggml_hip_attn_paged_ragged_dev, ggml_hip_kv_store_paged_ragged_dev, ggml_hip_ragged_positions_dev; common.h kv_ragged) ----
 // The paged kernels with a query count PER SEQUENCE read on the device (q_start, prefix sums over packed rows): an index launch turns q_start into row slots
@@ -234,14 +243,22 @@ __device__ __forceinline__ void load4(const uint8_t *row, int d4, float (&v)[4])
 // kb / vb + j * nb_pos -- where the chunk lies in memory is the caller's, the arithmetic does not know.  q and work are the sequence's own.
 // VAR (the _ex kernels): the partial goes to work-buffer chunk index wc = c - c_lo, the score may be soft-capped, and a row's visible range
 // inside the chunk is [f, n) instead of [0, n): its a[d] chain starts at f, and a chunk with no visible position writes no partial.
-template <bool Q8, int D, bool VAR>
+// MSK (the mask kernels, always with VAR): mrow0 = the mask row of the sequence's query 0, ld halves between rows; the score thread adds
+// slope_h * mask[t][j0 + j] in one fma, a mask value of -inf makes the position invisible to the row (its score becomes the marker -inf and
+// its weight the marker -1: it is skipped, never multiplied).  The a[d] chain runs from the row's first to its last MASK-VISIBLE position of
+// the chunk (wave ballots, handed to the P V pass through LDS); a (row, chunk) inside the row's structural range with none writes the partial
+// (m = -inf, l = 0, a = 0), which the merge takes as nothing.
+template <bool Q8, int D, bool VAR, bool MSK = false>
 __device__ __forceinline__ void attn_decode_chunk(uint8_t *lds, const float *__restrict__ q, int64_t ldq_tok, int64_t ldq_head, const uint8_t *__restrict__ kb,
                                                   const uint8_t *__restrict__ vb, int64_t nb_pos, int n_head, int G, int n_q, int n_kv, int c, int wc, int hk,
-                                                  int causal, float scale, float *__restrict__ work, int n_chunks_max, const attn_var &vo) {
+                                                  int causal, float scale, float *__restrict__ work, int n_chunks_max, const attn_var &vo,
+                                                  const attn_bias &bs = attn_bias{}) {
+    static_assert(!MSK || VAR, "the mask kernels run the VAR bodies");
     constexpr int RB = row_bytes_of<Q8>(D), ST = stage_stride<Q8>(D), PPR = RB / 8;
     uint8_t *kst = lds, *vst = lds + C * ST;
     float *qt = (float *)(lds + 2 * C * ST);                         // [DEC_RT][D]
     float *sc = qt + DEC_RT * D;                                     // [DEC_RT][C]
+    int *fl = (int *)(sc + DEC_RT * C);                              // MSK: [DEC_RT][2] first / last mask-visible position of the pass's rows (decode_lds)
     static_assert((2 * C * ST) % 16 == 0, "the query tile is read as float4");
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int j0 = c * C;
@@ -287,6 +304,18 @@ __device__ __forceinline__ void attn_decode_chunk(uint8_t *lds, const float *__r
         {
             const int j = tid & (C - 1), hs = tid >> 7;
             float acc[4] = {0.f, 0.f, 0.f, 0.f};
+            uint32_t mb[4] = {0u, 0u, 0u, 0u};                       // MSK: the mask halves of this thread's four rows, in flight under the dot products
+            float slope[4] = {1.0f, 1.0f, 1.0f, 1.0f};
+            if constexpr (MSK) {
+#pragma unroll
+                for (int i = 0; i < 4; ++i) {
+                    const int r = r0 + 4 * hs + i;
+                    if (r < R && j < cnt) {                          // (column j0 + j < n_kv <= ld; a row past R has no mask row)
+                        mb[i] = bs.mask[(int64_t)(r / G) * bs.ld + j0 + j];
+                        if (bs.slopes) slope[i] = bs.slopes[hk * G + r % G];
+                    }
+                }
+            }
             if (j < cnt) {
                 const uint8_t *krow = kst + j * ST;
 #pragma unroll 2
@@ -308,6 +337,7 @@ __device__ __forceinline__ void attn_decode_chunk(uint8_t *lds, const float *__r
                 float s;
                 if constexpr (VAR) s = vo.cap != 0.0f ? vo.cap * tanhf(vo.sc * acc[i]) : scale * acc[i];
                 else s = scale * acc[i];
+                if constexpr (MSK) s = mb[i] == 0xFC00u ? -__builtin_inff() : fmaf(slope[i], f16_bits_to_f32(mb[i]), s);       // (+0.0 where nothing was read)
                 sc[(4 * hs + i) * C + j] = s;
             }
         }
@@ -325,14 +355,23 @@ __device__ __forceinline__ void attn_decode_chunk(uint8_t *lds, const float *__r
                 f = max(window_lo(hi, vo.window) - j0, 0);
                 if (f >= n) continue;
             }
-            const bool in0 = lane >= f && lane < n, in1 = lane + 64 >= f && lane + 64 < n;
+            bool in0 = lane >= f && lane < n, in1 = lane + 64 >= f && lane + 64 < n;
             const float ninf = -__builtin_inff();
             const float s0 = in0 ? sc[ri * C + lane] : ninf, s1 = in1 ? sc[ri * C + lane + 64] : ninf;
+            if constexpr (MSK) {
+                in0 = in0 && s0 != ninf; in1 = in1 && s1 != ninf;    // (the score thread's marker: masked)
+                const unsigned long long b0 = __ballot(in0), b1 = __ballot(in1);
+                if (lane == 0) {
+                    fl[2 * ri] = b0 ? __builtin_ctzll(b0) : b1 ? 64 + __builtin_ctzll(b1) : C;
+                    fl[2 * ri + 1] = b1 ? 127 - __builtin_clzll(b1) : b0 ? 63 - __builtin_clzll(b0) : -1;
+                }
+            }
             float m = fmaxf(s0, s1);
 #pragma unroll
             for (int dd = 32; dd >= 1; dd >>= 1) m = fmaxf(m, __shfl_xor(m, dd));
             const float p0 = in0 ? (s0 == m ? 1.0f : expf(s0 - m)) : 0.0f, p1 = in1 ? (s1 == m ? 1.0f : expf(s1 - m)) : 0.0f;
-            sc[ri * C + lane] = p0; sc[ri * C + lane + 64] = p1;
+            if constexpr (MSK) { sc[ri * C + lane] = in0 ? p0 : -1.0f; sc[ri * C + lane + 64] = in1 ? p1 : -1.0f; }
+            else { sc[ri * C + lane] = p0; sc[ri * C + lane + 64] = p1; }
             float l = p0 + p1;
 #pragma unroll
             for (int dd = 32; dd >= 1; dd >>= 1) l = l + __shfl_xor(l, dd);
@@ -359,16 +398,36 @@ __device__ __forceinline__ void attn_decode_chunk(uint8_t *lds, const float *__r
                     if (f >= n) continue;
                 }
                 float v[4], a[4];
-                load4<Q8>(vst + f * ST, d4, v);
-                const float pf = sc[ri * C + f];
+                if constexpr (MSK) {
+                    const int first = fl[2 * ri], last = fl[2 * ri + 1];
+                    if (last < 0) {                                  // every position masked: the empty partial
 #pragma unroll
-                for (int i = 0; i < 4; ++i) a[i] = pf * v[i];
+                        for (int i = 0; i < 4; ++i) a[i] = 0.0f;
+                    } else {
+                        load4<Q8>(vst + first * ST, d4, v);
+                        const float pf = sc[ri * C + first];
+#pragma unroll
+                        for (int i = 0; i < 4; ++i) a[i] = pf * v[i];
 #pragma unroll 4
-                for (int j = f + 1; j < n; ++j) {
-                    load4<Q8>(vst + j * ST, d4, v);
-                    const float p = sc[ri * C + j];
+                        for (int j = first + 1; j <= last; ++j) {
+                            load4<Q8>(vst + j * ST, d4, v);
+                            const float p = sc[ri * C + j];
 #pragma unroll
-                    for (int i = 0; i < 4; ++i) a[i] = fmaf(p, v[i], a[i]);
+                            for (int i = 0; i < 4; ++i) a[i] = p < 0.0f ? a[i] : fmaf(p, v[i], a[i]);     // (the marker -1: masked -- a[] is kept, the product is never taken)
+                        }
+                    }
+                } else {
+                    load4<Q8>(vst + f * ST, d4, v);
+                    const float pf = sc[ri * C + f];
+#pragma unroll
+                    for (int i = 0; i < 4; ++i) a[i] = pf * v[i];
+#pragma unroll 4
+                    for (int j = f + 1; j < n; ++j) {
+                        load4<Q8>(vst + j * ST, d4, v);
+                        const float p = sc[ri * C + j];
+#pragma unroll
+                        for (int i = 0; i < 4; ++i) a[i] = fmaf(p, v[i], a[i]);
+                    }
                 }
                 const int64_t gr = (int64_t)(r / G) * n_head + hk * G + r % G;
                 *(float4 *)(work + (gr * n_chunks_max + wc) * (D + 4) + 4 + 4 * d4) = make_float4(a[0], a[1], a[2], a[3]);
@@ -394,11 +453,13 @@ __global__ __launch_bounds__(256) void attn_decode_kernel(const float *__restric
 }
 
 // the _ex DECODE kernel: workgroup x serves chunk c_lo + x, c_lo the chunk of row 0's first visible position, from the same clamped n_kv
-template <bool Q8, int D>
+// MSK (here and in every _ex / ragged kernel below): the mask kernel of the _bias entries -- the same kernel with the mask handed to the body as q is
+// (the sequence's first row); MSK = false never reads bs and is the _ex kernel as it was
+template <bool Q8, int D, bool MSK>
 __global__ __launch_bounds__(256) void attn_decode_ex_kernel(const float *__restrict__ q, int64_t ldq_tok, int64_t ldq_head, const uint8_t *__restrict__ kc,
                                                              const uint8_t *__restrict__ vc, int64_t nb_pos, int64_t nb_head, int n_head, int G, int n_q,
                                                              int n_kv_host, const int32_t *__restrict__ d_n_kv, int n_kv_max, int causal, float scale,
-                                                             float *__restrict__ work, int n_chunks_max, const attn_var vo) {
+                                                             float *__restrict__ work, int n_chunks_max, const attn_var vo, const attn_bias bs) {
     extern __shared__ __attribute__((aligned(16))) uint8_t lds[];
     const int hk = blockIdx.y;
     const int n_kv = device_count(d_n_kv, n_kv_host, n_kv_max);
@@ -406,8 +467,8 @@ __global__ __launch_bounds__(256) void attn_decode_ex_kernel(const float *__rest
     const int j0 = c * C;
     if (j0 >= n_kv) return;                                          // (the whole workgroup: no barrier was reached)
     const int64_t off = (int64_t)j0 * nb_pos + (int64_t)hk * nb_head;
-    attn_decode_chunk<Q8, D, true>(lds, q, ldq_tok, ldq_head, kc + off, vc + off, nb_pos, n_head, G, n_q, n_kv, c, (int)blockIdx.x, hk, causal, scale, work,
-                                   n_chunks_max, vo);
+    attn_decode_chunk<Q8, D, true, MSK>(lds, q, ldq_tok, ldq_head, kc + off, vc + off, nb_pos, n_head, G, n_q, n_kv, c, (int)blockIdx.x, hk, causal, scale, work,
+                                        n_chunks_max, vo, bs);
 }
 
 // the paged DECODE kernel: grid (chunks of n_kv_max) x (kv heads) x (sequences).  The sequence's length and the chunk's page id are
@@ -432,11 +493,11 @@ __global__ __launch_bounds__(256) void attn_decode_paged_kernel(const float *__r
 }
 
 // the _ex paged DECODE kernel: chunk c_lo[b] + x of sequence b; table entries below c_lo[b] are never read
-template <bool Q8, int D>
+template <bool Q8, int D, bool MSK>
 __global__ __launch_bounds__(256) void attn_decode_paged_ex_kernel(const float *__restrict__ q, int64_t ldq_tok, int64_t ldq_head, const uint8_t *__restrict__ kc,
                                                                    const uint8_t *__restrict__ vc, int64_t nb_pos, int64_t nb_head, int n_head, int G, int n_q,
                                                                    const kv_pages pg, int len_bias, int causal, float scale, float *__restrict__ work,
-                                                                   int n_chunks_max, const attn_var vo) {
+                                                                   int n_chunks_max, const attn_var vo, const attn_bias bs) {
     extern __shared__ __attribute__((aligned(16))) uint8_t lds[];
     const int hk = blockIdx.y, b = blockIdx.z;
     const int n_kv = paged_count(pg, b, len_bias);
@@ -446,13 +507,17 @@ __global__ __launch_bounds__(256) void attn_decode_paged_ex_kernel(const float *
     if (page < 0 || page >= pg.n_pages) return;                      // (before any address is formed from it; the merge writes zeros)
     const int64_t off = (int64_t)page * pg.nb_page + (int64_t)hk * nb_head;
     const int64_t row0 = (int64_t)b * n_q;
-    attn_decode_chunk<Q8, D, true>(lds, q + row0 * ldq_tok, ldq_tok, ldq_head, kc + off, vc + off, nb_pos, n_head, G, n_q, n_kv, c, (int)blockIdx.x, hk, causal,
-                                   scale, work + row0 * n_head * n_chunks_max * (D + 4), n_chunks_max, vo);
+    attn_bias bb = bs;
+    if constexpr (MSK) bb.mask += row0 * bs.ld;
+    attn_decode_chunk<Q8, D, true, MSK>(lds, q + row0 * ldq_tok, ldq_tok, ldq_head, kc + off, vc + off, nb_pos, n_head, G, n_q, n_kv, c, (int)blockIdx.x, hk, causal,
+                                        scale, work + row0 * n_head * n_chunks_max * (D + 4), n_chunks_max, vo, bb);
 }
 
 // the merge of one query row (t, h) whose partials start at `part`; thread d owns column d, every thread the row's (M, L)
 // VAR: the row's chunks are lo / 128 .. (vis - 1) / 128, at work-buffer index c - c_lo (part points at index 0); head h's sink joins M and L
-template <int D, bool VAR>
+// MSK: a chunk of the row's range may hold the empty partial (m = -inf, l = 0, a = 0): its b is expf(-inf) = 0 against a finite M and it adds
+// nothing; with M = -inf (every chunk empty, no finite sink) the row has no visible position and is +0.0f
+template <int D, bool VAR, bool MSK = false>
 __device__ __forceinline__ void attn_merge_row(const float *__restrict__ part, int t, int n_q, int n_kv, int causal, float *__restrict__ out, int h,
                                                const attn_var &vo) {
     const int d = threadIdx.x;
@@ -469,6 +534,7 @@ __device__ __forceinline__ void attn_merge_row(const float *__restrict__ part, i
     float M = part[0];
     for (int c = 1; c < nc; ++c) M = fmaxf(M, part[(int64_t)c * (D + 4)]);
     if constexpr (VAR) if (vo.sinks) M = fmaxf(M, sink);
+    if constexpr (MSK) if (M == -__builtin_inff()) { *out = 0.0f; return; }
     float L, A;
     {
         const float m = part[0], b = m == M ? 1.0f : expf(m - M);
@@ -495,14 +561,14 @@ __global__ __launch_bounds__(D) void attn_merge_kernel(const float *__restrict__
                              dst + (int64_t)t * ldd_tok + (int64_t)h * ldd_head + threadIdx.x, h, attn_var{});
 }
 
-template <int D>
+template <int D, bool MSK>
 __global__ __launch_bounds__(D) void attn_merge_ex_kernel(const float *__restrict__ work, int n_chunks_max, int n_head, int n_q, int n_kv_host,
                                                           const int32_t *__restrict__ d_n_kv, int n_kv_max, int causal, float *__restrict__ dst, int64_t ldd_tok,
                                                           int64_t ldd_head, const attn_var vo) {
     const int t = blockIdx.x / n_head, h = blockIdx.x - t * n_head;
     const int n_kv = device_count(d_n_kv, n_kv_host, n_kv_max);
-    attn_merge_row<D, true>(work + (int64_t)blockIdx.x * n_chunks_max * (D + 4), t, n_q, n_kv, causal,
-                            dst + (int64_t)t * ldd_tok + (int64_t)h * ldd_head + threadIdx.x, h, vo);
+    attn_merge_row<D, true, MSK>(work + (int64_t)blockIdx.x * n_chunks_max * (D + 4), t, n_q, n_kv, causal,
+                                 dst + (int64_t)t * ldd_tok + (int64_t)h * ldd_head + threadIdx.x, h, vo);
 }
 
 // 1 where one of the entries [first, ceil(n_kv / 128)) of a sequence's table row lies outside [0, n_pages), the same answer in every thread
@@ -531,7 +597,7 @@ __global__ __launch_bounds__(D) void attn_merge_paged_kernel(const float *__rest
     attn_merge_row<D, false>(work + (int64_t)blockIdx.x * n_chunks_max * (D + 4), t, n_q, n_kv, causal, out, h, attn_var{});
 }
 
-template <int D>
+template <int D, bool MSK>
 __global__ __launch_bounds__(D) void attn_merge_paged_ex_kernel(const float *__restrict__ work, int n_chunks_max, int n_head, int n_q, const kv_pages pg,
                                                                 int len_bias, int causal, float *__restrict__ dst, int64_t ldd_tok, int64_t ldd_head,
                                                                 const attn_var vo) {
@@ -541,7 +607,7 @@ __global__ __launch_bounds__(D) void attn_merge_paged_ex_kernel(const float *__r
     float *out = dst + (int64_t)bt * ldd_tok + (int64_t)h * ldd_head + threadIdx.x;
     const int c_lo = window_lo(visible(0, n_kv, n_q, causal), vo.window) / C;
     if (paged_any_invalid<D>(pg.pages + (int64_t)b * pg.ld_pages, c_lo, n_kv, pg.n_pages)) { *out = 0.0f; return; }
-    attn_merge_row<D, true>(work + (int64_t)blockIdx.x * n_chunks_max * (D + 4), t, n_q, n_kv, causal, out, h, vo);
+    attn_merge_row<D, true, MSK>(work + (int64_t)blockIdx.x * n_chunks_max * (D + 4), t, n_q, n_kv, causal, out, h, vo);
 }
 
 // ------------------------------------------------------------------------------------------------ PROMPT form
@@ -573,11 +639,15 @@ __device__ __forceinline__ f16x8 stage_load8(const uint8_t *row, int d8) {      
 // PAGED: chunk c lies at pool + pages[c] * nb_page (pages: the sequence's table row, its first ceil(n_kv / 128) entries checked by the caller); otherwise at cache + 128 c * nb_pos.  Nothing else knows where a chunk lies.
 // VAR (the _ex kernels): a lane's visible range is [lo, vis), the workgroup starts at the chunk of its first row's lo and a wave skips the
 // chunks wholly below its first row's lo; the score may be soft-capped; head h's sink joins the denominator after the last chunk.
-template <bool Q8, int D, bool PAGED, bool VAR>
+// MSK (the mask kernels, always with VAR): mrow0 / ld as in attn_decode_chunk.  The lane's positions of register group (ct, i >> 2) are four consecutive
+// columns of ITS OWN mask row from column j0 + 32 ct + 8 (i >> 2) + 4 hh (a multiple of 4; ld % 8 == 0 and a 16-byte aligned base: one 8-byte load, read
+// only where the first column is below the lane's vis <= n_kv <= ld; all 16 pieces of a chunk are issued before its stage).  -inf: invisible (the element mask); otherwise s = fma(slope_h, mask, s).
+template <bool Q8, int D, bool PAGED, bool VAR, bool MSK = false>
 __device__ __forceinline__ void attn_prompt_tile(uint8_t *lds, const float *__restrict__ q, int64_t ldq_tok, int64_t ldq_head, const uint8_t *__restrict__ kc,
                                                  const uint8_t *__restrict__ vc, int64_t nb_pos, int64_t nb_head, const int32_t *__restrict__ pages,
                                                  int64_t nb_page, int G, int n_q, int n_kv, int tile, int h, int causal, float scale, float *__restrict__ dst,
-                                                 int64_t ldd_tok, int64_t ldd_head, const attn_var &vo) {
+                                                 int64_t ldd_tok, int64_t ldd_head, const attn_var &vo, const attn_bias &bs = attn_bias{}) {
+    static_assert(!MSK || VAR, "the mask kernels run the VAR bodies");
     constexpr int KS = prompt_k_stride<D>(), VS = PROMPT_VT_STRIDE, NKS = D / 16, NDT = D / 32, NCT = C / 32;
     uint8_t *kst = lds, *vt = lds + C * KS;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, r = lane & 31, hh = lane >> 5;
@@ -611,10 +681,27 @@ __device__ __forceinline__ void attn_prompt_tile(uint8_t *lds, const float *__re
         for (int i = 0; i < 16; ++i) o[dt][i] = 0.0f;
     const float ninf = -__builtin_inff();
     float m = ninf, l = 0.0f;
+    const uint16_t *mrow = nullptr;
+    float slope = 1.0f;
+    if constexpr (MSK) {
+        mrow = bs.mask + (int64_t)tq * bs.ld;
+        if (bs.slopes) slope = bs.slopes[h];
+    }
     const int nc = (wg_vis + C - 1) / C;
     for (int c = c_first; c < nc; ++c) {
         const int j0 = c * C, cnt = min(C, n_kv - j0);               // (j0 < wg_vis <= n_kv: cnt >= 1)
         if (c > c_first) __syncthreads();                                  // (every wave is done with the previous stage)
+        f16x4 mw[NCT][4];                                            // MSK: the 16 8-byte pieces of this lane's mask row under the chunk, in flight under the stage
+        if constexpr (MSK) {
+            const _Float16 hninf = (_Float16)(-__builtin_inff());
+#pragma unroll
+            for (int ct = 0; ct < NCT; ++ct)
+#pragma unroll
+                for (int g = 0; g < 4; ++g) {
+                    const int col = j0 + 32 * ct + 8 * g + 4 * hh;
+                    mw[ct][g] = col < vis ? *(const f16x4 *)(mrow + col) : f16x4{hninf, hninf, hninf, hninf};
+                }
+        }
         // ---- stage: K rows as they lie, V transposed; 16 bytes of f16 per item, consecutive lanes along a row ----
         {
             const int64_t off = (PAGED ? (int64_t)pages[c] * nb_page : (int64_t)j0 * nb_pos) + (int64_t)hk * nb_head;
@@ -651,17 +738,34 @@ __device__ __forceinline__ void attn_prompt_tile(uint8_t *lds, const float *__re
         }
         // ---- the online softmax of this lane's query; register i of a tile is row (i & 3) + 8 (i >> 2) + 4 hh ----
         float cm = ninf;
+        if constexpr (MSK) {                                         // the score first, the cap decided ONCE per chunk (a branch, not 64 selects around tanhf)
+            if (vo.cap != 0.0f) {
 #pragma unroll
-        for (int ct = 0; ct < NCT; ++ct)
+                for (int ct = 0; ct < NCT; ++ct)
+#pragma unroll
+                    for (int i = 0; i < 16; ++i) s[ct][i] = vo.cap * tanhf(vo.sc * s[ct][i]);
+            } else {
+#pragma unroll
+                for (int ct = 0; ct < NCT; ++ct)
+#pragma unroll
+                    for (int i = 0; i < 16; ++i) s[ct][i] = scale * s[ct][i];
+            }
+        }
+#pragma unroll
+        for (int ct = 0; ct < NCT; ++ct) {
 #pragma unroll
             for (int i = 0; i < 16; ++i) {
                 const int j = j0 + 32 * ct + (i & 3) + 8 * (i >> 2) + 4 * hh;
                 float v;
-                if constexpr (VAR) v = (j < vis && j >= lo) ? (vo.cap != 0.0f ? vo.cap * tanhf(vo.sc * s[ct][i]) : scale * s[ct][i]) : ninf;
+                if constexpr (MSK) {
+                    const float mk = (float)mw[ct][i >> 2][i & 3];       // (exact)
+                    v = (j < vis && j >= lo && mk != ninf) ? fmaf(slope, mk, s[ct][i]) : ninf;
+                } else if constexpr (VAR) v = (j < vis && j >= lo) ? (vo.cap != 0.0f ? vo.cap * tanhf(vo.sc * s[ct][i]) : scale * s[ct][i]) : ninf;
                 else v = j < vis ? scale * s[ct][i] : ninf;
                 s[ct][i] = v;
                 cm = fmaxf(cm, v);
             }
+        }
         cm = fmaxf(cm, __shfl_xor(cm, 32));
         const float mn = fmaxf(m, cm);
         const bool any = mn != ninf;                                 // (false: this query has seen no visible position yet)
@@ -733,15 +837,15 @@ __global__ __launch_bounds__(256) void attn_prompt_kernel(const float *__restric
                                           ldd_tok, ldd_head, attn_var{});
 }
 
-template <bool Q8, int D>
+template <bool Q8, int D, bool MSK>
 __global__ __launch_bounds__(256) void attn_prompt_ex_kernel(const float *__restrict__ q, int64_t ldq_tok, int64_t ldq_head, const uint8_t *__restrict__ kc,
                                                              const uint8_t *__restrict__ vc, int64_t nb_pos, int64_t nb_head, int G, int n_q, int n_kv_host,
                                                              const int32_t *__restrict__ d_n_kv, int n_kv_max, int causal, float scale, float *__restrict__ dst,
-                                                             int64_t ldd_tok, int64_t ldd_head, const attn_var vo) {
+                                                             int64_t ldd_tok, int64_t ldd_head, const attn_var vo, const attn_bias bs) {
     extern __shared__ __attribute__((aligned(16))) uint8_t lds[];
     const int n_kv = device_count(d_n_kv, n_kv_host, n_kv_max);
-    attn_prompt_tile<Q8, D, false, true>(lds, q, ldq_tok, ldq_head, kc, vc, nb_pos, nb_head, nullptr, 0, G, n_q, n_kv, (int)blockIdx.x, (int)blockIdx.y, causal, scale, dst,
-                                         ldd_tok, ldd_head, vo);
+    attn_prompt_tile<Q8, D, false, true, MSK>(lds, q, ldq_tok, ldq_head, kc, vc, nb_pos, nb_head, nullptr, 0, G, n_q, n_kv, (int)blockIdx.x, (int)blockIdx.y, causal, scale, dst,
+                                              ldd_tok, ldd_head, vo, bs);
 }
 
 // the paged PROMPT kernel: grid (query tiles) x (heads) x (sequences).  The workgroup scans its sequence's needed page ids before its first
@@ -749,11 +853,11 @@ __global__ __launch_bounds__(256) void attn_prompt_ex_kernel(const float *__rest
 // VAR (the _ex kernel): the scan starts at c_lo[b], the chunk of the sequence's row 0's first visible position; the body reads no entry below it
 // b, row0, n_q, n_kv: the sequence, its first row of q / dst, its rows and its clamped length; tile, h: the workgroup's query tile and head -- all the
 // caller's (the paged kernels: blockIdx and b * n_q; the ragged kernel: its tile list and the index tables)
-template <bool Q8, int D, bool VAR>
+template <bool Q8, int D, bool VAR, bool MSK = false>
 __device__ __forceinline__ void attn_prompt_paged_body(uint8_t *lds, const float *__restrict__ q, int64_t ldq_tok, int64_t ldq_head, const uint8_t *__restrict__ kc,
                                                        const uint8_t *__restrict__ vc, int64_t nb_pos, int64_t nb_head, int G, int n_q, const kv_pages &pg, int b,
                                                        int64_t row0, int n_kv, int tile, int h, int causal, float scale, float *__restrict__ dst,
-                                                       int64_t ldd_tok, int64_t ldd_head, const attn_var &vo) {
+                                                       int64_t ldd_tok, int64_t ldd_head, const attn_var &vo, const attn_bias &bs = attn_bias{}) {
     const int32_t *pages = pg.pages + (int64_t)b * pg.ld_pages;
     float *dst_b = dst + row0 * ldd_tok;
     int c_lo = 0;
@@ -767,8 +871,10 @@ __device__ __forceinline__ void attn_prompt_paged_body(uint8_t *lds, const float
         }
         return;
     }
-    attn_prompt_tile<Q8, D, true, VAR>(lds, q + row0 * ldq_tok, ldq_tok, ldq_head, kc, vc, nb_pos, nb_head, pages, pg.nb_page, G, n_q, n_kv, tile, h, causal, scale,
-                                       dst_b, ldd_tok, ldd_head, vo);
+    attn_bias bb = bs;
+    if constexpr (MSK) bb.mask += row0 * bs.ld;                      // (the sequence's first mask row, as q)
+    attn_prompt_tile<Q8, D, true, VAR, MSK>(lds, q + row0 * ldq_tok, ldq_tok, ldq_head, kc, vc, nb_pos, nb_head, pages, pg.nb_page, G, n_q, n_kv, tile, h, causal, scale,
+                                            dst_b, ldd_tok, ldd_head, vo, bb);
 }
 
 template <bool Q8, int D>
@@ -782,15 +888,15 @@ __global__ __launch_bounds__(256) void attn_prompt_paged_kernel(const float *__r
                                          (int)blockIdx.x, (int)blockIdx.y, causal, scale, dst, ldd_tok, ldd_head, attn_var{});
 }
 
-template <bool Q8, int D>
+template <bool Q8, int D, bool MSK>
 __global__ __launch_bounds__(256) void attn_prompt_paged_ex_kernel(const float *__restrict__ q, int64_t ldq_tok, int64_t ldq_head, const uint8_t *__restrict__ kc,
                                                                    const uint8_t *__restrict__ vc, int64_t nb_pos, int64_t nb_head, int G, int n_q,
                                                                    const kv_pages pg, int len_bias, int causal, float scale, float *__restrict__ dst,
-                                                                   int64_t ldd_tok, int64_t ldd_head, const attn_var vo) {
+                                                                   int64_t ldd_tok, int64_t ldd_head, const attn_var vo, const attn_bias bs) {
     extern __shared__ __attribute__((aligned(16))) uint8_t lds[];
     const int b = blockIdx.z;
-    attn_prompt_paged_body<Q8, D, true>(lds, q, ldq_tok, ldq_head, kc, vc, nb_pos, nb_head, G, n_q, pg, b, (int64_t)b * n_q, paged_count(pg, b, len_bias),
-                                        (int)blockIdx.x, (int)blockIdx.y, causal, scale, dst, ldd_tok, ldd_head, vo);
+    attn_prompt_paged_body<Q8, D, true, MSK>(lds, q, ldq_tok, ldq_head, kc, vc, nb_pos, nb_head, G, n_q, pg, b, (int64_t)b * n_q, paged_count(pg, b, len_bias),
+                                             (int)blockIdx.x, (int)blockIdx.y, causal, scale, dst, ldd_tok, ldd_head, vo, bs);
 }
 
 // ------------------------------------------------------------------------------------------------ RAGGED
@@ -893,11 +999,11 @@ __global__ __launch_bounds__(RAG_NT) void attn_ragged_index_kernel(const kv_ragg
 // LAUNCH 2, the grid of attn_decode_paged_kernel / attn_decode_paged_ex_kernel: (chunks) x (kv heads) x (sequences).  A workgroup whose sequence is
 // not DECODE or has no slot leaves before its first barrier; otherwise those kernels' guards and the chunk body with the sequence's own n_q, its
 // rows of q from its first packed row and its partials from its first row slot.
-template <bool Q8, int D, bool VAR>
+template <bool Q8, int D, bool VAR, bool MSK>
 __global__ __launch_bounds__(256) void attn_decode_ragged_kernel(const float *__restrict__ q, int64_t ldq_tok, int64_t ldq_head, const uint8_t *__restrict__ kc,
                                                                  const uint8_t *__restrict__ vc, int64_t nb_pos, int64_t nb_head, int n_head, int G,
                                                                  const kv_pages pg, const int4 *__restrict__ seq, int add_q, int len_bias, int causal, float scale,
-                                                                 float *__restrict__ work, int n_chunks_max, const attn_var vo) {
+                                                                 float *__restrict__ work, int n_chunks_max, const attn_var vo, const attn_bias bs) {
     extern __shared__ __attribute__((aligned(16))) uint8_t lds[];
     const int hk = blockIdx.y, b = blockIdx.z;
     const int4 sq = seq[b];
@@ -910,12 +1016,14 @@ __global__ __launch_bounds__(256) void attn_decode_ragged_kernel(const float *__
     const int page = pg.pages[(int64_t)b * pg.ld_pages + c];         // (c < ceil(n_kv[b] / 128) <= ld_pages)
     if (page < 0 || page >= pg.n_pages) return;                      // (before any address is formed from it; the merge writes zeros)
     const int64_t off = (int64_t)page * pg.nb_page + (int64_t)hk * nb_head;
-    attn_decode_chunk<Q8, D, VAR>(lds, q + (int64_t)sq.y * ldq_tok, ldq_tok, ldq_head, kc + off, vc + off, nb_pos, n_head, G, n_q, n_kv, c, (int)blockIdx.x, hk,
-                                  causal, scale, work + (int64_t)sq.x * n_head * n_chunks_max * (D + 4), n_chunks_max, vo);
+    attn_bias bb = bs;
+    if constexpr (MSK) bb.mask += (int64_t)sq.y * bs.ld;             // (the sequence's first packed row, as q)
+    attn_decode_chunk<Q8, D, VAR, MSK>(lds, q + (int64_t)sq.y * ldq_tok, ldq_tok, ldq_head, kc + off, vc + off, nb_pos, n_head, G, n_q, n_kv, c, (int)blockIdx.x, hk,
+                                       causal, scale, work + (int64_t)sq.x * n_head * n_chunks_max * (D + 4), n_chunks_max, vo, bb);
 }
 
 // LAUNCH 3, one workgroup per row slot and head, blockIdx.x = slot * n_head + h: the paged merge (its id scan, its zero row) for the slot's (b, t)
-template <int D, bool VAR>
+template <int D, bool VAR, bool MSK>
 __global__ __launch_bounds__(D) void attn_merge_ragged_kernel(const float *__restrict__ work, int n_chunks_max, int n_head, const kv_pages pg,
                                                               const int4 *__restrict__ seq, const int2 *__restrict__ slots, int add_q, int len_bias, int causal,
                                                               float *__restrict__ dst, int64_t ldd_tok, int64_t ldd_head, const attn_var vo) {
@@ -929,27 +1037,28 @@ __global__ __launch_bounds__(D) void attn_merge_ragged_kernel(const float *__res
     int c_lo = 0;
     if constexpr (VAR) c_lo = window_lo(visible(0, n_kv, n_q, causal), vo.window) / C;
     if (paged_any_invalid<D>(pg.pages + (int64_t)bt.x * pg.ld_pages, c_lo, n_kv, pg.n_pages)) { *out = 0.0f; return; }
-    attn_merge_row<D, VAR>(work + (int64_t)blockIdx.x * n_chunks_max * (D + 4), bt.y, n_q, n_kv, causal, out, h, vo);
+    attn_merge_row<D, VAR, MSK>(work + (int64_t)blockIdx.x * n_chunks_max * (D + 4), bt.y, n_q, n_kv, causal, out, h, vo);
 }
 
 // LAUNCH 4, grid (heads) x (tile bound): a workgroup past the list's length leaves at once, otherwise the paged PROMPT body for its (b, tile).  The heads
 // are the grid's x so that the list is walked in dispatch order: every entry past its length comes AFTER the last tile.  With the list on x the
 // empty workgroups of one head stood in front of the next head's tiles, each waiting for a whole CU's registers only to leave (measured: DESIGN.md 22).
-template <bool Q8, int D, bool VAR>
+template <bool Q8, int D, bool VAR, bool MSK>
 __global__ __launch_bounds__(256) void attn_prompt_ragged_kernel(const float *__restrict__ q, int64_t ldq_tok, int64_t ldq_head, const uint8_t *__restrict__ kc,
                                                                  const uint8_t *__restrict__ vc, int64_t nb_pos, int64_t nb_head, int G, const kv_pages pg,
                                                                  const int4 *__restrict__ seq, const int2 *__restrict__ tiles, const int32_t *__restrict__ n_tiles,
                                                                  int add_q, int len_bias, int causal, float scale, float *__restrict__ dst, int64_t ldd_tok,
-                                                                 int64_t ldd_head, const attn_var vo) {
+                                                                 int64_t ldd_head, const attn_var vo, const attn_bias bs) {
     extern __shared__ __attribute__((aligned(16))) uint8_t lds[];
     if ((int)blockIdx.y >= *n_tiles) return;
     const int2 bt = tiles[blockIdx.y];
     const int4 sq = seq[bt.x];
-    attn_prompt_paged_body<Q8, D, VAR>(lds, q, ldq_tok, ldq_head, kc, vc, nb_pos, nb_head, G, sq.z, pg, bt.x, (int64_t)sq.y, ragged_count(pg, bt.x, sq.z, add_q, len_bias),
-                                       bt.y, (int)blockIdx.x, causal, scale, dst, ldd_tok, ldd_head, vo);
+    attn_prompt_paged_body<Q8, D, VAR, MSK>(lds, q, ldq_tok, ldq_head, kc, vc, nb_pos, nb_head, G, sq.z, pg, bt.x, (int64_t)sq.y, ragged_count(pg, bt.x, sq.z, add_q, len_bias),
+                                            bt.y, (int)blockIdx.x, causal, scale, dst, ldd_tok, ldd_head, vo, bs);
 }
 
-template <bool Q8, int D> constexpr int decode_lds() { return 2 * C * stage_stride<Q8>(D) + DEC_RT * D * 4 + DEC_RT * C * 4; }
+// (+ 64: the mask kernels' [DEC_RT][2] first / last positions behind the scores)
+template <bool Q8, int D, bool MSK = false> constexpr int decode_lds() { return 2 * C * stage_stride<Q8>(D) + DEC_RT * D * 4 + DEC_RT * C * 4 + (MSK ? 64 : 0); }
 
 }  // namespace
 
@@ -997,8 +1106,9 @@ hipError_t launch_kv_store_paged_ragged(int kv_type, const float *src, int64_t l
 }
 
 // every grid and every offset into the work buffer is the plan's (plan_attn_ragged); a launch whose grid the bounds leave empty is not made
+// bs: the mask kernels (always the VAR bodies; var is then not read)
 hipError_t launch_attn_paged_ragged(const attn_ragged_plan &pl, const attn_args &a, const kv_ragged &rg, const kv_pages &pg, int add_q, int len_bias, bool var,
-                                    const attn_var &vo, hipStream_t st) {
+                                    const attn_var &vo, hipStream_t st, const attn_bias *bs) {
     if (pl.launches == 0) return hipSuccess;
     const bool q8 = a.kv_type == GGML_TYPE_Q8_0;
     const int G = a.n_head / a.n_head_kv;
@@ -1012,28 +1122,30 @@ hipError_t launch_attn_paged_ragged(const attn_ragged_plan &pl, const attn_args 
                                                         a.D);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
-#define RAGGED(Q, DD, V)                                                                                                                               \
+    const attn_bias bv = bs ? *bs : attn_bias{};
+#define RAGGED(Q, DD, V, MK)                                                                                                                           \
     do {                                                                                                                                              \
         if (pl.decode_wgs > 0) {                                                                                                                      \
-            e = launch_lds(kfn<attn_decode_ragged_kernel<Q, DD, V>>, dim3((unsigned)pl.n_chunks, (unsigned)a.n_head_kv, (unsigned)rg.n_seq), dim3(256), \
-                           (size_t)decode_lds<Q, DD>(), decode_lds<Q, DD>(), st, a.q, a.ldq_tok, a.ldq_head, kc, vc, a.nb_pos, a.nb_head, a.n_head, G, pg, \
-                           (const int4 *)seq, add_q, len_bias, a.causal, a.scale, part, (int)pl.n_chunks, vo);                                        \
+            e = launch_lds(kfn<attn_decode_ragged_kernel<Q, DD, V, MK>>, dim3((unsigned)pl.n_chunks, (unsigned)a.n_head_kv, (unsigned)rg.n_seq), dim3(256), \
+                           (size_t)decode_lds<Q, DD, MK>(), decode_lds<Q, DD, MK>(), st, a.q, a.ldq_tok, a.ldq_head, kc, vc, a.nb_pos, a.nb_head, a.n_head, G, pg, \
+                           (const int4 *)seq, add_q, len_bias, a.causal, a.scale, part, (int)pl.n_chunks, vo, bv);                                    \
             if (e != hipSuccess) return e;                                                                                                            \
         }                                                                                                                                             \
         if (pl.merge_wgs > 0)                                                                                                                         \
-            attn_merge_ragged_kernel<DD, V><<<dim3((unsigned)pl.merge_wgs), DD, 0, st>>>(part, (int)pl.n_chunks, a.n_head, pg, seq, slots, add_q, len_bias, \
-                                                                                        a.causal, a.dst, a.ldd_tok, a.ldd_head, vo);                  \
+            attn_merge_ragged_kernel<DD, V, MK><<<dim3((unsigned)pl.merge_wgs), DD, 0, st>>>(part, (int)pl.n_chunks, a.n_head, pg, seq, slots, add_q, len_bias, \
+                                                                                            a.causal, a.dst, a.ldd_tok, a.ldd_head, vo);              \
         if (pl.prompt_wgs > 0) {                                                                                                                      \
-            e = launch_lds(kfn<attn_prompt_ragged_kernel<Q, DD, V>>, dim3((unsigned)a.n_head, (unsigned)pl.max_tiles), dim3(256), (size_t)prompt_lds<DD>(), \
+            e = launch_lds(kfn<attn_prompt_ragged_kernel<Q, DD, V, MK>>, dim3((unsigned)a.n_head, (unsigned)pl.max_tiles), dim3(256), (size_t)prompt_lds<DD>(), \
                            prompt_lds<DD>(), st, a.q, a.ldq_tok, a.ldq_head, kc, vc, a.nb_pos, a.nb_head, G, pg, (const int4 *)seq, (const int2 *)tiles, \
-                           (const int32_t *)n_tiles, add_q, len_bias, a.causal, a.scale, a.dst, a.ldd_tok, a.ldd_head, vo);                           \
+                           (const int32_t *)n_tiles, add_q, len_bias, a.causal, a.scale, a.dst, a.ldd_tok, a.ldd_head, vo, bv);                       \
             if (e != hipSuccess) return e;                                                                                                            \
         }                                                                                                                                             \
     } while (0)
 #define RAGGED_V(Q, DD)                                                                                                                                \
     do {                                                                                                                                              \
-        if (var) RAGGED(Q, DD, true);                                                                                                                 \
-        else RAGGED(Q, DD, false);                                                                                                                    \
+        if (bs) RAGGED(Q, DD, true, true);                                                                                                            \
+        else if (var) RAGGED(Q, DD, true, false);                                                                                                     \
+        else RAGGED(Q, DD, false, false);                                                                                                             \
     } while (0)
     if (q8 && a.D == 64) RAGGED_V(true, 64);
     else if (q8) RAGGED_V(true, 128);
@@ -1046,76 +1158,104 @@ hipError_t launch_attn_paged_ragged(const attn_ragged_plan &pl, const attn_args 
 
 // the grids are the plan's: DECODE pl.n_chunks x kv heads x sequences and one merge workgroup per row; PROMPT query tiles x heads x sequences
 // the _ex launches: the same grids from plan_attn_ex / plan_attn_paged_ex (a windowed DECODE grid follows the window), the _ex kernels, vo by value
-hipError_t launch_attn_paged_ex(const attn_plan &pl, const attn_args &a, int64_t n_seq, const kv_pages &pg, int len_bias, const attn_var &vo, hipStream_t st) {
+// bs: null the _ex kernels (MSK = false), otherwise the mask kernels; the same grids
+hipError_t launch_attn_paged_ex(const attn_plan &pl, const attn_args &a, int64_t n_seq, const kv_pages &pg, int len_bias, const attn_var &vo, hipStream_t st,
+                                const attn_bias *bs) {
+    const attn_bias bv = bs ? *bs : attn_bias{};
     const bool q8 = a.kv_type == GGML_TYPE_Q8_0;
     const int G = a.n_head / a.n_head_kv;
     const uint8_t *kc = (const uint8_t *)a.k, *vc = (const uint8_t *)a.v;
     if (pl.form == ATTN_FORM_DECODE) {
         const dim3 grid((unsigned)pl.n_chunks, (unsigned)a.n_head_kv, (unsigned)n_seq);
         float *work = (float *)a.work;
-#define DECODE(Q, DD)                                                                                                                                 \
+#define DECODE_M(Q, DD, MK)                                                                                                                           \
     do {                                                                                                                                              \
         if (pl.n_chunks > 0) {                                                                                                                        \
-            hipError_t e = launch_lds(kfn<attn_decode_paged_ex_kernel<Q, DD>>, grid, dim3(256), (size_t)decode_lds<Q, DD>(), decode_lds<Q, DD>(), st, a.q, \
+            hipError_t e = launch_lds(kfn<attn_decode_paged_ex_kernel<Q, DD, MK>>, grid, dim3(256), (size_t)decode_lds<Q, DD, MK>(), decode_lds<Q, DD, MK>(), st, a.q, \
                                       a.ldq_tok, a.ldq_head, kc, vc, a.nb_pos, a.nb_head, a.n_head, G, (int)a.n_q, pg, len_bias, a.causal, a.scale, work, \
-                                      (int)pl.n_chunks, vo);                                                                                          \
+                                      (int)pl.n_chunks, vo, bv);                                                                                      \
             if (e != hipSuccess) return e;                                                                                                            \
         }                                                                                                                                             \
-        attn_merge_paged_ex_kernel<DD><<<dim3((unsigned)(n_seq * a.n_q * a.n_head)), DD, 0, st>>>(work, (int)pl.n_chunks, a.n_head, (int)a.n_q, pg, len_bias, \
-                                                                                                 a.causal, a.dst, a.ldd_tok, a.ldd_head, vo);         \
+        attn_merge_paged_ex_kernel<DD, MK><<<dim3((unsigned)(n_seq * a.n_q * a.n_head)), DD, 0, st>>>(work, (int)pl.n_chunks, a.n_head, (int)a.n_q, pg, len_bias, \
+                                                                                                     a.causal, a.dst, a.ldd_tok, a.ldd_head, vo);     \
+    } while (0)
+#define DECODE(Q, DD)                                                                                                                                 \
+    do {                                                                                                                                              \
+        if (bs) DECODE_M(Q, DD, true);                                                                                                                \
+        else DECODE_M(Q, DD, false);                                                                                                                  \
     } while (0)
         if (q8 && a.D == 64) DECODE(true, 64);
         else if (q8) DECODE(true, 128);
         else if (a.D == 64) DECODE(false, 64);
         else DECODE(false, 128);
 #undef DECODE
+#undef DECODE_M
         return hipGetLastError();
     }
     const dim3 grid((unsigned)((a.n_q + 127) / 128), (unsigned)a.n_head, (unsigned)n_seq);
+#define PROMPT_M(Q, DD, MK)                                                                                                                            \
+    return launch_lds(kfn<attn_prompt_paged_ex_kernel<Q, DD, MK>>, grid, dim3(256), (size_t)prompt_lds<DD>(), prompt_lds<DD>(), st, a.q, a.ldq_tok, a.ldq_head, \
+                      kc, vc, a.nb_pos, a.nb_head, G, (int)a.n_q, pg, len_bias, a.causal, a.scale, a.dst, a.ldd_tok, a.ldd_head, vo, bv)
 #define PROMPT(Q, DD)                                                                                                                                  \
-    return launch_lds(kfn<attn_prompt_paged_ex_kernel<Q, DD>>, grid, dim3(256), (size_t)prompt_lds<DD>(), prompt_lds<DD>(), st, a.q, a.ldq_tok, a.ldq_head, \
-                      kc, vc, a.nb_pos, a.nb_head, G, (int)a.n_q, pg, len_bias, a.causal, a.scale, a.dst, a.ldd_tok, a.ldd_head, vo)
+    do {                                                                                                                                              \
+        if (bs) PROMPT_M(Q, DD, true);                                                                                                                \
+        else PROMPT_M(Q, DD, false);                                                                                                                  \
+    } while (0)
     if (q8 && a.D == 64) PROMPT(true, 64);
     else if (q8) PROMPT(true, 128);
     else if (a.D == 64) PROMPT(false, 64);
     else PROMPT(false, 128);
 #undef PROMPT
+#undef PROMPT_M
 }
 
-hipError_t launch_attn_ex(const attn_plan &pl, const attn_args &a, const attn_var &vo, hipStream_t st) {
+hipError_t launch_attn_ex(const attn_plan &pl, const attn_args &a, const attn_var &vo, hipStream_t st, const attn_bias *bs) {
+    const attn_bias bv = bs ? *bs : attn_bias{};
     const bool q8 = a.kv_type == GGML_TYPE_Q8_0;
     const int G = a.n_head / a.n_head_kv;
     const uint8_t *kc = (const uint8_t *)a.k, *vc = (const uint8_t *)a.v;
     if (pl.form == ATTN_FORM_DECODE) {
         const dim3 grid((unsigned)pl.n_chunks, (unsigned)a.n_head_kv);
         float *work = (float *)a.work;
-#define DECODE(Q, DD)                                                                                                                                 \
+#define DECODE_M(Q, DD, MK)                                                                                                                           \
     do {                                                                                                                                              \
         if (pl.n_chunks > 0) {                                                                                                                        \
-            hipError_t e = launch_lds(kfn<attn_decode_ex_kernel<Q, DD>>, grid, dim3(256), (size_t)decode_lds<Q, DD>(), decode_lds<Q, DD>(), st, a.q,   \
+            hipError_t e = launch_lds(kfn<attn_decode_ex_kernel<Q, DD, MK>>, grid, dim3(256), (size_t)decode_lds<Q, DD, MK>(), decode_lds<Q, DD, MK>(), st, a.q, \
                                       a.ldq_tok, a.ldq_head, kc, vc, a.nb_pos, a.nb_head, a.n_head, G, (int)a.n_q, (int)a.n_kv, a.d_n_kv, (int)a.n_kv_max, \
-                                      a.causal, a.scale, work, (int)pl.n_chunks, vo);                                                                 \
+                                      a.causal, a.scale, work, (int)pl.n_chunks, vo, bv);                                                             \
             if (e != hipSuccess) return e;                                                                                                            \
         }                                                                                                                                             \
-        attn_merge_ex_kernel<DD><<<dim3((unsigned)(a.n_q * a.n_head)), DD, 0, st>>>(work, (int)pl.n_chunks, a.n_head, (int)a.n_q, (int)a.n_kv, a.d_n_kv, \
-                                                                                   (int)a.n_kv_max, a.causal, a.dst, a.ldd_tok, a.ldd_head, vo);      \
+        attn_merge_ex_kernel<DD, MK><<<dim3((unsigned)(a.n_q * a.n_head)), DD, 0, st>>>(work, (int)pl.n_chunks, a.n_head, (int)a.n_q, (int)a.n_kv, a.d_n_kv, \
+                                                                                       (int)a.n_kv_max, a.causal, a.dst, a.ldd_tok, a.ldd_head, vo);  \
+    } while (0)
+#define DECODE(Q, DD)                                                                                                                                 \
+    do {                                                                                                                                              \
+        if (bs) DECODE_M(Q, DD, true);                                                                                                                \
+        else DECODE_M(Q, DD, false);                                                                                                                  \
     } while (0)
         if (q8 && a.D == 64) DECODE(true, 64);
         else if (q8) DECODE(true, 128);
         else if (a.D == 64) DECODE(false, 64);
         else DECODE(false, 128);
 #undef DECODE
+#undef DECODE_M
         return hipGetLastError();
     }
     const dim3 grid((unsigned)((a.n_q + 127) / 128), (unsigned)a.n_head);
+#define PROMPT_M(Q, DD, MK)                                                                                                                            \
+    return launch_lds(kfn<attn_prompt_ex_kernel<Q, DD, MK>>, grid, dim3(256), (size_t)prompt_lds<DD>(), prompt_lds<DD>(), st, a.q, a.ldq_tok, a.ldq_head, kc, vc, \
+                      a.nb_pos, a.nb_head, G, (int)a.n_q, (int)a.n_kv, a.d_n_kv, (int)a.n_kv_max, a.causal, a.scale, a.dst, a.ldd_tok, a.ldd_head, vo, bv)
 #define PROMPT(Q, DD)                                                                                                                                  \
-    return launch_lds(kfn<attn_prompt_ex_kernel<Q, DD>>, grid, dim3(256), (size_t)prompt_lds<DD>(), prompt_lds<DD>(), st, a.q, a.ldq_tok, a.ldq_head, kc, vc, \
-                      a.nb_pos, a.nb_head, G, (int)a.n_q, (int)a.n_kv, a.d_n_kv, (int)a.n_kv_max, a.causal, a.scale, a.dst, a.ldd_tok, a.ldd_head, vo)
+    do {                                                                                                                                              \
+        if (bs) PROMPT_M(Q, DD, true);                                                                                                                \
+        else PROMPT_M(Q, DD, false);                                                                                                                  \
+    } while (0)
     if (q8 && a.D == 64) PROMPT(true, 64);
     else if (q8) PROMPT(true, 128);
     else if (a.D == 64) PROMPT(false, 64);
     else PROMPT(false, 128);
 #undef PROMPT
+#undef PROMPT_M
 }
 
 hipError_t launch_attn_paged(const attn_plan &pl, const attn_args &a, int64_t n_seq, const kv_pages &pg, int len_bias, hipStream_t st) {

@@ -452,8 +452,12 @@ hipError_t launch_attn(const attn_plan &pl, const attn_args &a, hipStream_t st);
 // The options of the _ex entries (ggml_hip_attn_ex_dev, ggml_hip_attn_paged_ex_dev), by value to the _ex kernels: sinks f32 [n_head] or null;
 // window 0 (none) or W >= 1 (row at position P sees j with P - j < W; clamped to 2^30 by the entry); cap 0 (none) or > 0 with sc = scale / cap
 struct attn_var { const float *sinks; int window; float cap, sc; };
+// The mask and the ALiBi slopes of the _bias entries (ggml_hip_attn_bias_dev and its paged / ragged twins), by value to the mask kernels: mask f16
+// [rows][ld] (the bits of IEEE halves; row = the query's row index in q, column = the position), never null here; slopes f32 [n_head] or null (1.0f)
+struct attn_bias { const uint16_t *mask; int64_t ld; const float *slopes; };
 // pl: plan_attn_ex's (a windowed DECODE grid holds the chunks the window can touch, workgroup x serves chunk c_lo + x)
-hipError_t launch_attn_ex(const attn_plan &pl, const attn_args &a, const attn_var &vo, hipStream_t st);
+// bs: null runs the _ex kernels; otherwise the mask kernels -- the VAR bodies with the mask (vo may have everything off)
+hipError_t launch_attn_ex(const attn_plan &pl, const attn_args &a, const attn_var &vo, hipStream_t st, const attn_bias *bs = nullptr);
 // The PAGED cache of the paged entries (ggml_hip_kv_store_paged_dev, ggml_hip_rope_kv_store_paged_dev, ggml_hip_attn_paged_dev): a pool of
 // n_pages pages of ATTN_CHUNK positions, nb_page bytes apart; entry c of sequence b's table row (ld_pages int32 apart) names the page of its
 // positions [128 c, 128 c + 128); len[b] is the positions it held before this step.  Goes to the kernels by value.
@@ -470,7 +474,8 @@ hipError_t launch_kv_store_paged(int kv_type, const float *src, int64_t ldx_tok,
 // pl: plan_attn_paged's
 hipError_t launch_attn_paged(const attn_plan &pl, const attn_args &a, int64_t n_seq, const kv_pages &pg, int len_bias, hipStream_t st);
 // pl: plan_attn_paged_ex's; table entries below a sequence's c_lo are never read
-hipError_t launch_attn_paged_ex(const attn_plan &pl, const attn_args &a, int64_t n_seq, const kv_pages &pg, int len_bias, const attn_var &vo, hipStream_t st);
+hipError_t launch_attn_paged_ex(const attn_plan &pl, const attn_args &a, int64_t n_seq, const kv_pages &pg, int len_bias, const attn_var &vo, hipStream_t st,
+                                const attn_bias *bs = nullptr);
 // The RAGGED batch of the ragged entries (ggml_hip_ragged_positions_dev, ggml_hip_kv_store_paged_ragged_dev, ggml_hip_rope_kv_store_paged_ragged_dev,
 // ggml_hip_attn_paged_ragged_dev): q_start int32 [n_seq + 1] on the device, prefix sums; sequence b owns the packed rows q_start[b] .. q_start[b+1] - 1 and
 // is PRESENT when 0 <= q_start[b] <= q_start[b+1] <= n_tokens_max.  Goes to the kernels by value.
@@ -502,7 +507,7 @@ hipError_t launch_kv_store_paged_ragged(int kv_type, const float *src, int64_t l
 // in front; n_kv[b] = clamp(len[b] + (add_q ? n_q[b] : 0) + len_bias, 0, n_kv_max).  pl: plan_attn_ragged's, every grid and offset; var: the VAR bodies, vo theirs
 struct attn_ragged_plan;
 hipError_t launch_attn_paged_ragged(const attn_ragged_plan &pl, const attn_args &a, const kv_ragged &rg, const kv_pages &pg, int add_q, int len_bias, bool var,
-                                    const attn_var &vo, hipStream_t st);
+                                    const attn_var &vo, hipStream_t st, const attn_bias *bs = nullptr);
 // rope.hip: the rotation of Q / K rows (ggml_hip_rope_dev) and the rotation fused with kv_store (ggml_hip_rope_kv_store_dev; rope.cpp).
 // The per-pair constants are the HOST's (ggml_hip_rope_table) and go to the kernels by value: eff[i] for pair i < n_dims / 2, and mscale
 #define ROPE_MAX_PAIRS 128

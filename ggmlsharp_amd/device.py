@@ -267,6 +267,27 @@ def attn_opts(window=0, softcap=0.0, sinks=None):
     return _lib.ggml_hip_attn_opts_t(sinks.data_ptr() if sinks is not None else None, int(window), float(softcap), 0)
 
 
+def alibi_slopes(n_head, max_bias):
+    """upstream's ALiBi slopes of n_head heads as a numpy f32 vector (ggml_hip_alibi_slopes: host only; max_bias 0 gives ones); upload it for slopes="""
+    out = np.empty(n_head, np.float32)
+    check(lib().ggml_hip_alibi_slopes(int(n_head), float(max_bias), out.ctypes.data_as(C.c_void_p)), "ggml_hip_alibi_slopes")
+    return out
+
+
+def attn_bias(mask=None, slopes=None):
+    """a ggml_hip_attn_bias_t, or None without a mask and slopes.  mask: an f16 tensor [rows, >= n_kv_max] on the device, last stride 1, row stride a
+    multiple of 8, row = the query's row index in q, column = the position (-inf: hidden; else added to the score times the head's slope); slopes:
+    f32 [n_head] on the device.  Both are kept alive by the caller."""
+    if mask is None and slopes is None:
+        return None
+    if mask is not None:
+        assert mask.is_cuda and mask.dtype == torch.float16 and mask.dim() == 2 and mask.stride(1) == 1
+    if slopes is not None:
+        assert slopes.is_cuda and slopes.dtype == torch.float32 and slopes.is_contiguous()
+    return _lib.ggml_hip_attn_bias_t(mask.data_ptr() if mask is not None else None, mask.stride(0) if mask is not None else 0,
+                                     slopes.data_ptr() if slopes is not None else None)
+
+
 def attn_ex_plan(kv_type, D, n_head, n_head_kv, n_q, n_kv_max, window=0, softcap=0.0):
     """attn_plan under the options: a windowed DECODE call has min(ceil(n_kv_max / 128), ceil((window + n_q - 1) / 128) + 1) chunks; no device needed"""
     out = _lib.ggml_hip_attn_plan_t()
@@ -276,13 +297,15 @@ def attn_ex_plan(kv_type, D, n_head, n_head_kv, n_q, n_kv_max, window=0, softcap
 
 
 def attention(kv_type, q, k, v, nb_pos, nb_head, n_head_kv, n_kv, d_n_kv=None, n_kv_max=None, causal=True, scale=None, out=None, work=None, window=0,
-              softcap=0.0, sinks=None):
+              softcap=0.0, sinks=None, mask=None, slopes=None):
     """out[t, h] = softmax_j(scale * q[t, h] . K[j, h / G]) V[j, h / G] over the visible j of an F16 / Q8_0 cache, on the current stream.
     q f32 [n_q, n_head, D] (last stride 1); k, v: uint8 tensors whose first byte is row (position 0, kv head 0), rows nb_pos / nb_head bytes
     apart; causal: the batch is the last n_q of the n_kv positions.  d_n_kv: an int32 tensor on the device read instead of n_kv (clamped to
     n_kv_max, which sizes the launch; default n_kv).  scale defaults to 1 / sqrt(D).
     window (0: none; W: a row at position P sees j with P - j < W), softcap (0: none) and sinks (f32 [n_head] on the device) go through
-    ggml_hip_attn_ex_dev; with all three off the call is ggml_hip_attn_dev as before."""
+    ggml_hip_attn_ex_dev; with all three off the call is ggml_hip_attn_dev as before.
+    mask (f16 [n_q, >= n_kv_max] on the device: -inf hides position j from row t, any other value is added to the score times the head's slope) and
+    slopes (f32 [n_head] on the device, alibi_slopes) go through ggml_hip_attn_bias_dev, with the options."""
     assert q.is_cuda and q.dtype == torch.float32 and q.dim() == 3 and q.stride(2) == 1
     assert k.is_cuda and v.is_cuda and k.dtype == torch.uint8 and v.dtype == torch.uint8
     assert d_n_kv is None or (d_n_kv.is_cuda and d_n_kv.dtype == torch.int32)
@@ -297,6 +320,14 @@ def attention(kv_type, q, k, v, nb_pos, nb_head, n_head_kv, n_kv, d_n_kv=None, n
     if work is None:
         work = torch.empty(max(attn_work_size(kv_type, D, n_head, n_head_kv, n_q, n_kv_max), 16), dtype=torch.uint8, device=q.device)
     opts = attn_opts(window, softcap, sinks)
+    bias = attn_bias(mask, slopes)
+    if bias is not None:
+        check(lib().ggml_hip_attn_bias_dev(kv_type, C.c_void_p(q.data_ptr()), q.stride(0), q.stride(1), C.c_void_p(k.data_ptr()), C.c_void_p(v.data_ptr()), nb_pos,
+                                           nb_head, n_head, n_head_kv, D, n_q, int(n_kv), C.c_void_p(d_n_kv.data_ptr()) if d_n_kv is not None else None, n_kv_max,
+                                           int(bool(causal)), float(scale), C.byref(opts) if opts is not None else None, C.byref(bias),
+                                           C.c_void_p(out.data_ptr()), out.stride(0), out.stride(1), C.c_void_p(work.data_ptr()), work.numel(), _stream()),
+              "ggml_hip_attn_bias_dev")
+        return out
     if opts is not None:
         check(lib().ggml_hip_attn_ex_dev(kv_type, C.c_void_p(q.data_ptr()), q.stride(0), q.stride(1), C.c_void_p(k.data_ptr()), C.c_void_p(v.data_ptr()), nb_pos,
                                          nb_head, n_head, n_head_kv, D, n_q, int(n_kv), C.c_void_p(d_n_kv.data_ptr()) if d_n_kv is not None else None, n_kv_max,
@@ -426,12 +457,14 @@ def attn_paged_ex_plan(kv_type, D, n_head, n_head_kv, n_seq, n_q, n_kv_max, wind
     return out
 
 
-def attn_paged(pc, q, n_head_kv, len_bias=0, causal=True, scale=None, out=None, work=None, window=0, softcap=0.0, sinks=None):
+def attn_paged(pc, q, n_head_kv, len_bias=0, causal=True, scale=None, out=None, work=None, window=0, softcap=0.0, sinks=None, mask=None, slopes=None):
     """attention of n_seq independent sequences over the paged cache pc in one call: q f32 [n_seq * n_q, n_head, D] (last stride 1), sequence b
     over its n_kv[b] = clamp(d_len[b] + len_bias, 0, n_kv_max) positions; its rows are bit for bit attention() on a contiguous copy of its cache.
     len_bias = n_q behind a store of this step's tokens.  A sequence with n_kv 0 or an invalid needed page id returns +0.0 rows.
     window, softcap, sinks: as attention(), through ggml_hip_attn_paged_ex_dev; under a window the table entries below a sequence's first
-    needed chunk are never read (the host may recycle those pages)."""
+    needed chunk are never read (the host may recycle those pages).
+    mask (f16 [n_seq * n_q, >= n_kv_max], row = the row of q, column = the position in that row's own sequence) and slopes: as attention(), through
+    ggml_hip_attn_paged_bias_dev."""
     assert q.is_cuda and q.dtype == torch.float32 and q.dim() == 3 and q.stride(2) == 1
     n_rows, n_head, D = q.shape
     assert n_rows % pc.n_seq == 0, "n_seq * n_q rows"
@@ -445,6 +478,14 @@ def attn_paged(pc, q, n_head_kv, len_bias=0, causal=True, scale=None, out=None, 
         work = torch.empty(max(attn_paged_work_size(pc.kv_type, D, n_head, n_head_kv, pc.n_seq, n_q, pc.n_kv_max), 16), dtype=torch.uint8, device=q.device)
     nbp, nbo, nbh, n_pages, d_pages, ld_pages, d_len = pc._args()
     opts = attn_opts(window, softcap, sinks)
+    bias = attn_bias(mask, slopes)
+    if bias is not None:
+        check(lib().ggml_hip_attn_paged_bias_dev(pc.kv_type, C.c_void_p(q.data_ptr()), q.stride(0), q.stride(1), C.c_void_p(pc.k.data_ptr()),
+                                                 C.c_void_p(pc.v.data_ptr()), nbp, nbo, nbh, n_pages, d_pages, ld_pages, d_len, int(len_bias), pc.n_seq, n_head,
+                                                 n_head_kv, D, n_q, pc.n_kv_max, int(bool(causal)), float(scale), C.byref(opts) if opts is not None else None,
+                                                 C.byref(bias), C.c_void_p(out.data_ptr()), out.stride(0), out.stride(1), C.c_void_p(work.data_ptr()),
+                                                 work.numel(), _stream()), "ggml_hip_attn_paged_bias_dev")
+        return out
     if opts is not None:
         check(lib().ggml_hip_attn_paged_ex_dev(pc.kv_type, C.c_void_p(q.data_ptr()), q.stride(0), q.stride(1), C.c_void_p(pc.k.data_ptr()),
                                                C.c_void_p(pc.v.data_ptr()), nbp, nbo, nbh, n_pages, d_pages, ld_pages, d_len, int(len_bias), pc.n_seq, n_head,
@@ -512,12 +553,14 @@ def attn_paged_ragged_work_size(kv_type, D, n_head, n_head_kv, n_seq, n_tokens_m
 
 
 def attn_paged_ragged(pc, q_start, q, n_head_kv, add_q=False, len_bias=0, n_dec_rows_max=None, causal=True, scale=None, out=None, work=None, window=0,
-                      softcap=0.0, sinks=None):
+                      softcap=0.0, sinks=None, mask=None, slopes=None):
     """attn_paged with a query count per sequence read on the device: q f32 [n_tokens_max, n_head, D] packed, the rows of sequence b at q_start[b] ..
     q_start[b+1] - 1 (q_start int32 [n_seq + 1] on the device), over n_kv[b] = clamp(d_len[b] + (add_q ? n_q[b] : 0) + len_bias, 0, n_kv_max) positions.
     A sequence's rows are bit for bit attn_paged for it alone; the form (DECODE up to 8 rows, PROMPT above) follows n_q[b] per sequence.
     n_dec_rows_max (default min(n_tokens_max, 8 n_seq), which never overflows) bounds the DECODE rows of the work buffer: a DECODE sequence that does
-    not fit returns +0.0 rows.  out must be given for rows of no present sequence to keep what they held: they are not written."""
+    not fit returns +0.0 rows.  out must be given for rows of no present sequence to keep what they held: they are not written.
+    mask (f16 [n_tokens_max, >= n_kv_max], row = the packed row, column = the position in that row's own sequence) and slopes: as attention(), through
+    ggml_hip_attn_paged_ragged_bias_dev."""
     assert q_start.is_cuda and q_start.dtype == torch.int32 and q_start.is_contiguous() and q_start.numel() == pc.n_seq + 1
     assert q.is_cuda and q.dtype == torch.float32 and q.dim() == 3 and q.stride(2) == 1
     n_tokens_max, n_head, D = q.shape
@@ -533,6 +576,16 @@ def attn_paged_ragged(pc, q_start, q, n_head_kv, add_q=False, len_bias=0, n_dec_
                            dtype=torch.uint8, device=q.device)
     nbp, nbo, nbh, n_pages, d_pages, ld_pages, d_len = pc._args()
     opts = attn_opts(window, softcap, sinks)
+    bias = attn_bias(mask, slopes)
+    if bias is not None:
+        check(lib().ggml_hip_attn_paged_ragged_bias_dev(pc.kv_type, C.c_void_p(q.data_ptr()), q.stride(0), q.stride(1), C.c_void_p(pc.k.data_ptr()),
+                                                        C.c_void_p(pc.v.data_ptr()), nbp, nbo, nbh, n_pages, d_pages, ld_pages, d_len, int(bool(add_q)),
+                                                        int(len_bias), pc.n_seq, C.c_void_p(q_start.data_ptr()), n_tokens_max, int(n_dec_rows_max), n_head,
+                                                        n_head_kv, D, pc.n_kv_max, int(bool(causal)), float(scale),
+                                                        C.byref(opts) if opts is not None else None, C.byref(bias), C.c_void_p(out.data_ptr()),
+                                                        out.stride(0), out.stride(1), C.c_void_p(work.data_ptr()), work.numel(), _stream()),
+              "ggml_hip_attn_paged_ragged_bias_dev")
+        return out
     check(lib().ggml_hip_attn_paged_ragged_dev(pc.kv_type, C.c_void_p(q.data_ptr()), q.stride(0), q.stride(1), C.c_void_p(pc.k.data_ptr()),
                                                C.c_void_p(pc.v.data_ptr()), nbp, nbo, nbh, n_pages, d_pages, ld_pages, d_len, int(bool(add_q)), int(len_bias),
                                                pc.n_seq, C.c_void_p(q_start.data_ptr()), n_tokens_max, int(n_dec_rows_max), n_head, n_head_kv, D, pc.n_kv_max,

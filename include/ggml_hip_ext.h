@@ -682,8 +682,8 @@ int    ggml_hip_attn_paged_dev(int kv_type, const float *d_q, int64_t ldq_tok, i
 /* ---------------- ATTENTION OPTIONS: a sliding window, attention sinks and a logit soft-cap over either cache ----------------
  * ggml_hip_attn_dev and ggml_hip_attn_paged_dev compute softmax(scale Q K^T + causal mask) V and refuse upstream's other parameters.  The
  * four entries below serve three of them -- what Mistral / Gemma 2, 3 / Phi-3 / gpt-oss layers need -- with NO mask tensor: the window is a
- * number, the sinks a vector per head, the cap a number.  A mask tensor and ALiBi stay unserved everywhere: these entries have no parameter
- * for them.  The base entries keep their signatures, their refusals and their bits.
+ * number, the sinks a vector per head, the cap a number.  A mask tensor and ALiBi are not served here: these entries have no parameter
+ * for them (the _bias entries of the section ATTENTION WITH A MASK TENSOR AND ALiBi SLOPES below take them).  The base entries keep their signatures, their refusals and their bits.
  *
  * ggml_hip_attn_opts_t:  d_sinks: device f32 [n_head], 4-byte aligned, or NULL (none).  window: 0 (none), or W >= 1: the row at position P
  * sees position j only if P - j < W (upstream's pos_q - pos_k < n_swa); needs causal != 0.  logit_softcap: 0 (none) or a finite cap > 0.
@@ -844,6 +844,87 @@ int    ggml_hip_attn_paged_ragged_dev(int kv_type, const float *d_q, int64_t ldq
                                       int n_head, int n_head_kv, int D, int64_t n_kv_max,
                                       int causal, float scale, const ggml_hip_attn_opts_t *opts,
                                       float *d_dst, int64_t ldd_tok, int64_t ldd_head, void *d_work, size_t work_bytes, void *stream);
+
+/* ---------------- ATTENTION WITH A MASK TENSOR AND ALiBi SLOPES: the _ex and the ragged entries with upstream's mask and max_bias ----------------
+ * The entries above express "the last n_q positions, causal, minus a window".  Upstream's ggml_flash_attn_ext also takes a MASK tensor, added to
+ * the scores, and max_bias, which scales it per head (ALiBi).  The three entries below take both over the contiguous, the paged and the ragged
+ * cache: a draft TREE in speculative decoding (a draft row sees the committed cache and its own ancestors), bidirectional spans inside a causal
+ * prompt (prefix-LM, image tokens), additive position biases and ALiBi models.  The base and the _ex entries keep their signatures, their
+ * refusals (a mask or max_bias != 0 on the base entries included) and their bits.
+ *
+ * ggml_hip_attn_bias_t:
+ *   d_mask:   device f16 [rows][ld_mask], or NULL (none).  THE MASK ROW OF A QUERY ROW is the row with the same row index as in q: contiguous
+ *             row t; paged the row b * n_q + t; ragged the packed row.  COLUMN j is position j of that row's own sequence.  The mask is shared
+ *             by all heads (upstream's broadcast).  Only rows of queries that exist are read, in 8-byte pieces that begin below the sequence's
+ *             n_kv (so never at or beyond ld_mask); a value at or beyond n_kv is never used, whatever it is.
+ *   ld_mask:  halves between mask rows.  ld_mask >= n_kv_max, ld_mask % 8 == 0 and d_mask 16-byte aligned, otherwise GGML_HIP_ERR_SHAPE.
+ *   d_slopes: device f32 [n_head], or NULL: every slope 1.0f.  Misaligned (4 bytes), or given without d_mask (there is nothing to multiply):
+ *             GGML_HIP_ERR_ARG.  The caller uploads the vector, as it does the sinks; ggml_hip_alibi_slopes computes upstream's.
+ * bias == NULL, or a bias whose d_mask and d_slopes are both NULL (ld_mask is then not looked at), runs the kernels of ggml_hip_attn_ex_dev /
+ * ggml_hip_attn_paged_ex_dev / ggml_hip_attn_paged_ragged_dev and returns their bits.
+ * EVERY RULE of those entries carries over: opts and its refusals, shapes, strides, alignment, null pointers, n_q = 0, every refusal decided
+ * before a device is touched, no synchronize, no allocation, capturable, no atomics, the clamped device-side lengths, the page-id guards (an
+ * invalid needed id gives +0.0f rows and no address is formed from it), +0.0f for a row with no visible position.
+ * NO NEW PLAN OR WORK-SIZE FUNCTION: the form follows n_q alone (per sequence in the ragged entry), the grids are those of ggml_hip_attn_ex_plan /
+ * ggml_hip_attn_paged_ex_plan / ggml_hip_attn_paged_ragged_plan for the same opts, and the work buffer is ggml_hip_attn_work_size /
+ * ggml_hip_attn_paged_work_size / ggml_hip_attn_paged_ragged_work_size: ALWAYS ENOUGH, a mask needs no partial the base entry does not have.
+ *
+ * THE ARITHMETIC.  Everything not named here is the statement of the two forms and of the options above.  Let s_j be the score as the form
+ * computes it: scale * dot, or cap * tanhf(sc' * dot) under the soft-cap -- upstream's order, the cap before the mask.  With a mask, for the
+ * query row's mask row r:
+ *     mk = (float)mask[r][j]                       the exact widening
+ *     mk == -inf:  position j is INVISIBLE to the row, in addition to the causal and the window rule
+ *     otherwise:   s_j = fmaf(slope_h, mk, s_j)    ONE rounding; slope_h = d_slopes ? d_slopes[h] : 1.0f
+ *   DECODE: an invisible position takes part in nothing (it is never multiplied: what the cache holds there does not matter); inside a chunk the
+ *     a[d] chain starts at the row's FIRST visible position of the chunk, as under a window, and runs over the visible ones in ascending order.
+ *   PROMPT: an invisible position is a zero operand of the matrix core, as above the diagonal.
+ *   +inf or NaN in a mask row gives unspecified values in that row and nothing else.
+ *   SINKS are unchanged: the denominator only, not biased.  THE WINDOW stays structural: the windowed DECODE grid, c_lo, and the page-table
+ *     entries below c_lo[b] that are never read; the mask acts inside it.
+ *   FULLY MASKED.  A (row, chunk) whose positions are all invisible -- by the mask alone included -- contributes nothing, anywhere in the walk:
+ *     DECODE writes the partial (m = -inf, l = 0, a = 0) for it and the merge's b_c = expf(-inf - M) = 0 adds nothing; PROMPT's online softmax
+ *     keeps (m, l, O) across it (alpha = 1, every P = 0) or stays empty (m = -inf).  A row with NO visible position at all writes +0.0f, never
+ *     NaN: the merge finds M = -inf (with sinks: M = sink_h, A = 0, dst = 0 / L), PROMPT finds l = 0.
+ * CONSEQUENCES (the tests hold the kernels to them bit for bit, in both forms):
+ *   1. bias == NULL and a bias with both pointers NULL give the _ex / ragged entry's bits.
+ *   2. A mask of +0.0 everywhere without slopes gives the _ex entry's bits (fmaf(1, +0, s) = s; an s of -0 becomes +0, which no later step
+ *      tells apart).  d_slopes == NULL gives the bits of slopes all 1.0f.
+ *   3. causal = 0 with the causal pattern written into the mask (0 / -inf) gives the bits of causal = 1 without a mask, where no output or V
+ *      element is a zero whose sign could differ.
+ *   4. Paged equals contiguous per sequence; ragged equals the paged entry called for the sequence alone (n_seq = 1, n_q = n_q[b], the mask
+ *      advanced to the sequence's first packed row): the same chunk bodies.  The result does not depend on the page assignment, n_kv_max,
+ *      ld_mask, the strides or, without slopes, on n_head.
+ *
+ * ggml_hip_alibi_slopes (HOST ONLY, no device; the kernels never call powf) is upstream's rule and its definition here, as
+ * ggml_hip_rope_table is for rope: with n2 = 2^floor(log2 n_head), m0 = powf(2, -max_bias / n2), m1 = powf(2, -(max_bias / 2) / n2), all binary32:
+ *     out[h] = powf(m0, h + 1)               for h <  n2
+ *     out[h] = powf(m1, 2 (h - n2) + 1)      for h >= n2
+ * and max_bias == 0 gives every slope 1.0f exactly.  n_head outside 1 .. 65535, out == NULL, or a max_bias that is negative or not finite:
+ * GGML_HIP_ERR_ARG.  An ALiBi layer passes the mask -(P - j) (or upstream's own mask tensor) and these slopes. */
+typedef struct ggml_hip_attn_bias_t {
+    const void  *d_mask;    /* device f16 [rows][ld_mask], or NULL: none */
+    int64_t      ld_mask;   /* halves between mask rows */
+    const float *d_slopes;  /* device f32 [n_head], or NULL: every slope 1.0f */
+} ggml_hip_attn_bias_t;
+int    ggml_hip_alibi_slopes(int n_head, float max_bias, float *out);
+int    ggml_hip_attn_bias_dev(int kv_type, const float *d_q, int64_t ldq_tok, int64_t ldq_head,
+                              const void *d_k, const void *d_v, int64_t nb_pos, int64_t nb_head,
+                              int n_head, int n_head_kv, int D, int64_t n_q, int64_t n_kv, const int32_t *d_n_kv, int64_t n_kv_max,
+                              int causal, float scale, const ggml_hip_attn_opts_t *opts, const ggml_hip_attn_bias_t *bias,
+                              float *d_dst, int64_t ldd_tok, int64_t ldd_head, void *d_work, size_t work_bytes, void *stream);
+int    ggml_hip_attn_paged_bias_dev(int kv_type, const float *d_q, int64_t ldq_tok, int64_t ldq_head,
+                                    const void *d_k, const void *d_v, int64_t nb_page, int64_t nb_pos, int64_t nb_head, int n_pages,
+                                    const int32_t *d_pages, int64_t ld_pages, const int32_t *d_len, int len_bias, int64_t n_seq,
+                                    int n_head, int n_head_kv, int D, int64_t n_q, int64_t n_kv_max,
+                                    int causal, float scale, const ggml_hip_attn_opts_t *opts, const ggml_hip_attn_bias_t *bias,
+                                    float *d_dst, int64_t ldd_tok, int64_t ldd_head, void *d_work, size_t work_bytes, void *stream);
+int    ggml_hip_attn_paged_ragged_bias_dev(int kv_type, const float *d_q, int64_t ldq_tok, int64_t ldq_head,
+                                           const void *d_k, const void *d_v, int64_t nb_page, int64_t nb_pos, int64_t nb_head, int n_pages,
+                                           const int32_t *d_pages, int64_t ld_pages, const int32_t *d_len, int add_q, int len_bias, int64_t n_seq,
+                                           const int32_t *d_q_start, int64_t n_tokens_max, int64_t n_dec_rows_max,
+                                           int n_head, int n_head_kv, int D, int64_t n_kv_max,
+                                           int causal, float scale, const ggml_hip_attn_opts_t *opts, const ggml_hip_attn_bias_t *bias,
+                                           float *d_dst, int64_t ldd_tok, int64_t ldd_head, void *d_work, size_t work_bytes, void *stream);
 
 /* ---------------- THE ENDS OF A DECODE STEP: a token id -> its embedding row; the LM head's logits -> the next token id ----------------
  * Upstream's ggml_get_rows over the token-embedding matrix and its ggml_argmax / top-k -> temperature -> softmax -> top-p -> pick sampler

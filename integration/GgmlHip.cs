@@ -166,6 +166,28 @@ internal static unsafe partial class GgmlHip
         long nbPos, long nbHead, int nPages, int* dPages, long ldPages, int* dLen, int addQ, int lenBias, long nSeq, int* dQStart, long nTokensMax, long nDecRowsMax,
         int nHead, int nHeadKv, int d, long nKvMax, int causal, float scale, ggml_hip_attn_opts_t* opts, float* dDst, long lddTok, long lddHead, void* dWork,
         nuint workBytes, void* stream);
+    // ... attention with a MASK tensor and ALiBi slopes over the three caches: the _ex / ragged entries with a bias.  d_mask f16 [rows][ld_mask] on the
+    // device (row = the query's row index in q, column = the position; -inf hides the position from the row, any other value is added to the score
+    // times the head's slope; shared by all heads), ld_mask >= nKvMax and a multiple of 8, d_mask 16-byte aligned; d_slopes f32 [nHead] or null (1.0f),
+    // only with a mask.  bias null or empty: the _ex / ragged entry's bits.  The same plans and work sizes serve.  ggml_hip_alibi_slopes is host only
+    [StructLayout(LayoutKind.Sequential)]
+    public struct ggml_hip_attn_bias_t
+    {
+        public void* d_mask;
+        public long ld_mask;
+        public float* d_slopes;
+    }
+    [DllImport(Lib)] public static extern int ggml_hip_alibi_slopes(int nHead, float maxBias, float* slopes);
+    [DllImport(Lib)] public static extern int ggml_hip_attn_bias_dev(int kvType, float* dQ, long ldqTok, long ldqHead, void* dK, void* dV, long nbPos, long nbHead,
+        int nHead, int nHeadKv, int d, long nQ, long nKv, int* dNKv, long nKvMax, int causal, float scale, ggml_hip_attn_opts_t* opts, ggml_hip_attn_bias_t* bias,
+        float* dDst, long lddTok, long lddHead, void* dWork, nuint workBytes, void* stream);
+    [DllImport(Lib)] public static extern int ggml_hip_attn_paged_bias_dev(int kvType, float* dQ, long ldqTok, long ldqHead, void* dK, void* dV, long nbPage, long nbPos,
+        long nbHead, int nPages, int* dPages, long ldPages, int* dLen, int lenBias, long nSeq, int nHead, int nHeadKv, int d, long nQ, long nKvMax, int causal,
+        float scale, ggml_hip_attn_opts_t* opts, ggml_hip_attn_bias_t* bias, float* dDst, long lddTok, long lddHead, void* dWork, nuint workBytes, void* stream);
+    [DllImport(Lib)] public static extern int ggml_hip_attn_paged_ragged_bias_dev(int kvType, float* dQ, long ldqTok, long ldqHead, void* dK, void* dV, long nbPage,
+        long nbPos, long nbHead, int nPages, int* dPages, long ldPages, int* dLen, int addQ, int lenBias, long nSeq, int* dQStart, long nTokensMax, long nDecRowsMax,
+        int nHead, int nHeadKv, int d, long nKvMax, int causal, float scale, ggml_hip_attn_opts_t* opts, ggml_hip_attn_bias_t* bias, float* dDst, long lddTok,
+        long lddHead, void* dWork, nuint workBytes, void* stream);
     // ... the ends of a decode step (device entries, capturable, scratch from the caller): rows of a resident weight by int32 ids on the device, bit
     // for bit download + dequantize, an id outside [0, M) a row of +0; the k best logits of every row (larger first, ties to the smaller index, NaN
     // last), p = softmax((l - l0) * invTemp) over them, top-p and the pick by the caller's uniforms dU (null: no pick) -- the int32 written to dToken
