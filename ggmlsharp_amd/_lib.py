@@ -298,6 +298,8 @@ HIP_SYMBOLS = {
     "ggml_hip_topk_work_size": (C.c_size_t, [C.c_int64, C.c_int64, C.c_int]),
     "ggml_hip_argmax_rows_dev": (C.c_int, [_P, C.c_int64, C.c_int64, C.c_int64, _P, _P, C.c_size_t, _P]),
     "ggml_hip_sample_topk_dev": (C.c_int, [_P, C.c_int64, C.c_int64, C.c_int64, C.c_int, C.c_float, C.c_float, _P, _P, _P, _P, _P, C.c_size_t, _P]),
+    # ... and the last row of every sequence of a ragged step: the rows the LM head needs
+    "ggml_hip_ragged_last_rows_dev": (C.c_int, [_P, C.c_int64, _P, C.c_int64, C.c_int64, C.c_int64, _P, C.c_int64, _P]),
 }
 SYMBOLS = HIP_SYMBOLS
 

@@ -400,6 +400,21 @@ int ggml_hip_ragged_positions_dev(const int32_t *d_q_start, const int32_t *d_len
     return GGML_HIP_OK;
 }
 
+int ggml_hip_ragged_last_rows_dev(const float *d_x, int64_t ldx, const int32_t *d_q_start, int64_t n_seq, int64_t n_tokens_max, int64_t K, float *d_dst,
+                                  int64_t ldd, void *stream) {
+    if (n_seq < 1 || n_seq > ATTN_PAGED_MAX_SEQ) return fail(GGML_HIP_ERR_SHAPE, "n_seq %lld (1 .. %lld)", (long long)n_seq, (long long)ATTN_PAGED_MAX_SEQ);
+    kv_ragged rg;
+    const int rc = check_kv_ragged(d_q_start, n_seq, n_tokens_max, &rg);
+    if (rc) return rc;
+    if (K < 0 || K > ((int64_t)1 << 24)) return fail(GGML_HIP_ERR_SHAPE, "K %lld (0 .. 2^24)", (long long)K);
+    if (ldx < K || ldd < K) return fail(GGML_HIP_ERR_SHAPE, "ldx %lld and ldd %lld must be at least K %lld", (long long)ldx, (long long)ldd, (long long)K);
+    if (K == 0) return GGML_HIP_OK;
+    if (!d_x || !d_dst) return fail(GGML_HIP_ERR_ARG, "d_x and d_dst must not be null");
+    if ((((uintptr_t)d_x | (uintptr_t)d_dst) & 3) != 0) return fail(GGML_HIP_ERR_SHAPE, "d_x and d_dst must be 4-byte aligned");
+    HIP_TRY(launch_ragged_last_rows(rg, d_x, ldx, K, d_dst, ldd, (hipStream_t)stream));
+    return GGML_HIP_OK;
+}
+
 int ggml_hip_kv_store_paged_ragged_dev(int kv_type, const float *d_src, int64_t ldx_tok, int64_t ldx_head, int n_head_kv, int D, int64_t n_seq,
                                        const int32_t *d_q_start, int64_t n_tokens_max, void *d_pool, int64_t nb_page, int64_t nb_pos, int64_t nb_head, int n_pages,
                                        const int32_t *d_pages, int64_t ld_pages, const int32_t *d_len, int64_t n_kv_max, void *stream) {

@@ -500,6 +500,8 @@ __device__ __forceinline__ int ragged_find(const kv_ragged &rg, int64_t row, int
 #endif
 // d_pos[i] = len[b] + t for row i = (b, t) of a present sequence, 0 for the other rows below n_tokens_max
 hipError_t launch_ragged_positions(const kv_ragged &rg, const int32_t *len, int32_t *pos, hipStream_t st);
+// dst[s][0 .. K) = x[q_start[s+1] - 1][0 .. K) for a present sequence s that is not empty, +0.0f for every other s < n_seq (get_rows.hip)
+hipError_t launch_ragged_last_rows(const kv_ragged &rg, const float *x, int64_t ldx, int64_t K, float *dst, int64_t ldd, hipStream_t st);
 // launch_kv_store_paged over packed rows [n_tokens_max][n_head_kv][D]: the same bytes for a row of a present sequence, nothing for the others
 hipError_t launch_kv_store_paged_ragged(int kv_type, const float *src, int64_t ldx_tok, int64_t ldx_head, int n_head_kv, int D, const kv_ragged &rg, void *pool,
                                         int64_t nb_pos, int64_t nb_head, const kv_pages &pg, hipStream_t st);

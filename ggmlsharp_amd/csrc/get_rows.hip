@@ -23,6 +23,9 @@
 // where dst and ldd allow, one element at a time otherwise, the same bits.  Threads of a workgroup walk (id, k-block) with the k-block
 // fastest, so a workgroup covers several ids where K is small and a contiguous stretch of one row where it is large.
 // An id outside [0, M) writes +0.0f and forms no address from the id.
+//
+// The other gather of a step lives here too: ggml_hip_ragged_last_rows_dev (attn.cpp) copies the last packed f32 row of every sequence of a
+// ragged batch, the rows the LM head needs (ragged_last_rows_kernel, the dense kernel's geometry).
 #include "common.h"
 
 namespace {
@@ -148,7 +151,40 @@ __global__ __launch_bounds__(256) void get_rows_dense_kernel(const void *__restr
     }
 }
 
+// ggml_hip_ragged_last_rows_dev: row s of dst = the LAST packed row of sequence s, q_start[s+1] - 1, or +0.0f where the sequence is empty or not
+// present.  The guard comes before the address it protects; a thread owns 4 consecutive elements (VEC) or one, as get_rows_dense_kernel's.
+template <bool VEC>
+__global__ __launch_bounds__(256) void ragged_last_rows_kernel(const kv_ragged rg, const float *__restrict__ x, int64_t ldx, int64_t K, int blocks_per_row,
+                                                               float *__restrict__ dst, int64_t ldd) {
+    const int64_t s = blockIdx.x / blocks_per_row;
+    const int64_t k = ((int64_t)(blockIdx.x % blocks_per_row) * 256 + threadIdx.x) * (VEC ? 4 : 1);
+    if (k >= K) return;
+    const int64_t qs = rg.q_start[s], qe = rg.q_start[s + 1];
+    const bool ok = qs >= 0 && qs < qe && qe <= rg.n_tokens_max;
+    float *o = dst + s * ldd + k;
+    if (VEC) {                                              // (K % 4 == 0: whole quads)
+        float4 r = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+        if (ok) r = *(const float4 *)(x + (qe - 1) * ldx + k);
+        *(float4 *)o = r;
+    } else {
+        float r = 0.0f;
+        if (ok) r = x[(qe - 1) * ldx + k];
+        *o = r;
+    }
+}
+
 }  // namespace
+
+hipError_t launch_ragged_last_rows(const kv_ragged &rg, const float *x, int64_t ldx, int64_t K, float *dst, int64_t ldd, hipStream_t st) {
+    if (rg.n_seq <= 0 || K <= 0) return hipSuccess;
+    const bool vec = (((uintptr_t)x | (uintptr_t)dst) & 15) == 0 && ldx % 4 == 0 && ldd % 4 == 0 && K % 4 == 0;
+    const int64_t per_block = vec ? 1024 : 256, bpr = (K + per_block - 1) / per_block;
+    if (bpr > 0x7FFFFFFF / rg.n_seq) return hipErrorInvalidValue;
+    const dim3 grid((unsigned)(rg.n_seq * bpr));
+    if (vec) ragged_last_rows_kernel<true><<<grid, 256, 0, st>>>(rg, x, ldx, K, (int)bpr, dst, ldd);
+    else ragged_last_rows_kernel<false><<<grid, 256, 0, st>>>(rg, x, ldx, K, (int)bpr, dst, ldd);
+    return hipGetLastError();
+}
 
 // w: a resident weight of a served type (decode_ends.cpp checks); ids / dst on the weight's device
 hipError_t launch_get_rows(const ggml_hip_weight *w, const int32_t *ids, int64_t n_ids, float *dst, int64_t ldd, hipStream_t st) {

@@ -650,6 +650,23 @@ def sample_topk(logits, k, inv_temp=1.0, top_p=1.0, u=None, ids=None, probs=None
     return ids, probs, (token if u is not None else None)
 
 
+def ragged_last_rows(x, q_start, n_tokens_max=None, out=None):
+    """out[s] = x[q_start[s + 1] - 1] for every sequence s of a ragged step that is present and not empty, a row of +0.0 otherwise: the rows the LM head needs,
+    gathered on the device so that a captured step follows q_start.  x f32 [n_tokens_max, K] with last stride 1, q_start int32 [n_seq + 1] on the device."""
+    assert x.is_cuda and x.dtype == torch.float32 and x.dim() == 2 and x.stride(1) == 1
+    assert q_start.is_cuda and q_start.dtype == torch.int32 and q_start.is_contiguous() and q_start.numel() >= 2
+    n_seq, K = q_start.numel() - 1, x.shape[1]
+    if n_tokens_max is None:
+        n_tokens_max = x.shape[0]
+    assert n_tokens_max <= x.shape[0]
+    if out is None:
+        out = torch.empty((n_seq, K), dtype=torch.float32, device=x.device)
+    assert out.is_cuda and out.dtype == torch.float32 and out.dim() == 2 and out.stride(1) == 1 and out.shape[0] >= n_seq and out.shape[1] >= K
+    check(lib().ggml_hip_ragged_last_rows_dev(C.c_void_p(x.data_ptr()), x.stride(0), C.c_void_p(q_start.data_ptr()), n_seq, n_tokens_max, K,
+                                              C.c_void_p(out.data_ptr()), out.stride(0), _stream()), "ggml_hip_ragged_last_rows_dev")
+    return out
+
+
 def quantize_rows(type, x):
     """x f32 [nrows, k] on the device -> uint8 [nrows, k/32*type_size] reference-format blocks."""
     assert x.is_cuda and x.dtype == torch.float32 and x.is_contiguous()

@@ -783,6 +783,14 @@ int    ggml_hip_attn_paged_ex_dev(int kv_type, const float *d_q, int64_t ldq_tok
  * ggml_hip_ragged_positions_dev: d_pos[i] = d_len[b] + t for every packed row i = (b, t) of a present sequence, 0 for the other rows below
  *   n_tokens_max: the int32 position array ggml_hip_rope_dev takes for Q, so a captured step follows d_q_start.  d_pos: int32 [n_tokens_max],
  *   4-byte aligned; NULL d_len / d_pos: GGML_HIP_ERR_ARG.
+ * ggml_hip_ragged_last_rows_dev: the rows the LM head needs from a ragged step, gathered on the device.  d_x, d_dst: f32 rows of K elements,
+ *   ldx / ldd apart.  For every s < n_seq, d_dst[s * ldd + k] = d_x[(d_q_start[s+1] - 1) * ldx + k], k < K, where
+ *   0 <= d_q_start[s] < d_q_start[s+1] <= n_tokens_max; an EMPTY sequence or one that is not present gets a row of +0.0f and no address is
+ *   formed from its bounds.  Columns K .. ldd - 1 and rows past n_seq are not written.  d_dst may not overlap d_x.  16-byte copies where d_x
+ *   and d_dst are 16-byte aligned and K, ldx and ldd are multiples of 4, one element at a time otherwise: the same bits.  One launch.
+ *   d_q_start, n_seq and n_tokens_max: the refusals of ggml_hip_ragged_positions_dev (n_tokens_max = 0: every row is +0.0f).  0 <= K <= 2^24
+ *   and ldx, ldd >= K, else GGML_HIP_ERR_SHAPE; K = 0 returns 0 and writes nothing.  NULL d_x / d_dst: GGML_HIP_ERR_ARG; not 4-byte aligned:
+ *   GGML_HIP_ERR_SHAPE.
  * ggml_hip_kv_store_paged_ragged_dev, ggml_hip_rope_kv_store_paged_ragged_dev: the paged stores over packed rows, one thread per 32 (Q8_0) or 4
  *   (F16) elements as theirs.  The thread finds its row's sequence by bisection of d_q_start, and every guard comes before the address it
  *   protects: a present sequence, the row inside it, the position inside [0, n_kv_max), the page id inside [0, n_pages).
@@ -824,6 +832,8 @@ typedef struct ggml_hip_attn_ragged_plan_t {
     int64_t index_bytes;                     /* the index tables in front of the partials, rounded up to 256 */
 } ggml_hip_attn_ragged_plan_t;
 int    ggml_hip_ragged_positions_dev(const int32_t *d_q_start, const int32_t *d_len, int64_t n_seq, int64_t n_tokens_max, int32_t *d_pos, void *stream);
+int    ggml_hip_ragged_last_rows_dev(const float *d_x, int64_t ldx, const int32_t *d_q_start, int64_t n_seq, int64_t n_tokens_max,
+                                     int64_t K, float *d_dst, int64_t ldd, void *stream);
 int    ggml_hip_kv_store_paged_ragged_dev(int kv_type, const float *d_src, int64_t ldx_tok, int64_t ldx_head, int n_head_kv, int D,
                                           int64_t n_seq, const int32_t *d_q_start, int64_t n_tokens_max,
                                           void *d_pool, int64_t nb_page, int64_t nb_pos, int64_t nb_head, int n_pages,

@@ -153,6 +153,9 @@ internal static unsafe partial class GgmlHip
         public long n_chunks, max_tiles, decode_workgroups, merge_workgroups, prompt_workgroups, index_bytes;
     }
     [DllImport(Lib)] public static extern int ggml_hip_ragged_positions_dev(int* dQStart, int* dLen, long nSeq, long nTokensMax, int* dPos, void* stream);
+    // (the rows the LM head needs: dDst[s] = row dQStart[s+1] - 1 of dX, +0 for an empty or absent sequence)
+    [DllImport(Lib)] public static extern int ggml_hip_ragged_last_rows_dev(float* dX, long ldx, int* dQStart, long nSeq, long nTokensMax, long k, float* dDst, long ldd,
+        void* stream);
     [DllImport(Lib)] public static extern int ggml_hip_kv_store_paged_ragged_dev(int kvType, float* dSrc, long ldxTok, long ldxHead, int nHeadKv, int d, long nSeq,
         int* dQStart, long nTokensMax, void* dPool, long nbPage, long nbPos, long nbHead, int nPages, int* dPages, long ldPages, int* dLen, long nKvMax, void* stream);
     [DllImport(Lib)] public static extern int ggml_hip_rope_kv_store_paged_ragged_dev(ggml_hip_rope_params_t* rp, int kvType, float* dX, long ldxTok, long ldxHead,
