@@ -22,7 +22,7 @@ import numpy as np
 
 U = 2.0 ** -24
 Z_MAX = 60.0
-MODEL_WORST = 0.38         # the worst statistic() of probs32 over the cases of test_decode_ends.py; the bar is 1.0
+MODEL_WORST = 0.44         # the worst statistic() of probs32 over the cases of test_decode_ends.py (0.4332, among 4096 rows at k = 2); the bar is 1.0
 
 
 def topk_ids(logits, k):

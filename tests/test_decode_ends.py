@@ -10,7 +10,12 @@ Yardsticks:
   the loop   a captured step get_rows -> rms_norm_mul -> mul_mat -> argmax whose token feeds the next replay: the tokens of eager steps and of
              a host loop that looks up and picks in numpy.
 Shapes are the smallest at which each mechanism can go wrong: K of one and two k-blocks (super-blocks), M on both sides of the 256-row pad,
-one id, a few, more than one workgroup's worth; vocabularies below / at / past one lane set, one chunk, two chunks; a chunk shorter than k."""
+one id, a few, more than one workgroup's worth; vocabularies below / at / past one lane set, one chunk, two chunks; a chunk shorter than k.
+The merge stage of the sampler is picked by size (launch_sample_topk: 1, 2, 4, ... 64 candidate keys per thread, and the k = 1 form): the
+vocabularies above reach the rungs 1, 2 and 4; BIG_KINDS below are chosen by chunk count so that k = 64 fills every rung 1 .. 64 exactly
+(4, 8, ... 128 chunks and 2^20 logits) and enters every rung 2 .. 64 at one chunk more than the rung below holds (5, 9, ... 129 chunks, the
+last of one logit), with k = 1, 2 and 40 at three of them; test_the_cases_reach_every_form_of_the_merge counts the rungs.  Two further cases
+have 130 and 4096 rows."""
 import ctypes as C
 import os
 import re
@@ -207,29 +212,154 @@ def _ks(V):
     return [k for k in KS if k <= V]
 
 
-def test_the_generator_stays_inside_the_spread_the_bound_assumes():
-    """(l_0 - l_(k-1)) * inv_temp <= 60 for every probability-checked row of every case: no e_s is subnormal.  No case is left out."""
+# ---- the vocabularies that select the upper rungs of the merge ladder, by chunk count
+BIG_FULL = (4, 8, 16, 32, 64, 128)                                    # n_vocab = n_chunks * C: with k = 64 the rung n_chunks / 4 is full
+BIG_NEXT = (5, 9, 17, 33, 65, 129)                                    # n_vocab = (n_chunks - 1) * C + 1: the next rung up, a last chunk of one logit
+BIG_TOP = 256                                                         # n_vocab = 2^20, the header's maximum
+BIG_KS = {n: (64,) for n in BIG_FULL + BIG_NEXT + (BIG_TOP,)}
+for _n in (17, 65, 256):
+    BIG_KS[_n] = (2, 40) + BIG_KS[_n]
+for _n in (5, 65, 256):
+    BIG_KS[_n] = (1,) + BIG_KS[_n]
+BIG_KINDS = tuple("%dC" % n for n in BIG_FULL) + tuple("%dC+1" % (n - 1) for n in BIG_NEXT) + ("2^20",)
+ROW_COUNT_CASES = ((130, "2C+5", 64), (4096, "65", 2))                # (n_rows, a kind of VOCAB_KINDS, k): blockIdx / n_chunks away from 9 rows
+MERGE_RUNGS = (1, 2, 4, 8, 16, 32, 64)
+
+
+def _big_chunks(kind):
+    return BIG_TOP if kind == "2^20" else int(kind.split("C")[0]) + (1 if kind.endswith("+1") else 0)
+
+
+def _big_vocab(kind):
+    Cn, n = _lib.lib().ggml_hip_topk_chunk(), _big_chunks(kind)
+    return 1 << 20 if kind == "2^20" else (n - 1) * Cn + 1 if kind.endswith("+1") else n * Cn
+
+
+def big_rows(kind):
+    """nine rows of n_vocab logits (computed once per vocabulary and never written), with `top` above every plain logit: 0 plain; 1 all equal;
+    2 the 64 best inside the last full chunk at permuted offsets, top + 0.125 s, under a larger value at n_vocab - 1; 3 one winner in each of
+    min(64, n_chunks) chunks from the first to the last, at offset 37 c modulo the chunk's length, top + 16 - 0.25 s; 4 `top` at the last index
+    of every chunk: with more than k chunks, more than k equal maxima; 5 three values; 6 NaN and +-inf sprinkled; 7 / 8 in the second chunk,
+    the sixteen best where ONE thread of the chunk kernel holds them all under the one-by-one / the float4 load, descending.
+    -> (x [9, n_vocab], its rank order [9, 64] under S.topk_ids: a prefix of it is the rank order of a smaller k)"""
+    if ("big", kind) in _ROWS:
+        return _ROWS["big", kind]
+    V, Cn, n_chunks = _big_vocab(kind), _lib.lib().ggml_hip_topk_chunk(), _big_chunks(kind)
+    rng = np.random.default_rng(2000 + V)
+    x = rng.normal(0.0, 3.0, (9, V)).astype(np.float32)
+    top = np.float32(np.ceil(np.abs(x).max()) + 1.0)                  # (an integer: the steps of 1/8 below are exact)
+    x[1] = np.float32(1.5)
+    full = n_chunks - 1 if V % Cn == 0 else n_chunks - 2              # the last FULL chunk
+    offs = rng.permutation(Cn - 1)[:64]                               # (not its last index: n_vocab - 1 may be that)
+    x[2, full * Cn + offs] = top + np.float32(0.125) * np.arange(64, dtype=np.float32)
+    x[2, V - 1] = top + np.float32(8.0)
+    chunks = np.unique(np.round(np.linspace(0, n_chunks - 1, min(64, n_chunks))).astype(np.int64))
+    assert len(chunks) == min(64, n_chunks) and chunks[0] == 0 and chunks[-1] == n_chunks - 1
+    lens = np.minimum(Cn, V - chunks * Cn)
+    x[3, chunks * Cn + (chunks * 37) % lens] = top + np.float32(16.0) - np.float32(0.25) * np.arange(len(chunks), dtype=np.float32)
+    x[4, np.minimum(np.arange(1, n_chunks + 1) * Cn, V) - 1] = top
+    x[5] = rng.integers(0, 3, V).astype(np.float32)
+    n6 = max(1, V // 7)
+    for val in (np.nan, np.inf, -np.inf):
+        x[6, rng.integers(0, V, n6)] = np.float32(val)
+    down = top + np.float32(8.0) - np.float32(0.25) * np.arange(16, dtype=np.float32)
+    x[7, Cn + 7 + 256 * np.arange(16)] = down
+    x[8, [Cn + (256 * j + 7) * 4 + q for j in range(4) for q in range(4)]] = down
+    x.setflags(write=False)
+    order = S.topk_ids(x, 64)
+    order.setflags(write=False)
+    _ROWS["big", kind] = (x, order)
+    return _ROWS["big", kind]
+
+
+def many_rows(n_rows, kind):
+    """n_rows plain rows of a vocabulary of VOCAB_KINDS, every row different (computed once) -> (x, its rank order [n_rows, 64 or n_vocab])"""
+    if (n_rows, kind) not in _ROWS:
+        V = _vocab(kind)
+        x = np.random.default_rng(3000 + n_rows).normal(0.0, 3.0, (n_rows, V)).astype(np.float32)
+        x.setflags(write=False)
+        order = S.topk_ids(x, min(64, V))
+        order.setflags(write=False)
+        _ROWS[(n_rows, kind)] = (x, order)
+    return _ROWS[(n_rows, kind)]
+
+
+def _merge_form(n_vocab, k, probs):
+    """launch_sample_topk's ladder restated: the merge kernel's keys per thread, "ONE" for the k = 1 form without probabilities"""
+    Cn = _lib.lib().ggml_hip_topk_chunk()
+    n_cand = -(-n_vocab // Cn) * k
+    if k == 1 and not probs:
+        return "ONE", n_cand
+    npt = -(-n_cand // 256)
+    return next(N for N in MERGE_RUNGS if npt <= N), n_cand
+
+
+def test_the_cases_reach_every_form_of_the_merge():
+    """A RESTATEMENT of launch_sample_topk's ladder (csrc/sample.hip): npt = ceil(n_chunks * k / 256) rounded up to 1, 2, 4, ... 64, and the
+    form of k == 1 && !probs.  A change to the ladder there changes _merge_form here.  Over the (vocabulary, k) of the GPU tests below: all
+    seven rungs run, every rung N >= 2 both FULL (n_cand == 256 N) and at its lowest occupancy under k = 64 (one chunk more than the rung
+    below holds, n_cand == 128 N + 64), and the k = 1 form runs at the large vocabularies too."""
+    Cn = _lib.lib().ggml_hip_topk_chunk()
+    assert len(BIG_KINDS) == 13 and len(set(BIG_KINDS)) == 13
+    for kind in BIG_KINDS:
+        V, n = _big_vocab(kind), _big_chunks(kind)
+        assert -(-V // Cn) == n and V <= 1 << 20, (kind, V)
+        assert V - (n - 1) * Cn == (1 if kind.endswith("+1") else Cn), kind      # the last chunk: one logit, shorter than k, or full
+        assert _lib.lib().ggml_hip_topk_work_size(9, V, 64) == 9 * n * 64 * 8
+    assert _big_vocab("2^20") == 1 << 20
+    reached = {}                                                      # rung -> the n_cand it ran at
+    for kind in BIG_KINDS:
+        for k in BIG_KS[_big_chunks(kind)]:
+            form, n_cand = _merge_form(_big_vocab(kind), k, True)
+            reached.setdefault(form, set()).add(n_cand)
+    for n_rows, kind, k in ROW_COUNT_CASES:
+        form, n_cand = _merge_form(_vocab(kind), k, True)
+        reached.setdefault(form, set()).add(n_cand)
+    assert sorted(reached) == list(MERGE_RUNGS), sorted(reached)
+    for N in MERGE_RUNGS[1:]:
+        assert 256 * N in reached[N], ("no case fills rung", N)
+        assert 128 * N + 64 in reached[N], ("no case enters rung at its lowest occupancy", N)
+    small = {_merge_form(_vocab(kind), k, True)[0] for kind in VOCAB_KINDS for k in _ks(_vocab(kind))}
+    assert small == {1, 2, 4}                                         # what the small vocabularies alone reach
+    assert {n for n in BIG_KS if 1 in BIG_KS[n]} == {5, 65, 256}      # the argmax entry: 5, 65 and 256 keys in the ONE form's 256 threads
+    assert all(_merge_form(_big_vocab(kind), 1, False) == ("ONE", _big_chunks(kind)) for kind in BIG_KINDS)
+
+
+def _probability_cases():
+    """every (label, x, rank order for k, k) whose probabilities a GPU test checks: the yardstick's CPU guards run over all of them"""
     for kind in VOCAB_KINDS:
         x = sampler_rows(kind)
         for k in _ks(x.shape[1]):
-            ids = S.topk_ids(x, k)
-            rows = list(PROB_ROWS)
-            sp = S.spread(x[rows], ids[rows], INV_TEMP[k])
-            assert sp <= S.Z_MAX, (kind, k, sp)
-            assert np.isfinite(np.take_along_axis(x[rows], ids[rows].astype(np.int64), axis=1)).all()
+            yield (kind, k), x[list(PROB_ROWS)], S.topk_ids(x, k)[list(PROB_ROWS)], k
+    for kind in BIG_KINDS:
+        x, order = big_rows(kind)
+        for k in BIG_KS[_big_chunks(kind)]:
+            yield (kind, k), x[list(PROB_ROWS)], order[list(PROB_ROWS), :k], k
+    for n_rows, kind, k in ROW_COUNT_CASES:
+        x, order = many_rows(n_rows, kind)
+        yield (n_rows, kind, k), x, order[:, :k], k
+
+
+def test_the_generator_stays_inside_the_spread_the_bound_assumes():
+    """(l_0 - l_(k-1)) * inv_temp <= 60 for every probability-checked row of every case: no e_s is subnormal.  No case is left out."""
+    n = 0
+    for label, x, ids, k in _probability_cases():
+        sp = S.spread(x, ids, INV_TEMP[k])
+        assert sp <= S.Z_MAX, (label, sp)
+        assert np.isfinite(np.take_along_axis(x, ids.astype(np.int64), axis=1)).all()
+        n += 1
+    assert n == sum(len(_ks(_vocab(kind))) for kind in VOCAB_KINDS) + sum(len(BIG_KS[_big_chunks(kind)]) for kind in BIG_KINDS) + len(ROW_COUNT_CASES)
 
 
 def test_the_model_constant_is_what_the_model_measures():
     """the numpy f32 model of the statement over the GPU test's inputs: inside the derived bound, and MODEL_WORST records its worst"""
-    worst = 0.0
-    for kind in VOCAB_KINDS:
-        x = sampler_rows(kind)
-        for k in _ks(x.shape[1]):
-            ids = S.topk_ids(x, k)
-            rows = list(PROB_ROWS)
-            worst = max(worst, S.statistic(S.probs32(x[rows], ids[rows], INV_TEMP[k]), x[rows], ids[rows], INV_TEMP[k]))
+    worst, where = 0.0, None
+    for label, x, ids, k in _probability_cases():
+        st = S.statistic(S.probs32(x, ids, INV_TEMP[k]), x, ids, INV_TEMP[k])
+        if st > worst:
+            worst, where = st, label
     # (no lower edge: another numpy build's f32 exp may round better than the one the constant was recorded with)
-    print("model worst statistic", worst, "recorded", S.MODEL_WORST, "bar 1.0")
+    print("model worst statistic", worst, "at", where, "recorded", S.MODEL_WORST, "bar 1.0")
     assert worst <= S.MODEL_WORST < 1.0, worst
 
 
@@ -468,6 +598,76 @@ def test_n_keep_and_the_pick_are_the_sequential_statement_on_the_written_probabi
                     if r in PROB_ROWS:
                         n_keep, s = S.keep_pick(p[r], top_p, uu[r])
                         assert tok[r] == ids[r, s], (kind, k, top_p, float(uu[r]), r, n_keep, s)
+
+
+def _held_to_the_yardsticks(x, ids, p, want_ids, k, where):
+    """ids exact on every row; the probabilities of rows x (all of them probability-checked) inside the derived bound, summing to 1 -> the statistic"""
+    assert np.array_equal(ids, want_ids), (where, "first differing rows", np.nonzero((ids != want_ids).any(axis=1))[0][:4].tolist())
+    st = S.statistic(p, x, ids, INV_TEMP[k])
+    print(where, "probability statistic", st)
+    assert st <= 1.0, (where, st)
+    assert (np.abs(p.astype(np.float64).sum(axis=1) - 1.0) <= (k + 2) * S.U).all(), where
+    return st
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("kind", BIG_KINDS)
+def test_every_merge_rung_at_both_edges(dev, kind):
+    """big_rows at the k of BIG_KS: the nine rows at ld = n_vocab and n_vocab + 3 (between them the float4 and the one-by-one load of every
+    vocabulary: for (n - 1) C + 1 logits, + 3 is the aligned stride, with a tail of one), rows 2, 3 and 4 alone, the ids-only call, and the
+    argmax entry at both strides.  Ids exact, probabilities inside the bound and bitwise the same every time, the token by keep_pick."""
+    x, order = big_rows(kind)
+    V = x.shape[1]
+    rows = list(PROB_ROWS)
+    worst = 0.0
+    for ld in (V, V + 3):
+        am, _, _ = _sample(dev, x, ld, 1, argmax=True)
+        assert np.array_equal(am[:, 0], order[:, 0]), (kind, "argmax", ld)
+    for k in BIG_KS[_big_chunks(kind)]:
+        it = INV_TEMP[k]
+        want_ids = order[:, :k]
+        ref = None
+        for ld in (V, V + 3):
+            ids, p, tok = _sample(dev, x, ld, k, inv_temp=it, top_p=INDEP_TOP_P, u=INDEP_U)
+            assert np.array_equal(ids, want_ids), (kind, k, ld, "first differing rows", np.nonzero((ids != want_ids).any(axis=1))[0].tolist())
+            if ref is None:
+                ref = (ids, p.view(np.uint32), tok)
+                worst = max(worst, _held_to_the_yardsticks(x[rows], ids[rows], p[rows], want_ids[rows], k, (kind, k)))
+            assert np.array_equal(p.view(np.uint32), ref[1]), (kind, k, ld)
+            _check_tokens(p, ids, tok, range(9), INDEP_U, (kind, k, ld))
+            assert np.array_equal(tok[rows], ref[2][rows]), (kind, k, ld)
+        for r in (2, 3, 4):                                          # alone, with the uniform the row had among the nine
+            ids, p, tok = _sample(dev, x[r:r + 1], V + 3, k, inv_temp=it, top_p=INDEP_TOP_P, u=INDEP_U[r:r + 1])
+            assert np.array_equal(ids[0], ref[0][r]) and np.array_equal(p.view(np.uint32)[0], ref[1][r]), (kind, k, r)
+            _check_tokens(p, ids, tok, [r], INDEP_U[r:r + 1], (kind, k, "alone"))
+            assert tok[0] == ref[2][r], (kind, k, r)
+        ids_only, none, _ = _sample(dev, x, V + 3, k, inv_temp=it, probs=False)        # ids alone (k = 1: the ONE form, as the argmax entry)
+        assert np.array_equal(ids_only, want_ids) and none is None, (kind, k)
+    print(kind, "worst probability statistic", worst, "model", S.MODEL_WORST, "bar 1.0")
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("n_rows,kind,k", ROW_COUNT_CASES)
+def test_a_row_is_found_among_many(dev, n_rows, kind, k):
+    """many plain rows, all different: a workgroup's row and chunk come from blockIdx / n_chunks, and row r reads u[r]"""
+    x, order = many_rows(n_rows, kind)
+    V = x.shape[1]
+    want_ids = order[:, :k]
+    u = np.random.default_rng(n_rows).random(n_rows).astype(np.float32)
+    ref = None
+    for ld in (V, V + 3):
+        ids, p, tok = _sample(dev, x, ld, k, inv_temp=INV_TEMP[k], top_p=INDEP_TOP_P, u=u)
+        if ref is None:
+            ref = p.view(np.uint32)
+            _held_to_the_yardsticks(x, ids, p, want_ids, k, (n_rows, kind, k))
+        assert np.array_equal(ids, want_ids) and np.array_equal(p.view(np.uint32), ref), (n_rows, kind, k, ld)
+        for r in range(n_rows):
+            n_keep, s = S.keep_pick(p[r], INDEP_TOP_P, u[r])
+            assert tok[r] == ids[r, s], (n_rows, kind, k, ld, r, n_keep, s)
+        am, _, _ = _sample(dev, x, ld, 1, argmax=True)
+        assert np.array_equal(am[:, 0], want_ids[:, 0]), (n_rows, kind, ld)
+    ids_only, none, _ = _sample(dev, x, V, k, inv_temp=INV_TEMP[k], probs=False)
+    assert np.array_equal(ids_only, want_ids) and none is None
 
 
 # ---- the loop

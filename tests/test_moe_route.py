@@ -10,7 +10,11 @@ The yardsticks are the header's statements restated in numpy below:
   combine  exact: the float32 restatement, one rounding per product and per sum, ascending slots;
   silu_mul exact: the oracle's silu (GGML_SILU_FP16) and a float32 product -- what the silu_mul seam is held to (tests/test_fused.py).
 Shapes are the smallest at which each mechanism can go wrong: fewer experts than lanes, one per lane, one past, sixteen per lane; one
-token, a partial workgroup of tokens (5), several workgroups (70); row lengths below, at and past one vector and one workgroup."""
+token, a partial workgroup of tokens (5), several workgroups (70); row lengths below, at and past one vector and one workgroup.
+The router kernel is picked by size (launch_moe_topk: 1, 2, 4, 8 or 16 experts per lane): the expert counts stand on both edges of every
+rung (64 | 65, 128 | 129, 256 | 257, 512 | 513, 1024), ids and weights alike, and test_the_cases_reach_every_form_of_the_router counts
+them.  The combine's slot loop is unrolled by four: n_used - 1 is a whole number of bodies (5, 9), leaves 1, 2 or 3 (6, 3, 64), and 64 is
+the contract's maximum."""
 import ctypes as C
 import os
 import re
@@ -90,6 +94,34 @@ def test_the_restatements_on_rows_worked_by_hand():
     assert np_combine(y, np.array([[0.5, 0.25]], np.float32), np.array([[1.0, 1.0]], np.float32)).tolist() == [[4.0, 7.0]]
 
 
+# ---------------------------------------------------------------- the router's cases, and the kernel forms they select
+IDS_EXPERTS = (2, 8, 60, 64, 65, 128, 129, 256, 257, 384, 512, 513, 1024)
+SPECIAL_CASES = ((8, 4), (130, 8), (384, 8), (512, 64), (1024, 64))                    # (n_expert, n_used)
+WEIGHT_CASES = ((8, 2), (60, 8), (65, 8), (128, 8), (129, 8), (256, 8), (257, 8), (384, 8), (512, 64), (513, 1), (1024, 64))
+ROUTER_RUNGS = (1, 2, 4, 8, 16)
+
+
+def _router_form(n_expert):
+    """launch_moe_topk's ladder restated: the experts a lane holds"""
+    npl = -(-n_expert // 64)
+    return next(N for N in ROUTER_RUNGS if npl <= N)
+
+
+def test_the_cases_reach_every_form_of_the_router():
+    """A RESTATEMENT of launch_moe_topk's ladder (csrc/moe_route.hip): npl = ceil(n_expert / 64) rounded up to 1, 2, 4, 8, 16.  A change to
+    the ladder there changes _router_form here.  The ids and the weights are each checked in all five forms, the ids on both edges of every
+    rung past the first (64 N experts fill it, 32 N + 1 enter it); the special rows run in every form with more than two registers."""
+    assert {_router_form(e) for e in IDS_EXPERTS} == set(ROUTER_RUNGS)
+    assert {_router_form(e) for e, _ in WEIGHT_CASES} == set(ROUTER_RUNGS)
+    for N in ROUTER_RUNGS[1:]:
+        assert 64 * N in IDS_EXPERTS and 32 * N + 1 in IDS_EXPERTS, N
+        assert _router_form(64 * N) == _router_form(32 * N + 1) == N
+    for N in (4, 8):                                                  # the two rungs between the small shapes and 1024, weights on both edges
+        assert {64 * N, 32 * N + 1} <= {e for e, _ in WEIGHT_CASES}, N
+    assert {_router_form(e) for e, _ in SPECIAL_CASES} >= {1, 4, 8, 16}
+    assert all(u <= e and u <= 64 for e, u in SPECIAL_CASES + WEIGHT_CASES)
+
+
 # ---------------------------------------------------------------- GPU
 @pytest.fixture(scope="module")
 def dev():
@@ -140,7 +172,7 @@ def _route(dev, logits_np, ld, n_used, gating, normalize, scale):
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("n_expert", (2, 8, 60, 64, 65, 128, 1024))
+@pytest.mark.parametrize("n_expert", IDS_EXPERTS)
 def test_the_ids_are_exact(dev, n_expert):
     rng = np.random.default_rng(n_expert)
     for n_tokens in (1, 5, 70):
@@ -182,11 +214,18 @@ def _special_rows(n_expert, n_used, rng):
     r = base.copy()
     r[n_expert - 2] = inf
     rows["+inf at one index"] = r
+    r = base.copy()                                                  # lane 5 holds experts 5 + 64 j: every round takes one of ITS registers, in a shuffled order
+    own = 5 + 64 * np.arange(min(n_used, (n_expert - 5 + 63) // 64))
+    r[own] = np.float32(10.0) + rng.permutation(len(own)).astype(np.float32)
+    rows["one lane owns every winner"] = r
+    r = base.copy()                                                  # the n_used largest from n_expert - 1 downwards: the highest registers, the last lanes
+    r[n_expert - 1 - np.arange(n_used)] = np.float32(10.0) + np.float32(0.25) * rng.permutation(n_used).astype(np.float32)
+    rows["the last registers"] = r
     return rows
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("n_expert,n_used", ((8, 4), (130, 8), (1024, 64)))
+@pytest.mark.parametrize("n_expert,n_used", SPECIAL_CASES)
 def test_the_special_rows_are_exact_on_ids(dev, n_expert, n_used):
     rng = np.random.default_rng(1000 + n_expert)
     n_tokens, where = 70, (0, 37, 69)
@@ -204,7 +243,7 @@ def test_the_special_rows_are_exact_on_ids(dev, n_expert, n_used):
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("n_expert,n_used", ((8, 2), (60, 8), (65, 8), (128, 8), (1024, 64)))
+@pytest.mark.parametrize("n_expert,n_used", WEIGHT_CASES)
 def test_the_weights_are_within_the_derived_bound_of_the_float64_restatement(dev, n_expert, n_used):
     rng = np.random.default_rng(2000 + n_expert)
     logits = rng.uniform(-8.0, 8.0, (70, n_expert)).astype(np.float32)
@@ -251,7 +290,7 @@ def _combine(dev, d_y, d_w, T, U, M, ld, off, mode, add_np):
 def test_the_combine_is_bit_exact(dev, M):
     rng = np.random.default_rng(3000 + M)
     for n_tokens in (1, 70):
-        for n_used in (1, 2, 8):
+        for n_used in (1, 2, 8) + ((3, 5, 6, 9, 64) if M in (7, 4100) else ()):     # (the vector form's slot loop is unrolled by four)
             y = rng.standard_normal((n_tokens, n_used, M)).astype(np.float32)
             y[n_tokens // 2, n_used - 1] = 0.0                       # a pair row of +0.0f: what an id outside the set leaves
             if n_tokens > 1:

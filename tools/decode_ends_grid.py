@@ -11,7 +11,10 @@ Timed as tools/rope_grid.py times: a REPLAYED graph of 32 calls rotating over bu
   sample     ggml_hip_sample_topk_dev, k = 40, top_p 0.9, with the pick; the same shapes.        bytes: the same
   sample-k1  the same entry at k = 1 (one round in each stage): sample - sample-k1 is what the 39 further rounds of both stages cost
 roof = bytes / time / 8 TB/s.  floor = time / 3 us, the launch floor DESIGN.md 17 measured (one launch; the sampler is two): given for the
-one-row (one-id) cases, which move kilobytes and measure launches, not the memory system."""
+one-row (one-id) cases, which move kilobytes and measure launches, not the memory system.
+Timed here, not checked: the kernel forms these vocabularies select (k = 40: 8 / 38 / 64 chunks, 2 / 8 / 16 candidate keys per thread in the
+merge) are held to their yardsticks by tests/test_decode_ends.py, at vocabularies of 4, 8, 16, 32, 64 and 128 chunks of 4096 logits, of
+4, 8, ... 128 chunks and one logit, and of 2^20 logits (every merge form, full and nearly empty)."""
 import os
 import sys
 
