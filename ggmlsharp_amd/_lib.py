@@ -108,6 +108,12 @@ class ggml_hip_attn_ragged_plan_t(C.Structure):
                 ("decode_workgroups", C.c_int64), ("merge_workgroups", C.c_int64), ("prompt_workgroups", C.c_int64), ("index_bytes", C.c_int64)]
 
 
+class ggml_hip_ssm_plan_t(C.Structure):
+    """include/ggml_hip_ext.h: the plan of one selective-scan call (csrc/plan.cpp plan_ssm_scan)"""
+    _fields_ = [("form", C.c_int32), ("launches", C.c_int32), ("slices", C.c_int32), ("lanes_per_row", C.c_int32),
+                ("rows_per_workgroup", C.c_int64), ("workgroups", C.c_int64)]
+
+
 class ggml_hip_rope_params_t(C.Structure):
     """include/ggml_hip_ext.h: the parameters of a rotary embedding (mode 0 NORMAL, 2 NEOX)"""
     _fields_ = [("n_dims", C.c_int32), ("mode", C.c_int32), ("n_ctx_orig", C.c_int32),
@@ -300,6 +306,15 @@ HIP_SYMBOLS = {
     "ggml_hip_sample_topk_dev": (C.c_int, [_P, C.c_int64, C.c_int64, C.c_int64, C.c_int, C.c_float, C.c_float, _P, _P, _P, _P, _P, C.c_size_t, _P]),
     # ... and the last row of every sequence of a ragged step: the rows the LM head needs
     "ggml_hip_ragged_last_rows_dev": (C.c_int, [_P, C.c_int64, _P, C.c_int64, C.c_int64, C.c_int64, _P, C.c_int64, _P]),
+    # the recurrent ops of a Mamba / Mamba-2 block over a ragged batch and a pool of state slots: the slot sizes and the scan's plan (host only), the
+    # causal conv with its rolling window, the selective scan
+    "ggml_hip_ssm_conv_state_bytes": (C.c_size_t, [C.c_int64, C.c_int]),
+    "ggml_hip_ssm_state_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
+    "ggml_hip_ssm_scan_plan": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int64, _P]),
+    "ggml_hip_ssm_conv_ragged_dev": (C.c_int, [_P, C.c_int64, _P, _P, C.c_int, C.c_int64, C.c_int, C.c_int64, _P, C.c_int64, _P, _P, _P, C.c_int64, C.c_int64,
+                                               _P, C.c_int64, _P]),
+    "ggml_hip_ssm_scan_ragged_dev": (C.c_int, [_P, C.c_int64, C.c_int64, _P, C.c_int64, _P, _P, C.c_int64, C.c_int, _P, _P, C.c_int64, _P, C.c_int, C.c_int,
+                                               C.c_int, C.c_int, C.c_int64, _P, C.c_int64, _P, _P, _P, C.c_int64, C.c_int64, _P, C.c_int64, C.c_int64, _P]),
 }
 SYMBOLS = HIP_SYMBOLS
 

@@ -530,6 +530,25 @@ hipError_t launch_rope_kv_store_paged(const rope_table &tab, const rope_args &a,
 // the same over packed rows: a.n_tokens = rg.n_tokens_max, the row's sequence and position from ragged_find
 hipError_t launch_rope_kv_store_paged_ragged(const rope_table &tab, const rope_args &a, int kv_type, const kv_ragged &rg, void *pool, int64_t nb_pos,
                                              int64_t nb_head, const kv_pages &pg, hipStream_t st);
+// ssm.hip: the causal conv and the selective scan of a Mamba block over a ragged batch and a pool of f32 state slots (ggml_hip_ssm_conv_ragged_dev /
+// ggml_hip_ssm_scan_ragged_dev, ssm.cpp; the grids are plan.h's plan_ssm_conv / plan_ssm_scan).  len / slot: int32 [n_seq]; slot_elems: floats between slots
+struct ssm_conv_plan;
+struct ssm_scan_plan;
+hipError_t launch_ssm_conv(const ssm_conv_plan &pl, const kv_ragged &rg, const int32_t *len, const int32_t *slot, int n_slots, const float *x, int64_t ldx,
+                           const float *w, const float *bias, int act, int64_t n_ch, int d_conv, float *state, int64_t slot_elems, float *dst, int64_t ldd,
+                           hipStream_t st);
+struct ssm_scan_args {
+    const float *x; int64_t ldx_tok, ldx_head;                       // [tok][n_head][P]
+    const float *dt; int64_t ld_dt; const float *dt_bias;            // [tok][n_head]; [n_head] or null
+    const float *A; int64_t a_ld; int a_per_state;                   // [n_head][a_ld]: one value per head, or N per head
+    const float *B, *C; int64_t ld_bc;                               // [tok][n_group][N], ld_bc floats between tokens (both)
+    const float *D;                                                  // [n_head] or null
+    int n_head, P, N, n_group;
+    const int32_t *len, *slot; int n_slots;
+    float *state; int64_t slot_elems;
+    float *dst; int64_t ldd_tok, ldd_head;
+};
+hipError_t launch_ssm_scan(const ssm_scan_plan &pl, const kv_ragged &rg, const ssm_scan_args &a, hipStream_t st);
 // gemm_q8s.hip / gemm_qmx.hip: ONE K3s launch over the tile table -- workgroup -> (weight tile group, column tile t); t >= *n_tiles leaves at once;
 // the expert's planes come from tab[tiles[t].expert], the 32 sorted rows at 32 t of the image p (K1's image of `32 * max_tiles` rows); res [rows][ldr]
 hipError_t launch_gemm_q8_small_grouped(const mm_plan &g, int type, const moe_gexpert *tab, const moe_tile *tiles, const int32_t *n_tiles, int64_t max_tiles,

@@ -695,3 +695,32 @@ attn_ragged_plan plan_attn_ragged(int kv_type, int D, int n_head, int n_head_kv,
     p.work_bytes = p.part_off + (size_t)n_dec_rows_max * (size_t)n_head * (size_t)cdiv(n_kv_max, ATTN_CHUNK) * (size_t)(D + 4) * 4;
     return p;
 }
+
+// The SSM entries (plan.h has the statement): one launch each, a workgroup row per sequence, sized by the shape and n_seq alone.
+ssm_conv_plan plan_ssm_conv(int64_t n_ch, int d_conv, int64_t n_seq) {
+    ssm_conv_plan p = {};
+    if (n_ch < 1 || n_ch > SSM_MAX_CHANNELS || d_conv < 2 || d_conv > 4 || n_seq < 1 || n_seq > ATTN_PAGED_MAX_SEQ) return p;
+    p.ok = 1;
+    p.launches = 1;
+    p.state_bytes = (size_t)(d_conv - 1) * (size_t)n_ch * 4;
+    p.wgs_x = cdiv(n_ch, 256);
+    p.wgs = p.wgs_x * n_seq;
+    return p;
+}
+
+ssm_scan_plan plan_ssm_scan(int n_head, int P, int N, int n_group, int64_t n_seq) {
+    ssm_scan_plan p = {};
+    if (n_head < 1 || n_head > SSM_MAX_HEADS || P < 1 || P > 256 || N < 16 || N > 256 || N % 16 != 0) return p;
+    if (n_group < 1 || n_head % n_group != 0 || n_seq < 1 || n_seq > ATTN_PAGED_MAX_SEQ) return p;
+    p.ok = 1;
+    p.form = SSM_FORM_SEQUENTIAL;
+    p.launches = 1;
+    p.slices = N / 16;
+    p.lanes_per_row = 1;
+    while (p.lanes_per_row < p.slices) p.lanes_per_row *= 2;
+    p.rows_per_wg = 256 / p.lanes_per_row;
+    p.state_bytes = (size_t)n_head * (size_t)P * (size_t)N * 4;
+    p.wgs_x = cdiv((int64_t)n_head * P, p.rows_per_wg);
+    p.wgs = p.wgs_x * n_seq;
+    return p;
+}

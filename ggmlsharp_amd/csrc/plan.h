@@ -168,6 +168,21 @@ struct attn_ragged_plan {
 int64_t attn_ragged_max_tiles(int64_t n_tokens_max, int64_t n_seq);
 attn_ragged_plan plan_attn_ragged(int kv_type, int D, int n_head, int n_head_kv, int64_t n_seq, int64_t n_tokens_max, int64_t n_dec_rows_max, int64_t n_kv_max,
                                   int64_t window);
+// ---- the SSM entries: causal conv and selective scan over a ragged batch and a pool of state slots (ssm.hip; ggml_hip_ssm_*_ragged_dev) ----
+// ONE launch each, grid (x) x (n_seq): a workgroup row per sequence, so a token loop's trip count is uniform over a workgroup.  Nothing follows the
+// batch or n_tokens_max.  ok = 0: the shape is not served.
+//   conv: one thread per (sequence, channel), 256 channels per workgroup.  1 <= n_ch <= 2^24, d_conv 2 .. 4.  A slot is [d_conv - 1][n_ch] f32.
+//   scan: ONE form, sequential over a sequence's tokens, one lane per (sequence, head, p, slice of 16 states).  A state row of N = 16 * slices
+//         elements lives in an aligned group of lanes_per_row = the next power of two at or above slices (1, 2, 4, 8, 16; the lanes past `slices` idle),
+//         256 / lanes_per_row rows per workgroup.  1 <= n_head <= 2^20, 1 <= P <= 256, N a multiple of 16 up to 256, n_group divides n_head.
+//         A slot is [n_head][P][N] f32.
+constexpr int64_t SSM_MAX_CHANNELS = 1 << 24;
+constexpr int SSM_MAX_HEADS = 1 << 20;
+enum ssm_form { SSM_FORM_NONE = 0, SSM_FORM_SEQUENTIAL = 1 };
+struct ssm_conv_plan { int ok, launches; size_t state_bytes; int64_t wgs_x, wgs; };
+struct ssm_scan_plan { int ok, form, launches, slices, lanes_per_row, rows_per_wg; size_t state_bytes; int64_t wgs_x, wgs; };
+ssm_conv_plan plan_ssm_conv(int64_t n_ch, int d_conv, int64_t n_seq);
+ssm_scan_plan plan_ssm_scan(int n_head, int P, int N, int n_group, int64_t n_seq);
 // the K1 image for (type, K, N) with no weight at hand (no M: the exception cannot apply)
 int plan_image_kind(int type, int64_t K, int64_t N);
 // thread-local test switch (ggml_hip_debug_force_gemm): 0 auto, 1 int8, 2 f16, 3 MX

@@ -667,6 +667,86 @@ def ragged_last_rows(x, q_start, n_tokens_max=None, out=None):
     return out
 
 
+def ssm_scan_plan(n_head, head_dim, d_state, n_group=1, n_seq=1):
+    """the ggml_hip_ssm_plan_t of one selective-scan call: the form, the lanes of a state row, the workgroups; no device needed"""
+    out = _lib.ggml_hip_ssm_plan_t()
+    check(lib().ggml_hip_ssm_scan_plan(n_head, head_dim, d_state, n_group, n_seq, C.byref(out)), "ggml_hip_ssm_scan_plan")
+    return out
+
+
+def ssm_state_bytes(n_head, head_dim, d_state):
+    return int(lib().ggml_hip_ssm_state_bytes(n_head, head_dim, d_state))
+
+
+def ssm_conv_state_bytes(n_ch, d_conv):
+    return int(lib().ggml_hip_ssm_conv_state_bytes(n_ch, d_conv))
+
+
+def _ssm_batch(q_start, d_len, slot, state):
+    """(n_seq, nb_slot, n_slots) of a ragged SSM batch: q_start int32 [n_seq + 1], d_len / slot int32 [n_seq], state f32 [n_slots, >= slot elements]"""
+    assert q_start.is_cuda and q_start.dtype == torch.int32 and q_start.is_contiguous() and q_start.numel() >= 2
+    n_seq = q_start.numel() - 1
+    for t in (d_len, slot):
+        assert t.is_cuda and t.dtype == torch.int32 and t.is_contiguous() and t.numel() == n_seq
+    assert state.is_cuda and state.dtype == torch.float32 and state.dim() == 2 and state.stride(1) == 1
+    return n_seq, state.stride(0) * 4, state.shape[0]
+
+
+def ssm_conv_ragged(x, w, q_start, d_len, slot, state, bias=None, act=False, n_tokens_max=None, out=None):
+    """upstream's ggml_ssm_conv over a ragged batch: x f32 [n_tokens_max, n_ch] packed rows (last stride 1), w f32 [n_ch, d_conv], bias f32 [n_ch] or
+    None, act: a plain f32 silu behind it.  Sequence b owns rows q_start[b] .. q_start[b+1] - 1 and the slot state[slot[b]] ([d_conv - 1, n_ch] f32): the
+    window starts from zeros where d_len[b] == 0 (the slot is not read), from the slot otherwise, and the slot then holds the sequence's last d_conv - 1
+    rows.  A slot id outside the pool gives +0.0 rows and writes no state.  out may be x.  Rows of no present sequence are not written."""
+    assert x.is_cuda and x.dtype == torch.float32 and x.dim() == 2 and x.stride(1) == 1
+    assert w.is_cuda and w.dtype == torch.float32 and w.dim() == 2 and w.is_contiguous() and w.shape[0] == x.shape[1]
+    assert bias is None or (bias.is_cuda and bias.dtype == torch.float32 and bias.is_contiguous() and bias.numel() == x.shape[1])
+    n_seq, nb_slot, n_slots = _ssm_batch(q_start, d_len, slot, state)
+    n_ch, d_conv = w.shape
+    if n_tokens_max is None:
+        n_tokens_max = x.shape[0]
+    assert n_tokens_max <= x.shape[0]
+    if out is None:
+        out = torch.zeros((x.shape[0], n_ch), dtype=torch.float32, device=x.device)
+    assert out.is_cuda and out.dtype == torch.float32 and out.dim() == 2 and out.stride(1) == 1 and out.shape[0] >= n_tokens_max and out.shape[1] >= n_ch
+    check(lib().ggml_hip_ssm_conv_ragged_dev(C.c_void_p(x.data_ptr()), x.stride(0), C.c_void_p(w.data_ptr()), _opt(bias), int(bool(act)), n_ch, d_conv, n_seq,
+                                             C.c_void_p(q_start.data_ptr()), n_tokens_max, C.c_void_p(d_len.data_ptr()), C.c_void_p(slot.data_ptr()),
+                                             C.c_void_p(state.data_ptr()), nb_slot, n_slots, C.c_void_p(out.data_ptr()), out.stride(0), _stream()),
+          "ggml_hip_ssm_conv_ragged_dev")
+    return out
+
+
+def ssm_scan_ragged(x, dt, A, B, C_, q_start, d_len, slot, state, dt_bias=None, D=None, n_tokens_max=None, out=None):
+    """upstream's ggml_ssm_scan over a ragged batch: x f32 [n_tokens_max, n_head, P] (last stride 1), dt f32 [n_tokens_max, n_head], A f32 [n_head]
+    (one value per head, Mamba-2) or [n_head, N] (per state, Mamba-1), B / C_ f32 [n_tokens_max, G, N] views with ONE token stride and contiguous groups,
+    dt_bias / D f32 [n_head] or None.  Per token: delta = softplus(dt + dt_bias), h = h * exp(delta * A) + (delta * x) * B, y = sum_n h_n C_n + D x, in
+    the order include/ggml_hip_ext.h fixes.  Sequence b continues from state[slot[b]] ([n_head, P, N] f32; zeros where d_len[b] == 0, the slot is not
+    read) and leaves its final state there.  A sequence's bits do not depend on the batch or on how its tokens are split over calls."""
+    assert x.is_cuda and x.dtype == torch.float32 and x.dim() == 3 and x.stride(2) == 1
+    n_rows, n_head, P = x.shape
+    assert dt.is_cuda and dt.dtype == torch.float32 and dt.dim() == 2 and dt.stride(1) == 1 and dt.shape[1] == n_head
+    assert A.is_cuda and A.dtype == torch.float32 and A.dim() in (1, 2) and A.shape[0] == n_head and A.stride(-1) == 1
+    for t in (B, C_):
+        assert t.is_cuda and t.dtype == torch.float32 and t.dim() == 3 and t.stride(2) == 1 and t.stride(1) == t.shape[2]
+    assert B.shape == C_.shape and B.stride(0) == C_.stride(0)
+    G, N = B.shape[1], B.shape[2]
+    for t in (dt_bias, D):
+        assert t is None or (t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and t.numel() == n_head)
+    n_seq, nb_slot, n_slots = _ssm_batch(q_start, d_len, slot, state)
+    if n_tokens_max is None:
+        n_tokens_max = n_rows
+    assert n_tokens_max <= min(n_rows, dt.shape[0], B.shape[0])
+    if out is None:
+        out = torch.zeros((n_rows, n_head, P), dtype=torch.float32, device=x.device)
+    assert out.is_cuda and out.dtype == torch.float32 and out.dim() == 3 and out.stride(2) == 1 and tuple(out.shape) == (n_rows, n_head, P)
+    per_state = A.dim() == 2
+    check(lib().ggml_hip_ssm_scan_ragged_dev(C.c_void_p(x.data_ptr()), x.stride(0), x.stride(1), C.c_void_p(dt.data_ptr()), dt.stride(0), _opt(dt_bias),
+                                             C.c_void_p(A.data_ptr()), A.stride(0), int(per_state), C.c_void_p(B.data_ptr()), C.c_void_p(C_.data_ptr()),
+                                             B.stride(0), _opt(D), n_head, P, N, G, n_seq, C.c_void_p(q_start.data_ptr()), n_tokens_max,
+                                             C.c_void_p(d_len.data_ptr()), C.c_void_p(slot.data_ptr()), C.c_void_p(state.data_ptr()), nb_slot, n_slots,
+                                             C.c_void_p(out.data_ptr()), out.stride(0), out.stride(1), _stream()), "ggml_hip_ssm_scan_ragged_dev")
+    return out
+
+
 def quantize_rows(type, x):
     """x f32 [nrows, k] on the device -> uint8 [nrows, k/32*type_size] reference-format blocks."""
     assert x.is_cuda and x.dtype == torch.float32 and x.is_contiguous()

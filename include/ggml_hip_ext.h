@@ -995,6 +995,90 @@ int ggml_hip_sample_topk_dev(const float *d_logits, int64_t ld, int64_t n_rows, 
                              int32_t *d_ids, float *d_probs, int32_t *d_token,
                              void *d_work, size_t work_bytes, void *stream);
 
+/* ---------------- SSM: the causal conv and the selective scan of a Mamba / Mamba-2 block over a ragged batch and a pool of state slots ----------------
+ * Upstream's ggml_ssm_conv and ggml_ssm_scan, EXTENSIONS like rope (the reference lists nothing): device entries only.  With the in / out
+ * projections, ggml_hip_silu_mul_rows_dev, the norms and the sampler they serve a recurrent layer, and a hybrid model that interleaves such layers
+ * with attention, inside one captured step.  Both entries are stream-ordered on `stream` on the current device; neither synchronizes or allocates;
+ * both may be captured; no atomics and no hand-off between workgroups.  Every refusal below is decided before a device is touched.
+ *
+ * THE BATCH (shared by both entries) is the ragged batch of the RAGGED PAGED ATTENTION section: packed rows, d_q_start int32 [n_seq + 1] on the device
+ *   (never NULL: GGML_HIP_ERR_ARG; 4-byte aligned, else GGML_HIP_ERR_SHAPE), n_tokens_max 0 .. 2^20 (negative: GGML_HIP_ERR_ARG; above:
+ *   GGML_HIP_ERR_SHAPE), 1 <= n_seq <= 4096 (else GGML_HIP_ERR_SHAPE).  Sequence b is PRESENT when 0 <= d_q_start[b] <= d_q_start[b+1] <= n_tokens_max;
+ *   n_q[b] = 0 is an idle slot.  An idle sequence and one that is not present write nothing, neither rows nor state, and no address is formed from
+ *   their bounds.  Rows that belong to no present sequence are not written.  Every sequence is looked at by itself (as attention does), so a present
+ *   sequence is served whatever the others' bounds are; present sequences that overlap are the caller's error.  n_tokens_max = 0 returns 0 and
+ *   writes nothing (after every other check).
+ * THE STATE CACHE.  d_state: a pool of n_slots >= 1 f32 slots (n_slots < 1: GGML_HIP_ERR_ARG), slot s at d_state + s * nb_slot bytes; d_state 16-byte
+ *   aligned, nb_slot a multiple of 16 and at least the slot's bytes (ggml_hip_ssm_conv_state_bytes / ggml_hip_ssm_state_bytes), n_slots * nb_slot
+ *   <= 2^48: else GGML_HIP_ERR_SHAPE.  d_slot: int32 [n_seq] on the device: sequence b uses slot d_slot[b].  An id outside [0, n_slots) makes the
+ *   sequence's output rows +0.0f and writes no state; no address is ever formed from such an id.  Two present sequences that name one slot are the
+ *   caller's error.  d_len: int32 [n_seq] on the device, the array attention takes: d_len[b] == 0 is a FRESH sequence, which starts from an all-zero
+ *   state -- the slot's old contents are NOT read, so NaN bytes left there do not matter -- and d_len[b] != 0 continues from the slot.  A replayed
+ *   graph therefore follows admissions and evictions with no host memset.  NULL d_len / d_slot / d_state: GGML_HIP_ERR_ARG; d_len / d_slot not
+ *   4-byte aligned: GGML_HIP_ERR_SHAPE.  AFTER THE CALL the slot of a present, non-idle sequence holds the state after its last token; every other
+ *   slot, and the bytes between slots, are untouched.  A state element is read at most once and written at most once per call: one token per
+ *   sequence moves the state twice and nothing more.
+ *
+ * ggml_hip_ssm_conv_ragged_dev: upstream's ggml_ssm_conv with its rolling window.  d_x, d_dst: f32 [n_tokens_max][n_ch], ldx / ldd >= n_ch apart;
+ *   d_w: f32 [n_ch][d_conv] contiguous; d_bias: f32 [n_ch] or NULL; a slot is [d_conv - 1][n_ch] f32, oldest row first.  1 <= n_ch <= 2^24 and
+ *   2 <= d_conv <= 4, else GGML_HIP_ERR_SHAPE; act 0 (none) or 1 (silu), else GGML_HIP_ERR_ARG.  NULL d_x / d_w / d_dst: GGML_HIP_ERR_ARG; a pointer
+ *   that is not 4-byte aligned: GGML_HIP_ERR_SHAPE.  d_dst == d_x (with ldd == ldx) is allowed; any other overlap is not.
+ *   THE STATEMENT.  For token t of sequence b and channel c let win be the slot's d_conv - 1 rows (zeros for a fresh sequence) followed by the
+ *   sequence's rows of this call.  Every operation is one binary32 rounding:
+ *       acc = w[c][0] * win[t][c];   acc = fmaf(w[c][k], win[t + k][c], acc) for k = 1 .. d_conv - 1 ascending;   acc = acc + bias[c] if given;
+ *       act = 1:  dst = acc / (1.0f + expf(-acc))     -- plain f32 with the library's expf, NOT the reference's f16-table silu
+ *   and the new slot is the last d_conv - 1 rows of win (for n_q[b] < d_conv - 1 that keeps old rows).  THE CONTRACT: act = 0 is bit for bit the
+ *   statement; act = 1 is within 3 * 2^-24 relative of the silu of those bits (expf within 1 ulp).  The slot is bit for bit.  Nothing depends on
+ *   the other sequences, the slot number, n_tokens_max, the strides or on how a sequence's tokens are split over calls.
+ *   One launch: one thread per (sequence, channel) walks the sequence's tokens.
+ *
+ * ggml_hip_ssm_scan_ragged_dev: upstream's ggml_ssm_scan in both of its forms.  n_head heads of head_dim P (1 .. 256), d_state N (a multiple of 16,
+ *   at most 256), n_group G dividing n_head, 1 <= n_head <= 2^20: else GGML_HIP_ERR_SHAPE.  A slot is [n_head][P][N] f32.
+ *   d_x, d_dst: f32 [n_tokens_max][n_head][P], token / head strides ldx_tok, ldx_head (ldd_tok, ldd_head) >= P elements; d_dst may not overlap an input.
+ *   d_dt:  f32 [n_tokens_max][n_head], ld_dt >= n_head apart.  d_dt_bias: f32 [n_head] or NULL.
+ *   d_A:   f32 [n_head][a_ld].  a_per_state = 0: A_n = A[h][0] for every n, a_ld >= 1 (Mamba-2).  a_per_state = 1: A_n = A[h][n], a_ld >= N and a
+ *          multiple of 4, d_A 16-byte aligned (Mamba-1, where P = 1 and n_head = d_inner).  Another value: GGML_HIP_ERR_ARG.
+ *   d_B, d_C: f32 [n_tokens_max][G][N], both ld_bc >= G * N apart, ld_bc a multiple of 4, both 16-byte aligned.  Head h reads group h / (n_head / G).
+ *   d_D:   f32 [n_head] or NULL.
+ *   A stride or alignment outside these: GGML_HIP_ERR_SHAPE.  NULL d_x / d_dt / d_A / d_B / d_C / d_dst: GGML_HIP_ERR_ARG.
+ *   THE STATEMENT, per token of a sequence in order, for head h, row p and state n; every operation is one binary32 rounding, expf and log1pf the
+ *   library's functions; h_n is the state element (zero for a fresh sequence):
+ *       d     = dt[t][h] + dt_bias[h]                       (d = dt[t][h] without a bias)
+ *       delta = d <= 20.0f ? log1pf(expf(d)) : d
+ *       a_n   = expf(delta * A_n)
+ *       h_n   = fmaf(h_n, a_n, (delta * x[t][h][p]) * B[t][g][n])
+ *       s_j   = h_16j * C_16j;   s_j = fmaf(h_n, C[t][g][n], s_j) for n = 16 j + 1 .. 16 j + 15 ascending        (slice j of 16 states, j < N / 16)
+ *       THE BUTTERFLY: with L = N / 16 and LP the least power of two >= L, s_j = +0.0f for L <= j < LP; then for d = 1, 2, 4, .. < LP in this order
+ *                      every s_j becomes s_j + s_(j xor d), all j at once.  y = s_0 (every s_j holds the same bits).
+ *       y     = fmaf(D[h], x[t][h][p], y) if D is given;    dst[t][h][p] = y
+ *   THREE BIT-LEVEL CONTRACTS: (i) a sequence's rows and final state are bit for bit those of a call with n_seq = 1; (ii) splitting a sequence's
+ *   tokens over several calls at any point gives the same bits as one call; (iii) nothing depends on the other sequences, the slot number,
+ *   n_tokens_max or the strides.
+ *   ONE FORM (ggml_hip_ssm_scan_plan, host only, shows it): sequential over a sequence's tokens, one lane per (sequence, head, p, slice); a state row
+ *   rides in the registers of an aligned group of LP lanes (lanes_per_row; L of them work) and the butterfly is lane moves inside the group.  One
+ *   launch of ceil(n_head * P * LP / 256) * n_seq workgroups, sized by the shape and n_seq alone.
+ *   LIMITS.  That form is exactly right for decode.  A long prefill walks its tokens one after the other with n_head * P * LP lanes: the chunked
+ *   matrix form (SSD) for long prefills is a follow-up, as is a token-parallel conv.  N that is no power-of-two multiple of 16 idles LP - L lanes of a
+ *   group.  States are f32 only.
+ * ggml_hip_ssm_state_bytes / ggml_hip_ssm_conv_state_bytes (host only): the bytes of one slot, n_head * P * N * 4 and (d_conv - 1) * n_ch * 4; 0 for a
+ *   shape the entries refuse. */
+typedef struct ggml_hip_ssm_plan_t {
+    int32_t form, launches;                  /* 1: sequential over tokens, parallel over (sequence, head, p, slice); launches of one call (1) */
+    int32_t slices, lanes_per_row;           /* L = N / 16; LP, the lanes of a state row's group */
+    int64_t rows_per_workgroup, workgroups;  /* 256 / LP; ceil(n_head * P / rows_per_workgroup) * n_seq */
+} ggml_hip_ssm_plan_t;
+size_t ggml_hip_ssm_conv_state_bytes(int64_t n_ch, int d_conv);
+size_t ggml_hip_ssm_state_bytes(int n_head, int head_dim, int d_state);
+int    ggml_hip_ssm_scan_plan(int n_head, int head_dim, int d_state, int n_group, int64_t n_seq, ggml_hip_ssm_plan_t *out);
+int    ggml_hip_ssm_conv_ragged_dev(const float *d_x, int64_t ldx, const float *d_w, const float *d_bias, int act, int64_t n_ch, int d_conv,
+                                    int64_t n_seq, const int32_t *d_q_start, int64_t n_tokens_max, const int32_t *d_len, const int32_t *d_slot,
+                                    float *d_state, int64_t nb_slot, int64_t n_slots, float *d_dst, int64_t ldd, void *stream);
+int    ggml_hip_ssm_scan_ragged_dev(const float *d_x, int64_t ldx_tok, int64_t ldx_head, const float *d_dt, int64_t ld_dt, const float *d_dt_bias,
+                                    const float *d_A, int64_t a_ld, int a_per_state, const float *d_B, const float *d_C, int64_t ld_bc,
+                                    const float *d_D, int n_head, int head_dim, int d_state_n, int n_group,
+                                    int64_t n_seq, const int32_t *d_q_start, int64_t n_tokens_max, const int32_t *d_len, const int32_t *d_slot,
+                                    float *d_state, int64_t nb_slot, int64_t n_slots, float *d_dst, int64_t ldd_tok, int64_t ldd_head, void *stream);
+
 #if defined(__GNUC__)
 #pragma GCC visibility pop
 #endif

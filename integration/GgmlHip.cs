@@ -202,6 +202,25 @@ internal static unsafe partial class GgmlHip
     [DllImport(Lib)] public static extern int ggml_hip_argmax_rows_dev(float* dLogits, long ld, long nRows, long nVocab, int* dIds, void* dWork, nuint workBytes, void* stream);
     [DllImport(Lib)] public static extern int ggml_hip_sample_topk_dev(float* dLogits, long ld, long nRows, long nVocab, int k, float invTemp, float topP, float* dU,
         int* dIds, float* dProbs, int* dToken, void* dWork, nuint workBytes, void* stream);
+    // ... the recurrent ops of a Mamba / Mamba-2 block (upstream's ggml_ssm_conv / ggml_ssm_scan) over the ragged batch (dQStart, nTokensMax) and a pool of
+    // f32 state slots: sequence b uses slot dSlot[b] (an id outside [0, nSlots): +0 rows, no state written), starts from zeros where dLen[b] == 0 (the
+    // slot is not read) and leaves the state after its last token in the slot.  conv: a slot is [dConv - 1][nCh], act 1 = plain f32 silu; dDst may be dX.
+    // scan: a slot is [nHead][headDim][dState]; aPerState 0: A is one value per head (Mamba-2), 1: [nHead][dState] (Mamba-1, headDim 1); B / C
+    // [tok][nGroup][dState].  A sequence's bits do not depend on the batch or on how its tokens are split over calls.  The sizes and the plan are host only
+    [StructLayout(LayoutKind.Sequential)]
+    public struct ggml_hip_ssm_plan_t
+    {
+        public int form, launches, slices, lanes_per_row;
+        public long rows_per_workgroup, workgroups;
+    }
+    [DllImport(Lib)] public static extern nuint ggml_hip_ssm_conv_state_bytes(long nCh, int dConv);
+    [DllImport(Lib)] public static extern nuint ggml_hip_ssm_state_bytes(int nHead, int headDim, int dState);
+    [DllImport(Lib)] public static extern int ggml_hip_ssm_scan_plan(int nHead, int headDim, int dState, int nGroup, long nSeq, ggml_hip_ssm_plan_t* plan);
+    [DllImport(Lib)] public static extern int ggml_hip_ssm_conv_ragged_dev(float* dX, long ldx, float* dW, float* dBias, int act, long nCh, int dConv, long nSeq,
+        int* dQStart, long nTokensMax, int* dLen, int* dSlot, float* dState, long nbSlot, long nSlots, float* dDst, long ldd, void* stream);
+    [DllImport(Lib)] public static extern int ggml_hip_ssm_scan_ragged_dev(float* dX, long ldxTok, long ldxHead, float* dDt, long ldDt, float* dDtBias, float* dA,
+        long aLd, int aPerState, float* dB, float* dC, long ldBc, float* dD, int nHead, int headDim, int dState, int nGroup, long nSeq, int* dQStart,
+        long nTokensMax, int* dLen, int* dSlot, float* dStatePool, long nbSlot, long nSlots, float* dDst, long lddTok, long lddHead, void* stream);
 
     // Seam 2: the quantize_fns_t slots (TypeDefinitions.cs:334-342), type-indexed
     [DllImport(Lib)] public static extern int ggml_hip_quantize_row(int type, float* x, void* y, int k);
