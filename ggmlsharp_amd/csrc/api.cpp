@@ -1,6 +1,7 @@
 // api.cpp -- the C-ABI of include/ggml_hip.h, part 1: lifecycle and device slots, resident weights, the hot path on
-// device-resident data, the row functions (Seam 2).  seams.cpp holds the host-pointer seams, multi.cpp the row split
-// over several devices.  No CPU fallback anywhere: without a device every compute entry returns GGML_HIP_ERR_NO_DEVICE.
+// device-resident data, the row functions (Seam 2).  seams.cpp holds the host-pointer seams, scope.cpp the graph scope,
+// wcache.cpp the Seam-1 weight cache, multi.cpp the row split over several devices.  No CPU fallback anywhere: without a
+// device every compute entry returns GGML_HIP_ERR_NO_DEVICE.
 #include "ctx.h"
 #include "plan.h"
 #include <algorithm>
@@ -94,51 +95,6 @@ int DeviceCtx::make_current() const {
     if (e != hipSuccess) return fail(GGML_HIP_ERR_RUNTIME, "hipSetDevice(%d): %s", device, hipGetErrorString(e));
     return GGML_HIP_OK;
 }
-uint64_t DeviceCtx::scratch_sig() const {
-    uint64_t h = 1469598103934665603ull;
-    const void *ps[] = {src1.p, dst.p, dst2.p, work.p, stage.p, aux[0].p, aux[1].p, aux[2].p, aux[3].p};
-    for (const void *q : ps) { h ^= (uint64_t)(uintptr_t)q; h *= 1099511628211ull; }
-    return h;
-}
-void DeviceCtx::scope_dirty() {
-    if (scope_mode == 1) { scope_clean = false; return; }
-    if (scope_mode != 2) return;
-    // capturing, and the next thing cannot be captured: end the capture, run what it holds, go on live
-    scope_mode = 0;
-    {   // (a weight re-upload after an invalidation lands here once; a scope that keeps doing it is left alone)
-        Captured &e = captured[scope_key];
-        e.seen = 0;
-        if (++e.strikes >= 3) { e.refused = true; ++n_refused; }
-    }
-    // (the capture is begun in relaxed mode, so the thread that ends it need not be the one that began it: a foreign thread's seam
-    // on this slot lands here too, seams.cpp Call::begin)
-    hipGraph_t g = nullptr;
-    hipError_t e = hipStreamEndCapture(stream, &g);
-    hipGraphExec_t ex = nullptr;
-    if (e == hipSuccess && !g) e = hipErrorStreamCaptureInvalidated;
-    if (e == hipSuccess) e = hipGraphInstantiate(&ex, g, nullptr, nullptr, 0);
-    if (e == hipSuccess) e = hipGraphLaunch(ex, stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(stream);
-    if (ex) (void)hipGraphExecDestroy(ex);
-    if (g) (void)hipGraphDestroy(g);
-    if (e != hipSuccess) {
-        // what the scope had issued so far did not run and cannot be issued again from here: its owner is told at the scope's end
-        // (ggml_hip_graph_end returns the error), the key is never captured again
-        (void)hipGetLastError();
-        scope_lost = true;
-        Captured &c = captured[scope_key];
-        if (!c.refused) { c.refused = true; ++n_refused; }
-        fail(GGML_HIP_ERR_RUNTIME, "a graph scope's capture could not be ended and issued live (%s): its nodes so far did not run", hipGetErrorString(e));
-    }
-}
-void DeviceCtx::drop_captured() {
-    for (auto &kv : captured) {
-        if (kv.second.exec) (void)hipGraphExecDestroy(kv.second.exec);
-        if (kv.second.graph) (void)hipGraphDestroy(kv.second.graph);
-        for (Resident &r : kv.second.buffers) pool.push_back(r);
-    }
-    captured.clear();
-}
 int DeviceCtx::sync_all() {
     scope_dirty();
     d2h_busy = false;
@@ -147,183 +103,27 @@ int DeviceCtx::sync_all() {
     if (e == hipSuccess) e = hipStreamSynchronize(s_d2h);
     return e == hipSuccess ? GGML_HIP_OK : fail(GGML_HIP_ERR_RUNTIME, "stream synchronize: %s", hipGetErrorString(e));
 }
-void *DeviceCtx::take(size_t n) {
-    // best fit: a graph that is computed again asks for the same sizes again and must find every one of them (a first fit
-    // hands a larger buffer to a smaller request and sends the larger request to hipMalloc -- four computes of a decoder layer
-    // until the pool had settled, and an allocation keeps a named scope from being captured)
-    size_t best = pool.size();
-    for (size_t i = 0; i < pool.size(); ++i)
-        if (pool[i].bytes >= n && pool[i].bytes <= 2 * n + 4096 && (best == pool.size() || pool[i].bytes < pool[best].bytes)) best = i;
-    if (best != pool.size()) {
-        void *p = pool[best].p;
-        pool.erase(pool.begin() + (long)best);
-        return p;
-    }
-    scope_dirty();                                 // (an allocation is not something a capture may contain)
-    void *p = nullptr;
-    if (hipMalloc(&p, n) != hipSuccess) return nullptr;
-    return p;
-}
-const void *DeviceCtx::resident_lookup(const void *host, size_t bytes) {
-    auto r = resident.find(host);
-    if (r != resident.end() && r->second.bytes >= bytes) return r->second.p;
-    return nullptr;
-}
-// a write to host range [host, host + bytes) makes every OTHER resident copy that overlaps it stale (a view with an
-// offset gets its own entry; the parent's device copy must not be served afterwards)
-void DeviceCtx::owe(void *host, const void *dev, size_t bytes) {
-    if (bytes >= OWE_EARLY_BYTES && wanted(host)) {
-        // a large result goes home at once, by DMA on the copy stream, beside the kernels that follow (a prompt-sized batch
-        // owes tens of MB per decoder layer: PCIe time that has to overlap the compute, not follow it); such a scope is
-        // issued live (a captured graph runs its branches one after the other)
-        scope_dirty();
-        for (size_t i = 0; i < owed.size(); ++i)
-            if (owed[i].host == host) { owed.erase(owed.begin() + (long)i); break; }
-        hipError_t e = hipEventRecord(ev_ready, stream);
-        if (e == hipSuccess) e = hipStreamWaitEvent(s_d2h, ev_ready, 0);
-        if (e == hipSuccess) e = hipMemcpyAsync(host, dev, bytes, hipMemcpyDeviceToHost, s_d2h);
-        if (e == hipSuccess) { d2h_busy = true; d2h_bytes += bytes; return; }
-        (void)hipGetLastError();                   // could not: owe it like a small one
-    }
-    for (Owed &o : owed)
-        if (o.host == host) { o.dev = dev; o.bytes = bytes; return; }
-    owed.push_back(Owed{host, dev, bytes});
-}
-// a buffer is about to be reused while a copy on the copy stream may still read it: later kernels wait for that stream
-void DeviceCtx::join_copies() {
-    if (!d2h_busy) return;
-    if (hipEventRecord(ev_d2h, s_d2h) != hipSuccess || hipStreamWaitEvent(stream, ev_d2h, 0) != hipSuccess) (void)hipGetLastError();
-}
-int DeviceCtx::pay(const void *only_dev, size_t only_bytes) {
-    if (owed.empty()) return GGML_HIP_OK;
-    std::vector<Owed> now, keep;
-    // (a product with ne02 > 1 owes one entry per 2-D slice, all inside one resident buffer: every entry that lies in
-    // [only_dev, only_dev + only_bytes) goes out before that buffer is recycled, not just the one at its base)
-    const uint8_t *lo = (const uint8_t *)only_dev, *hi = lo + (only_bytes ? only_bytes : 1);
-    for (const Owed &o : owed) (only_dev == nullptr || ((const uint8_t *)o.dev >= lo && (const uint8_t *)o.dev < hi) ? now : keep).push_back(o);
-    owed.swap(keep);
-    if (now.empty()) return GGML_HIP_OK;
-    d2h_busy = true;
-    // through the device mapping of the registered pool: one kernel for up to 32 copies; anything else: a DMA each
-    std::vector<const void *> src; std::vector<void *> dst; std::vector<size_t> nb;
-    hipError_t e = hipSuccess;
-    for (const Owed &o : now) {
-        d2h_bytes += o.bytes;
-        void *m = ((uintptr_t)o.host % 4 == 0 && (uintptr_t)o.dev % 4 == 0 && o.bytes % 4 == 0) ? host_range_device_ptr(o.host, o.bytes) : nullptr;
-        if (m) { src.push_back(o.dev); dst.push_back(m); nb.push_back(o.bytes); }
-        else if (e == hipSuccess) e = hipMemcpyAsync(o.host, o.dev, o.bytes, hipMemcpyDeviceToHost, stream);
-    }
-    for (size_t i = 0; i < src.size() && e == hipSuccess; i += 32) {
-        const int n = (int)(src.size() - i < 32 ? src.size() - i : 32);
-        e = launch_scatter_copy(src.data() + i, dst.data() + i, nb.data() + i, n, stream);
-    }
-    return e == hipSuccess ? GGML_HIP_OK : fail(GGML_HIP_ERR_RUNTIME, "device -> host copy of graph results: %s", hipGetErrorString(e));
-}
-// Only what may still be on its way matters: a range that is owed a result is paid first; copies already issued are waited
-// for; otherwise (the common case in a graph scope: leaves and nothing in flight) the upload can go out at once.
-int DeviceCtx::before_host_read(const void *host, size_t bytes) {
-    const uint8_t *a = (const uint8_t *)host, *b = a + bytes;
-    for (const Owed &o : owed) {
-        const uint8_t *x = (const uint8_t *)o.host, *y = x + o.bytes;
-        if (x < b && a < y) return pay_and_sync();
-    }
-    return d2h_busy ? sync_all() : GGML_HIP_OK;
-}
-int DeviceCtx::pay_and_sync() {
-    int rc = pay();
-    const int r2 = sync_all();
-    return rc ? rc : r2;
-}
-void DeviceCtx::drop_overlapping(const void *host, size_t bytes, bool keep_exact) {
-    const uint8_t *a = (const uint8_t *)host, *b = a + bytes;
-    for (auto it = resident.begin(); it != resident.end();) {
-        const uint8_t *x = (const uint8_t *)it->first, *y = x + it->second.bytes;
-        const bool overlap = x < b && a < y;
-        if (overlap && !(keep_exact && it->first == host)) {
-            (void)pay(it->second.p, it->second.bytes);   // its host copies go out (stream-ordered) before the buffer is reused
-            join_copies();
-            pool.push_back(it->second);
-            it = resident.erase(it);
-        } else {
-            ++it;
-        }
-    }
-}
-void *DeviceCtx::resident_buffer(const void *host, size_t bytes) {
-    drop_overlapping(host, bytes, true);
-    auto old = resident.find(host);
-    if (old != resident.end()) {
-        if (old->second.bytes >= bytes) return old->second.p;      // the same tensor computed again: reuse its buffer
-        (void)pay(old->second.p, old->second.bytes);
-        join_copies();
-        pool.push_back(old->second);
-        resident.erase(old);
-    }
-    void *p = take(bytes);
-    if (!p) return nullptr;
-    // the entry records the bytes the TENSOR occupies on the host, not the (possibly larger) capacity of a recycled buffer
-    resident[host] = Resident{p, bytes};
-    return p;
-}
-void DeviceCtx::drain(bool free_all) {
-    if (!owed.empty()) (void)pay_and_sync();       // (graph end has paid already; a shutdown inside a scope has not)
-    for (auto &kv : resident) pool.push_back(kv.second);
-    resident.clear();
-    for (ggml_hip_weight *w : transient) ggml_hip_weight_free(w);
-    transient.clear();
-    if (free_all) {
-        drop_captured();
-        for (Resident &r : pool) (void)hipFree(r.p);
-        pool.clear();
-    }
-}
-void DeviceCtx::invalidate(const void *host, size_t bytes) {
-    const uint8_t *a = (const uint8_t *)host, *b = a + (bytes ? bytes : 1);
-    bool synced = false;
-    for (auto it = cache.begin(); it != cache.end();) {
-        const uint8_t *x = (const uint8_t *)it->second.host, *y = x + (it->second.host_bytes ? it->second.host_bytes : 1);
-        if (x < b && a < y) {
-            if (!synced) { (void)sync_all(); drop_captured(); synced = true; }     // kernels of an open graph scope may still read the entry
-            for (ggml_hip_weight *w : it->second.slices) ggml_hip_weight_free(w);
-            cache_bytes -= it->second.dev_bytes < cache_bytes ? it->second.dev_bytes : cache_bytes;
-            it = cache.erase(it);
-        } else {
-            ++it;
-        }
-    }
-}
-void DeviceCtx::free_cache() {
-    drop_captured();
-    for (auto &kv : cache)
-        for (ggml_hip_weight *w : kv.second.slices) ggml_hip_weight_free(w);
-    cache.clear();
-    cache_bytes = 0;
-}
-size_t DeviceCtx::evict_lru(size_t need, size_t budget, const CacheKey *keep) {
-    size_t freed = 0;
-    bool synced = false;
-    for (;;) {
-        const bool over = budget ? cache_bytes + need > budget : freed < need;
-        if (!over) break;
-        auto victim = cache.end();
-        for (auto it = cache.begin(); it != cache.end(); ++it) {
-            if (keep && it->first == *keep) continue;
-            if (victim == cache.end() || it->second.last_use < victim->second.last_use) victim = it;
-        }
-        if (victim == cache.end()) break;                   // nothing left that may go
-        if (!synced) { (void)sync_all(); drop_captured(); synced = true; }     // kernels in flight (an open graph scope) may still read the entry
-        for (ggml_hip_weight *w : victim->second.slices) ggml_hip_weight_free(w);
-        freed += victim->second.dev_bytes;
-        cache_bytes -= victim->second.dev_bytes < cache_bytes ? victim->second.dev_bytes : cache_bytes;
-        cache.erase(victim);
-        ++cache_evictions;
-    }
-    return freed;
-}
 
 int n_slots() { return g_nslots.load(std::memory_order_acquire); }
 DeviceCtx *slot(int i) { return (i >= 0 && i < n_slots()) ? g_slots[i] : nullptr; }
 int bound_slot() { return (t_slot >= 0 && t_slot < n_slots()) ? t_slot : -1; }
+
+int Call::begin() {
+    int rc = ensure_init();
+    if (rc) return rc;
+    const int b = bound_slot();
+    if (b >= 0) ctxs.push_back(slot(b));
+    else for (int i = 0; i < n_slots(); ++i) ctxs.push_back(slot(i));
+    for (DeviceCtx *c : ctxs) {
+        if (!c) return fail(GGML_HIP_ERR_RUNTIME, "library was shut down during the call");
+        locks.emplace_back(c->mu);                 // slot order: no lock-order inversion between callers
+        if (c->dead) return fail(GGML_HIP_ERR_RUNTIME, "library was shut down during the call");   // (ggml_hip_shutdown won the race for this slot's lock)
+        // another thread is capturing a named scope on this slot's stream: this call's launches are none of that graph's
+        // business -- the capture is ended and issued live (its owner carries on live), then this call runs
+        if (c->scope_mode == 2 && c->scope_owner != std::this_thread::get_id()) c->scope_dirty();
+    }
+    return GGML_HIP_OK;
+}
 
 namespace {
 

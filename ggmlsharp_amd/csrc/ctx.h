@@ -42,6 +42,13 @@ inline size_t row_bytes_of(int t, int64_t k) { return TSIZE[t] * (size_t)(k / BL
 inline int64_t k_unit(const wtype *r) { return is_q(r->resident) && r->blck < QK ? QK : r->blck; }
 inline int64_t nelem(const ggml_tensor *t) { return t->ne[0] * t->ne[1] * t->ne[2] * t->ne[3]; }
 bool contiguous_f32(const ggml_tensor *t);
+inline size_t tensor_host_bytes(const ggml_tensor *t) {   // bytes from data to the end of the last element (strided tensors included)
+    const int blck = BLCK[t->type];
+    size_t end = (size_t)((t->ne[0] + blck - 1) / blck) * TSIZE[t->type];
+    for (int i = 1; i < 4; ++i)
+        if (t->ne[i] > 1) end += (size_t)(t->ne[i] - 1) * t->nb[i];
+    return end;
+}
 int act_image_kind(int type, int64_t K, int64_t N);              // by type, K and N alone (plan.cpp)
 int weight_image_kind(const ggml_hip_weight *w, int64_t N);         // ... for one weight (kind 0 when its planes exceed 32-bit offsets)
 mm_plan weight_plan(const ggml_hip_weight *w, int64_t N, bool one_call);   // plan.h: the one decision per product
@@ -161,8 +168,13 @@ struct DeviceCtx {
     const void *resident_lookup(const void *host, size_t bytes);
     void drop_overlapping(const void *host, size_t bytes, bool keep_exact);
     void drain(bool free_all);
+    // the weight cache (wcache.cpp)
     void invalidate(const void *host, size_t bytes);          // weight-cache entries built from an overlapping host range
     void free_cache();
+    // Seam 1's weights on this slot: rows [r0, r1) of every 2-D slice of src0 into *W -- the cached entry (cacheable: src0 is a leaf), else
+    // an upload that becomes one; the upload of a computed src0 belongs to the open graph scope (`transient`) or, outside one, goes to *owned
+    int acquire_weights(const ggml_tensor *src0, int64_t r0, int64_t r1, bool cacheable, bool in_graph, std::vector<ggml_hip_weight *> *W,
+                        std::vector<ggml_hip_weight *> *owned);
 };
 
 // ---- the slot table ----
@@ -171,6 +183,16 @@ DeviceCtx *slot(int i);
 int ensure_init();                                 // lazily ggml_hip_init(0), as before
 int bound_slot();                                  // the calling thread's slot, -1 = unbound (all slots)
 extern std::mutex g_table_mu;
+
+// which slots serve a call.  A thread bound to a slot (ggml_hip_bind_thread) runs on that slot alone; an unbound caller gets every slot, i.e.
+// the reference's row partition (Ggml.cs:6665-6672) for mul_mat and replicated execution for the cheap element-wise nodes.
+struct Call {
+    std::vector<DeviceCtx *> ctxs;
+    std::vector<std::unique_lock<std::recursive_mutex>> locks;
+    int begin();                                   // initialises the library if need be; locks the slots, in slot order
+    int G() const { return (int)ctxs.size(); }
+    bool in_graph() const { return ctxs[0]->graph_depth_ > 0; }
+};
 
 // host memory registered for DMA (ggml_hip_register_host_pool): true when [p, p + n) lies inside a registered range
 bool host_range_pinned(const void *p, size_t n);

@@ -313,3 +313,230 @@ def test_projection_groups_of_a_batch_go_down_together(dev, N):
                 assert np.array_equal(got[i].view(np.uint32), G.tensor_f32(gf.nodes[i]).view(np.uint32)), (N, it, i, gf.nodes[i].contents.op)
     finally:
         G.ggml_free(ctx)
+
+
+# ------------------------------------------------------------------ the host paths of the fused entries and of the element-wise seams
+# Every test below is Q4_0 with M = K = 64 and asserts bitwise equality with the same nodes run one by one through their own seams.
+FM = FK = 64
+
+
+def _view(t):
+    """numpy view of an f32 tensor's host data by its ne / nb (a padded row stride or a shared data pointer included)"""
+    c = t.contents
+    n = sum((c.ne[i] - 1) * c.nb[i] for i in range(4)) + 4
+    buf = np.ctypeslib.as_array((C.c_uint8 * n).from_address(c.data)).view(np.float32)
+    return np.lib.stride_tricks.as_strided(buf, shape=tuple(c.ne[i] for i in (3, 2, 1, 0)), strides=tuple(c.nb[i] for i in (3, 2, 1, 0)))
+
+
+def _f32(ctx, ne0, ne1, ne2=1, fill=None, pad=0):
+    """an f32 leaf [ne0, ne1, ne2] of random values (or `fill`); pad: that many unused floats behind every row (nb[1] = (ne0 + pad) * 4)"""
+    t = G.ggml_new_tensor_3d(ctx, G.F32, ne0 + pad, ne1, ne2)
+    t.contents.ne[0] = ne0
+    _view(t)[:] = _rand((ne2, ne1, ne0)) if fill is None else fill
+    return t
+
+
+def _alias(ctx, of):
+    """a second tensor on the same data: what a view node (an in-place op) is"""
+    c = of.contents
+    t = G.ggml_new_tensor_3d(ctx, G.F32, c.ne[0], c.ne[1], c.ne[2])
+    for i in range(4):
+        t.contents.nb[i] = c.nb[i]
+    t.contents.data = c.data
+    return t
+
+
+def _q4(ctx, K, M, ne2=1):
+    w = G.ggml_new_tensor_3d(ctx, G.Q4_0, K, M, ne2)
+    G.tensor_bytes(w)[:] = O.quantize_row(O.Q4_0, _rand((ne2 * M, K))).reshape(-1).view(np.uint8)
+    return w
+
+
+def _scoped(scoped, fn):
+    """fn() inside a plain graph scope (or on its own); the scope's end must succeed either way"""
+    L = _lib.lib()
+    if scoped:
+        _lib.check(L.ggml_hip_graph_begin(), "begin")
+    rc = fn()
+    if scoped:
+        _lib.check(L.ggml_hip_graph_end(), "end")
+    return rc, L.ggml_hip_last_error() if rc else b""
+
+
+def _snap(outs):
+    return [np.array(_view(t), copy=True).view(np.uint32) for t in outs]
+
+
+@pytest.fixture()
+def two_slots():
+    """two slots on the one device for the test, back to one slot on device 0 afterwards"""
+    L = _lib.lib()
+    L.ggml_hip_shutdown()
+    _lib.check(L.ggml_hip_init_devices(2, (C.c_int * 2)(0, 0)), "ggml_hip_init_devices")
+    yield
+    L.ggml_hip_shutdown()
+    _lib.check(L.ggml_hip_init(0), "ggml_hip_init")
+
+
+def _fallback(entry, case):
+    """One fused entry on operands its fused form does not take (case: "padded" dst rows, two "slices", or "slots": the caller has set two up), at
+    N = 2 and N = 5, inside and outside a graph scope: what the entry returns and leaves in every node's host memory is what the nodes' own seams
+    return and leave, one after the other."""
+    L = _lib.lib()
+    p = _params()
+    M, K = FM, FK
+    ns = 2 if case == "slices" else 1
+    pad = 4 if case == "padded" else 0
+    ctx = G.ggml_init(8 * 1024 * 1024)
+    try:
+        for N in (2, 5):
+            for scoped in (False, True):
+                W = _q4(ctx, K, M, ns)
+                X, Gn = _f32(ctx, K, N, ns, None), _f32(ctx, K, N, ns)
+                R, S = _f32(ctx, M, N, ns), _f32(ctx, 1, 1, 1, 0.375)
+                MM = _f32(ctx, M, N, ns, -7.0, pad)
+                ADD, NORM, MUL = _f32(ctx, M, N, ns, -7.0), _f32(ctx, K, N, ns, -7.0), _f32(ctx, K, N, ns, -7.0)
+                SC = _alias(ctx, MM)
+                with_add = entry == "mul_mat_add" or (entry == "norm_mul_mat" and not pad)
+                if entry == "mul_mat_add":
+                    outs = [MM, ADD]
+                    fused = lambda: L.ggml_hip_compute_forward_mul_mat_add(C.byref(p), W, X, MM, R, ADD)
+                    single = [lambda: L.ggml_hip_compute_forward_mul_mat(C.byref(p), W, X, MM), lambda: L.ggml_hip_compute_forward_add(C.byref(p), MM, R, ADD)]
+                elif entry == "mul_mat_scale":
+                    outs = [MM]
+                    fused = lambda: L.ggml_hip_compute_forward_mul_mat_scale(C.byref(p), W, X, MM, S, SC)
+                    single = [lambda: L.ggml_hip_compute_forward_mul_mat(C.byref(p), W, X, MM), lambda: L.ggml_hip_compute_forward_scale(C.byref(p), MM, S, SC)]
+                else:
+                    outs = [NORM, MUL, MM] + ([ADD] if with_add else [])
+                    fused = lambda: L.ggml_hip_compute_forward_norm_mul_mat(C.byref(p), X, Gn, NORM, MUL, W, MM, R if with_add else None, ADD if with_add else None)
+                    single = [lambda: L.ggml_hip_compute_forward_rms_norm(C.byref(p), X, NORM), lambda: L.ggml_hip_compute_forward_mul(C.byref(p), NORM, Gn, MUL),
+                              lambda: L.ggml_hip_compute_forward_mul_mat(C.byref(p), W, MUL, MM)] + ([lambda: L.ggml_hip_compute_forward_add(C.byref(p), MM, R, ADD)] if with_add else [])
+
+                def one_by_one():
+                    for f in single:
+                        rc = f()
+                        if rc:
+                            return rc
+                    return 0
+                rc, msg = _scoped(scoped, fused)
+                got = _snap(outs)
+                for t in outs:
+                    _view(t)[:] = -7.0
+                rc1, msg1 = _scoped(False, one_by_one)
+                want = _snap(outs)
+                what = (entry, case, N, scoped)
+                assert (rc, msg) == (rc1, msg1), what
+                # (a padded product cannot feed the add or the scale seam, which take contiguous operands only: there the entry's answer is theirs)
+                assert rc == (_lib.ERR_SHAPE if pad and entry != "norm_mul_mat" else 0), (what, msg)
+                for a, b in zip(got, want):
+                    assert np.array_equal(a, b), what
+                assert not np.array_equal(got[0], np.full_like(got[0], np.float32(-7.0).view(np.uint32))), what
+    finally:
+        G.ggml_free(ctx)
+
+
+@pytest.mark.parametrize("case", ["padded", "slices"])
+@pytest.mark.parametrize("entry", ["mul_mat_add", "mul_mat_scale", "norm_mul_mat"])
+def test_fused_entries_fall_back_to_the_single_seams(dev, entry, case):
+    """The not-fusable fallbacks of mul_mat_add, mul_mat_scale and norm_mul_mat: a dst whose row stride is padded (nb[1] = (M + 4) * 4) and two
+    slices (ne02 = 2); see _fallback.  With a padded product mul_mat_add and mul_mat_scale cannot succeed -- the add and the scale seam refuse a
+    non-contiguous operand, and refusals are part of the interface -- so there the entry must answer exactly as the single seams do (ERR_SHAPE with
+    their message, the product written); everywhere else the entry returns success."""
+    _fallback(entry, case)
+
+
+@pytest.mark.parametrize("entry", ["mul_mat_add", "mul_mat_scale", "norm_mul_mat"])
+def test_fused_entries_fall_back_on_two_slots(two_slots, entry):
+    _fallback(entry, "slots")
+
+
+@pytest.mark.parametrize("op", ["add", "mul"])
+def test_binary_seam_in_place_is_bitwise_the_out_of_place_seam(dev, op):
+    """add / mul whose dst shares src0's data (N * M = 128 elements), applied twice, inside and outside a graph scope (inside, the second
+    application finds its src0 resident in the buffer it writes): the shared data ends as the out-of-place seam's result."""
+    L = _lib.lib()
+    p = _params()
+    f = L.ggml_hip_compute_forward_add if op == "add" else L.ggml_hip_compute_forward_mul
+    ctx = G.ggml_init(4 * 1024 * 1024)
+    try:
+        for scoped in (False, True):
+            A, B = _f32(ctx, FM, 2), _f32(ctx, FM, 2)
+            D = _alias(ctx, A)
+            T1, T2 = _f32(ctx, FM, 2, 1, -7.0), _f32(ctx, FM, 2, 1, -7.0)
+            _lib.check(f(C.byref(p), A, B, T1), "out of place")
+            _lib.check(f(C.byref(p), T1, B, T2), "out of place")
+            rc, msg = _scoped(scoped, lambda: f(C.byref(p), A, B, D) or f(C.byref(p), D, B, D))
+            assert rc == 0, msg
+            assert np.array_equal(_snap([A])[0], _snap([T2])[0]), (op, scoped)
+    finally:
+        G.ggml_free(ctx)
+
+
+def test_scale_seam_scales_dst_own_memory_when_it_is_no_view_of_src0(dev):
+    """scale whose dst is NOT a view of src0 (128 elements): the result is dst's old contents times the scalar, whatever src0 holds --
+    bitwise what the in-place seam makes of the same contents -- inside and outside a graph scope."""
+    L = _lib.lib()
+    p = _params()
+    ctx = G.ggml_init(4 * 1024 * 1024)
+    try:
+        for scoped in (False, True):
+            S = _f32(ctx, 1, 1, 1, 0.375)
+            src0, D, V = _f32(ctx, FM, 2), _f32(ctx, FM, 2), _f32(ctx, FM, 2)
+            old = np.array(_view(D), copy=True)
+            _view(V)[:] = old
+            _lib.check(L.ggml_hip_compute_forward_scale(C.byref(p), V, S, _alias(ctx, V)), "in place")
+            rc, msg = _scoped(scoped, lambda: L.ggml_hip_compute_forward_scale(C.byref(p), src0, S, D))
+            assert rc == 0, msg
+            assert np.array_equal(_snap([D])[0], _snap([V])[0]), scoped
+            assert np.array_equal(_view(D), old * np.float32(0.375)), scoped
+    finally:
+        G.ggml_free(ctx)
+
+
+def test_norm_mul_mat_multi_chain_is_replayed_bitwise(dev):
+    """norm -> mul -> two mul_mats through ggml_hip_compute_forward_mul_mat_multi (n = 2, N = 2) inside a keyed scope run three times -- observed,
+    captured, replayed (the scope counters say so) -- after the nodes ran one by one (the reference; it also fills the weight cache and grows the
+    scratch) and two plain scopes settled the buffer pool: every run's results are bitwise the first keyed run's and the one-by-one seams'."""
+    L = _lib.lib()
+    p = _params()
+    N = 2
+    ctx = G.ggml_init(8 * 1024 * 1024)
+    try:
+        W = [_q4(ctx, FK, FM), _q4(ctx, FK, FM)]
+        X, Gn = _f32(ctx, FK, N), _f32(ctx, FK, N)
+        NORM, MUL = _f32(ctx, FK, N, 1, -7.0), _f32(ctx, FK, N, 1, -7.0)
+        Dst = [_f32(ctx, FM, N, 1, -7.0), _f32(ctx, FM, N, 1, -7.0)]
+        outs = [NORM, MUL] + Dst
+        _lib.check(L.ggml_hip_compute_forward_rms_norm(C.byref(p), X, NORM), "norm")
+        _lib.check(L.ggml_hip_compute_forward_mul(C.byref(p), NORM, Gn, MUL), "mul")
+        for w, d in zip(W, Dst):
+            _lib.check(L.ggml_hip_compute_forward_mul_mat(C.byref(p), w, MUL, d), "mul_mat")
+        want = _snap(outs)
+
+        def run(key):
+            for t in outs:
+                _view(t)[:] = -7.0
+            _lib.check(L.ggml_hip_graph_begin_keyed(key) if key else L.ggml_hip_graph_begin(), "begin")
+            _lib.check(L.ggml_hip_compute_forward_mul_mat_multi(C.byref(p), 2, (G._T * 2)(*W), MUL, (G._T * 2)(*Dst), X, Gn, NORM), "multi")
+            _lib.check(L.ggml_hip_graph_end(), "end")
+            return _snap(outs)
+
+        def counters():
+            v = [C.c_uint64() for _ in range(4)]
+            L.ggml_hip_debug_scope_counters(*[C.byref(x) for x in v])
+            return tuple(int(x.value) for x in v)        # observed, captured, replayed, refused
+        for _ in range(2):
+            run(0)
+        c0 = counters()
+        first = run(0x5EA31)
+        second = run(0x5EA31)
+        c2 = counters()
+        third = run(0x5EA31)
+        c3 = counters()
+        assert tuple(b - a for a, b in zip(c0, c2)) == (1, 1, 0, 0), (c0, c2)
+        assert tuple(b - a for a, b in zip(c2, c3)) == (0, 0, 1, 0), (c2, c3)
+        for r in (second, third, want):
+            for a, b in zip(first, r):
+                assert np.array_equal(a, b)
+    finally:
+        G.ggml_free(ctx)
