@@ -84,10 +84,7 @@ int act_image_kind(int type, int64_t K, int64_t N) { return plan_image_kind(type
 mm_plan weight_plan(const ggml_hip_weight *w, int64_t N, bool one_call) { return plan_mul_mat(w->type, w->ext_type, w->M, w->K, N, one_call); }
 // ... for ONE weight, as the two-phase entries see it (INIT writes it, COMPUTE reads it): the stated exception included -- planes beyond
 // 32-bit buffer offsets are served by the int8 family and its image
-int weight_image_kind(const ggml_hip_weight *w, int64_t N) {
-    const mm_plan pl = weight_plan(w, N, false);
-    return (pl.image >= 0 && pl.image <= 3 ? pl.image : 0) | ((pl.flags & MM_FLAG_MIN_PIECES) ? ACT_IMAGE_MIN_PIECES : 0);
-}
+int weight_image_kind(const ggml_hip_weight *w, int64_t N) { return plan_act_image(weight_plan(w, N, false)); }
 
 // ---------------- DeviceCtx ----------------
 int DeviceCtx::make_current() const {
@@ -471,11 +468,11 @@ static int check_src1_alignment(const float *d_src1, int64_t ld1) {
     return GGML_HIP_OK;
 }
 
-int ggml_hip_mul_mat_init_dev(const ggml_hip_weight *w, const float *d_src1, int64_t N, int64_t ld1, void *d_work,
-                              size_t work_bytes, void *stream) {
-    if (!w || !d_src1) return fail(GGML_HIP_ERR_ARG, "null argument");
-    if (N <= 0) return GGML_HIP_OK;
-    if (!is_q(w->type)) return GGML_HIP_OK;  // dense: INIT is a no-op for f32 (Ggml.cs:6117-6120); f16 rounds in-kernel
+// ONE plan per call: an entry plans once and hands the plan to the INIT and COMPUTE steps below, so the two agree because they hold the
+// same plan.  A one-call plan that is not the fused mat-vec IS the COMPUTE-only plan, field for field (tools/plan_dump.cpp --check).
+// The INIT step of a quantized weight: K1 writes the image of `pl` (d_src1 is not null, N > 0)
+static int mul_mat_init_step(const ggml_hip_weight *w, const mm_plan &pl, const float *d_src1, int64_t N, int64_t ld1, void *d_work,
+                             size_t work_bytes, void *stream) {
     if (ld1 < w->K) return fail(GGML_HIP_ERR_SHAPE, "ld1 < K");
     int rc = check_src1_alignment(d_src1, ld1);
     if (rc) return rc;
@@ -484,8 +481,16 @@ int ggml_hip_mul_mat_init_dev(const ggml_hip_weight *w, const float *d_src1, int
     rc = weight_device_current(w);
     if (rc) return rc;
     act_planes p = act_carve(d_work, w->K, pad_act(N));
-    HIP_TRY(launch_quantize_act(d_src1, N, w->K, ld1, p, weight_image_kind(w, N), (hipStream_t)stream, weight_row(w)->q8k));
+    HIP_TRY(launch_quantize_act(d_src1, N, w->K, ld1, p, plan_act_image(pl), (hipStream_t)stream, weight_row(w)->q8k));
     return GGML_HIP_OK;
+}
+
+int ggml_hip_mul_mat_init_dev(const ggml_hip_weight *w, const float *d_src1, int64_t N, int64_t ld1, void *d_work,
+                              size_t work_bytes, void *stream) {
+    if (!w || !d_src1) return fail(GGML_HIP_ERR_ARG, "null argument");
+    if (N <= 0) return GGML_HIP_OK;
+    if (!is_q(w->type)) return GGML_HIP_OK;  // dense: INIT is a no-op for f32 (Ggml.cs:6117-6120); f16 rounds in-kernel
+    return mul_mat_init_step(w, weight_plan(w, N, false), d_src1, N, ld1, d_work, work_bytes, stream);
 }
 
 int ggml_hip_act_image_kind(int type, int64_t K, int64_t N) {
@@ -548,20 +553,25 @@ static hipError_t launch_planned(const ggml_hip_weight *w, const mm_plan &pl, ac
     }
 }
 
+// The COMPUTE step of a quantized weight on the image the INIT step wrote for the same plan (d_dst is not null, N > 0, M > 0)
+static int mul_mat_compute_step(const ggml_hip_weight *w, const mm_plan &pl, int64_t N, float *d_dst, int64_t ldd, const void *d_work,
+                                size_t work_bytes, void *stream) {
+    if (ldd < w->M) return fail(GGML_HIP_ERR_SHAPE, "ldd < M");
+    if (!d_work || work_bytes < ggml_hip_mul_mat_work_size(w->type, w->K, N)) return fail(GGML_HIP_ERR_ARG, "work buffer too small");
+    int rc = weight_device_current(w);
+    if (rc) return rc;
+    const act_planes p = act_carve((void *)d_work, w->K, pad_act(N));
+    HIP_TRY(launch_planned(w, pl, p, N, d_dst, ldd, (hipStream_t)stream, nullptr));
+    if (pl.flags & MM_FLAG_MIN_PASS) HIP_TRY(launch_q2k_min_pass(w, p, N, d_dst, ldd, (hipStream_t)stream));   // (Q2_K: dst -= its min term)
+    return GGML_HIP_OK;
+}
+
 int ggml_hip_mul_mat_compute_dev(const ggml_hip_weight *w, int64_t N, float *d_dst, int64_t ldd, const void *d_work,
                                  size_t work_bytes, void *stream) {
     if (!w || !d_dst) return fail(GGML_HIP_ERR_ARG, "null argument");
     if (N <= 0 || w->M <= 0) return GGML_HIP_OK;
     if (!is_q(w->type)) return fail(GGML_HIP_ERR_TYPE, "compute_dev is the quantized COMPUTE phase; use ggml_hip_mul_mat_dev for dense");
-    if (ldd < w->M) return fail(GGML_HIP_ERR_SHAPE, "ldd < M");
-    if (!d_work || work_bytes < ggml_hip_mul_mat_work_size(w->type, w->K, N)) return fail(GGML_HIP_ERR_ARG, "work buffer too small");
-    int rc = weight_device_current(w);
-    if (rc) return rc;
-    const mm_plan pl = weight_plan(w, N, false);            // (the COMPUTE-only entry: INIT wrote this plan's image)
-    const act_planes p = act_carve((void *)d_work, w->K, pad_act(N));
-    HIP_TRY(launch_planned(w, pl, p, N, d_dst, ldd, (hipStream_t)stream, nullptr));
-    if (pl.flags & MM_FLAG_MIN_PASS) HIP_TRY(launch_q2k_min_pass(w, p, N, d_dst, ldd, (hipStream_t)stream));   // (Q2_K: dst -= its min term)
-    return GGML_HIP_OK;
+    return mul_mat_compute_step(w, weight_plan(w, N, false), N, d_dst, ldd, d_work, work_bytes, stream);   // (INIT wrote this plan's image)
 }
 
 // the Q2_K min pass alone, on the image ggml_hip_mul_mat_init_dev wrote (TEST HOOK: the two forms side by side, and the pass's own time)
@@ -579,15 +589,13 @@ int ggml_hip_debug_q2k_min_pass_dev(const ggml_hip_weight *w, int64_t N, float *
     return GGML_HIP_OK;
 }
 
-int ggml_hip_mul_mat_dev(const ggml_hip_weight *w, const float *d_src1, int64_t N, int64_t ld1, float *d_dst,
-                         int64_t ldd, void *d_work, size_t work_bytes, void *stream) {
-    if (!w) return fail(GGML_HIP_ERR_ARG, "null weight");
-    if (N <= 0 || w->M <= 0) return GGML_HIP_OK;
+// the product under its one-call plan `pl` (w is not null, N > 0, M > 0)
+static int mul_mat_planned(const ggml_hip_weight *w, const mm_plan &pl, const float *d_src1, int64_t N, int64_t ld1, float *d_dst,
+                           int64_t ldd, void *d_work, size_t work_bytes, void *stream) {
     if (!d_src1 || !d_dst) return fail(GGML_HIP_ERR_ARG, "null argument");
     if (ld1 < w->K || ldd < w->M) return fail(GGML_HIP_ERR_SHAPE, "ld1 < K or ldd < M");
     int rc = weight_device_current(w);
     if (rc) return rc;
-    const mm_plan pl = weight_plan(w, N, true);
     if (!is_q(w->type)) {
         if (pl.family == MMF_DENSE16 || pl.family == MMF_DENSE32) {
             // The matrix-core forms need INIT scratch (the reference's own wdata for F16, Ggml.cs:6362-6379; three bf16 pieces per element for
@@ -615,19 +623,26 @@ int ggml_hip_mul_mat_dev(const ggml_hip_weight *w, const float *d_src1, int64_t 
         HIP_TRY(launch_gemv_q_fused(w, d_src1, ld1, N, d_dst, ldd, (hipStream_t)stream));
         return GGML_HIP_OK;
     }
-    rc = ggml_hip_mul_mat_init_dev(w, d_src1, N, ld1, d_work, work_bytes, stream);
+    rc = mul_mat_init_step(w, pl, d_src1, N, ld1, d_work, work_bytes, stream);
     if (rc) return rc;
-    return ggml_hip_mul_mat_compute_dev(w, N, d_dst, ldd, d_work, work_bytes, stream);
+    return mul_mat_compute_step(w, pl, N, d_dst, ldd, d_work, work_bytes, stream);
 }
 
-// does a kernel form with a fused store-phase epilogue serve this (weight, N)?  The fused mat-vec (N <= 4), the MX mat-mat (Q4_0 / Q4_1),
-// K3p and Q8_0's batched-decode form; every other form runs the epilogue as its own launch behind the mat-mul.  (The plan's flag: selection,
-// this report and the launch agree by construction -- ADVICE r3.)
-static bool epilogue_is_fused(const ggml_hip_weight *w, int64_t N) {
-    return is_q(w->type) && w->ext_type == 0 && (weight_plan(w, N, true).flags & MM_FLAG_EPILOGUE_FUSED) != 0;
+int ggml_hip_mul_mat_dev(const ggml_hip_weight *w, const float *d_src1, int64_t N, int64_t ld1, float *d_dst,
+                         int64_t ldd, void *d_work, size_t work_bytes, void *stream) {
+    if (!w) return fail(GGML_HIP_ERR_ARG, "null weight");
+    if (N <= 0 || w->M <= 0) return GGML_HIP_OK;
+    return mul_mat_planned(w, weight_plan(w, N, true), d_src1, N, ld1, d_dst, ldd, d_work, work_bytes, stream);
 }
 
-int ggml_hip_mul_mat_epilogue_fused(const ggml_hip_weight *w, int64_t N) { return w && epilogue_is_fused(w, N) ? 1 : 0; }
+// does a kernel form with a fused store-phase epilogue serve this weight under its one-call plan?  The fused mat-vec (N <= 4), the MX
+// mat-mat (Q4_0 / Q4_1), K3p and Q8_0's batched-decode form; every other form runs the epilogue as its own launch behind the mat-mul.
+// (The plan's flag: selection, this report and the launch agree by construction -- ADVICE r3.)
+static bool epilogue_is_fused(const ggml_hip_weight *w, const mm_plan &pl) {
+    return is_q(w->type) && w->ext_type == 0 && (pl.flags & MM_FLAG_EPILOGUE_FUSED) != 0;
+}
+
+int ggml_hip_mul_mat_epilogue_fused(const ggml_hip_weight *w, int64_t N) { return w && epilogue_is_fused(w, weight_plan(w, N, true)) ? 1 : 0; }
 
 int ggml_hip_mul_mat_epilogue_dev(const ggml_hip_weight *w, const float *d_src1, int64_t N, int64_t ld1, float *d_dst, int64_t ldd,
                                   void *d_work, size_t work_bytes, int mode, const float *d_addend, int64_t ld_add, float *d_dst2,
@@ -638,19 +653,19 @@ int ggml_hip_mul_mat_epilogue_dev(const ggml_hip_weight *w, const float *d_src1,
     if (N <= 0 || w->M <= 0) return GGML_HIP_OK;
     if (mode == 1 && (!d_addend || !d_dst2 || ld_add < w->M || ldd2 < w->M)) return fail(GGML_HIP_ERR_ARG, "add epilogue: addend / dst2 missing or too narrow");
     const mm_epilogue ep = {mode, d_addend, ld_add, d_dst2, ldd2, scale};
-    if (epilogue_is_fused(w, N)) {
+    const mm_plan plan = weight_plan(w, N, true);
+    if (epilogue_is_fused(w, plan)) {
         if (!d_src1 || !d_dst) return fail(GGML_HIP_ERR_ARG, "null argument");
         if (ld1 < w->K || ldd < w->M) return fail(GGML_HIP_ERR_SHAPE, "ld1 < K or ldd < M");
         int rc = weight_device_current(w);
         if (rc) return rc;
-        const mm_plan plan = weight_plan(w, N, true);
         if (plan.family == MMF_GEMV_FUSED) {
             rc = check_src1_alignment(d_src1, ld1);
             if (rc) return rc;
             HIP_TRY(launch_gemv_q_fused(w, d_src1, ld1, N, d_dst, ldd, (hipStream_t)stream, &ep));
             return GGML_HIP_OK;
         }
-        rc = ggml_hip_mul_mat_init_dev(w, d_src1, N, ld1, d_work, work_bytes, stream);
+        rc = mul_mat_init_step(w, plan, d_src1, N, ld1, d_work, work_bytes, stream);
         if (rc) return rc;
         const hipError_t e = launch_planned(w, plan, act_carve(d_work, w->K, pad_act(N)), N, d_dst, ldd, (hipStream_t)stream, &ep);
         if (e == hipSuccess) return GGML_HIP_OK;
@@ -660,7 +675,7 @@ int ggml_hip_mul_mat_epilogue_dev(const ggml_hip_weight *w, const float *d_src1,
         (void)hipGetLastError();
     }
     // no fused form for this kernel: the product, then the node's own kernel row by row (same values)
-    int rc = ggml_hip_mul_mat_dev(w, d_src1, N, ld1, d_dst, ldd, d_work, work_bytes, stream);
+    int rc = mul_mat_planned(w, plan, d_src1, N, ld1, d_dst, ldd, d_work, work_bytes, stream);
     if (rc) return rc;
     if (mode == 2) {
         if (ldd == w->M) HIP_TRY(launch_scale_f32(d_dst, N * w->M, scale, (hipStream_t)stream));
@@ -675,14 +690,16 @@ int ggml_hip_mul_mat_epilogue_dev(const ggml_hip_weight *w, const float *d_src1,
 /* ---- the row split's product + exchange ---- */
 // Which kernel forms store to the peers themselves: the staged MX forms and K3p (plan.h).  The others compute into this rank's own buffer
 // and hand their columns to the peers with the column-push kernel (layout.hip) behind the product: the same bytes, one more launch.
-static bool push_is_fused(const ggml_hip_weight *w, int64_t N, int n_peers) {
+static bool push_is_fused(const ggml_hip_weight *w, const mm_plan &pl, int n_peers) {
     if (!is_q(w->type) || n_peers - 1 > MM_PUSH_MAX) return false;
-    const mm_plan pl = weight_plan(w, N, true);
     if (pl.flags & MM_FLAG_MIN_PASS) return false;          // (Q2_K: the min pass must run before the columns leave)
     const int f = pl.family;
-    return f == MMF_MX || f == MMF_K3P_MX || f == MMF_K3P_I8 || f == MMF_K3S_MX || f == MMF_K3S_I8;   // (r5: the batched-decode forms too -- a short shard at prompt sizes runs them)
+    // (r5: the batched-decode forms too -- a short shard at prompt sizes runs them)
+    return f == MMF_MX || f == MMF_K3P_MX || f == MMF_K3P_I8 || f == MMF_K3S_MX || f == MMF_K3S_I8;
 }
-int ggml_hip_mul_mat_push_fused(const ggml_hip_weight *w, int64_t N, int n_peers) { return w && push_is_fused(w, N, n_peers) ? 1 : 0; }
+int ggml_hip_mul_mat_push_fused(const ggml_hip_weight *w, int64_t N, int n_peers) {
+    return w && push_is_fused(w, weight_plan(w, N, true), n_peers) ? 1 : 0;
+}
 
 int ggml_hip_mul_mat_push_dev(const ggml_hip_weight *w, const float *d_src1, int64_t N, int64_t ld1, float *const *d_peers, int n_peers, int own,
                               int64_t ld_total, int64_t col0, void *d_work, size_t work_bytes, void *stream) {
@@ -691,7 +708,8 @@ int ggml_hip_mul_mat_push_dev(const ggml_hip_weight *w, const float *d_src1, int
     if (N <= 0 || w->M <= 0) return GGML_HIP_OK;
     if (col0 < 0 || ld_total < col0 + w->M) return fail(GGML_HIP_ERR_SHAPE, "ld_total < col0 + M");
     float *mine = d_peers[own] + col0;
-    if (push_is_fused(w, N, n_peers)) {
+    const mm_plan plan = weight_plan(w, N, true);
+    if (push_is_fused(w, plan, n_peers)) {
         if (!d_src1) return fail(GGML_HIP_ERR_ARG, "null argument");
         if (ld1 < w->K) return fail(GGML_HIP_ERR_SHAPE, "ld1 < K");
         mm_epilogue ep = {3, nullptr, 0, nullptr, 0, 1.0f, 0, {}};
@@ -699,9 +717,8 @@ int ggml_hip_mul_mat_push_dev(const ggml_hip_weight *w, const float *d_src1, int
             if (g != own && d_peers[g]) ep.push[ep.npush++] = d_peers[g] + col0;
         int rc = weight_device_current(w);
         if (rc) return rc;
-        rc = ggml_hip_mul_mat_init_dev(w, d_src1, N, ld1, d_work, work_bytes, stream);
+        rc = mul_mat_init_step(w, plan, d_src1, N, ld1, d_work, work_bytes, stream);
         if (rc) return rc;
-        const mm_plan plan = weight_plan(w, N, true);
         const hipError_t e = launch_planned(w, plan, act_carve(d_work, w->K, pad_act(N)), N, mine, ld_total, (hipStream_t)stream, &ep);
         if (e == hipSuccess) return GGML_HIP_OK;
         // not supported = ld_total beyond what the store phase addresses (a tile's rows past the 32-bit buffer offsets of the staged MX forms,
@@ -710,7 +727,7 @@ int ggml_hip_mul_mat_push_dev(const ggml_hip_weight *w, const float *d_src1, int
         if (e != hipErrorNotSupported) HIP_TRY(e);
         (void)hipGetLastError();
     }
-    int rc = ggml_hip_mul_mat_dev(w, d_src1, N, ld1, mine, ld_total, d_work, work_bytes, stream);
+    int rc = mul_mat_planned(w, plan, d_src1, N, ld1, mine, ld_total, d_work, work_bytes, stream);
     if (rc) return rc;
     std::vector<float *> others((size_t)n_peers);
     for (int g = 0; g < n_peers; ++g) others[(size_t)g] = g == own ? nullptr : d_peers[g];
@@ -799,18 +816,18 @@ int ggml_hip_mul_mat_multi_work_dev(const ggml_hip_weight *const *w, int n_w, co
     }
     if (n_w >= 2 && multi_ok(w, n_w, N)) return ggml_hip_mul_mat_multi_dev(w, n_w, d_src1, ld1, N, d_dst, ldd, nullptr, 0, nullptr, nullptr, stream);
     // one image for all of them?  (the image kind of a type follows N and K; M enters for shapes beyond the 32-bit offsets only)
-    const mm_plan pl0 = weight_plan(w[0], N, false);
-    const int kind = weight_image_kind(w[0], N);
-    bool shared = pl0.family != MMF_GEMV_ROWS && w[0]->ext_type == 0;
-    for (int i = 1; i < n_w && shared; ++i) shared = weight_image_kind(w[i], N) == kind;
-    if (!shared) {
+    mm_plan pl[4];
+    for (int i = 0; i < n_w; ++i) pl[i] = weight_plan(w[i], N, false);   // (the COMPUTE-only plans: one INIT, then a COMPUTE each)
+    bool shared = pl[0].family != MMF_GEMV_ROWS && w[0]->ext_type == 0;
+    for (int i = 1; i < n_w && shared; ++i) shared = plan_act_image(pl[i]) == plan_act_image(pl[0]);
+    if (!shared) {                                          // (each matrix through the one-call entry, under its own one-call plan)
         for (int i = 0; i < n_w; ++i) {
             const int rc = ggml_hip_mul_mat_dev(w[i], d_src1, N, ld1, d_dst[i], ldd[i], d_work, work_bytes, stream);
             if (rc) return rc;
         }
         return GGML_HIP_OK;
     }
-    int rc = ggml_hip_mul_mat_init_dev(w[0], d_src1, N, ld1, d_work, work_bytes, stream);
+    int rc = mul_mat_init_step(w[0], pl[0], d_src1, N, ld1, d_work, work_bytes, stream);
     if (rc) return rc;
     int64_t M[4], Mpad[4];
     for (int i = 0; i < n_w; ++i) { M[i] = w[i]->M; Mpad[i] = w[i]->Mpad; }
@@ -824,7 +841,8 @@ int ggml_hip_mul_mat_multi_work_dev(const ggml_hip_weight *const *w, int n_w, co
         if (e != hipErrorNotSupported) { (void)hipGetLastError(); return fail(GGML_HIP_ERR_RUNTIME, "multi mul_mat: %s", hipGetErrorString(e)); }
     }
     for (int i = 0; i < n_w; ++i) {
-        rc = ggml_hip_mul_mat_compute_dev(w[i], N, d_dst[i], ldd[i], d_work, work_bytes, stream);
+        if (w[i]->M <= 0) continue;
+        rc = mul_mat_compute_step(w[i], pl[i], N, d_dst[i], ldd[i], d_work, work_bytes, stream);
         if (rc) return rc;
     }
     return GGML_HIP_OK;

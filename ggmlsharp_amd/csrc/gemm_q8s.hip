@@ -621,7 +621,7 @@ hipError_t launch_q8_small_multi(const mm_plan &g, const ggml_hip_weight *const 
 
 hipError_t launch_q8_small(const ggml_hip_weight *w, const mm_plan &pl, act_planes p, int64_t N, float *dst, int64_t ldd, hipStream_t st, const mm_epilogue &ep) {
     constexpr int KS = 8;
-    // k-blocks per wave, tiles per workgroup (one up to 256 tile groups, two beyond: same bits) and the slots from plan.cpp (plan_k3s_i8, plan_k3s_slots)
+    // k-blocks per wave, tiles per workgroup (one up to 256 tile groups, two beyond: same bits) and the slots from plan.cpp (plan_k3s, plan_k3s_slots)
     const int nbkp = (int)pad_kblocks(w->nbk);
     const int nloc = pl.nloc, wmt = pl.wmt;
     const int ncol = (int)((N + 31) / 32);
@@ -629,7 +629,7 @@ hipError_t launch_q8_small(const ggml_hip_weight *w, const mm_plan &pl, act_plan
     // scale multiplications differs.  (It ran the staged f16 forms here: 4096 x 4096 x 64 16.3 us against Q8_0's 7.8.)
     // ... and Q5_1 (9 .. 64 rows): Q5_0's block term on planes of the unsigned values + the min-term product in front of the blocks
     // (4096 x 4096 x 64 17.3 us on the staged forms, 4096 x 11008 x 32 36.4).
-    // ... and Q4_2 (9 .. 256 rows -- it was 17 .. 64; plan.cpp q8_small_serves has the measurements): int8 planes of nib - 8 (built at upload, r4), two K = 16 MFMAs per block
+    // ... and Q4_2 (9 .. 256 rows -- it was 17 .. 64; docs/PLAN_BOUNDS.md has the measurements): int8 planes of nib - 8 (built at upload, r4), two K = 16 MFMAs per block
     // (4096 x 4096 x 32 40.3 us on the staged int8 kernel).
     const bool q42 = w->type == GGML_TYPE_Q4_2;
     const bool q41 = w->type == GGML_TYPE_Q4_1;             // (r5: from 65 rows -- unsigned values 0..15 on the int8 planes, an f32 min: Q5_K's instantiation, as in K3p)
@@ -645,7 +645,7 @@ hipError_t launch_q8_small(const ggml_hip_weight *w, const mm_plan &pl, act_plan
     if (wq_bytes > 0xFFFFFFFFull || aq_bytes > 0xFFFFFFFFull) return hipErrorInvalidValue;
     const k3s_slots s = plan_k3s_slots(pl, w->type);
     if (pl.tile_m == 16) {
-        // r5: 16-row tiles (plan_k3s_i8: Q8_0 / Q5_0 where the 32-row tiles leave CUs idle) -- the same tree, NCT 16-column slices per workgroup
+        // r5: 16-row tiles (plan.cpp k3s_tile16: Q8_0 / Q5_0 where the 32-row tiles leave CUs idle) -- the same tree, NCT 16-column slices per workgroup
         const int nct = pl.tile_n / 16;
         const int ncg = (int)((N + pl.tile_n - 1) / pl.tile_n);
         if (p.Npad < (int64_t)pl.tile_n * ncg || w->Mpad % 16 != 0) return hipErrorInvalidValue;

@@ -665,13 +665,13 @@ hipError_t launch_gemm_q8_mid(const ggml_hip_weight *w, const mm_plan &pl, act_p
     if (pl.family != MMF_K3P_I8 || !planes || !w->d || (with_min && (!w->m || !w->mp3 || !p.sp3)) || (two && !w->m)) return hipErrorInvalidValue;
     if (ldd > 0x7FFFFFFF) return hipErrorNotSupported;     // (the kernel carries the row stride as an int: callers with an unfused form fall back)
     // applicability (at least 8 k-blocks per wave, the eight scale tables within 160 KB of LDS, every offset within 32 bits) and the
-    // k-blocks per wave were decided by plan.cpp (plan_k3p_i8); the checks below only guard the kernel's assumptions
+    // k-blocks per wave were decided by plan.cpp (plan_k3p); the checks below only guard the kernel's assumptions
     const int nbkp = (int)pad_kblocks(w->nbk);
     const int nloc = pl.nloc;
     const uint64_t wq_bytes = (uint64_t)nbkp * 2 * (uint64_t)w->Mpad * 16, aq_bytes = (uint64_t)nbkp * 2 * (uint64_t)p.Npad * 16;
     if (nloc < 8 || (nloc & 1) || KS * nloc < nbkp) return hipErrorInvalidValue;
     if ((uint64_t)(KS * nloc + 2) * 2 * (uint64_t)w->Mpad * 16 > 0xFFFFFFFFull || (uint64_t)(KS * nloc + 2) * 2 * (uint64_t)p.Npad * 16 > 0xFFFFFFFFull) return hipErrorInvalidValue;
-    const int wmt = pl.tile_m / 32;                         // (r5: 128-row wave tiles, or 64-row ones where those leave CUs idle: plan_k3p_i8 -- the same tree)
+    const int wmt = pl.tile_m / 32;                         // (r5: 128-row wave tiles, or 64-row ones where those leave CUs idle: plan_k3p -- the same tree)
     if ((wmt != 4 && wmt != 2) || w->Mpad % (32 * wmt) != 0 || p.Npad % (32 * WNT) != 0) return hipErrorInvalidValue;
     const int tiles_m = (int)((w->M + 32 * wmt - 1) / (32 * wmt)), tiles_n = (int)((N + 32 * WNT - 1) / (32 * WNT));
     // (K > 20480: table slices of `ch` k-blocks per wave, + one row behind the last slice for the loop's look-ahead of the next row's scales)
@@ -696,7 +696,7 @@ hipError_t launch_gemm_q8_mid(const ggml_hip_weight *w, const mm_plan &pl, act_p
     return q8_mid_go<GGML_TYPE_Q5_1, false>(sliced, wmt, go);
 }
 
-// Q4_0 (plan.cpp plan_k3p_mx: at least 8 k-blocks per wave, tables within LDS, offsets within 32 bits)
+// Q4_0 (plan.cpp plan_k3p: at least 8 k-blocks per wave, tables within LDS, offsets within 32 bits)
 hipError_t launch_gemm_qmx_mid(const ggml_hip_weight *w, const mm_plan &pl, act_planes p, int64_t N, float *dst, int64_t ldd, hipStream_t st, const mm_epilogue *ep) {
     if (pl.family != MMF_K3P_MX || w->type != GGML_TYPE_Q4_0 || !w->q6a || !w->q6b) return hipErrorInvalidValue;
     if (ldd > 0x7FFFFFFF) return hipErrorNotSupported;     // (see launch_gemm_q8_mid)
@@ -708,7 +708,7 @@ hipError_t launch_gemm_qmx_mid(const ggml_hip_weight *w, const mm_plan &pl, act_
     const uint64_t a_bytes = nba * 48 * (uint64_t)p.Npad;
     // (32-bit buffer offsets, the look-ahead past a wave's range included)
     if ((uint64_t)(KS * nloc + 2) * (uint64_t)w->Mpad * 16 > 0xFFFFFFFFull || (uint64_t)(KS * nloc + 2) * 48 * (uint64_t)p.Npad > 0xFFFFFFFFull) return hipErrorInvalidValue;
-    const int wmt = pl.tile_m / 32;                         // (r5: 128-row wave tiles, or 64-row ones where those leave CUs idle: plan_k3p_mx -- the same tree)
+    const int wmt = pl.tile_m / 32;                         // (r5: 128-row wave tiles, or 64-row ones where those leave CUs idle: plan_k3p -- the same tree)
     if ((wmt != 4 && wmt != 2) || w->Mpad % (32 * wmt) != 0 || p.Npad % (32 * WNT) != 0) return hipErrorInvalidValue;
     const int tiles_m = (int)((w->M + 32 * wmt - 1) / (32 * wmt)), tiles_n = (int)((N + 32 * WNT - 1) / (32 * WNT));
     const bool sliced = nloc > K3P_TABLE_ROWS;

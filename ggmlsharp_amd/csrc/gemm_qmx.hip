@@ -1144,7 +1144,7 @@ hipError_t launch_small(const ggml_hip_weight *w, const mm_plan &pl, act_planes 
     constexpr int KS = 8;
     constexpr bool Q40 = TYPE == GGML_TYPE_Q4_0, Q41 = TYPE == GGML_TYPE_Q4_1;
     if (!w->q6a || !w->q6b) return hipErrorInvalidValue;
-    // geometry, applicability and the slots were decided by plan.cpp (plan_k3s_mx, plan_k3s_slots): k-blocks per wave, 32-row tiles per workgroup (more tiles than CUs:
+    // geometry, applicability and the slots were decided by plan.cpp (plan_k3s, plan_k3s_slots): k-blocks per wave, 32-row tiles per workgroup (more tiles than CUs:
     // two of them per workgroup, four beyond 512 tiles -- every workgroup pulls the whole activation image through its CU's vector
     // memory path, and that path is what bounds the form; same blocks in the same order per element: the same bits)
     const int nbkp = (int)pad_kblocks(w->nbk);
@@ -1156,7 +1156,7 @@ hipError_t launch_small(const ggml_hip_weight *w, const mm_plan &pl, act_planes 
     if (nloc > 128 || wq_bytes > 0xFFFFFFFFull || a_bytes > 0xFFFFFFFFull || s.lds > 160 * 1024) return hipErrorInvalidValue;    // (the plan never sends such a shape here)
     const mm_epilogue e = epilogue_or_none(ep);
     if (pl.tile_m == 16) {
-        // r5: 16-row tiles (plan_k3s_mx: where the 32-row tiles leave CUs idle) -- the same tree, NCT 16-column slices per workgroup
+        // r5: 16-row tiles (plan.cpp k3s_tile16: where the 32-row tiles leave CUs idle) -- the same tree, NCT 16-column slices per workgroup
         const int nct = pl.tile_n / 16, ncg = (int)((N + pl.tile_n - 1) / pl.tile_n);
         if (p.Npad < (int64_t)pl.tile_n * ncg || w->Mpad % 16 != 0 || (nloc & 1)) return hipErrorInvalidValue;
         if (nct != 1 && nct != 2) return hipErrorInvalidValue;

@@ -183,7 +183,9 @@ struct ssm_conv_plan { int ok, launches; size_t state_bytes; int64_t wgs_x, wgs;
 struct ssm_scan_plan { int ok, form, launches, slices, lanes_per_row, rows_per_wg; size_t state_bytes; int64_t wgs_x, wgs; };
 ssm_conv_plan plan_ssm_conv(int64_t n_ch, int d_conv, int64_t n_seq);
 ssm_scan_plan plan_ssm_scan(int n_head, int P, int N, int n_group, int64_t n_seq);
-// the K1 image for (type, K, N) with no weight at hand (no M: the exception cannot apply)
+// the K1 image INIT writes for a plan: its image where that is one of K1's (0 .. 3; else 0), + ACT_IMAGE_MIN_PIECES under MM_FLAG_MIN_PIECES
+int plan_act_image(const mm_plan &p);
+// the K1 image for (type, K, N) with no weight at hand: plan_act_image of the COMPUTE-only plan at M = 1 (no M: the exception cannot apply)
 int plan_image_kind(int type, int64_t K, int64_t N);
 // thread-local test switch (ggml_hip_debug_force_gemm): 0 auto, 1 int8, 2 f16, 3 MX
 int plan_force_gemm();

@@ -584,7 +584,7 @@ def test_k3p_beyond_one_scale_table_slices_refill_inside_the_K_loop(dev, t, K):
 @pytest.mark.parametrize("t,K,N", [(4, 4096, 9), (4, 4096, 16), (4, 2048, 128), (4, 4096, 100), (Q8_0, 11008, 100), (Q8_0, 11008, 128), (Q5_0, 13824, 96),
                                    (7, 11008, 128), (Q4_0, 11008, 128), (3, 11008, 96)])
 def test_batched_decode_forms_beyond_their_round_3_ranges(dev, t, K, N):
-    """The stage-free batched-decode forms (gemm_q8s.hip, gemm_qmx.hip K3s) where the end of round 4 put them (plan.cpp q8_small_serves, plan_mx):
+    """The stage-free batched-decode forms (gemm_q8s.hip, gemm_qmx.hip K3s) where the end of round 4 put them (plan.cpp k3_stage_free):
     the two-scale type Q4_2 from 9 rows (up to 256 in r4; r5: 128, K3p beyond), every other type up to 128 rows behind K >= 11008 -- three and more column tiles per weight
     tile.  fp64 evaluation of the block arithmetic; a row shard is the bitwise slice (the form is chosen by type, K and N alone)."""
     import ctypes as C

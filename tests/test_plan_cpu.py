@@ -3,6 +3,8 @@ stands on -- the order of an element's additions (tree_id) is a function of (typ
 over a sweep of type x K x N x M that includes vocabulary-sized matrices and the stated 32-bit-offset exception (the
 three shard-identity violations of round 3 were found by GPU sweeps only; each of them fails this test in the build container)."""
 import ctypes as C
+import os
+import re
 
 import pytest
 
@@ -55,19 +57,43 @@ def test_summation_tree_is_a_function_of_type_K_and_N_only(t):
 
 
 def test_the_image_of_a_plan_is_the_image_of_its_type_K_and_N():
+    """... under every forced family too (the switch is thread-local: back to 0 whatever happens), and for the k-quants in their resident forms."""
     L = _lib.lib()
-    for t in QUANT:
-        for K in KS:
-            for N in NS:
-                for M in (100, 4096, 32000):
-                    p = plan(t, M, K, N)
-                    if p.flags & WIDE:
+    try:
+        for force in (0, 1, 2, 3):
+            L.ggml_hip_debug_force_gemm(force)
+            for t in QUANT + (Q5_K, Q4_K, Q6_K):
+                for K in KS:
+                    if t in (Q5_K, Q4_K, Q6_K) and K % 256:
                         continue
-                    if p.family == FAM["gemv_fused"]:
-                        assert p.image_kind == -1 and not (p.flags & NEEDS_WORK)
-                    else:
-                        assert p.image_kind == L.ggml_hip_act_image_kind(t, K, N), (t, M, K, N)
-                        assert p.flags & NEEDS_WORK
+                    for N in NS:
+                        for M in (100, 4096, 32000):
+                            p = plan(t, M, K, N)
+                            if p.flags & WIDE:
+                                continue
+                            if p.family == FAM["gemv_fused"]:
+                                assert p.image_kind == -1 and not (p.flags & NEEDS_WORK)
+                            else:
+                                assert p.image_kind == L.ggml_hip_act_image_kind(t, K, N), (force, t, M, K, N)
+                                assert p.flags & NEEDS_WORK
+    finally:
+        L.ggml_hip_debug_force_gemm(0)
+
+
+def test_the_image_kind_of_a_type_is_the_image_INIT_writes_where_the_stage_free_form_refuses():
+    """Q5_1 behind K = 79872 at 65536 src1 rows: K3p-int8 serves the row count but the activation planes are beyond its 32-bit offsets, so the
+    staged int8 family runs on image 0 without the min-term piece planes -- and ggml_hip_act_image_kind, derived from the plan, says so."""
+    p = plan(Q5_1, 4096, 79872, 65536)
+    assert _lib.lib().ggml_hip_act_image_kind(Q5_1, 79872, 65536) == p.image_kind == 0
+
+
+def test_every_bounds_section_plan_cpp_cites_exists():
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    with open(os.path.join(root, "ggmlsharp_amd", "csrc", "plan.cpp")) as f:
+        cited = {s for line in f if "PLAN_BOUNDS.md" in line for s in re.findall(r'"([^"]+)"', line.split("PLAN_BOUNDS.md", 1)[1])}
+    with open(os.path.join(root, "docs", "PLAN_BOUNDS.md")) as f:
+        sections = {line[3:].strip() for line in f if line.startswith("## ")}
+    assert len(cited) >= 10 and cited <= sections, sorted(cited - sections)
 
 
 def test_baseline_configs_get_the_kernels_design_md_names():
