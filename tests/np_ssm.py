@@ -1,5 +1,5 @@
 """Yardsticks for the SSM entries (include/ggml_hip_ext.h, SSM; csrc/ssm.hip): the statement of ggml_hip_ssm_scan_ragged_dev in float64, a float32 model of
-it, the bar both are compared under, four mutants of the statement, and the conv's statement with an exact binary32 fma.  Everything is for ONE sequence:
+it, the bar both are compared under, four mutants of the statement and two of the kernel's form, and the conv's statement with an exact binary32 fma.  Everything is for ONE sequence:
 the ragged batch, the slots and the fresh / continued rule are the tests' business.
 
 THE STATEMENT (per token t, head h, row p, state n; g = h // (n_head // G)):
@@ -36,6 +36,17 @@ F = np.float32
 U = 2.0 ** -24
 TINY = 2.0 ** -125
 MUTANTS = ("no_softplus", "swap_bc", "group_off_by_one", "drop_D")
+# mistakes only a kernel form can make, which no mutant of the statement resembles: the butterfly one step short (lane 0 of a group of LP lanes never meets
+# the slices j with j & (LP / 2); judged where LP >= 2), and every state taking the A of state 0 (the per-state index lost; judged where A is per state)
+KERNEL_MUTANTS = ("short_butterfly", "a_of_state_0")
+
+
+def lanes_per_row(N):
+    """LP: the least power of two >= N / 16"""
+    LP = 1
+    while LP < N // 16:
+        LP *= 2
+    return LP
 
 
 def fmaf(a, b, c):
@@ -65,7 +76,8 @@ def _group_of(n_head, G, mutant):
 
 def scan_f64(x, dt, A, B, C, D=None, dt_bias=None, h0=None, mutant=None, want_bar=False):
     """the statement in float64 for one sequence.  x [T, H, P], dt [T, H], A [H] or [H, N], B / C [T, G, N], D / dt_bias [H] or None, h0 [H, P, N] or None
-    (zeros).  -> (y [T, H, P], h [H, P, N]) and with want_bar the bars (bar_y, bar_h) of the docstring above, all float64.  mutant: one of MUTANTS"""
+    (zeros).  -> (y [T, H, P], h [H, P, N]) and with want_bar the bars (bar_y, bar_h) of the docstring above, all float64.  mutant: one of MUTANTS or of
+    KERNEL_MUTANTS"""
     x, dt, A, B, C = (np.asarray(v, np.float64) for v in (x, dt, A, B, C))
     T, H, P = x.shape
     G, N = B.shape[1:]
@@ -73,14 +85,17 @@ def scan_f64(x, dt, A, B, C, D=None, dt_bias=None, h0=None, mutant=None, want_ba
     if mutant == "swap_bc":
         B, C = C, B
     An = (A[:, None] if A.ndim == 1 else A)[:, None, :]              # [H, 1, N or 1]
+    if mutant == "a_of_state_0":
+        An = An[:, :, :1]
     h = np.zeros((H, P, N)) if h0 is None else np.asarray(h0, np.float64).copy()
     E = np.zeros((H, P, N))
     y = np.zeros((T, H, P))
     bar_y = np.zeros((T, H, P))
-    LP = 1
-    while LP < N // 16:
-        LP *= 2
+    LP = lanes_per_row(N)
     ky = 16 + int(np.log2(LP))
+    met = np.ones(N)                                                 # the states whose slice reaches lane 0 of the group
+    if mutant == "short_butterfly":
+        met = ((np.arange(N) // 16 & (LP // 2)) == 0).astype(np.float64)
     for t in range(T):
         d = dt[t] + (0.0 if dt_bias is None else np.asarray(dt_bias, np.float64))
         delta = d if mutant == "no_softplus" else np.where(d <= 20.0, np.log1p(np.exp(np.minimum(d, 20.0))), d)
@@ -93,7 +108,7 @@ def scan_f64(x, dt, A, B, C, D=None, dt_bias=None, h0=None, mutant=None, want_ba
             Fe = E * a + ka * U * (np.abs(h) + E) * a + (kd + 2.0) * U * np.abs(inp) + TINY * (1.0 + np.abs(h) + E)
         h = h * a + inp
         Ct = C[t][g][:, None, :]
-        y[t] = (h * Ct).sum(-1)
+        y[t] = (h * Ct * met).sum(-1)
         Dx = 0.0
         if D is not None and mutant != "drop_D":
             Dx = np.asarray(D, np.float64)[:, None] * x[t]
@@ -111,9 +126,7 @@ def scan_f32(x, dt, A, B, C, D=None, dt_bias=None, h0=None):
     T, H, P = x.shape
     G, N = B.shape[1:]
     L = N // 16
-    LP = 1
-    while LP < L:
-        LP *= 2
+    LP = lanes_per_row(N)
     g = _group_of(H, G, None)
     An = (A[:, None] if A.ndim == 1 else A)[:, None, :]
     h = np.zeros((H, P, N), F) if h0 is None else np.asarray(h0, F).copy()

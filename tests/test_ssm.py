@@ -9,7 +9,14 @@ ONE ragged batch serves every shape: counts 0, 1, 2, 3, 9 and 130 (below, at and
 slot id of -1 and one of n_slots, fresh (d_len 0, the slot preloaded with NaN bytes) and continued sequences, two packed rows nobody owns.
 Scan shapes: the Mamba-1 form (P = 1, N = 16, per-state A) at 8 and 264 heads (one workgroup, more than one); the Mamba-2 form (P = 64, N = 128) with one and
 two groups; N = 48, three slices in a group of four lanes, with rows that fill no whole wave; 7 heads of the Mamba-1 form and N = 32 with 9 rows, whose
-lanes end inside a quad (the state moves by quads of lanes where no lane of a group idles).  Conv: 1, 5, 64 and 1028 channels (more than one workgroup)."""
+lanes end inside a quad (the state moves by quads of lanes where no lane of a group idles).  Conv: 1, 5, 64 and 1028 channels (more than one workgroup).
+
+ONE SHAPE PER KERNEL FORM.  The scan is compiled once per (lanes of a row LP, FULL: N == 16 LP, A per state); twelve more shapes (SHAPES, below the first
+seven) reach the forms those seven do not, and test_every_form_the_plan_can_pick_has_a_shape compares the forms of SHAPES with the forms the plan hands out
+over every N, so a form added to the plan must bring its shape.  Two kernel-shaped mutants (np_ssm.KERNEL_MUTANTS: the butterfly a step short, the A of
+state 0 for every state) exceed the bar a hundredfold where they apply.  The batch call of every shape gives dst, dt and A strides of their own (other than
+x's, above n_head, above N or 1) with 3.0e38 or the sentinel in the gaps; D and dt_bias are null at two shapes.  A SECOND batch (BATCH_2) has sequences of
+exactly 7, 8 and 16 tokens (the conv's token loop is unrolled by 8) and the other ways to be absent: an end beyond n_tokens_max, a start above the end."""
 import ctypes as C
 import fnmatch
 import functools
@@ -44,20 +51,58 @@ SERVED = (1, 3, 4, 5, 8)                                            # present, n
 ZEROED = (6, 7)                                                     # present, not idle, a slot id outside the pool: +0.0f rows, no state
 SPLITS = ((4, 4), (5, 1), (5, 64))                                  # (sequence, tokens in the first of two calls)
 
+# the second batch: 7, 8 and 16 tokens (one short of, exactly and twice the conv's unroll of 8) and 5; sequence 3 and 6 end beyond n_tokens_max, sequence 4
+# starts above its end and beyond n_tokens_max; rows 31, 32, 38 and 39 belong to nobody
+N_TOKENS_MAX_2 = 40
+Q_START_2 = np.array([0, 7, 15, 31, 50, 33, 38, 44], np.int32)
+D_LEN_2 = np.array([0, 3, 0, 2, 1, 4, 1], np.int32)
+SLOT_2 = np.array([4, 0, 9, 1, 2, 6, 3], np.int32)
+SERVED_2 = (0, 1, 2, 5)
+
+
+class Batch:
+    """a ragged batch over the pool of N_SLOTS slots; the packed rows it addresses are rows [0, n_tokens_max) of a case's inputs"""
+
+    def __init__(self, n_tokens_max, q_start, d_len, slot, served, zeroed):
+        self.n_tokens_max, self.q_start, self.d_len, self.slot, self.served, self.zeroed = n_tokens_max, q_start, d_len, slot, served, zeroed
+        self.n_seq = slot.size
+
+    def rows(self, b):
+        return int(self.q_start[b]), int(self.q_start[b + 1])
+
+
+BATCH_1 = Batch(N_TOKENS_MAX, Q_START, D_LEN, SLOT, SERVED, ZEROED)
+BATCH_2 = Batch(N_TOKENS_MAX_2, Q_START_2, D_LEN_2, SLOT_2, SERVED_2, ())
+
+# seed: the inputs of a shape follow it alone (the first seven keep the seeds they had as the only shapes, 71 + their place in the sorted names)
 SHAPES = {
-    "mamba1_8": dict(H=8, P=1, N=16, G=1, aps=True),
-    "mamba1_264": dict(H=264, P=1, N=16, G=1, aps=True),
-    "mamba2_g1": dict(H=4, P=64, N=128, G=1, aps=False),
-    "mamba2_g2": dict(H=4, P=64, N=128, G=2, aps=False),
-    "n48": dict(H=4, P=5, N=48, G=2, aps=False),
+    "mamba1_8": dict(H=8, P=1, N=16, G=1, aps=True, seed=73),
+    "mamba1_264": dict(H=264, P=1, N=16, G=1, aps=True, seed=71),
+    "mamba2_g1": dict(H=4, P=64, N=128, G=1, aps=False, seed=74),
+    "mamba2_g2": dict(H=4, P=64, N=128, G=2, aps=False, seed=75),
+    "n48": dict(H=4, P=5, N=48, G=2, aps=False, seed=77),
     # the state moves by quads of lanes where N is a power-of-two multiple of 16: a last quad that is only partly inside the rows, one and two lanes per row
-    "mamba1_7": dict(H=7, P=1, N=16, G=1, aps=True),
-    "n32": dict(H=3, P=3, N=32, G=3, aps=False),
+    "mamba1_7": dict(H=7, P=1, N=16, G=1, aps=True, seed=72),
+    "n32": dict(H=3, P=3, N=32, G=3, aps=False, seed=76),
+    # one shape per (LP, FULL, A per state) the seven above do not reach -- the smallest that does, with what else it covers
+    "n16_head": dict(H=5, P=3, N=16, G=1, aps=False, seed=79),       # 1, FULL, per head; 15 rows: a partial last quad
+    "n32_aps": dict(H=3, P=43, N=32, G=1, aps=True, seed=84),        # 2, FULL; 129 rows: a second workgroup that holds one row
+    "n48_aps": dict(H=2, P=3, N=48, G=2, aps=True, seed=86),         # 4, plain
+    "n64": dict(H=5, P=13, N=64, G=1, aps=False, seed=87),           # 4, FULL; 65 rows: a second workgroup that holds one row
+    "n64_aps": dict(H=2, P=2, N=64, G=2, aps=True, seed=88),         # 4, FULL
+    "n80": dict(H=4, P=3, N=80, G=2, aps=False, seed=89),            # 8, plain: 5 of 8 lanes live
+    "n112_aps": dict(H=3, P=11, N=112, G=1, aps=True, seed=76),      # 8, plain; 33 rows: a second workgroup
+    "n128_aps": dict(H=2, P=3, N=128, G=1, aps=True, seed=77),       # 8, FULL
+    "n144": dict(H=3, P=5, N=144, G=3, aps=False, seed=78),          # 16, plain: 9 of 16 lanes live
+    "n240_aps": dict(H=2, P=3, N=240, G=1, aps=True, seed=80),       # 16, plain: 15 of 16 lanes live
+    "n256": dict(H=6, P=3, N=256, G=2, aps=False, seed=81),          # 16, FULL; 18 rows: a second workgroup that holds two
+    "n256_aps": dict(H=2, P=2, N=256, G=1, aps=True, seed=82),       # 16, FULL
 }
+FIRST_SEVEN = ("mamba1_264", "mamba1_7", "mamba1_8", "mamba2_g1", "mamba2_g2", "n32", "n48")
 
 
 def _rows(b):
-    return int(Q_START[b]), int(Q_START[b + 1])
+    return BATCH_1.rows(b)
 
 
 def test_the_batch_is_what_it_says():
@@ -72,12 +117,36 @@ def test_the_batch_is_what_it_says():
     assert len({int(SLOT[b]) for b in SERVED}) == len(SERVED)
 
 
+def test_the_second_batch_is_what_it_says():
+    q, n = Q_START_2, SLOT_2.size
+    assert n == 7 and D_LEN_2.size == n and q.size == n + 1
+    present = tuple(b for b in range(n) if 0 <= q[b] <= q[b + 1] <= N_TOKENS_MAX_2)
+    assert present == SERVED_2 and all(0 <= SLOT_2[b] < N_SLOTS for b in range(n))
+    assert [int(q[b + 1] - q[b]) for b in SERVED_2] == [7, 8, 16, 5]
+    assert q[3] <= q[4] and q[4] > N_TOKENS_MAX_2                    # 3: ends beyond n_tokens_max
+    assert q[4] > q[5] and q[4] > N_TOKENS_MAX_2                     # 4: starts above its end, and beyond n_tokens_max
+    assert 0 <= q[6] <= q[7] and q[7] > N_TOKENS_MAX_2               # 6: ends beyond n_tokens_max
+    owned = np.zeros(N_TOKENS_MAX_2, bool)
+    for b in SERVED_2:
+        assert not owned[q[b]:q[b + 1]].any()
+        owned[q[b]:q[b + 1]] = True
+    assert list(np.flatnonzero(~owned)) == [31, 32, 38, 39]
+    assert [int(D_LEN_2[b]) == 0 for b in SERVED_2] == [True, False, True, False]
+    assert len({int(s) for s in SLOT_2}) == n                        # (the absent sequences name slots of their own: what must stay unchanged)
+    assert all(D_LEN_2[b] > 0 for b in range(n) if b not in SERVED_2)
+
+
+def test_the_first_seven_shapes_keep_their_inputs():
+    assert [SHAPES[name]["seed"] for name in FIRST_SEVEN] == list(range(71, 78)) and len(SHAPES) == 19
+    assert sorted(FIRST_SEVEN) == list(FIRST_SEVEN) and list(SHAPES)[:7] == ["mamba1_8", "mamba1_264", "mamba2_g1", "mamba2_g2", "n48", "mamba1_7", "n32"]
+
+
 # ---------------------------------------------------------------- the scan's inputs and references, computed once
 @functools.lru_cache(maxsize=None)
 def scan_case(name):
     s = SHAPES[name]
     H, P, N, G = s["H"], s["P"], s["N"], s["G"]
-    rng = np.random.default_rng(sorted(SHAPES).index(name) + 71)
+    rng = np.random.default_rng(s["seed"])
     c = dict(s)
     c["x"] = rng.normal(0.0, 1.0, (N_TOKENS_MAX, H, P)).astype(F)
     c["dt"] = (2.0 * rng.normal(0.0, 1.0, (N_TOKENS_MAX, H)) - 1.0).astype(F)
@@ -91,17 +160,18 @@ def scan_case(name):
     return c
 
 
-def _seq_args(c, b):
-    lo, hi = _rows(b)
-    h0 = None if D_LEN[b] == 0 else c["pool"][SLOT[b]]
-    return (c["x"][lo:hi], c["dt"][lo:hi], c["A"], c["B"][lo:hi], c["C"][lo:hi]), dict(D=c["D"], dt_bias=c["dt_bias"], h0=h0)
+def _seq_args(c, b, k=BATCH_1, with_D=True, with_bias=True):
+    lo, hi = k.rows(b)
+    h0 = None if k.d_len[b] == 0 else c["pool"][k.slot[b]]
+    return ((c["x"][lo:hi], c["dt"][lo:hi], c["A"], c["B"][lo:hi], c["C"][lo:hi]),
+            dict(D=c["D"] if with_D else None, dt_bias=c["dt_bias"] if with_bias else None, h0=h0))
 
 
 @functools.lru_cache(maxsize=None)
-def scan_ref(name, b):
-    """(y, h, bar_y, bar_h) of sequence b in float64"""
-    a, k = _seq_args(scan_case(name), b)
-    return np_ssm.scan_f64(*a, want_bar=True, **k)
+def scan_ref(name, b, k=BATCH_1, with_D=True, with_bias=True):
+    """(y, h, bar_y, bar_h) of sequence b of batch k in float64"""
+    a, kw = _seq_args(scan_case(name), b, k, with_D, with_bias)
+    return np_ssm.scan_f64(*a, want_bar=True, **kw)
 
 
 # ---------------------------------------------------------------- CPU
@@ -130,36 +200,102 @@ def test_the_exact_fma_of_the_yardstick():
     assert np.array_equal(np_ssm.fmaf(x, y, np.zeros_like(z)), x * y) and np.array_equal(np_ssm.fmaf(x, np.ones_like(y), z), x + z)
 
 
-@pytest.mark.parametrize("name", sorted(SHAPES))
-def test_the_float32_model_is_within_the_bar(name):
+def _model_within_the_bar(name, k=BATCH_1, with_D=True, with_bias=True):
     c = scan_case(name)
-    for b in SERVED:
-        y, h, bar_y, bar_h = scan_ref(name, b)
-        a, k = _seq_args(c, b)
-        y32, h32 = np_ssm.scan_f32(*a, **k)
+    for b in k.served:
+        y, h, bar_y, bar_h = scan_ref(name, b, k, with_D, with_bias)
+        a, kw = _seq_args(c, b, k, with_D, with_bias)
+        y32, h32 = np_ssm.scan_f32(*a, **kw)
         ry, rh = float((np.abs(y32 - y) / bar_y).max()), float((np.abs(h32 - h) / bar_h).max())
         print(f"{name} seq {b}: model / bar  y {ry:.3f}  state {rh:.3f};  bar / |y| median {float(np.median(bar_y / np.maximum(np.abs(y), 1e-30))):.2e}")
         assert ry <= 1.0 and rh <= 1.0, (name, b, ry, rh)
 
 
-@pytest.mark.parametrize("name", sorted(SHAPES))
-def test_four_mutants_of_the_statement_exceed_the_bar_a_hundredfold(name):
-    """(a group index off by one is the statement itself with one group: that mutant is judged where G = 2)"""
+def _mutants_exceed_the_bar(name, mutants, k=BATCH_1, with_D=True, with_bias=True):
     c = scan_case(name)
-    for mutant in np_ssm.MUTANTS:
-        if mutant == "group_off_by_one" and c["G"] == 1:
-            continue
-        for b in SERVED:
-            y, h, bar_y, bar_h = scan_ref(name, b)
-            a, k = _seq_args(c, b)
+    for mutant in mutants:
+        for b in k.served:
+            y, h, bar_y, bar_h = scan_ref(name, b, k, with_D, with_bias)
+            a, kw = _seq_args(c, b, k, with_D, with_bias)
             with np.errstate(all="ignore"):
-                ym, _ = np_ssm.scan_f64(*a, mutant=mutant, **k)
+                ym, _ = np_ssm.scan_f64(*a, mutant=mutant, **kw)
                 diff = np.abs(ym - y)
                 worst = float(np.where(np.isfinite(diff), diff / bar_y, np.inf).max())
+            print(f"{name} seq {b}: {mutant} / bar  y {worst:.3g}")
             assert worst >= 100.0, (name, mutant, b, worst)
 
 
-@pytest.mark.parametrize("name", ("mamba1_8", "n48"))
+def _statement_mutants(name, with_D=True):
+    """(a group index off by one is the statement itself with one group, a dropped D the statement itself without D)"""
+    G = SHAPES[name]["G"]
+    return tuple(m for m in np_ssm.MUTANTS if not (m == "group_off_by_one" and G == 1) and not (m == "drop_D" and not with_D))
+
+
+@pytest.mark.parametrize("name", sorted(SHAPES))
+def test_the_float32_model_is_within_the_bar(name):
+    _model_within_the_bar(name)
+
+
+@pytest.mark.parametrize("name", sorted(SHAPES))
+def test_four_mutants_of_the_statement_exceed_the_bar_a_hundredfold(name):
+    """(a group index off by one is the statement itself with one group: that mutant is judged where G = 2)"""
+    _mutants_exceed_the_bar(name, _statement_mutants(name))
+
+
+@pytest.mark.parametrize("name", sorted(SHAPES))
+def test_two_kernel_shaped_mutants_exceed_the_bar_a_hundredfold(name):
+    """the butterfly one step short where a row has more than one lane, the A of state 0 for every state where A is per state: every shape but the
+    one-lane per-head one is judged by at least one"""
+    s = SHAPES[name]
+    mutants = (("short_butterfly",) if s["N"] > 16 else ()) + (("a_of_state_0",) if s["aps"] else ())
+    assert mutants or name == "n16_head"
+    _mutants_exceed_the_bar(name, mutants)
+
+
+OPTIONAL_SHAPES = ("n144", "n32_aps")
+OPTIONAL_OPERANDS = ((False, True), (True, False), (False, False))  # (with D, with dt_bias)
+
+
+@pytest.mark.parametrize("with_D,with_bias", OPTIONAL_OPERANDS)
+@pytest.mark.parametrize("name", OPTIONAL_SHAPES)
+def test_the_model_and_the_mutants_without_the_optional_operands(name, with_D, with_bias):
+    _model_within_the_bar(name, BATCH_1, with_D, with_bias)
+    _mutants_exceed_the_bar(name, _statement_mutants(name, with_D), BATCH_1, with_D, with_bias)
+
+
+SECOND_BATCH_SHAPES = ("mamba1_8", "n144", "n256")
+
+
+@pytest.mark.parametrize("name", SECOND_BATCH_SHAPES)
+def test_the_model_and_the_mutants_over_the_second_batch(name):
+    _model_within_the_bar(name, BATCH_2)
+    _mutants_exceed_the_bar(name, _statement_mutants(name), BATCH_2)
+
+
+def _forms(shapes):
+    return {(_plan(s["H"], s["P"], s["N"], s["G"], 1)[1][3], s["N"] == 16 * _plan(s["H"], s["P"], s["N"], s["G"], 1)[1][3], int(s["aps"])) for s in shapes}
+
+
+def test_every_form_the_plan_can_pick_has_a_shape():
+    """the scan is compiled once per (lanes_per_row, N == 16 lanes_per_row, A per state): the forms of SHAPES are the forms the plan hands out over every
+    served N, so a form added to the plan fails here until a shape reaches it -- and so does taking any one of the twelve later shapes away"""
+    reachable = set()
+    for N in range(16, 257, 16):
+        rc, p = _plan(4, 64, N, 1, 1)
+        assert rc == OK and p[3] == np_ssm.lanes_per_row(N)
+        reachable |= {(p[3], N == 16 * p[3], aps) for aps in (0, 1)}
+    assert len(reachable) == 16 and _forms(SHAPES.values()) == reachable
+    for name in SHAPES:
+        if name not in FIRST_SEVEN:
+            assert _forms(s for n, s in SHAPES.items() if n != name) != reachable, name
+    for lp in (2, 4, 8, 16):
+        rows = [s["H"] * s["P"] for s in SHAPES.values() if np_ssm.lanes_per_row(s["N"]) == lp]
+        assert any(r > 256 // lp for r in rows), ("no shape with more than one workgroup", lp)
+        assert any(r % (256 // lp) for r in rows), ("no shape with a partly filled last workgroup", lp)
+    assert any(s["H"] * s["P"] % 256 for s in SHAPES.values() if s["N"] == 16)
+
+
+@pytest.mark.parametrize("name", ("mamba1_8", "n48", "n256", "n240_aps"))
 def test_the_model_does_not_care_where_a_sequence_is_split(name):
     c = scan_case(name)
     for b, cut in SPLITS:
@@ -354,84 +490,118 @@ class Pool:
         return 4 * self.stride
 
 
-def _batch_pool(contents, elems, pad):
+def _batch_pool(contents, elems, pad, k=BATCH_1):
     """the pool of the batch: every slot holds contents[s], the fresh sequences' slots NaN bytes"""
     pool = Pool(N_SLOTS, elems, pad)
     for s in range(N_SLOTS):
         pool.put(s, contents[s])
-    for b in range(1, N_SEQ):
-        if D_LEN[b] == 0 and 0 <= SLOT[b] < N_SLOTS:
-            pool.put_nan(int(SLOT[b]))
+    for b in range(k.n_seq):
+        if k.d_len[b] == 0 and 0 <= k.slot[b] < N_SLOTS:
+            pool.put_nan(int(k.slot[b]))
     return pool
 
 
-def _scan_call(dev, c, q_start, d_len, slot, pool, n_tokens_max, row0=0, pad_head=0, pad_tok=0, pad_bc=0):
-    """one scan call over rows [row0, row0 + n_tokens_max) of the case's packed inputs, with the given paddings of the strides.
-    -> (dst bits [n_tokens_max][H][P + pad_head] with the token padding cut off, the pool image after the call); the guards of dst are checked here"""
+def _rows_and_pool_of_the_batch(k, y, after, pool, elems):
+    """what both entries owe a batch beside the served sequences' values.  Rows (y: uint32 [n_tokens_max, ...], preloaded with the sentinel): a slot id
+    outside the pool gives +0.0f, and no row but a served or zeroed sequence's is written -- not the rows nobody owns, not those an absent sequence names.
+    The pool: the fresh served sequences' slots were NaN bytes before the call, and only the served sequences' slots changed -- not the gaps, the guards,
+    the idle and the absent sequences' slots.  -> the mask of the owned rows"""
+    owned = np.zeros(k.n_tokens_max, bool)
+    changed = np.zeros(after.size, bool)
+    for b in k.served:
+        lo, hi = k.rows(b)
+        owned[lo:hi] = True
+        s0 = GUARD + int(k.slot[b]) * pool.stride
+        changed[s0:s0 + elems] = True
+        if k.d_len[b] == 0:
+            assert (pool.slot(pool.image, int(k.slot[b])) == NAN_BYTES).all(), b
+    for b in k.zeroed:
+        lo, hi = k.rows(b)
+        owned[lo:hi] = True
+        assert not y[lo:hi].any(), b
+    assert (y[~owned] == SENTINEL).all(), "a row of no present sequence was written"
+    assert np.array_equal(after[~changed], pool.image[~changed]), "state outside the served slots was written"
+    return owned
+
+
+def _scan_call(dev, c, q_start, d_len, slot, pool, n_tokens_max, row0=0, pad_head=0, pad_tok=0, pad_bc=0, pad_head_d=None, pad_tok_d=None, pad_dt=0, pad_a=0,
+               with_D=True, with_bias=True):
+    """one scan call over rows [row0, row0 + n_tokens_max) of the case's packed inputs, with the given paddings of the strides: pad_head / pad_tok of x
+    (and of dst, unless pad_head_d / pad_tok_d give dst its own), pad_bc of B and C, pad_dt of dt (ld_dt = n_head + pad_dt), pad_a of A (a_ld = N + pad_a
+    per state, 1 + pad_a per head); every gap of an input holds 3.0e38.  with_D / with_bias False: a null pointer.
+    -> (dst bits [n_tokens_max][H][P], the pool image after the call); the guards and the paddings of dst and every input are checked here"""
     H, P, N, G = c["H"], c["P"], c["N"], c["G"]
     n = n_tokens_max
     sl = slice(row0, row0 + n)
     ldh, ldt = P + pad_head, H * (P + pad_head) + pad_tok
+    ldh_d = P + (pad_head if pad_head_d is None else pad_head_d)
+    ldt_d = H * ldh_d + (pad_tok if pad_tok_d is None else pad_tok_d)
     x = np.full((n, ldt), 3.0e38, F)
     x[:, :H * ldh].reshape(n, H, ldh)[:, :, :P] = c["x"][sl]
     ld_bc = 2 * G * N + pad_bc
     bc = np.full((n, ld_bc), 3.0e38, F)
     bc[:, :G * N] = c["B"][sl].reshape(n, G * N)
     bc[:, G * N:2 * G * N] = c["C"][sl].reshape(n, G * N)
-    d_x, d_bc, d_dt = _up(dev, x), _up(dev, bc), _up(dev, c["dt"][sl])
-    d_A, d_D, d_db = _up(dev, c["A"]), _up(dev, c["D"]), _up(dev, c["dt_bias"])
+    ld_dt = H + pad_dt
+    dt = np.full((n, ld_dt), 3.0e38, F)
+    dt[:, :H] = c["dt"][sl]
+    a_ld = (N if c["aps"] else 1) + pad_a
+    A = np.full((H, a_ld), 3.0e38, F)
+    A[:, :a_ld - pad_a] = c["A"].reshape(H, -1)
+    d_x, d_bc, d_dt, d_A = _up(dev, x), _up(dev, bc), _up(dev, dt), _up(dev, A)
+    d_D, d_db = _up(dev, c["D"]), _up(dev, c["dt_bias"])
     d_q, d_l, d_s = _up(dev, np.asarray(q_start, np.int32)), _up(dev, np.asarray(d_len, np.int32)), _up(dev, np.asarray(slot, np.int32))
     d_pool = _up(dev, pool.image)
-    dst = dev.torch.full((GUARD + max(n, 1) * ldt + GUARD,), SENTINEL, dtype=dev.torch.int32, device="cuda")
+    dst = dev.torch.full((GUARD + max(n, 1) * ldt_d + GUARD,), SENTINEL, dtype=dev.torch.int32, device="cuda")
     rc = _lib.lib().ggml_hip_ssm_scan_ragged_dev(
-        _p(d_x.data_ptr()), ldt, ldh, _p(d_dt.data_ptr()), H, _p(d_db.data_ptr()), _p(d_A.data_ptr()), N if c["aps"] else 1, int(c["aps"]),
-        _p(d_bc.data_ptr()), _p(d_bc.data_ptr() + 4 * G * N), ld_bc, _p(d_D.data_ptr()), H, P, N, G, len(slot), _p(d_q.data_ptr()), n, _p(d_l.data_ptr()),
-        _p(d_s.data_ptr()), _p(pool.ptr(d_pool)), pool.nb_slot, pool.n_slots, _p(dst.data_ptr() + 4 * GUARD), ldt, ldh, _stream(dev))
+        _p(d_x.data_ptr()), ldt, ldh, _p(d_dt.data_ptr()), ld_dt, _p(d_db.data_ptr()) if with_bias else None, _p(d_A.data_ptr()), a_ld, int(c["aps"]),
+        _p(d_bc.data_ptr()), _p(d_bc.data_ptr() + 4 * G * N), ld_bc, _p(d_D.data_ptr()) if with_D else None, H, P, N, G, len(slot), _p(d_q.data_ptr()), n,
+        _p(d_l.data_ptr()), _p(d_s.data_ptr()), _p(pool.ptr(d_pool)), pool.nb_slot, pool.n_slots, _p(dst.data_ptr() + 4 * GUARD), ldt_d, ldh_d, _stream(dev))
     assert rc == 0, _lib.lib().ggml_hip_last_error()
     dev.torch.cuda.synchronize()
     out = _bits(dst)
-    assert (out[:GUARD] == SENTINEL).all() and (out[GUARD + n * ldt:] == SENTINEL).all(), "guards of dst written"
-    body = out[GUARD:GUARD + n * ldt].reshape(n, ldt)
-    assert (body[:, H * ldh:] == SENTINEL).all(), "token padding of dst written"
-    body = body[:, :H * ldh].reshape(n, H, ldh)
+    assert (out[:GUARD] == SENTINEL).all() and (out[GUARD + n * ldt_d:] == SENTINEL).all(), "guards of dst written"
+    body = out[GUARD:GUARD + n * ldt_d].reshape(n, ldt_d)
+    assert (body[:, H * ldh_d:] == SENTINEL).all(), "token padding of dst written"
+    body = body[:, :H * ldh_d].reshape(n, H, ldh_d)
     assert (body[:, :, P:] == SENTINEL).all(), "head padding of dst written"
-    for t, want in ((d_x, x), (d_bc, bc)):
+    for t, want in ((d_x, x), (d_bc, bc), (d_dt, dt), (d_A, A)):
         assert np.array_equal(_bits(t), want.view(np.uint32).reshape(-1)), "an input was written"
     return body[:, :, :P], _bits(d_pool)
+
+
+def _scan_batch(dev, name, k, with_D=True, with_bias=True):
+    """the batch call of a shape: dst with paddings of its own (ldd_head != ldx_head, ldd_tok != ldx_tok), ld_dt above n_head, a_ld above N (by 4 or 8) or
+    3 for one A per head.  Served sequences against float64 under the bar, then what _rows_and_pool_of_the_batch states.  -> (y, after, pool)"""
+    c = scan_case(name)
+    H, P, N = c["H"], c["P"], c["N"]
+    elems = H * P * N
+    pool = _batch_pool(c["pool"].reshape(N_SLOTS, -1), elems, 8, k)
+    pad_a = (4 if N % 32 else 8) if c["aps"] else 2
+    y, after = _scan_call(dev, c, k.q_start, k.d_len, k.slot, pool, k.n_tokens_max, pad_head=3, pad_tok=5, pad_bc=4, pad_head_d=1, pad_tok_d=2, pad_dt=3,
+                          pad_a=pad_a, with_D=with_D, with_bias=with_bias)
+    for b in k.served:
+        lo, hi = k.rows(b)
+        ref_y, ref_h, bar_y, bar_h = scan_ref(name, b, k, with_D, with_bias)
+        got_y = y[lo:hi].view(F).astype(np.float64)
+        got_h = pool.slot(after, int(k.slot[b])).view(F).astype(np.float64).reshape(H, P, N)
+        ry, rh = float((np.abs(got_y - ref_y) / bar_y).max()), float((np.abs(got_h - ref_h) / bar_h).max())
+        print(f"{name} seq {b}: kernel / bar  y {ry:.3f}  state {rh:.3f}")
+        assert np.isfinite(got_y).all() and np.isfinite(got_h).all() and ry <= 1.0 and rh <= 1.0, (name, b, ry, rh)
+    _rows_and_pool_of_the_batch(k, y, after, pool, elems)
+    return y, after, pool
 
 
 @pytest.mark.gpu
 @pytest.mark.parametrize("name", sorted(SHAPES))
 def test_scan_over_the_ragged_batch(dev, name):
     c = scan_case(name)
-    H, P, N = c["H"], c["P"], c["N"]
-    elems = H * P * N
-    pool = _batch_pool(c["pool"].reshape(N_SLOTS, -1), elems, 8)
-    y, after = _scan_call(dev, c, Q_START, D_LEN, SLOT, pool, N_TOKENS_MAX, pad_head=3, pad_tok=5, pad_bc=4)
-    # rows: served sequences against float64 under the bar; a slot id outside the pool: +0.0f; everyone else's rows: not written
-    owned = np.zeros(N_TOKENS_MAX, bool)
-    for b in SERVED:
-        lo, hi = _rows(b)
-        owned[lo:hi] = True
-        ref_y, ref_h, bar_y, bar_h = scan_ref(name, b)
-        got_y = y[lo:hi].view(F).astype(np.float64)
-        got_h = pool.slot(after, int(SLOT[b])).view(F).astype(np.float64).reshape(H, P, N)
-        ry, rh = float((np.abs(got_y - ref_y) / bar_y).max()), float((np.abs(got_h - ref_h) / bar_h).max())
-        print(f"{name} seq {b}: kernel / bar  y {ry:.3f}  state {rh:.3f}")
-        assert np.isfinite(got_y).all() and np.isfinite(got_h).all() and ry <= 1.0 and rh <= 1.0, (name, b, ry, rh)
-    for b in ZEROED:
-        lo, hi = _rows(b)
-        owned[lo:hi] = True
-        assert not y[lo:hi].any(), b
-    assert (y[~owned] == SENTINEL).all(), "a row of no present sequence was written"
-    # the pool: only the served sequences' slots changed -- not the gaps, the guards, the idle and the absent sequence's slots
-    changed = np.zeros(after.size, bool)
-    for b in SERVED:
-        lo = GUARD + int(SLOT[b]) * pool.stride
-        changed[lo:lo + elems] = True
-    assert np.array_equal(after[~changed], pool.image[~changed]), "state outside the served slots was written"
+    elems = c["H"] * c["P"] * c["N"]
+    # rows: served sequences against float64 under the bar; a slot id outside the pool: +0.0f; everyone else's rows: not written.  The pool: only the
+    # served sequences' slots changed
+    y, after, pool = _scan_batch(dev, name, BATCH_1)
 
-    # (i) + (iii): every served sequence alone -- n_seq = 1, another slot number in another pool, other strides, another n_tokens_max
+    # (i) + (iii): every served sequence alone -- n_seq = 1, another slot number in another pool, other strides (of x, dst, dt and A), another n_tokens_max
     for b in SERVED:
         lo, hi = _rows(b)
         one = Pool(3, elems, 0)
@@ -451,6 +621,20 @@ def test_scan_over_the_ragged_batch(dev, name):
         assert np.array_equal(two.slot(end, 1), pool.slot(after, int(SLOT[b]))), ("state split", name, b, cut)
 
 
+@pytest.mark.gpu
+@pytest.mark.parametrize("with_D,with_bias", OPTIONAL_OPERANDS)
+@pytest.mark.parametrize("name", OPTIONAL_SHAPES)
+def test_scan_without_the_optional_operands(dev, name, with_D, with_bias):
+    """D and / or dt_bias null on the device: the statement without the term, under the same bar (its CPU twin holds the model and the mutants to it)"""
+    _scan_batch(dev, name, BATCH_1, with_D=with_D, with_bias=with_bias)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("name", SECOND_BATCH_SHAPES)
+def test_scan_over_the_second_batch(dev, name):
+    _scan_batch(dev, name, BATCH_2)
+
+
 # ---------------------------------------------------------------- the conv
 @functools.lru_cache(maxsize=None)
 def conv_case(n_ch, d_conv):
@@ -463,26 +647,26 @@ def conv_case(n_ch, d_conv):
     return c
 
 
-def _conv_call(dev, c, pool, bias, act, pad_x=0, pad_d=0, in_place=False):
-    n_ch, K = c["n_ch"], c["d_conv"]
+def _conv_call(dev, c, pool, bias, act, pad_x=0, pad_d=0, in_place=False, k=BATCH_1):
+    n_ch, K, n = c["n_ch"], c["d_conv"], k.n_tokens_max
     ldx = n_ch + pad_x
     ldd = ldx if in_place else n_ch + pad_d
-    x = np.full((N_TOKENS_MAX, ldx), 3.0e38, F)
-    x[:, :n_ch] = c["x"]
-    xbuf = np.full(GUARD + N_TOKENS_MAX * ldx + GUARD, SENTINEL, np.uint32)
+    x = np.full((n, ldx), 3.0e38, F)
+    x[:, :n_ch] = c["x"][:n]
+    xbuf = np.full(GUARD + n * ldx + GUARD, SENTINEL, np.uint32)
     xbuf[GUARD:-GUARD] = x.view(np.uint32).reshape(-1)
     d_x, d_w, d_b = _up(dev, xbuf), _up(dev, c["w"]), _up(dev, c["bias"])
-    d_q, d_l, d_s = _up(dev, Q_START), _up(dev, D_LEN), _up(dev, SLOT)
+    d_q, d_l, d_s = _up(dev, k.q_start), _up(dev, k.d_len), _up(dev, k.slot)
     d_pool = _up(dev, pool.image)
-    dst = d_x if in_place else dev.torch.full((GUARD + N_TOKENS_MAX * ldd + GUARD,), SENTINEL, dtype=dev.torch.int32, device="cuda")
+    dst = d_x if in_place else dev.torch.full((GUARD + n * ldd + GUARD,), SENTINEL, dtype=dev.torch.int32, device="cuda")
     rc = _lib.lib().ggml_hip_ssm_conv_ragged_dev(_p(d_x.data_ptr() + 4 * GUARD), ldx, _p(d_w.data_ptr()), _p(d_b.data_ptr()) if bias else None, int(act), n_ch, K,
-                                                 N_SEQ, _p(d_q.data_ptr()), N_TOKENS_MAX, _p(d_l.data_ptr()), _p(d_s.data_ptr()), _p(pool.ptr(d_pool)),
+                                                 k.n_seq, _p(d_q.data_ptr()), n, _p(d_l.data_ptr()), _p(d_s.data_ptr()), _p(pool.ptr(d_pool)),
                                                  pool.nb_slot, pool.n_slots, _p(dst.data_ptr() + 4 * GUARD), ldd, _stream(dev))
     assert rc == 0, _lib.lib().ggml_hip_last_error()
     dev.torch.cuda.synchronize()
     out = _bits(dst)
     assert (out[:GUARD] == SENTINEL).all() and (out[-GUARD:] == SENTINEL).all(), "guards of dst written"
-    body = out[GUARD:-GUARD].reshape(N_TOKENS_MAX, ldd)
+    body = out[GUARD:-GUARD].reshape(n, ldd)
     if in_place:
         assert np.array_equal(body[:, n_ch:], x.view(np.uint32)[:, n_ch:]), "padding columns written"
     else:
@@ -491,48 +675,60 @@ def _conv_call(dev, c, pool, bias, act, pad_x=0, pad_d=0, in_place=False):
     return body[:, :n_ch], _bits(d_pool)
 
 
-@pytest.mark.gpu
-@pytest.mark.parametrize("d_conv", (2, 4))
-@pytest.mark.parametrize("n_ch", (1, 5, 64, 1028))
-def test_conv_over_the_ragged_batch(dev, n_ch, d_conv):
+def _conv_batch(dev, n_ch, d_conv, k):
+    """the conv over batch k, every assertion of the entry: (act 0, bias) and (act 0, no bias) and their slots bit for bit, rows and pool as
+    _rows_and_pool_of_the_batch states, in place, (act 1, no bias) and (act 1, bias) within 3 * 2^-24 relative of the silu of the conv's bits"""
     c = conv_case(n_ch, d_conv)
+    n = k.n_tokens_max
     elems = (d_conv - 1) * n_ch
     pad = (-elems) % 4 + 4                                           # (a slot stride that is a multiple of 16 bytes, above the slot's bytes)
-    pool = _batch_pool(c["pool"].reshape(N_SLOTS, -1), elems, pad)
-    want, want_slot = {}, {}
-    for b in SERVED:
-        lo, hi = _rows(b)
-        want[b], want_slot[b] = np_ssm.conv_f32(c["x"][lo:hi], c["w"], c["bias"], None if D_LEN[b] == 0 else c["pool"][SLOT[b]])
-    y, after = _conv_call(dev, c, pool, bias=True, act=0, pad_x=3, pad_d=6)
-    owned = np.zeros(N_TOKENS_MAX, bool)
-    changed = np.zeros(after.size, bool)
-    for b in SERVED:
-        lo, hi = _rows(b)
-        owned[lo:hi] = True
-        assert np.array_equal(y[lo:hi], want[b].view(np.uint32)), ("rows", b)
-        assert np.array_equal(pool.slot(after, int(SLOT[b])), want_slot[b].view(np.uint32).reshape(-1)), ("slot", b)
-        s0 = GUARD + int(SLOT[b]) * pool.stride
-        changed[s0:s0 + elems] = True
-    for b in ZEROED:
-        lo, hi = _rows(b)
-        owned[lo:hi] = True
-        assert not y[lo:hi].any(), b
-    assert (y[~owned] == SENTINEL).all(), "a row of no present sequence was written"
-    assert np.array_equal(after[~changed], pool.image[~changed]), "state outside the served slots was written"
+    pool = _batch_pool(c["pool"].reshape(N_SLOTS, -1), elems, pad, k)
+
+    def statement(b, bias):
+        lo, hi = k.rows(b)
+        return np_ssm.conv_f32(c["x"][lo:hi], c["w"], c["bias"] if bias else None, None if k.d_len[b] == 0 else c["pool"][k.slot[b]])
+
+    y, after = _conv_call(dev, c, pool, bias=True, act=0, pad_x=3, pad_d=6, k=k)
+    for b in k.served:
+        lo, hi = k.rows(b)
+        want, want_slot = statement(b, True)
+        assert np.array_equal(y[lo:hi], want.view(np.uint32)), ("rows", b)
+        assert np.array_equal(pool.slot(after, int(k.slot[b])), want_slot.view(np.uint32).reshape(-1)), ("slot", b)
+    owned = _rows_and_pool_of_the_batch(k, y, after, pool, elems)
     # in place: d_dst == d_x gives the same rows (the rows nobody owns keep x) and the same pool
-    y2, after2 = _conv_call(dev, c, pool, bias=True, act=0, pad_x=3, in_place=True)
-    assert np.array_equal(y2[owned], y[owned]) and np.array_equal(y2[~owned], c["x"].view(np.uint32)[~owned]) and np.array_equal(after2, after)
-    # act = 1, no bias: within 3 * 2^-24 relative of the silu of the conv's bits; the slot does not see act or bias
-    y3, after3 = _conv_call(dev, c, pool, bias=False, act=1)
-    worst = 0.0
-    for b in SERVED:
-        lo, hi = _rows(b)
-        acc, _ = np_ssm.conv_f32(c["x"][lo:hi], c["w"], None, None if D_LEN[b] == 0 else c["pool"][SLOT[b]])
-        ref = np_ssm.silu64(acc)
-        worst = max(worst, float((np.abs(y3[lo:hi].view(F).astype(np.float64) - ref) / np.abs(ref)).max()))
-    print(f"n_ch {n_ch} d_conv {d_conv}: silu relative error / 2^-24 = {worst / U:.3f}")
-    assert worst <= 3.0 * U, worst / U
-    assert np.array_equal(after3, after)
+    y2, after2 = _conv_call(dev, c, pool, bias=True, act=0, pad_x=3, in_place=True, k=k)
+    assert np.array_equal(y2[owned], y[owned]) and np.array_equal(y2[~owned], c["x"][:n].view(np.uint32)[~owned]) and np.array_equal(after2, after)
+    # act = 0, no bias: bit for bit too; the slot does not see the bias
+    y4, after4 = _conv_call(dev, c, pool, bias=False, act=0, pad_d=1, k=k)
+    for b in k.served:
+        lo, hi = k.rows(b)
+        assert np.array_equal(y4[lo:hi], statement(b, False)[0].view(np.uint32)), ("rows without bias", b)
+    assert np.array_equal(y4[~owned], y[~owned]) and np.array_equal(after4, after)
+    # act = 1, without and with bias: within 3 * 2^-24 relative of the silu of the conv's bits; the slot does not see act or bias
+    for bias in (False, True):
+        y3, after3 = _conv_call(dev, c, pool, bias=bias, act=1, k=k)
+        worst = 0.0
+        for b in k.served:
+            lo, hi = k.rows(b)
+            ref = np_ssm.silu64(statement(b, bias)[0])
+            worst = max(worst, float((np.abs(y3[lo:hi].view(F).astype(np.float64) - ref) / np.abs(ref)).max()))
+        print(f"n_ch {n_ch} d_conv {d_conv} bias {int(bias)}: silu relative error / 2^-24 = {worst / U:.3f}")
+        assert worst <= 3.0 * U, worst / U
+        assert np.array_equal(y3[~owned], y[~owned]) and np.array_equal(after3, after)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("d_conv", (2, 3, 4))
+@pytest.mark.parametrize("n_ch", (1, 5, 64, 1028))
+def test_conv_over_the_ragged_batch(dev, n_ch, d_conv):
+    _conv_batch(dev, n_ch, d_conv, BATCH_1)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("d_conv", (2, 3, 4))
+@pytest.mark.parametrize("n_ch", (5, 1028))
+def test_conv_over_the_second_batch(dev, n_ch, d_conv):
+    _conv_batch(dev, n_ch, d_conv, BATCH_2)
 
 
 # ---------------------------------------------------------------- the python face, a captured step, no tokens at all
@@ -588,3 +784,66 @@ def test_a_captured_step_follows_the_batch_and_no_tokens_is_accepted(dev):
     torch.cuda.synchronize()
     for got, w in zip((pool, cpool, y, cy), before):
         assert np.array_equal(_bits(got), w)
+
+
+@pytest.mark.gpu
+def test_the_python_face_on_the_views_of_a_mamba2_block(dev):
+    """what a Mamba-2 block hands over: ONE [n_tokens, d_inner + 2 G N] tensor xBC, convolved in place, and the scan on views of it -- x, B and C with the
+    token stride of xBC, dt and out as views of wider tensors, a state pool with a slot stride above the slot, A one value per head.  Every stride the
+    wrapper derives is pinned: the rows and the final slots are bit for bit those of the raw entry on contiguous copies of the conv's output, and under
+    the float64 bar computed from that output"""
+    torch = dev.torch
+    name = "mamba2_g2"
+    c = scan_case(name)
+    H, P, N, G = c["H"], c["P"], c["N"], c["G"]
+    d_inner, gn, elems, n = H * P, G * N, H * P * N, N_TOKENS_MAX
+    assert (d_inner, 2 * gn) == (256, 512)
+    cc = conv_case(d_inner + 2 * gn, 4)
+    t = lambda a: torch.from_numpy(np.ascontiguousarray(a)).cuda()
+    d_q, d_l, d_s = t(Q_START), t(D_LEN), t(SLOT)
+    fresh = [int(SLOT[b]) for b in SERVED if D_LEN[b] == 0]
+
+    def pool_of(contents, pad):                                      # [N_SLOTS, elements] as a view of a wider tensor; the fresh slots hold NaN bytes
+        wide = torch.full((N_SLOTS, contents.shape[1] + pad), float("nan"), dtype=torch.float32, device="cuda")
+        view = wide[:, :contents.shape[1]]
+        view.copy_(t(contents))
+        view.view(torch.int32)[fresh] = -1
+        return view
+
+    cpool, pool = pool_of(cc["pool"].reshape(N_SLOTS, -1), 4), pool_of(c["pool"].reshape(N_SLOTS, -1), 8)
+    xBC = t(cc["x"])
+    assert tuple(xBC.shape) == (n, 768)
+    dev.ssm_conv_ragged(xBC, t(cc["w"]), d_q, d_l, d_s, cpool, bias=t(cc["bias"]), act=True, out=xBC)
+    x = xBC[:, :d_inner].unflatten(1, (H, P))
+    B = xBC[:, d_inner:d_inner + gn].unflatten(1, (G, N))
+    Cc = xBC[:, d_inner + gn:].unflatten(1, (G, N))
+    dt = torch.full((n, H + 3), 3.0e38, dtype=torch.float32, device="cuda")[:, :H]
+    dt.copy_(t(c["dt"]))
+    wide = torch.full((n, H, P + 8), float("nan"), dtype=torch.float32, device="cuda")
+    wide.view(torch.int32).fill_(SENTINEL)
+    out = wide[:, :, :P]
+    assert (x.stride(0), x.stride(1), out.stride(0), out.stride(1), dt.stride(0), pool.stride(0)) == (768, P, H * (P + 8), P + 8, H + 3, elems + 8)
+    got = dev.ssm_scan_ragged(x, dt, t(c["A"]), B, Cc, d_q, d_l, d_s, pool, dt_bias=t(c["dt_bias"]), D=t(c["D"]), out=out)
+    torch.cuda.synchronize()
+    assert got is out
+    conv = xBC.cpu().numpy()
+    y, state = _bits(wide)[:, :, :P], _bits(pool.contiguous())
+    assert (_bits(wide)[:, :, P:] == SENTINEL).all(), "the padding of out was written"
+    # the raw entry on contiguous copies of the conv's output, over the same pool contents
+    c2 = dict(c, x=conv[:, :d_inner].reshape(n, H, P).copy(), B=conv[:, d_inner:d_inner + gn].reshape(n, G, N).copy(),
+              C=conv[:, d_inner + gn:].reshape(n, G, N).copy())
+    raw_pool = _batch_pool(c["pool"].reshape(N_SLOTS, -1), elems, 0)
+    y_raw, after = _scan_call(dev, c2, Q_START, D_LEN, SLOT, raw_pool, n)
+    assert np.array_equal(y, y_raw), "rows"
+    for b in SERVED:
+        lo, hi = _rows(b)
+        assert np.array_equal(state[int(SLOT[b])], raw_pool.slot(after, int(SLOT[b]))), ("slot", b)
+        a, kw = _seq_args(c2, b)
+        ref_y, ref_h, bar_y, bar_h = np_ssm.scan_f64(*a, want_bar=True, **kw)
+        got_y, got_h = y[lo:hi].view(F).astype(np.float64), state[int(SLOT[b])].view(F).astype(np.float64).reshape(H, P, N)
+        ry, rh = float((np.abs(got_y - ref_y) / bar_y).max()), float((np.abs(got_h - ref_h) / bar_h).max())
+        print(f"{name} on the conv's output, seq {b}: kernel / bar  y {ry:.3f}  state {rh:.3f}")
+        assert np.isfinite(got_y).all() and np.isfinite(got_h).all() and ry <= 1.0 and rh <= 1.0, (b, ry, rh)
+    _rows_and_pool_of_the_batch(BATCH_1, y, after, raw_pool, elems)
+    unserved = [s for s in range(N_SLOTS) if s not in [int(SLOT[b]) for b in SERVED]]
+    assert np.array_equal(state[unserved], raw_pool.image[GUARD:GUARD + N_SLOTS * elems].reshape(N_SLOTS, elems)[unserved]), "a slot of no served sequence"
