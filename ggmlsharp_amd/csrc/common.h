@@ -497,6 +497,13 @@ __device__ __forceinline__ int ragged_find(const kv_ragged &rg, int64_t row, int
     *t = (int)(row - qs);
     return lo;
 }
+// sequence b by itself (the SSM entries): present -> its first packed row and its count
+__device__ __forceinline__ bool ssm_sequence(const kv_ragged &rg, int b, int64_t *qs, int *nq) {
+    const int64_t s = rg.q_start[b], e = rg.q_start[b + 1];
+    if (s < 0 || s > e || e > rg.n_tokens_max) return false;
+    *qs = s; *nq = (int)(e - s);
+    return true;
+}
 #endif
 // d_pos[i] = len[b] + t for row i = (b, t) of a present sequence, 0 for the other rows below n_tokens_max
 hipError_t launch_ragged_positions(const kv_ragged &rg, const int32_t *len, int32_t *pos, hipStream_t st);
@@ -547,8 +554,13 @@ struct ssm_scan_args {
     const int32_t *len, *slot; int n_slots;
     float *state; int64_t slot_elems;
     float *dst; int64_t ldd_tok, ldd_head;
+    int nq_max;                                                      // the sequential kernel serves sequences of 1 .. nq_max tokens in this call (INT_MAX: all)
 };
 hipError_t launch_ssm_scan(const ssm_scan_plan &pl, const kv_ragged &rg, const ssm_scan_args &a, hipStream_t st);
+// ssm_chunk.hip: the same call with the sequences above pl.seq_max_tokens in the chunked matrix form (ggml_hip_ssm_scan_chunked_ragged_dev; plan.h
+// plan_ssm_chunk has the launches and the work buffer).  a.nq_max is set here; work: the 256-byte aligned base, null where pl.form is sequential
+struct ssm_chunk_plan;
+hipError_t launch_ssm_scan_chunked(const ssm_chunk_plan &pl, const kv_ragged &rg, const ssm_scan_args &a, void *work, hipStream_t st);
 // gemm_q8s.hip / gemm_qmx.hip: ONE K3s launch over the tile table -- workgroup -> (weight tile group, column tile t); t >= *n_tiles leaves at once;
 // the expert's planes come from tab[tiles[t].expert], the 32 sorted rows at 32 t of the image p (K1's image of `32 * max_tiles` rows); res [rows][ldr]
 hipError_t launch_gemm_q8_small_grouped(const mm_plan &g, int type, const moe_gexpert *tab, const moe_tile *tiles, const int32_t *n_tiles, int64_t max_tiles,

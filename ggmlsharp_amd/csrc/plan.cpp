@@ -659,3 +659,32 @@ ssm_scan_plan plan_ssm_scan(int n_head, int P, int N, int n_group, int64_t n_seq
     p.wgs = p.wgs_x * n_seq;
     return p;
 }
+
+// The chunked scan (plan.h has the statement): the sequential plan for the short sequences, the bounds of the chunk list for the long ones.
+ssm_chunk_plan plan_ssm_chunk(int n_head, int P, int N, int n_group, int a_per_state, int64_t n_seq, int64_t n_tokens_max) {
+    ssm_chunk_plan p = {};
+    p.seq = plan_ssm_scan(n_head, P, N, n_group, n_seq);
+    if (!p.seq.ok || (a_per_state != 0 && a_per_state != 1) || n_tokens_max < 0 || n_tokens_max > ATTN_PAGED_MAX_ROWS) return p;
+    p.ok = 1;
+    p.form = SSM_FORM_SEQUENTIAL;
+    p.chunk = SSM_CHUNK;
+    p.seq_max_tokens = SSM_CHUNK_SEQ_MAX_TOKENS;
+    p.launches = 1;
+    if (a_per_state || P % 16 != 0 || n_tokens_max <= p.seq_max_tokens) return p;
+    p.form = SSM_FORM_CHUNKED;
+    p.launches = 5;
+    p.p_tile = P % 64 == 0 ? 64 : P % 32 == 0 ? 32 : 16;
+    p.p_tiles = P / p.p_tile;
+    p.kernel_state = p.kernel_out = p.p_tile;
+    p.seqs_max = n_tokens_max / (p.seq_max_tokens + 1) < n_seq ? n_tokens_max / (p.seq_max_tokens + 1) : n_seq;
+    p.chunks_max = p.seqs_max + (n_tokens_max - p.seqs_max) / SSM_CHUNK;
+    p.pass_wgs_x = cdiv((int64_t)n_head * P * N / 4, 256);
+    const auto up = [](size_t v) { return (v + 255) / 256 * 256; };
+    p.hdr_off = 0;
+    p.seqs_off = 256;
+    p.list_off = p.seqs_off + up(16 * (size_t)p.seqs_max);
+    p.csd_off = p.list_off + up(8 * (size_t)p.chunks_max);
+    p.state_off = p.csd_off + up((size_t)p.chunks_max * (size_t)n_head * 2 * SSM_CHUNK * 4);
+    p.work_bytes = p.state_off + up((size_t)p.chunks_max * (size_t)n_head * (size_t)P * (size_t)N * 4);
+    return p;
+}

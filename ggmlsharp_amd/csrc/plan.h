@@ -183,6 +183,32 @@ struct ssm_conv_plan { int ok, launches; size_t state_bytes; int64_t wgs_x, wgs;
 struct ssm_scan_plan { int ok, form, launches, slices, lanes_per_row, rows_per_wg; size_t state_bytes; int64_t wgs_x, wgs; };
 ssm_conv_plan plan_ssm_conv(int64_t n_ch, int d_conv, int64_t n_seq);
 ssm_scan_plan plan_ssm_scan(int n_head, int P, int N, int n_group, int64_t n_seq);
+// ---- the chunked scan (ssm_chunk.hip; ggml_hip_ssm_scan_chunked_ragged_dev): the form is picked PER SEQUENCE from its own count in the call ----
+// A sequence of 1 .. seq_max_tokens tokens runs plan_ssm_scan's sequential kernel; a longer one runs in chunks of `chunk` = 64 tokens counted from its
+// first row of the call, as matrix products on the f32 MFMA.  chunk and seq_max_tokens follow the SHAPE alone (DESIGN.md section 26 has the measurement),
+// so a sequence's bits follow the shape and its own count.  form = SEQUENTIAL (one launch, no work buffer) where no sequence can be chunked: A per state
+// (the decay mask would depend on n), P no multiple of 16, or n_tokens_max <= seq_max_tokens.  Else form = CHUNKED, FIVE launches:
+//   the sequential kernel          plan_ssm_scan's grid; sequences above seq_max_tokens leave at once
+//   index  (1 workgroup of 1024)   q_start -> the chunked sequences (b, first chunk, chunks) and the chunk list (b, chunk of b), clamped at seqs_max / chunks_max
+//   state  (n_head * p_tiles, chunks_max)   per (chunk, head, P tile of p_tile rows): delta, cs, and the chunk's own state contribution at its end
+//   pass   (ceil(n_head P N / 1024), seqs_max)   per (sequence, 4 state elements), over the sequence's chunks: H_in of each chunk, the final state into the slot
+//   out    (n_head * p_tiles, chunks_max)   per (chunk, head, P tile): y from H_in and the masked intra-chunk products
+// p_tile: 64 where it divides P, else 32, else 16; the state and out kernels are compiled once per p_tile (kernel_state = kernel_out = p_tile).
+// seqs_max = min(n_seq, n_tokens_max / (seq_max_tokens + 1)) chunked sequences fit in n_tokens_max rows; k such sequences of n_i rows have
+// sum (1 + (n_i - 1) / chunk) <= k + (n_tokens_max - k) / chunk chunks, which grows with k: chunks_max is that at k = seqs_max.
+// THE WORK BUFFER from its 256-byte aligned base, every part at a multiple of 256: int32 x 4 (chunks, chunked sequences, 0, 0) at hdr_off = 0;
+// int32 x 4 [seqs_max] at seqs_off; int32 x 2 [chunks_max] at list_off; f32 [chunks_max][n_head][2][chunk] (cs, delta) at csd_off;
+// f32 [chunks_max][n_head][P][N] at state_off (the chunk's contribution, then in place its H_in).  Nothing in it is read before the call writes it.
+constexpr int SSM_CHUNK = 64;
+constexpr int SSM_CHUNK_SEQ_MAX_TOKENS = 44;
+enum { SSM_FORM_CHUNKED = 2 };
+struct ssm_chunk_plan {
+    int ok, form, chunk, seq_max_tokens, launches, p_tile, p_tiles, kernel_state, kernel_out;
+    int64_t chunks_max, seqs_max, pass_wgs_x;
+    size_t hdr_off, seqs_off, list_off, csd_off, state_off, work_bytes;
+    ssm_scan_plan seq;
+};
+ssm_chunk_plan plan_ssm_chunk(int n_head, int P, int N, int n_group, int a_per_state, int64_t n_seq, int64_t n_tokens_max);
 // the K1 image INIT writes for a plan: its image where that is one of K1's (0 .. 3; else 0), + ACT_IMAGE_MIN_PIECES under MM_FLAG_MIN_PIECES
 int plan_act_image(const mm_plan &p);
 // the K1 image for (type, K, N) with no weight at hand: plan_act_image of the COMPUTE-only plan at M = 1 (no M: the exception cannot apply)

@@ -24,13 +24,6 @@ namespace {
 
 constexpr int CONV_UNROLL = 8;
 
-__device__ __forceinline__ bool ssm_sequence(const kv_ragged &rg, int b, int64_t *qs, int *nq) {
-    const int64_t s = rg.q_start[b], e = rg.q_start[b + 1];
-    if (s < 0 || s > e || e > rg.n_tokens_max) return false;
-    *qs = s; *nq = (int)(e - s);
-    return true;
-}
-
 template <int KC>
 __global__ __launch_bounds__(256) void ssm_conv_kernel(const kv_ragged rg, const int32_t *__restrict__ len, const int32_t *__restrict__ slot, int n_slots,
                                                        const float *x, int64_t ldx, const float *__restrict__ w, const float *__restrict__ bias, int act,
@@ -85,6 +78,7 @@ struct scan_args {
     const int32_t *len, *slot; int n_slots;
     float *state; int64_t slot_elems;
     float *dst; int64_t ldd_tok, ldd_head;
+    int nq_max;                                                      // sequences above it belong to the chunked form (ssm_chunk.hip); INT_MAX: none
 };
 
 // the 4 x 4 transpose of v[0 .. 3] over the four lanes of a quad (r = lane & 3): lane r ends with what lane k held in v[r], k = 0 .. 3.  Two
@@ -110,7 +104,7 @@ template <int LP, bool APS, bool FULL>
 __global__ __launch_bounds__(256) void ssm_scan_kernel(const kv_ragged rg, const scan_args a) {
     const int b = blockIdx.y;
     int64_t qs; int nq;
-    if (!ssm_sequence(rg, b, &qs, &nq) || nq == 0) return;             // (uniform over the workgroup)
+    if (!ssm_sequence(rg, b, &qs, &nq) || nq == 0 || nq > a.nq_max) return;   // (uniform over the workgroup)
     const int64_t lane = (int64_t)blockIdx.x * 256 + threadIdx.x;
     const int64_t row = lane / LP;                                       // (head, p)
     const int j = (int)(lane % LP);                                      // the slice: states 16 j .. 16 j + 15
@@ -232,7 +226,7 @@ hipError_t launch_ssm_scan(const ssm_scan_plan &pl, const kv_ragged &rg, const s
     a.x = s.x; a.ldx_tok = s.ldx_tok; a.ldx_head = s.ldx_head; a.dt = s.dt; a.ld_dt = s.ld_dt; a.dt_bias = s.dt_bias; a.A = s.A; a.a_ld = s.a_ld;
     a.B = s.B; a.C = s.C; a.ld_bc = s.ld_bc; a.D = s.D; a.n_head = s.n_head; a.P = s.P; a.N = s.N; a.heads_per_group = s.n_head / s.n_group;
     a.len = s.len; a.slot = s.slot; a.n_slots = s.n_slots; a.state = s.state; a.slot_elems = s.slot_elems; a.dst = s.dst; a.ldd_tok = s.ldd_tok;
-    a.ldd_head = s.ldd_head;
+    a.ldd_head = s.ldd_head; a.nq_max = s.nq_max;
     const dim3 grid((unsigned)pl.wgs_x, (unsigned)rg.n_seq);
     const bool aps = s.a_per_state != 0;
     switch (pl.lanes_per_row) {

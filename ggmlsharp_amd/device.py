@@ -747,6 +747,54 @@ def ssm_scan_ragged(x, dt, A, B, C_, q_start, d_len, slot, state, dt_bias=None, 
     return out
 
 
+def ssm_scan_chunked_plan(n_head, head_dim, d_state, n_group=1, a_per_state=False, n_seq=1, n_tokens_max=0):
+    """the ggml_hip_ssm_chunk_plan_t of one chunked-scan call: the form, the chunk Q, seq_max_tokens, the bounds of the chunk list, the work bytes; no
+    device needed"""
+    out = _lib.ggml_hip_ssm_chunk_plan_t()
+    check(lib().ggml_hip_ssm_scan_chunked_plan(n_head, head_dim, d_state, n_group, int(bool(a_per_state)), n_seq, n_tokens_max, C.byref(out)),
+          "ggml_hip_ssm_scan_chunked_plan")
+    return out
+
+
+def ssm_scan_chunked_work_size(n_head, head_dim, d_state, n_group=1, a_per_state=False, n_seq=1, n_tokens_max=0):
+    return int(lib().ggml_hip_ssm_scan_chunked_work_size(n_head, head_dim, d_state, n_group, int(bool(a_per_state)), n_seq, n_tokens_max))
+
+
+def ssm_scan_chunked_ragged(x, dt, A, B, C_, q_start, d_len, slot, state, dt_bias=None, D=None, n_tokens_max=None, out=None, work=None):
+    """ssm_scan_ragged with the chunked matrix form for the sequences of more than seq_max_tokens tokens in this call (ssm_scan_chunked_plan); the shorter
+    ones are bit for bit ssm_scan_ragged's.  work: a uint8 tensor of at least ssm_scan_chunked_work_size(..) bytes (a captured step passes its own);
+    None allocates one.  Splitting a long sequence over calls keeps its bits only at multiples of the chunk."""
+    assert x.is_cuda and x.dtype == torch.float32 and x.dim() == 3 and x.stride(2) == 1
+    n_rows, n_head, P = x.shape
+    assert dt.is_cuda and dt.dtype == torch.float32 and dt.dim() == 2 and dt.stride(1) == 1 and dt.shape[1] == n_head
+    assert A.is_cuda and A.dtype == torch.float32 and A.dim() in (1, 2) and A.shape[0] == n_head and A.stride(-1) == 1
+    for t in (B, C_):
+        assert t.is_cuda and t.dtype == torch.float32 and t.dim() == 3 and t.stride(2) == 1 and t.stride(1) == t.shape[2]
+    assert B.shape == C_.shape and B.stride(0) == C_.stride(0)
+    G, N = B.shape[1], B.shape[2]
+    for t in (dt_bias, D):
+        assert t is None or (t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and t.numel() == n_head)
+    n_seq, nb_slot, n_slots = _ssm_batch(q_start, d_len, slot, state)
+    if n_tokens_max is None:
+        n_tokens_max = n_rows
+    assert n_tokens_max <= min(n_rows, dt.shape[0], B.shape[0])
+    if out is None:
+        out = torch.zeros((n_rows, n_head, P), dtype=torch.float32, device=x.device)
+    assert out.is_cuda and out.dtype == torch.float32 and out.dim() == 3 and out.stride(2) == 1 and tuple(out.shape) == (n_rows, n_head, P)
+    per_state = A.dim() == 2
+    need = ssm_scan_chunked_work_size(n_head, P, N, G, per_state, n_seq, n_tokens_max)
+    if work is None and need:
+        work = torch.empty(need, dtype=torch.uint8, device=x.device)
+    assert work is None or (work.is_cuda and work.dtype == torch.uint8 and work.is_contiguous() and work.numel() >= need)
+    check(lib().ggml_hip_ssm_scan_chunked_ragged_dev(C.c_void_p(x.data_ptr()), x.stride(0), x.stride(1), C.c_void_p(dt.data_ptr()), dt.stride(0), _opt(dt_bias),
+                                                     C.c_void_p(A.data_ptr()), A.stride(0), int(per_state), C.c_void_p(B.data_ptr()), C.c_void_p(C_.data_ptr()),
+                                                     B.stride(0), _opt(D), n_head, P, N, G, n_seq, C.c_void_p(q_start.data_ptr()), n_tokens_max,
+                                                     C.c_void_p(d_len.data_ptr()), C.c_void_p(slot.data_ptr()), C.c_void_p(state.data_ptr()), nb_slot, n_slots,
+                                                     C.c_void_p(out.data_ptr()), out.stride(0), out.stride(1), _opt(work), 0 if work is None else work.numel(),
+                                                     _stream()), "ggml_hip_ssm_scan_chunked_ragged_dev")
+    return out
+
+
 def quantize_rows(type, x):
     """x f32 [nrows, k] on the device -> uint8 [nrows, k/32*type_size] reference-format blocks."""
     assert x.is_cuda and x.dtype == torch.float32 and x.is_contiguous()

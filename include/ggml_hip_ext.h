@@ -1058,10 +1058,51 @@ int ggml_hip_sample_topk_dev(const float *d_logits, int64_t ld, int64_t n_rows, 
  *   rides in the registers of an aligned group of LP lanes (lanes_per_row; L of them work) and the butterfly is lane moves inside the group.  One
  *   launch of ceil(n_head * P * LP / 256) * n_seq workgroups, sized by the shape and n_seq alone.
  *   LIMITS.  That form is exactly right for decode.  A long prefill walks its tokens one after the other with n_head * P * LP lanes: the chunked
- *   matrix form (SSD) for long prefills is a follow-up, as is a token-parallel conv.  N that is no power-of-two multiple of 16 idles LP - L lanes of a
- *   group.  States are f32 only.
+ *   matrix form (SSD) for long prefills is ggml_hip_ssm_scan_chunked_ragged_dev below; a token-parallel conv is a follow-up.  N that is no
+ *   power-of-two multiple of 16 idles LP - L lanes of a group.  States are f32 only.
  * ggml_hip_ssm_state_bytes / ggml_hip_ssm_conv_state_bytes (host only): the bytes of one slot, n_head * P * N * 4 and (d_conv - 1) * n_ch * 4; 0 for a
- *   shape the entries refuse. */
+ *   shape the entries refuse.
+ *
+ * ggml_hip_ssm_scan_chunked_ragged_dev: the same scan with a SECOND FORM for long sequences, picked PER SEQUENCE from its own count in this call (as
+ *   ragged attention picks DECODE or PROMPT), so one call takes a mixed continuous-batching step.  Every argument of ggml_hip_ssm_scan_ragged_dev with
+ *   the same meaning and the same refusals, and d_work / work_bytes: at least ggml_hip_ssm_scan_chunked_work_size(..) bytes, any alignment, else
+ *   GGML_HIP_ERR_ARG (a size of 0 needs no buffer; NULL is accepted then).  Nothing in the buffer is read before the call has written it.  Stream-ordered,
+ *   capturable, no synchronize, no allocation, no atomics; every grid is sized by the shape, n_seq and n_tokens_max alone, so a captured graph follows
+ *   d_q_start, d_len and d_slot between replays -- a sequence may move from one form to the other.
+ *   SHORT: a sequence of 1 .. seq_max_tokens tokens runs the sequential kernel: its rows and state are bit for bit ggml_hip_ssm_scan_ragged_dev's.
+ *   LONG: a longer sequence runs the CHUNKED form where the shape is served by it: a_per_state = 0 and head_dim a multiple of 16 (16 .. 256), every
+ *   d_state.  Any other shape is NOT refused: the plan says form = 1 and every sequence runs sequential (Mamba-1's per-state A has a decay mask that
+ *   depends on n: no matrix form exists).  Absent and idle sequences, slot ids outside the pool (+0.0f rows, no state written, no address formed) and
+ *   fresh sequences over NaN slots behave as above.  Present sequences that overlap are still the caller's error; they write nothing outside dst,
+ *   the slots and the work buffer (the chunk list is clamped at chunks_max).
+ *   THE CHUNKED STATEMENT.  Chunks of Q = chunk tokens are counted from the sequence's first row OF THIS CALL; the last may be partial.  Per head h, with
+ *   d, delta as above and every operation one binary32 rounding:
+ *       la_t = delta_t * A[h][0];   cs_t = cs_(t-1) + la_t inside the chunk, ascending, cs_(-1) = +0.0f;   xd_s = delta_s * x[s][h][p]
+ *       S[p][n]     = sum_s (xd_s[p] * expf(cs_last - cs_s)) * B[s][g][n]              (s ascending over the chunk's tokens, an fmaf chain from +0.0f)
+ *       H_in        = the slot (zeros for a fresh sequence) for the first chunk, else H_out of the chunk before, as the f32 that went through memory
+ *       H_out[p][n] = fmaf(H_in[p][n], expf(cs_last), S[p][n])                         (the last chunk's H_out is the new slot)
+ *       G[t][s]     = sum_n C[t][g][n] * B[s][g][n];   M[t][s] = expf(cs_t - cs_s) * G[t][s] for s <= t
+ *       y[t][p]     = sum_n (expf(cs_t) * C[t][g][n]) * H_in[p][n] + sum_(s <= t) M[t][s] * xd_s[p]       (ONE fmaf chain from +0.0f, the n first)
+ *       y           = fmaf(D[h], x[t][h][p], y) if D is given
+ *   The sums over n run in the order n = 16 kb + 4 kq + c with kb, then c, then kq ascending (the f32-input MFMA's k order over float4 loads); the sum
+ *   over s <= t runs over every s below the next multiple of 16 above t, ascending, the masked terms being +0.0f * xd_s.
+ *   A decay is ONE expf of a difference of running sums, which is <= 0; never a quotient or product of separately exponentiated sums.  A mask -- s > t,
+ *   the rows beyond a partial chunk, the rows beyond the sequence -- is a SELECT: those rows are not loaded and may hold anything.
+ *   CONTRACTS.  Rows and final state are within the bar DERIVED in tests/np_ssm_chunk.py of the float64 sequential statement; that bar is wider than
+ *   the sequential form's (DESIGN.md section 26 has the ratio).  Bit level: (i) a sequence alone in a call gives the same bits; (iii) nothing depends
+ *   on the other sequences, the slot number, n_tokens_max, the strides or the work buffer's address and old contents; (ii') splitting a sequence at a
+ *   multiple of Q gives the bits of one call when both parts are longer than seq_max_tokens.  Contract (ii) of ggml_hip_ssm_scan_ragged_dev does NOT
+ *   hold at other split points (the chunk boundaries move): a caller who needs it keeps using that entry.
+ * ggml_hip_ssm_scan_chunked_plan / ggml_hip_ssm_scan_chunked_work_size (host only): what a call with these bounds does, and the bytes of its work
+ *   buffer (0 for a refused shape and where no sequence can be chunked).  chunk and seq_max_tokens follow the shape alone, never the batch. */
+typedef struct ggml_hip_ssm_chunk_plan_t {
+    int32_t form, chunk;                     /* 1: every sequence sequential; 2: chunked above seq_max_tokens.  Q, in tokens */
+    int32_t seq_max_tokens, launches;        /* a sequence with at most this many tokens in the call runs sequential; launches of one call (1 or 5) */
+    int32_t p_tile, p_tiles;                 /* rows of P a workgroup of the state / out kernels owns (16, 32, 64); head_dim / p_tile.  0 for form 1 */
+    int32_t kernel_state, kernel_out;        /* the compiled forms of the two matrix kernels: their p_tile.  0 for form 1 */
+    int64_t chunks_max, seqs_max;            /* the chunk list's and the chunked sequences' bounds over every batch inside n_seq and n_tokens_max */
+    uint64_t work_bytes;                     /* ggml_hip_ssm_scan_chunked_work_size */
+} ggml_hip_ssm_chunk_plan_t;
 typedef struct ggml_hip_ssm_plan_t {
     int32_t form, launches;                  /* 1: sequential over tokens, parallel over (sequence, head, p, slice); launches of one call (1) */
     int32_t slices, lanes_per_row;           /* L = N / 16; LP, the lanes of a state row's group */
@@ -1078,6 +1119,15 @@ int    ggml_hip_ssm_scan_ragged_dev(const float *d_x, int64_t ldx_tok, int64_t l
                                     const float *d_D, int n_head, int head_dim, int d_state_n, int n_group,
                                     int64_t n_seq, const int32_t *d_q_start, int64_t n_tokens_max, const int32_t *d_len, const int32_t *d_slot,
                                     float *d_state, int64_t nb_slot, int64_t n_slots, float *d_dst, int64_t ldd_tok, int64_t ldd_head, void *stream);
+size_t ggml_hip_ssm_scan_chunked_work_size(int n_head, int head_dim, int d_state, int n_group, int a_per_state, int64_t n_seq, int64_t n_tokens_max);
+int    ggml_hip_ssm_scan_chunked_plan(int n_head, int head_dim, int d_state, int n_group, int a_per_state, int64_t n_seq, int64_t n_tokens_max,
+                                      ggml_hip_ssm_chunk_plan_t *out);
+int    ggml_hip_ssm_scan_chunked_ragged_dev(const float *d_x, int64_t ldx_tok, int64_t ldx_head, const float *d_dt, int64_t ld_dt, const float *d_dt_bias,
+                                            const float *d_A, int64_t a_ld, int a_per_state, const float *d_B, const float *d_C, int64_t ld_bc,
+                                            const float *d_D, int n_head, int head_dim, int d_state_n, int n_group,
+                                            int64_t n_seq, const int32_t *d_q_start, int64_t n_tokens_max, const int32_t *d_len, const int32_t *d_slot,
+                                            float *d_state, int64_t nb_slot, int64_t n_slots, float *d_dst, int64_t ldd_tok, int64_t ldd_head,
+                                            void *d_work, size_t work_bytes, void *stream);
 
 #if defined(__GNUC__)
 #pragma GCC visibility pop

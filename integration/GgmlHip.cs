@@ -221,6 +221,23 @@ internal static unsafe partial class GgmlHip
     [DllImport(Lib)] public static extern int ggml_hip_ssm_scan_ragged_dev(float* dX, long ldxTok, long ldxHead, float* dDt, long ldDt, float* dDtBias, float* dA,
         long aLd, int aPerState, float* dB, float* dC, long ldBc, float* dD, int nHead, int headDim, int dState, int nGroup, long nSeq, int* dQStart,
         long nTokensMax, int* dLen, int* dSlot, float* dStatePool, long nbSlot, long nSlots, float* dDst, long lddTok, long lddHead, void* stream);
+    // ... and the same scan with the chunked matrix form (f32 MFMA) for the sequences of more than seq_max_tokens tokens in the call; the shorter ones are
+    // bit for bit ggml_hip_ssm_scan_ragged_dev's.  dWork: ggml_hip_ssm_scan_chunked_work_size bytes (0: none needed).  A long sequence keeps its bits over
+    // calls only when split at multiples of `chunk`; shapes the form does not serve (aPerState 1, headDim no multiple of 16) run sequential, form 1
+    [StructLayout(LayoutKind.Sequential)]
+    public struct ggml_hip_ssm_chunk_plan_t
+    {
+        public int form, chunk, seq_max_tokens, launches, p_tile, p_tiles, kernel_state, kernel_out;
+        public long chunks_max, seqs_max;
+        public ulong work_bytes;
+    }
+    [DllImport(Lib)] public static extern nuint ggml_hip_ssm_scan_chunked_work_size(int nHead, int headDim, int dState, int nGroup, int aPerState, long nSeq, long nTokensMax);
+    [DllImport(Lib)] public static extern int ggml_hip_ssm_scan_chunked_plan(int nHead, int headDim, int dState, int nGroup, int aPerState, long nSeq, long nTokensMax,
+        ggml_hip_ssm_chunk_plan_t* plan);
+    [DllImport(Lib)] public static extern int ggml_hip_ssm_scan_chunked_ragged_dev(float* dX, long ldxTok, long ldxHead, float* dDt, long ldDt, float* dDtBias, float* dA,
+        long aLd, int aPerState, float* dB, float* dC, long ldBc, float* dD, int nHead, int headDim, int dState, int nGroup, long nSeq, int* dQStart,
+        long nTokensMax, int* dLen, int* dSlot, float* dStatePool, long nbSlot, long nSlots, float* dDst, long lddTok, long lddHead, void* dWork, nuint workBytes,
+        void* stream);
 
     // Seam 2: the quantize_fns_t slots (TypeDefinitions.cs:334-342), type-indexed
     [DllImport(Lib)] public static extern int ggml_hip_quantize_row(int type, float* x, void* y, int k);
