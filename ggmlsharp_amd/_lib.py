@@ -120,6 +120,12 @@ class ggml_hip_ssm_chunk_plan_t(C.Structure):
                 ("kernel_state", C.c_int32), ("kernel_out", C.c_int32), ("chunks_max", C.c_int64), ("seqs_max", C.c_int64), ("work_bytes", C.c_uint64)]
 
 
+class ggml_hip_ssm_conv_plan_t(C.Structure):
+    """include/ggml_hip_ext.h: the plan of one tiled causal-conv call (csrc/plan.cpp plan_ssm_conv_tiled)"""
+    _fields_ = [("form", C.c_int32), ("tile", C.c_int32), ("seq_max_tokens", C.c_int32), ("launches", C.c_int32), ("vec", C.c_int32), ("reserved", C.c_int32),
+                ("tiles_max", C.c_int64), ("seqs_max", C.c_int64), ("work_bytes", C.c_uint64)]
+
+
 class ggml_hip_rope_params_t(C.Structure):
     """include/ggml_hip_ext.h: the parameters of a rotary embedding (mode 0 NORMAL, 2 NEOX)"""
     _fields_ = [("n_dims", C.c_int32), ("mode", C.c_int32), ("n_ctx_orig", C.c_int32),
@@ -328,6 +334,12 @@ HIP_SYMBOLS = {
     "ggml_hip_ssm_scan_chunked_ragged_dev": (C.c_int, [_P, C.c_int64, C.c_int64, _P, C.c_int64, _P, _P, C.c_int64, C.c_int, _P, _P, C.c_int64, _P, C.c_int, C.c_int,
                                                        C.c_int, C.c_int, C.c_int64, _P, C.c_int64, _P, _P, _P, C.c_int64, C.c_int64, _P, C.c_int64, C.c_int64,
                                                        _P, C.c_size_t, _P]),
+    # ... and the conv with the token-parallel tiled form for the long sequences of a call: its work size and plan (host only), the entry (the conv's
+    # arguments, then d_work, work_bytes, stream)
+    "ggml_hip_ssm_conv_tiled_work_size": (C.c_size_t, [C.c_int64, C.c_int, C.c_int64, C.c_int64]),
+    "ggml_hip_ssm_conv_tiled_plan": (C.c_int, [C.c_int64, C.c_int, C.c_int64, C.c_int64, _P]),
+    "ggml_hip_ssm_conv_tiled_ragged_dev": (C.c_int, [_P, C.c_int64, _P, _P, C.c_int, C.c_int64, C.c_int, C.c_int64, _P, C.c_int64, _P, _P, _P, C.c_int64,
+                                                     C.c_int64, _P, C.c_int64, _P, C.c_size_t, _P]),
 }
 SYMBOLS = HIP_SYMBOLS
 

@@ -543,7 +543,13 @@ struct ssm_conv_plan;
 struct ssm_scan_plan;
 hipError_t launch_ssm_conv(const ssm_conv_plan &pl, const kv_ragged &rg, const int32_t *len, const int32_t *slot, int n_slots, const float *x, int64_t ldx,
                            const float *w, const float *bias, int act, int64_t n_ch, int d_conv, float *state, int64_t slot_elems, float *dst, int64_t ldd,
-                           hipStream_t st);
+                           int nq_max, hipStream_t st);                  // nq_max: the kernel serves sequences of 1 .. nq_max tokens in this call (INT_MAX: all)
+// ssm_conv_tile.hip: the same call with the sequences above pl.seq_max_tokens in the token-parallel tiled form (ggml_hip_ssm_conv_tiled_ragged_dev; plan.h
+// plan_ssm_conv_tiled has the launches and the work buffer).  work: the 256-byte aligned base, null where pl.form is sequential
+struct ssm_conv_tiled_plan;
+hipError_t launch_ssm_conv_tiled(const ssm_conv_tiled_plan &pl, const kv_ragged &rg, const int32_t *len, const int32_t *slot, int n_slots, const float *x,
+                                 int64_t ldx, const float *w, const float *bias, int act, int64_t n_ch, int d_conv, float *state, int64_t slot_elems, float *dst,
+                                 int64_t ldd, void *work, hipStream_t st);
 struct ssm_scan_args {
     const float *x; int64_t ldx_tok, ldx_head;                       // [tok][n_head][P]
     const float *dt; int64_t ld_dt; const float *dt_bias;            // [tok][n_head]; [n_head] or null

@@ -688,3 +688,29 @@ ssm_chunk_plan plan_ssm_chunk(int n_head, int P, int N, int n_group, int a_per_s
     p.work_bytes = p.state_off + up((size_t)p.chunks_max * (size_t)n_head * (size_t)P * (size_t)N * 4);
     return p;
 }
+
+// The tiled conv (plan.h has the statement): the sequential plan for the short sequences, the bounds of the tile list for the long ones.
+// tile and seq_max_tokens are measured constants: docs/PLAN_BOUNDS.md "SSM_CONV_TILE"
+ssm_conv_tiled_plan plan_ssm_conv_tiled(int64_t n_ch, int d_conv, int64_t n_seq, int64_t n_tokens_max) {
+    ssm_conv_tiled_plan p = {};
+    p.seq = plan_ssm_conv(n_ch, d_conv, n_seq);
+    if (!p.seq.ok || n_tokens_max < 0 || n_tokens_max > ATTN_PAGED_MAX_ROWS) return p;
+    p.ok = 1;
+    p.form = SSM_FORM_SEQUENTIAL;
+    p.tile = SSM_CONV_TILE;
+    p.seq_max_tokens = SSM_CONV_SEQ_MAX_TOKENS;
+    p.launches = 1;
+    p.vec = n_ch % 4 == 0 ? 4 : 1;
+    if (n_tokens_max <= p.seq_max_tokens) return p;
+    p.form = SSM_FORM_TILED;
+    p.launches = 4;
+    p.seqs_max = n_tokens_max / (p.seq_max_tokens + 1) < n_seq ? n_tokens_max / (p.seq_max_tokens + 1) : n_seq;
+    p.tiles_max = p.seqs_max + (n_tokens_max - p.seqs_max) / SSM_CONV_TILE;
+    p.halo_ld = (n_ch + 3) / 4 * 4;
+    const auto up = [](size_t v) { return (v + 255) / 256 * 256; };
+    p.hdr_off = 0;
+    p.list_off = 256;
+    p.halo_off = p.list_off + up(8 * (size_t)p.tiles_max);
+    p.work_bytes = p.halo_off + up((size_t)p.tiles_max * (size_t)(d_conv - 1) * (size_t)p.halo_ld * 4);
+    return p;
+}

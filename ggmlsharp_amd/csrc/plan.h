@@ -209,6 +209,36 @@ struct ssm_chunk_plan {
     ssm_scan_plan seq;
 };
 ssm_chunk_plan plan_ssm_chunk(int n_head, int P, int N, int n_group, int a_per_state, int64_t n_seq, int64_t n_tokens_max);
+// ---- the tiled conv (ssm_conv_tile.hip; ggml_hip_ssm_conv_tiled_ragged_dev): the form is picked PER SEQUENCE from its own count in the call ----
+// A sequence of 1 .. seq_max_tokens tokens runs plan_ssm_conv's sequential kernel; a longer one runs in tiles of `tile` = T tokens counted from its first
+// row of the call, one thread per (tile, `vec` adjacent channels).  The statement is a fixed fma chain per token, so the tiled form is bit for bit the
+// sequential one and a sequence may be split over calls and forms at any point.  tile and seq_max_tokens follow the SHAPE alone (here: nothing at all;
+// DESIGN.md section 27 has the measurement).  form = SEQUENTIAL (one launch, no work buffer) where n_tokens_max <= seq_max_tokens; else form = TILED,
+// FOUR launches:
+//   the sequential kernel          plan_ssm_conv's grid; sequences above seq_max_tokens leave at once
+//   index  (1 workgroup of 1024)   q_start -> the tile list (b, tile of b) and the count of long sequences, clamped at tiles_max / seqs_max
+//   edges  (tiles_max, ceil(n_ch / (256 vec)))   per (tile, vec channels): the d_conv - 1 rows in front of the tile into the work buffer -- from x, or for a
+//                                  sequence's first tile from the slot (zeros where fresh), and then THE SAME THREAD moves the sequence's last
+//                                  d_conv - 1 rows of x into the slot.  The only kernel of the form that touches slots; it only reads x
+//   tile   (tiles_max, ceil(n_ch / (256 vec)))   per (tile, vec channels; vec = 4 where n_ch, the strides and the pointers allow 16-byte moves, else 1): the window starts from the work buffer, then streams the tile's rows x -> dst
+// (a grid's y is capped at 32768 workgroups; the kernels step over the channel blocks by gridDim.y.)
+// INVARIANTS: tile >= d_conv - 1 (the rows in front of a later tile lie inside the sequence) and seq_max_tokens >= d_conv - 1 (a long sequence's new slot
+// is all x), both for the largest d_conv, 4.  seqs_max = min(n_seq, n_tokens_max / (seq_max_tokens + 1)) long sequences fit in n_tokens_max rows; k such
+// sequences of n_i rows have sum (1 + (n_i - 1) / tile) <= k + (n_tokens_max - k) / tile tiles, which grows with k: tiles_max is that at k = seqs_max.
+// So tiles_max and seqs_max bound every batch of non-overlapping sequences inside n_seq and n_tokens_max; the index kernel clamps the others.
+// THE WORK BUFFER from its 256-byte aligned base: int32 x 4 (tiles, long sequences, 0, 0) at hdr_off = 0; int32 x 2 [tiles_max] at list_off;
+// f32 [tiles_max][d_conv - 1][halo_ld] at halo_off, halo_ld = n_ch rounded up to 4.  Nothing in it is read before the call writes it.
+constexpr int SSM_CONV_TILE = 16;
+constexpr int SSM_CONV_SEQ_MAX_TOKENS = 135;
+static_assert(SSM_CONV_TILE >= 3 && SSM_CONV_SEQ_MAX_TOKENS >= 3, "a tile and a short sequence hold at least d_conv - 1 rows");
+enum { SSM_FORM_TILED = 2 };
+struct ssm_conv_tiled_plan {
+    int ok, form, tile, seq_max_tokens, launches, vec;
+    int64_t tiles_max, seqs_max, halo_ld;
+    size_t hdr_off, list_off, halo_off, work_bytes;
+    ssm_conv_plan seq;
+};
+ssm_conv_tiled_plan plan_ssm_conv_tiled(int64_t n_ch, int d_conv, int64_t n_seq, int64_t n_tokens_max);
 // the K1 image INIT writes for a plan: its image where that is one of K1's (0 .. 3; else 0), + ACT_IMAGE_MIN_PIECES under MM_FLAG_MIN_PIECES
 int plan_act_image(const mm_plan &p);
 // the K1 image for (type, K, N) with no weight at hand: plan_act_image of the COMPUTE-only plan at M = 1 (no M: the exception cannot apply)

@@ -1,7 +1,7 @@
-// ssm.cpp -- the C-ABI of include/ggml_hip_ext.h, SSM: the causal conv (ggml_hip_ssm_conv_ragged_dev) and the selective scan
-// (ggml_hip_ssm_scan_ragged_dev; ggml_hip_ssm_scan_chunked_ragged_dev with the chunked matrix form for long sequences) of a Mamba / Mamba-2 block over a
-// ragged batch and a pool of state slots, their slot sizes and the scans' plans (host only).  The kernels are ssm.hip's and ssm_chunk.hip's, every grid
-// is plan.cpp's.  No set, no handle: stream-ordered launches on the current device, no synchronize, no
+// ssm.cpp -- the C-ABI of include/ggml_hip_ext.h, SSM: the causal conv (ggml_hip_ssm_conv_ragged_dev; ggml_hip_ssm_conv_tiled_ragged_dev with the
+// token-parallel tiled form for long sequences) and the selective scan (ggml_hip_ssm_scan_ragged_dev; ggml_hip_ssm_scan_chunked_ragged_dev with the
+// chunked matrix form for long sequences) of a Mamba / Mamba-2 block over a ragged batch and a pool of state slots, their slot sizes and their plans
+// (host only).  The kernels are ssm.hip's, ssm_chunk.hip's and ssm_conv_tile.hip's, every grid is plan.cpp's.  No set, no handle: stream-ordered launches on the current device, no synchronize, no
 // allocation; capturable.  Every refusal is decided here, before a device is touched.
 #include "ctx.h"
 
@@ -9,7 +9,7 @@ using namespace ghip;
 
 namespace {
 
-constexpr size_t SSM_WORK_ALIGN = 256;                             // the chunked scan rounds its work buffer's base up to it
+constexpr size_t SSM_WORK_ALIGN = 256;                             // the chunked scan and the tiled conv round their work buffer's base up to it
 
 // the batch and the state cache both entries share: n_seq, d_q_start, n_tokens_max (check_kv_ragged), d_len, d_slot, the pool; 0 or an error code
 int check_ssm_batch(int64_t n_seq, const int32_t *d_q_start, int64_t n_tokens_max, const int32_t *d_len, const int32_t *d_slot, const float *d_state,
@@ -68,6 +68,25 @@ int check_ssm_scan(const float *d_x, int64_t ldx_tok, int64_t ldx_head, const fl
     return GGML_HIP_OK;
 }
 
+// every check both conv entries share, in the order the header states them; fills the sequential plan and the batch
+int check_ssm_conv(const float *d_x, int64_t ldx, const float *d_w, const float *d_bias, int act, int64_t n_ch, int d_conv, int64_t n_seq,
+                   const int32_t *d_q_start, int64_t n_tokens_max, const int32_t *d_len, const int32_t *d_slot, const float *d_state, int64_t nb_slot,
+                   int64_t n_slots, const float *d_dst, int64_t ldd, ssm_conv_plan *plan, kv_ragged *rg) {
+    if (n_ch < 1 || n_ch > SSM_MAX_CHANNELS) return fail(GGML_HIP_ERR_SHAPE, "n_ch %lld (1 .. 2^24)", (long long)n_ch);
+    if (d_conv < 2 || d_conv > 4) return fail(GGML_HIP_ERR_SHAPE, "d_conv %d (2 .. 4)", d_conv);
+    if (act != 0 && act != 1) return fail(GGML_HIP_ERR_ARG, "act %d: 0 (none) or 1 (silu)", act);
+    if (n_seq < 1 || n_seq > ATTN_PAGED_MAX_SEQ) return fail(GGML_HIP_ERR_SHAPE, "n_seq %lld (1 .. %lld)", (long long)n_seq, (long long)ATTN_PAGED_MAX_SEQ);
+    *plan = plan_ssm_conv(n_ch, d_conv, n_seq);
+    const int rc = check_ssm_batch(n_seq, d_q_start, n_tokens_max, d_len, d_slot, d_state, nb_slot, n_slots, plan->state_bytes, rg);
+    if (rc) return rc;
+    if (ldx < n_ch || ldd < n_ch || ldx > ((int64_t)1 << 32) || ldd > ((int64_t)1 << 32))
+        return fail(GGML_HIP_ERR_SHAPE, "ldx %lld and ldd %lld must be at least n_ch %lld", (long long)ldx, (long long)ldd, (long long)n_ch);
+    if (!d_x || !d_w || !d_dst) return fail(GGML_HIP_ERR_ARG, "d_x, d_w and d_dst must not be null");
+    if ((((uintptr_t)d_x | (uintptr_t)d_w | (uintptr_t)d_bias | (uintptr_t)d_dst) & 3) != 0)
+        return fail(GGML_HIP_ERR_SHAPE, "d_x, d_w, d_bias and d_dst must be 4-byte aligned");
+    return GGML_HIP_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -88,21 +107,49 @@ int ggml_hip_ssm_scan_plan(int n_head, int head_dim, int d_state, int n_group, i
 int ggml_hip_ssm_conv_ragged_dev(const float *d_x, int64_t ldx, const float *d_w, const float *d_bias, int act, int64_t n_ch, int d_conv, int64_t n_seq,
                                  const int32_t *d_q_start, int64_t n_tokens_max, const int32_t *d_len, const int32_t *d_slot, float *d_state, int64_t nb_slot,
                                  int64_t n_slots, float *d_dst, int64_t ldd, void *stream) {
-    if (n_ch < 1 || n_ch > SSM_MAX_CHANNELS) return fail(GGML_HIP_ERR_SHAPE, "n_ch %lld (1 .. 2^24)", (long long)n_ch);
-    if (d_conv < 2 || d_conv > 4) return fail(GGML_HIP_ERR_SHAPE, "d_conv %d (2 .. 4)", d_conv);
-    if (act != 0 && act != 1) return fail(GGML_HIP_ERR_ARG, "act %d: 0 (none) or 1 (silu)", act);
-    if (n_seq < 1 || n_seq > ATTN_PAGED_MAX_SEQ) return fail(GGML_HIP_ERR_SHAPE, "n_seq %lld (1 .. %lld)", (long long)n_seq, (long long)ATTN_PAGED_MAX_SEQ);
-    const ssm_conv_plan pl = plan_ssm_conv(n_ch, d_conv, n_seq);
-    kv_ragged rg;
-    const int rc = check_ssm_batch(n_seq, d_q_start, n_tokens_max, d_len, d_slot, d_state, nb_slot, n_slots, pl.state_bytes, &rg);
+    ssm_conv_plan pl; kv_ragged rg;
+    const int rc = check_ssm_conv(d_x, ldx, d_w, d_bias, act, n_ch, d_conv, n_seq, d_q_start, n_tokens_max, d_len, d_slot, d_state, nb_slot, n_slots, d_dst, ldd,
+                                  &pl, &rg);
     if (rc) return rc;
-    if (ldx < n_ch || ldd < n_ch || ldx > ((int64_t)1 << 32) || ldd > ((int64_t)1 << 32))
-        return fail(GGML_HIP_ERR_SHAPE, "ldx %lld and ldd %lld must be at least n_ch %lld", (long long)ldx, (long long)ldd, (long long)n_ch);
-    if (!d_x || !d_w || !d_dst) return fail(GGML_HIP_ERR_ARG, "d_x, d_w and d_dst must not be null");
-    if ((((uintptr_t)d_x | (uintptr_t)d_w | (uintptr_t)d_bias | (uintptr_t)d_dst) & 3) != 0)
-        return fail(GGML_HIP_ERR_SHAPE, "d_x, d_w, d_bias and d_dst must be 4-byte aligned");
     if (n_tokens_max == 0) return GGML_HIP_OK;
-    HIP_TRY(launch_ssm_conv(pl, rg, d_len, d_slot, (int)n_slots, d_x, ldx, d_w, d_bias, act, n_ch, d_conv, d_state, nb_slot / 4, d_dst, ldd, (hipStream_t)stream));
+    HIP_TRY(launch_ssm_conv(pl, rg, d_len, d_slot, (int)n_slots, d_x, ldx, d_w, d_bias, act, n_ch, d_conv, d_state, nb_slot / 4, d_dst, ldd, 0x7FFFFFFF,
+                            (hipStream_t)stream));
+    return GGML_HIP_OK;
+}
+
+size_t ggml_hip_ssm_conv_tiled_work_size(int64_t n_ch, int d_conv, int64_t n_seq, int64_t n_tokens_max) {
+    const ssm_conv_tiled_plan p = plan_ssm_conv_tiled(n_ch, d_conv, n_seq, n_tokens_max);
+    if (!p.ok || p.work_bytes == 0) return 0;
+    return p.work_bytes + SSM_WORK_ALIGN;                                // (the base is rounded up to a 256-byte boundary)
+}
+
+int ggml_hip_ssm_conv_tiled_plan(int64_t n_ch, int d_conv, int64_t n_seq, int64_t n_tokens_max, ggml_hip_ssm_conv_plan_t *out) {
+    if (!out) return fail(GGML_HIP_ERR_ARG, "null argument");
+    const ssm_conv_tiled_plan p = plan_ssm_conv_tiled(n_ch, d_conv, n_seq, n_tokens_max);
+    if (!p.ok)
+        return fail(GGML_HIP_ERR_SHAPE, "ssm tiled conv: n_ch %lld, d_conv %d, n_seq %lld, n_tokens_max %lld", (long long)n_ch, d_conv, (long long)n_seq,
+                    (long long)n_tokens_max);
+    out->form = p.form; out->tile = p.tile; out->seq_max_tokens = p.seq_max_tokens; out->launches = p.launches; out->vec = p.vec; out->reserved = 0;
+    out->tiles_max = p.tiles_max; out->seqs_max = p.seqs_max;
+    out->work_bytes = ggml_hip_ssm_conv_tiled_work_size(n_ch, d_conv, n_seq, n_tokens_max);
+    return GGML_HIP_OK;
+}
+
+int ggml_hip_ssm_conv_tiled_ragged_dev(const float *d_x, int64_t ldx, const float *d_w, const float *d_bias, int act, int64_t n_ch, int d_conv, int64_t n_seq,
+                                       const int32_t *d_q_start, int64_t n_tokens_max, const int32_t *d_len, const int32_t *d_slot, float *d_state,
+                                       int64_t nb_slot, int64_t n_slots, float *d_dst, int64_t ldd, void *d_work, size_t work_bytes, void *stream) {
+    ssm_conv_plan seq; kv_ragged rg;
+    const int rc = check_ssm_conv(d_x, ldx, d_w, d_bias, act, n_ch, d_conv, n_seq, d_q_start, n_tokens_max, d_len, d_slot, d_state, nb_slot, n_slots, d_dst, ldd,
+                                  &seq, &rg);
+    if (rc) return rc;
+    const ssm_conv_tiled_plan pl = plan_ssm_conv_tiled(n_ch, d_conv, n_seq, n_tokens_max);
+    if (!pl.ok) return fail(GGML_HIP_ERR_SHAPE, "the shape is not served");
+    const size_t need = ggml_hip_ssm_conv_tiled_work_size(n_ch, d_conv, n_seq, n_tokens_max);
+    if (need && (!d_work || work_bytes < need)) return fail(GGML_HIP_ERR_ARG, "work buffer too small: need %zu (ggml_hip_ssm_conv_tiled_work_size)", need);
+    if (n_tokens_max == 0) return GGML_HIP_OK;
+    void *work = need ? (void *)(((uintptr_t)d_work + SSM_WORK_ALIGN - 1) / SSM_WORK_ALIGN * SSM_WORK_ALIGN) : nullptr;
+    HIP_TRY(launch_ssm_conv_tiled(pl, rg, d_len, d_slot, (int)n_slots, d_x, ldx, d_w, d_bias, act, n_ch, d_conv, d_state, nb_slot / 4, d_dst, ldd, work,
+                                  (hipStream_t)stream));
     return GGML_HIP_OK;
 }
 

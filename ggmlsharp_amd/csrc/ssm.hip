@@ -8,7 +8,8 @@
 //
 //   ssm_conv_kernel<KC>   one thread per (sequence, channel); the window of KC - 1 rows rides in registers over the sequence's tokens.  The loads of up
 //                         to CONV_UNROLL tokens are issued together (they depend on nothing the loop computes); in place (dst == x) is safe because a
-//                         thread reads x[t][c] before it writes dst[t][c] and no other thread touches channel c of this sequence.
+//                         thread reads x[t][c] before it writes dst[t][c] and no other thread touches channel c of this sequence.  Sequences of more
+//                         than nq_max tokens belong to the tiled form (ssm_conv_tile.hip) and leave by whole workgroups; INT_MAX: none.
 //   ssm_scan_kernel<LP, APS, FULL>  one lane per (sequence, head, p, slice of 16 states); a state row of N = 16 L elements rides in the registers of L lanes
 //                         inside an aligned group of LP = the next power of two (lanes L .. LP - 1 of a group idle with a partial of +0.0f), and y meets
 //                         in the xor butterfly the header states: DPP moves inside a row of 16 lanes, no LDS.
@@ -27,11 +28,11 @@ constexpr int CONV_UNROLL = 8;
 template <int KC>
 __global__ __launch_bounds__(256) void ssm_conv_kernel(const kv_ragged rg, const int32_t *__restrict__ len, const int32_t *__restrict__ slot, int n_slots,
                                                        const float *x, int64_t ldx, const float *__restrict__ w, const float *__restrict__ bias, int act,
-                                                       int64_t n_ch, float *state, int64_t slot_elems, float *dst, int64_t ldd) {
+                                                       int64_t n_ch, float *state, int64_t slot_elems, float *dst, int64_t ldd, int nq_max) {
     const int b = blockIdx.y;
     const int64_t c = (int64_t)blockIdx.x * 256 + threadIdx.x;
     int64_t qs; int nq;
-    if (!ssm_sequence(rg, b, &qs, &nq) || nq == 0 || c >= n_ch) return;
+    if (!ssm_sequence(rg, b, &qs, &nq) || nq == 0 || nq > nq_max || c >= n_ch) return;   // (nq_max: uniform over the workgroup, as the scan's)
     const int sl = slot[b];
     if (sl < 0 || sl >= n_slots) {
         for (int t = 0; t < nq; ++t) dst[(qs + t) * ldd + c] = 0.0f;
@@ -210,12 +211,12 @@ void scan_launch(bool aps, dim3 grid, hipStream_t st, const kv_ragged &rg, const
 
 hipError_t launch_ssm_conv(const ssm_conv_plan &pl, const kv_ragged &rg, const int32_t *len, const int32_t *slot, int n_slots, const float *x, int64_t ldx,
                            const float *w, const float *bias, int act, int64_t n_ch, int d_conv, float *state, int64_t slot_elems, float *dst, int64_t ldd,
-                           hipStream_t st) {
+                           int nq_max, hipStream_t st) {
     const dim3 grid((unsigned)pl.wgs_x, (unsigned)rg.n_seq);
     switch (d_conv) {
-    case 2: ssm_conv_kernel<2><<<grid, 256, 0, st>>>(rg, len, slot, n_slots, x, ldx, w, bias, act, n_ch, state, slot_elems, dst, ldd); break;
-    case 3: ssm_conv_kernel<3><<<grid, 256, 0, st>>>(rg, len, slot, n_slots, x, ldx, w, bias, act, n_ch, state, slot_elems, dst, ldd); break;
-    case 4: ssm_conv_kernel<4><<<grid, 256, 0, st>>>(rg, len, slot, n_slots, x, ldx, w, bias, act, n_ch, state, slot_elems, dst, ldd); break;
+    case 2: ssm_conv_kernel<2><<<grid, 256, 0, st>>>(rg, len, slot, n_slots, x, ldx, w, bias, act, n_ch, state, slot_elems, dst, ldd, nq_max); break;
+    case 3: ssm_conv_kernel<3><<<grid, 256, 0, st>>>(rg, len, slot, n_slots, x, ldx, w, bias, act, n_ch, state, slot_elems, dst, ldd, nq_max); break;
+    case 4: ssm_conv_kernel<4><<<grid, 256, 0, st>>>(rg, len, slot, n_slots, x, ldx, w, bias, act, n_ch, state, slot_elems, dst, ldd, nq_max); break;
     default: return hipErrorInvalidValue;
     }
     return hipGetLastError();

@@ -715,6 +715,45 @@ def ssm_conv_ragged(x, w, q_start, d_len, slot, state, bias=None, act=False, n_t
     return out
 
 
+def ssm_conv_tiled_plan(n_ch, d_conv, n_seq=1, n_tokens_max=0):
+    """the ggml_hip_ssm_conv_plan_t of one tiled-conv call: the form, the tile T, seq_max_tokens, the bounds of the tile list, the work bytes; no device
+    needed"""
+    out = _lib.ggml_hip_ssm_conv_plan_t()
+    check(lib().ggml_hip_ssm_conv_tiled_plan(n_ch, d_conv, n_seq, n_tokens_max, C.byref(out)), "ggml_hip_ssm_conv_tiled_plan")
+    return out
+
+
+def ssm_conv_tiled_work_size(n_ch, d_conv, n_seq=1, n_tokens_max=0):
+    return int(lib().ggml_hip_ssm_conv_tiled_work_size(n_ch, d_conv, n_seq, n_tokens_max))
+
+
+def ssm_conv_tiled_ragged(x, w, q_start, d_len, slot, state, bias=None, act=False, n_tokens_max=None, out=None, work=None):
+    """ssm_conv_ragged with the token-parallel tiled form for the sequences of more than seq_max_tokens tokens in this call (ssm_conv_tiled_plan): the
+    same bits in both forms, wherever a sequence is split over calls.  work: a uint8 tensor of at least ssm_conv_tiled_work_size(..) bytes (a captured
+    step passes its own); None allocates one.  out may be x."""
+    assert x.is_cuda and x.dtype == torch.float32 and x.dim() == 2 and x.stride(1) == 1
+    assert w.is_cuda and w.dtype == torch.float32 and w.dim() == 2 and w.is_contiguous() and w.shape[0] == x.shape[1]
+    assert bias is None or (bias.is_cuda and bias.dtype == torch.float32 and bias.is_contiguous() and bias.numel() == x.shape[1])
+    n_seq, nb_slot, n_slots = _ssm_batch(q_start, d_len, slot, state)
+    n_ch, d_conv = w.shape
+    if n_tokens_max is None:
+        n_tokens_max = x.shape[0]
+    assert n_tokens_max <= x.shape[0]
+    if out is None:
+        out = torch.zeros((x.shape[0], n_ch), dtype=torch.float32, device=x.device)
+    assert out.is_cuda and out.dtype == torch.float32 and out.dim() == 2 and out.stride(1) == 1 and out.shape[0] >= n_tokens_max and out.shape[1] >= n_ch
+    need = ssm_conv_tiled_work_size(n_ch, d_conv, n_seq, n_tokens_max)
+    if work is None and need:
+        work = torch.empty(need, dtype=torch.uint8, device=x.device)
+    assert work is None or (work.is_cuda and work.dtype == torch.uint8 and work.is_contiguous() and work.numel() >= need)
+    check(lib().ggml_hip_ssm_conv_tiled_ragged_dev(C.c_void_p(x.data_ptr()), x.stride(0), C.c_void_p(w.data_ptr()), _opt(bias), int(bool(act)), n_ch, d_conv,
+                                                   n_seq, C.c_void_p(q_start.data_ptr()), n_tokens_max, C.c_void_p(d_len.data_ptr()),
+                                                   C.c_void_p(slot.data_ptr()), C.c_void_p(state.data_ptr()), nb_slot, n_slots, C.c_void_p(out.data_ptr()),
+                                                   out.stride(0), _opt(work), 0 if work is None else work.numel(), _stream()),
+          "ggml_hip_ssm_conv_tiled_ragged_dev")
+    return out
+
+
 def ssm_scan_ragged(x, dt, A, B, C_, q_start, d_len, slot, state, dt_bias=None, D=None, n_tokens_max=None, out=None):
     """upstream's ggml_ssm_scan over a ragged batch: x f32 [n_tokens_max, n_head, P] (last stride 1), dt f32 [n_tokens_max, n_head], A f32 [n_head]
     (one value per head, Mamba-2) or [n_head, N] (per state, Mamba-1), B / C_ f32 [n_tokens_max, G, N] views with ONE token stride and contiguous groups,

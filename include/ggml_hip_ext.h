@@ -1030,7 +1030,8 @@ int ggml_hip_sample_topk_dev(const float *d_logits, int64_t ld, int64_t n_rows, 
  *   and the new slot is the last d_conv - 1 rows of win (for n_q[b] < d_conv - 1 that keeps old rows).  THE CONTRACT: act = 0 is bit for bit the
  *   statement; act = 1 is within 3 * 2^-24 relative of the silu of those bits (expf within 1 ulp).  The slot is bit for bit.  Nothing depends on
  *   the other sequences, the slot number, n_tokens_max, the strides or on how a sequence's tokens are split over calls.
- *   One launch: one thread per (sequence, channel) walks the sequence's tokens.
+ *   One launch: one thread per (sequence, channel) walks the sequence's tokens.  That is right for decode; a long prefill is served by
+ *   ggml_hip_ssm_conv_tiled_ragged_dev below, which gives the same bits.
  *
  * ggml_hip_ssm_scan_ragged_dev: upstream's ggml_ssm_scan in both of its forms.  n_head heads of head_dim P (1 .. 256), d_state N (a multiple of 16,
  *   at most 256), n_group G dividing n_head, 1 <= n_head <= 2^20: else GGML_HIP_ERR_SHAPE.  A slot is [n_head][P][N] f32.
@@ -1058,7 +1059,8 @@ int ggml_hip_sample_topk_dev(const float *d_logits, int64_t ld, int64_t n_rows, 
  *   rides in the registers of an aligned group of LP lanes (lanes_per_row; L of them work) and the butterfly is lane moves inside the group.  One
  *   launch of ceil(n_head * P * LP / 256) * n_seq workgroups, sized by the shape and n_seq alone.
  *   LIMITS.  That form is exactly right for decode.  A long prefill walks its tokens one after the other with n_head * P * LP lanes: the chunked
- *   matrix form (SSD) for long prefills is ggml_hip_ssm_scan_chunked_ragged_dev below; a token-parallel conv is a follow-up.  N that is no
+ *   matrix form (SSD) for long prefills is ggml_hip_ssm_scan_chunked_ragged_dev below, and the conv's token-parallel form for them is
+ *   ggml_hip_ssm_conv_tiled_ragged_dev behind it.  N that is no
  *   power-of-two multiple of 16 idles LP - L lanes of a group.  States are f32 only.
  * ggml_hip_ssm_state_bytes / ggml_hip_ssm_conv_state_bytes (host only): the bytes of one slot, n_head * P * N * 4 and (d_conv - 1) * n_ch * 4; 0 for a
  *   shape the entries refuse.
@@ -1094,7 +1096,38 @@ int ggml_hip_sample_topk_dev(const float *d_logits, int64_t ld, int64_t n_rows, 
  *   multiple of Q gives the bits of one call when both parts are longer than seq_max_tokens.  Contract (ii) of ggml_hip_ssm_scan_ragged_dev does NOT
  *   hold at other split points (the chunk boundaries move): a caller who needs it keeps using that entry.
  * ggml_hip_ssm_scan_chunked_plan / ggml_hip_ssm_scan_chunked_work_size (host only): what a call with these bounds does, and the bytes of its work
- *   buffer (0 for a refused shape and where no sequence can be chunked).  chunk and seq_max_tokens follow the shape alone, never the batch. */
+ *   buffer (0 for a refused shape and where no sequence can be chunked).  chunk and seq_max_tokens follow the shape alone, never the batch.
+ *
+ * ggml_hip_ssm_conv_tiled_ragged_dev: the same conv with a SECOND, token-parallel FORM for long sequences, picked PER SEQUENCE from its own count in this
+ *   call as the chunked scan does, so one captured call serves a whole ragged step.  Every argument of ggml_hip_ssm_conv_ragged_dev with the same
+ *   meaning and the same refusals, and d_work / work_bytes: at least ggml_hip_ssm_conv_tiled_work_size(..) bytes, any alignment, else GGML_HIP_ERR_ARG
+ *   (a size of 0 needs no buffer; NULL is accepted then).  Nothing in the buffer is read before the call has written it.  Stream-ordered, capturable,
+ *   no synchronize, no allocation, no atomics, no hand-off between workgroups of one launch; every grid is sized by the shape, n_seq and n_tokens_max
+ *   alone, so a captured graph follows d_q_start, d_len and d_slot between replays -- a sequence may move from one form to the other.  n_tokens_max = 0
+ *   returns 0 after every other check.
+ *   SHORT: a sequence of 1 .. seq_max_tokens tokens runs the sequential kernel; where n_tokens_max <= seq_max_tokens the plan says form = 1 and the call
+ *   is exactly ggml_hip_ssm_conv_ragged_dev's one launch.
+ *   LONG: a longer sequence runs in TILES of `tile` tokens counted from the sequence's first row OF THIS CALL (the last may be partial), one thread per
+ *   (tile, 4 adjacent channels) with 16-byte loads and stores where n_ch, ldx and ldd are multiples of 4 and d_x, d_dst, d_w and d_bias are 16-byte
+ *   aligned, else one thread per (tile, channel) with the same bits.  The d_conv - 1 rows in front of every tile -- the slot's for a sequence's first
+ *   tile, zeros where it is fresh -- are staged in the work buffer before any row is written, and the thread that stages a slot element is the one that
+ *   then writes it from the sequence's last d_conv - 1 input rows.
+ *   THE CONTRACT is ggml_hip_ssm_conv_ragged_dev's, unchanged, in both forms: the statement is a fixed fma chain per token, so rows (act = 0) and the slot
+ *   are bit for bit the statement and act = 1 is the same expression on those bits.  (i) a sequence alone in a call gives the same bits; (ii) splitting a
+ *   sequence's tokens over calls at ANY point gives the same bits, also where a part moves from one form to the other; (iii) nothing depends on the
+ *   other sequences, the slot number, n_tokens_max, the strides or the work buffer's address and old contents.  Absent and idle sequences, slot ids
+ *   outside the pool (+0.0f rows, no state written, no address formed) and fresh sequences over NaN slots behave as above.  d_dst == d_x (with
+ *   ldd == ldx) is allowed and gives the bits of the out-of-place call.  Present sequences that overlap are still the caller's error; they write nothing
+ *   outside dst, the slots and the work buffer (the tile list is clamped at tiles_max).
+ * ggml_hip_ssm_conv_tiled_plan / ggml_hip_ssm_conv_tiled_work_size (host only): what a call with these bounds does, and the bytes of its work buffer
+ *   (0 for a refused shape and where no sequence can be long).  tile and seq_max_tokens follow the shape alone, never the batch. */
+typedef struct ggml_hip_ssm_conv_plan_t {
+    int32_t form, tile;                      /* 1: every sequence sequential; 2: tiled above seq_max_tokens.  T, in tokens */
+    int32_t seq_max_tokens, launches;        /* a sequence with at most this many tokens in the call runs sequential; launches of one call (1 or 4) */
+    int32_t vec, reserved;                   /* channels per thread of the tile kernel for aligned operands: 4 where n_ch is a multiple of 4, else 1; 0 */
+    int64_t tiles_max, seqs_max;             /* the tile list's and the long sequences' bounds over every batch inside n_seq and n_tokens_max.  0 for form 1 */
+    uint64_t work_bytes;                     /* ggml_hip_ssm_conv_tiled_work_size */
+} ggml_hip_ssm_conv_plan_t;
 typedef struct ggml_hip_ssm_chunk_plan_t {
     int32_t form, chunk;                     /* 1: every sequence sequential; 2: chunked above seq_max_tokens.  Q, in tokens */
     int32_t seq_max_tokens, launches;        /* a sequence with at most this many tokens in the call runs sequential; launches of one call (1 or 5) */
@@ -1128,6 +1161,12 @@ int    ggml_hip_ssm_scan_chunked_ragged_dev(const float *d_x, int64_t ldx_tok, i
                                             int64_t n_seq, const int32_t *d_q_start, int64_t n_tokens_max, const int32_t *d_len, const int32_t *d_slot,
                                             float *d_state, int64_t nb_slot, int64_t n_slots, float *d_dst, int64_t ldd_tok, int64_t ldd_head,
                                             void *d_work, size_t work_bytes, void *stream);
+size_t ggml_hip_ssm_conv_tiled_work_size(int64_t n_ch, int d_conv, int64_t n_seq, int64_t n_tokens_max);
+int    ggml_hip_ssm_conv_tiled_plan(int64_t n_ch, int d_conv, int64_t n_seq, int64_t n_tokens_max, ggml_hip_ssm_conv_plan_t *out);
+int    ggml_hip_ssm_conv_tiled_ragged_dev(const float *d_x, int64_t ldx, const float *d_w, const float *d_bias, int act, int64_t n_ch, int d_conv,
+                                          int64_t n_seq, const int32_t *d_q_start, int64_t n_tokens_max, const int32_t *d_len, const int32_t *d_slot,
+                                          float *d_state, int64_t nb_slot, int64_t n_slots, float *d_dst, int64_t ldd,
+                                          void *d_work, size_t work_bytes, void *stream);
 
 #if defined(__GNUC__)
 #pragma GCC visibility pop

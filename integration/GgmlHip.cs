@@ -238,6 +238,20 @@ internal static unsafe partial class GgmlHip
         long aLd, int aPerState, float* dB, float* dC, long ldBc, float* dD, int nHead, int headDim, int dState, int nGroup, long nSeq, int* dQStart,
         long nTokensMax, int* dLen, int* dSlot, float* dStatePool, long nbSlot, long nSlots, float* dDst, long lddTok, long lddHead, void* dWork, nuint workBytes,
         void* stream);
+    // ... and the same conv with the token-parallel tiled form for the sequences of more than seq_max_tokens tokens in the call: the same bits in both
+    // forms, wherever a sequence is split over calls; dDst may be dX.  dWork: ggml_hip_ssm_conv_tiled_work_size bytes (0: none needed)
+    [StructLayout(LayoutKind.Sequential)]
+    public struct ggml_hip_ssm_conv_plan_t
+    {
+        public int form, tile, seq_max_tokens, launches, vec, reserved;
+        public long tiles_max, seqs_max;
+        public ulong work_bytes;
+    }
+    [DllImport(Lib)] public static extern nuint ggml_hip_ssm_conv_tiled_work_size(long nCh, int dConv, long nSeq, long nTokensMax);
+    [DllImport(Lib)] public static extern int ggml_hip_ssm_conv_tiled_plan(long nCh, int dConv, long nSeq, long nTokensMax, ggml_hip_ssm_conv_plan_t* plan);
+    [DllImport(Lib)] public static extern int ggml_hip_ssm_conv_tiled_ragged_dev(float* dX, long ldx, float* dW, float* dBias, int act, long nCh, int dConv, long nSeq,
+        int* dQStart, long nTokensMax, int* dLen, int* dSlot, float* dState, long nbSlot, long nSlots, float* dDst, long ldd, void* dWork, nuint workBytes,
+        void* stream);
 
     // Seam 2: the quantize_fns_t slots (TypeDefinitions.cs:334-342), type-indexed
     [DllImport(Lib)] public static extern int ggml_hip_quantize_row(int type, float* x, void* y, int k);
