@@ -108,6 +108,15 @@ class ggml_hip_attn_ragged_plan_t(C.Structure):
                 ("decode_workgroups", C.c_int64), ("merge_workgroups", C.c_int64), ("prompt_workgroups", C.c_int64), ("index_bytes", C.c_int64)]
 
 
+class ggml_hip_attn_mla_plan_t(C.Structure):
+    """include/ggml_hip_ext.h: the plan of one MLA attention call (csrc/plan.cpp plan_attn_mla)"""
+    _fields_ = [("form", C.c_int32), ("chunk", C.c_int32), ("span", C.c_int32), ("q_tile", C.c_int32), ("step", C.c_int32), ("launches", C.c_int32),
+                ("n_spans", C.c_int64), ("workgroups", C.c_int64), ("merge_workgroups", C.c_int64), ("work_bytes", C.c_uint64)]
+
+
+assert C.sizeof(ggml_hip_attn_mla_plan_t) == 56
+
+
 class ggml_hip_ssm_plan_t(C.Structure):
     """include/ggml_hip_ext.h: the plan of one selective-scan call (csrc/plan.cpp plan_ssm_scan)"""
     _fields_ = [("form", C.c_int32), ("launches", C.c_int32), ("slices", C.c_int32), ("lanes_per_row", C.c_int32),
@@ -340,6 +349,18 @@ HIP_SYMBOLS = {
     "ggml_hip_ssm_conv_tiled_plan": (C.c_int, [C.c_int64, C.c_int, C.c_int64, C.c_int64, _P]),
     "ggml_hip_ssm_conv_tiled_ragged_dev": (C.c_int, [_P, C.c_int64, _P, _P, C.c_int, C.c_int64, C.c_int, C.c_int64, _P, C.c_int64, _P, _P, _P, C.c_int64,
                                                      C.c_int64, _P, C.c_int64, _P, C.c_size_t, _P]),
+    # MLA: latent attention over a latent KV cache (one row of 576 elements per position, shared by every head): plans and work sizes (host only), the
+    # contiguous and the paged entry, the paged store of latent rows
+    "ggml_hip_attn_mla_plan": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int64, C.c_int64, _P]),
+    "ggml_hip_attn_mla_work_size": (C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int64, C.c_int64]),
+    "ggml_hip_attn_mla_paged_plan": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int64, C.c_int64, C.c_int64, _P]),
+    "ggml_hip_attn_mla_paged_work_size": (C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int64, C.c_int64, C.c_int64]),
+    "ggml_hip_attn_mla_dev": (C.c_int, [C.c_int, _P, C.c_int64, C.c_int64, _P, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int64, C.c_int64, _P, C.c_int64, C.c_int,
+                                        C.c_float, _P, C.c_int64, C.c_int64, _P, C.c_size_t, _P]),
+    "ggml_hip_attn_mla_paged_dev": (C.c_int, [C.c_int, _P, C.c_int64, C.c_int64, _P, C.c_int64, C.c_int64, C.c_int, _P, C.c_int64, _P, C.c_int, C.c_int64, C.c_int,
+                                              C.c_int, C.c_int, C.c_int64, C.c_int64, C.c_int, C.c_float, _P, C.c_int64, C.c_int64, _P, C.c_size_t, _P]),
+    "ggml_hip_kv_store_latent_paged_dev": (C.c_int, [C.c_int, _P, C.c_int64, C.c_int64, C.c_int64, _P, C.c_int64, C.c_int64, C.c_int, _P, C.c_int64, _P, C.c_int64,
+                                                     _P]),
 }
 SYMBOLS = HIP_SYMBOLS
 

@@ -517,6 +517,24 @@ hipError_t launch_kv_store_paged_ragged(int kv_type, const float *src, int64_t l
 struct attn_ragged_plan;
 hipError_t launch_attn_paged_ragged(const attn_ragged_plan &pl, const attn_args &a, const kv_ragged &rg, const kv_pages &pg, int add_q, int len_bias, bool var,
                                     const attn_var &vo, hipStream_t st, const attn_bias *bs = nullptr);
+// mla.hip: latent attention over a latent KV cache (ggml_hip_attn_mla_dev / ggml_hip_attn_mla_paged_dev, mla.cpp; the form is plan.h's plan_attn_mla).
+// q [rows][n_head][576] f32, cache: one row of 576 elements per position (the contiguous cache, or the pool of a paged call), dst [rows][n_head][512];
+// n_q the rows PER SEQUENCE; n_kv / d_n_kv as attn_args' (a paged call reads neither); work: 256-byte aligned, n_spans = the plan's (SPLIT)
+struct mla_plan;
+struct mla_args {
+    int kv_type, n_head, causal;
+    const float *q; int64_t ldq_tok, ldq_head;
+    const void *cache; int64_t nb_pos;
+    int64_t n_q, n_kv; const int32_t *d_n_kv; int64_t n_kv_max;
+    float scale;
+    float *dst; int64_t ldd_tok, ldd_head;
+    float *work; int64_t n_spans;
+};
+// pg: null for the contiguous call (n_seq = 1)
+hipError_t launch_attn_mla(const mla_plan &pl, const mla_args &a, int64_t n_seq, const kv_pages *pg, int len_bias, hipStream_t st);
+// rows [n_seq * n_q][576] -> row (b, t) at the page row of position len[b] + t; a position outside [0, n_kv_max) or a page id outside [0, n_pages) writes nothing
+hipError_t launch_kv_store_latent_paged(int kv_type, const float *src, int64_t ld, int64_t n_seq, int64_t n_q, void *pool, int64_t nb_pos, const kv_pages &pg,
+                                        hipStream_t st);
 // rope.hip: the rotation of Q / K rows (ggml_hip_rope_dev) and the rotation fused with kv_store (ggml_hip_rope_kv_store_dev; rope.cpp).
 // The per-pair constants are the HOST's (ggml_hip_rope_table) and go to the kernels by value: eff[i] for pair i < n_dims / 2, and mscale
 #define ROPE_MAX_PAIRS 128

@@ -598,6 +598,27 @@ attn_plan plan_attn_paged_ex(int kv_type, int D, int n_head, int n_head_kv, int6
     return p;
 }
 
+// MLA (plan.h has the statement): the form from n_q alone, the grids from the shape alone.
+mla_plan plan_attn_mla(int kv_type, int n_head, int64_t n_seq, int64_t n_q, int64_t n_kv_max) {
+    mla_plan p = {};
+    if (!(kv_type == GGML_TYPE_F16 || kv_type == GGML_TYPE_Q8_0) || n_head < 1 || n_head > 256) return p;
+    if (n_q < 1 || n_q > (1 << 20) || n_kv_max < 0 || n_kv_max > (1 << 24)) return p;
+    if (n_seq < 1 || n_seq > ATTN_PAGED_MAX_SEQ || n_seq * n_q > ATTN_PAGED_MAX_ROWS || n_seq * n_q * n_head > 0x7FFFFFFF) return p;
+    p.chunk = ATTN_CHUNK; p.span = MLA_SPAN; p.q_tile = MLA_TILE; p.step = MLA_STEP;
+    p.n_spans = cdiv(n_kv_max, (int64_t)ATTN_CHUNK * MLA_SPAN);
+    p.tiles = cdiv(n_q * n_head, MLA_TILE);
+    if (n_q <= MLA_SPLIT_MAX_Q) {
+        p.form = MLA_FORM_SPLIT; p.launches = 2;
+        p.wgs = p.tiles * p.n_spans * n_seq;
+        p.merge_wgs = n_seq * n_q * n_head;
+        p.work_bytes = (size_t)p.merge_wgs * (size_t)p.n_spans * (size_t)(MLA_DV + 4) * 4;
+    } else {
+        p.form = MLA_FORM_WALK; p.launches = 1;
+        p.wgs = p.tiles * n_seq;
+    }
+    return p;
+}
+
 // The ragged paged call (plan.h has the statement): the bounds size everything, the batch nothing.
 int64_t attn_ragged_max_tiles(int64_t n_tokens_max, int64_t n_seq) {
     if (n_tokens_max < 9 || n_seq < 1) return 0;

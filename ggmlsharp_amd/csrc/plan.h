@@ -168,6 +168,34 @@ struct attn_ragged_plan {
 int64_t attn_ragged_max_tiles(int64_t n_tokens_max, int64_t n_seq);
 attn_ragged_plan plan_attn_ragged(int kv_type, int D, int n_head, int n_head_kv, int64_t n_seq, int64_t n_tokens_max, int64_t n_dec_rows_max, int64_t n_kv_max,
                                   int64_t window);
+// ---- MLA: latent attention over a latent KV cache (mla.hip; ggml_hip_attn_mla_dev / ggml_hip_attn_mla_paged_dev) ----
+// Only (D_k, D_v) = (576, 512).  The FORM is a function of n_q alone: SPLIT up to MLA_SPLIT_MAX_Q rows per sequence, WALK above.  Both own tiles of
+// MLA_TILE consecutive rows (t * n_head + h) of one sequence and walk the positions in steps of MLA_STEP, two per chunk.  SPLIT cuts the positions into
+// spans of MLA_SPAN chunks: grid tiles x n_spans x n_seq, n_spans = ceil(n_kv_max / (128 * MLA_SPAN)), a partial (m, l, O[512]) per (row, span) and a
+// merge launch of one workgroup per row.  WALK: grid tiles x 1 x n_seq, no work buffer.  NONE: kv_type, n_head outside 1 .. 256, n_q outside
+// 1 .. 2^20, n_kv_max outside 0 .. 2^24, n_seq outside 1 .. 4096, n_seq * n_q above 2^20 or n_seq * n_q * n_head at or above 2^31.
+// MLA_SPAN (one of 1, 2, 4, 8): a small span fills the chip at one sequence, a large one keeps the partials small at many.
+constexpr int MLA_DK = 576, MLA_DV = 512;
+constexpr int MLA_TILE = 64, MLA_STEP = 64;
+#ifndef GGML_HIP_MLA_SPAN                     // (a developer build may set 1, 2 or 8 to measure the other values: tools/attn_mla_grid.py)
+#define GGML_HIP_MLA_SPAN 4
+#endif
+constexpr int MLA_SPAN = GGML_HIP_MLA_SPAN;
+static_assert(MLA_SPAN == 1 || MLA_SPAN == 2 || MLA_SPAN == 4 || MLA_SPAN == 8, "MLA_SPAN");
+constexpr int MLA_SPLIT_MAX_Q = 8;
+enum mla_form { MLA_FORM_NONE = 0, MLA_FORM_SPLIT = 1, MLA_FORM_WALK = 2 };
+struct mla_plan {
+    int form;             // mla_form; NONE: the shape is not served
+    int chunk, span;      // positions per chunk; chunks per span (MLA_SPAN, both forms report it)
+    int q_tile, step;     // rows a workgroup owns; positions per online-softmax step
+    int launches;         // SPLIT 2 (partials, merge), WALK 1
+    int64_t n_spans;      // ceil(n_kv_max / (chunk * span)): SPLIT's grid y and partials per row (WALK: the same number, unused)
+    int64_t tiles;        // ceil(n_q * n_head / q_tile): grid x
+    int64_t wgs;          // workgroups of the main launch
+    int64_t merge_wgs;    // SPLIT: n_seq * n_q * n_head; WALK 0
+    size_t work_bytes;    // SPLIT: n_seq * n_q * n_head * n_spans * (512 + 4) floats; WALK 0
+};
+mla_plan plan_attn_mla(int kv_type, int n_head, int64_t n_seq, int64_t n_q, int64_t n_kv_max);
 // ---- the SSM entries: causal conv and selective scan over a ragged batch and a pool of state slots (ssm.hip; ggml_hip_ssm_*_ragged_dev) ----
 // ONE launch each, grid (x) x (n_seq): a workgroup row per sequence, so a token loop's trip count is uniform over a workgroup.  Nothing follows the
 // batch or n_tokens_max.  ok = 0: the shape is not served.

@@ -499,6 +499,96 @@ def attn_paged(pc, q, n_head_kv, len_bias=0, causal=True, scale=None, out=None, 
     return out
 
 
+MLA_DK, MLA_DV = 576, 512
+
+
+def attn_mla_plan(kv_type, n_head, n_q, n_kv_max, n_seq=None):
+    """the ggml_hip_attn_mla_plan_t of one MLA call (n_seq: the paged call): form 1 SPLIT (n_q <= 8), 2 WALK; span = MLA_SPAN chunks of 128 positions per
+    partial; n_spans, workgroups, merge_workgroups, work_bytes; no device needed"""
+    out = _lib.ggml_hip_attn_mla_plan_t()
+    if n_seq is None:
+        check(lib().ggml_hip_attn_mla_plan(kv_type, MLA_DK, MLA_DV, n_head, n_q, n_kv_max, C.byref(out)), "ggml_hip_attn_mla_plan")
+    else:
+        check(lib().ggml_hip_attn_mla_paged_plan(kv_type, MLA_DK, MLA_DV, n_head, n_seq, n_q, n_kv_max, C.byref(out)), "ggml_hip_attn_mla_paged_plan")
+    return out
+
+
+def attn_mla_work_size(kv_type, n_head, n_q, n_kv_max, n_seq=None):
+    if n_seq is None:
+        return int(lib().ggml_hip_attn_mla_work_size(kv_type, MLA_DK, MLA_DV, n_head, n_q, n_kv_max))
+    return int(lib().ggml_hip_attn_mla_paged_work_size(kv_type, MLA_DK, MLA_DV, n_head, n_seq, n_q, n_kv_max))
+
+
+def attention_mla(kv_type, q, cache, nb_pos, n_kv, scale, d_n_kv=None, n_kv_max=None, causal=True, out=None, work=None):
+    """MLA in the absorbed form: out[t, h] = softmax_j(scale * q[t, h] . row_j) row_j[:512] over the visible j of a latent cache, on the current stream.
+    q f32 [n_q, n_head, 576] (last stride 1); cache: a uint8 tensor whose first byte is position 0, ONE row of 576 elements (F16 / Q8_0) per position,
+    nb_pos bytes apart, shared by every head: columns 0 .. 511 are the latent and the value, 512 .. 575 the rotated key part.  scale is required (MLA's is
+    not 1 / sqrt(576)).  d_n_kv, n_kv_max, causal: as attention().  Returns f32 [n_q, n_head, 512]."""
+    assert q.is_cuda and q.dtype == torch.float32 and q.dim() == 3 and q.stride(2) == 1 and q.shape[2] == MLA_DK
+    assert cache.is_cuda and cache.dtype == torch.uint8
+    assert d_n_kv is None or (d_n_kv.is_cuda and d_n_kv.dtype == torch.int32)
+    n_q, n_head, _ = q.shape
+    if n_kv_max is None:
+        n_kv_max = n_kv
+    if out is None:
+        out = torch.empty((n_q, n_head, MLA_DV), dtype=torch.float32, device=q.device)
+    assert out.dtype == torch.float32 and out.dim() == 3 and out.stride(2) == 1 and tuple(out.shape) == (n_q, n_head, MLA_DV)
+    if work is None:
+        work = torch.empty(max(attn_mla_work_size(kv_type, n_head, n_q, n_kv_max), 16), dtype=torch.uint8, device=q.device)
+    check(lib().ggml_hip_attn_mla_dev(kv_type, C.c_void_p(q.data_ptr()), q.stride(0), q.stride(1), C.c_void_p(cache.data_ptr()), nb_pos, n_head, MLA_DK, MLA_DV, n_q,
+                                      int(n_kv), _opt(d_n_kv), n_kv_max, int(bool(causal)), float(scale), C.c_void_p(out.data_ptr()), out.stride(0), out.stride(1),
+                                      C.c_void_p(work.data_ptr()), work.numel(), _stream()), "ggml_hip_attn_mla_dev")
+    return out
+
+
+class LatentCache:
+    """how a paged LATENT cache is addressed (include/ggml_hip_ext.h, MLA): one pool (a uint8 tensor of n_pages pages of 128 positions, nb_page bytes apart;
+    the row of position jj of a page at jj * nb_pos, 576 elements of kv_type), the page table pages int32 [n_seq, ld_pages] and the lengths d_len int32
+    [n_seq] on the device, and n_kv_max, which sizes the launches.  The host owns the table."""
+
+    def __init__(self, kv_type, pool, nb_page, nb_pos, n_pages, pages, d_len, n_kv_max):
+        assert pool.is_cuda and pool.dtype == torch.uint8
+        assert pages.is_cuda and pages.dtype == torch.int32 and pages.dim() == 2 and pages.stride(1) == 1
+        assert d_len.is_cuda and d_len.dtype == torch.int32 and d_len.is_contiguous() and d_len.numel() == pages.shape[0]
+        self.kv_type, self.pool, self.nb_page, self.nb_pos = kv_type, pool, int(nb_page), int(nb_pos)
+        self.n_pages, self.pages, self.d_len, self.n_kv_max = int(n_pages), pages, d_len, int(n_kv_max)
+
+    @property
+    def n_seq(self):
+        return self.pages.shape[0]
+
+
+def kv_store_latent_paged(lc, x):
+    """x f32 [n_seq * n_q, 576] (last stride 1) -> row (b, t) to its page row at position d_len[b] + t, bit for bit kv_store's bytes at row_elems = 576; a
+    position outside [0, n_kv_max) or a page id outside [0, n_pages) writes nothing.  The rotation of columns 512 .. 575 is the caller's: rope() in place on
+    x[:, 512:].unsqueeze(1) first."""
+    assert x.is_cuda and x.dtype == torch.float32 and x.dim() == 2 and x.stride(1) == 1 and x.shape[1] == MLA_DK
+    assert x.shape[0] % lc.n_seq == 0, "n_seq * n_q rows"
+    check(lib().ggml_hip_kv_store_latent_paged_dev(lc.kv_type, C.c_void_p(x.data_ptr()), x.stride(0), lc.n_seq, x.shape[0] // lc.n_seq,
+                                                   C.c_void_p(lc.pool.data_ptr()), lc.nb_page, lc.nb_pos, lc.n_pages, C.c_void_p(lc.pages.data_ptr()),
+                                                   lc.pages.stride(0), C.c_void_p(lc.d_len.data_ptr()), lc.n_kv_max, _stream()), "ggml_hip_kv_store_latent_paged_dev")
+
+
+def attn_mla_paged(lc, q, scale, len_bias=0, causal=True, out=None, work=None):
+    """attention_mla of n_seq independent sequences over the paged latent cache lc in one call: q f32 [n_seq * n_q, n_head, 576], sequence b over its
+    n_kv[b] = clamp(d_len[b] + len_bias, 0, n_kv_max) positions; its rows are bit for bit attention_mla() on a contiguous copy of its cache.  A sequence
+    with n_kv 0 or an invalid needed page id returns +0.0 rows."""
+    assert q.is_cuda and q.dtype == torch.float32 and q.dim() == 3 and q.stride(2) == 1 and q.shape[2] == MLA_DK
+    n_rows, n_head, _ = q.shape
+    assert n_rows % lc.n_seq == 0, "n_seq * n_q rows"
+    n_q = n_rows // lc.n_seq
+    if out is None:
+        out = torch.empty((n_rows, n_head, MLA_DV), dtype=torch.float32, device=q.device)
+    assert out.dtype == torch.float32 and out.dim() == 3 and out.stride(2) == 1 and tuple(out.shape) == (n_rows, n_head, MLA_DV)
+    if work is None:
+        work = torch.empty(max(attn_mla_work_size(lc.kv_type, n_head, n_q, lc.n_kv_max, lc.n_seq), 16), dtype=torch.uint8, device=q.device)
+    check(lib().ggml_hip_attn_mla_paged_dev(lc.kv_type, C.c_void_p(q.data_ptr()), q.stride(0), q.stride(1), C.c_void_p(lc.pool.data_ptr()), lc.nb_page, lc.nb_pos,
+                                            lc.n_pages, C.c_void_p(lc.pages.data_ptr()), lc.pages.stride(0), C.c_void_p(lc.d_len.data_ptr()), int(len_bias),
+                                            lc.n_seq, n_head, MLA_DK, MLA_DV, n_q, lc.n_kv_max, int(bool(causal)), float(scale), C.c_void_p(out.data_ptr()),
+                                            out.stride(0), out.stride(1), C.c_void_p(work.data_ptr()), work.numel(), _stream()), "ggml_hip_attn_mla_paged_dev")
+    return out
+
+
 def _ragged(pc, q_start, x):
     """(n_tokens_max, heads, D) of packed rows x [n_tokens_max, heads, D] under q_start int32 [n_seq + 1] on the device"""
     assert x.is_cuda and x.dtype == torch.float32 and x.dim() == 3 and x.stride(2) == 1

@@ -1168,6 +1168,81 @@ int    ggml_hip_ssm_conv_tiled_ragged_dev(const float *d_x, int64_t ldx, const f
                                           float *d_state, int64_t nb_slot, int64_t n_slots, float *d_dst, int64_t ldd,
                                           void *d_work, size_t work_bytes, void *stream);
 
+
+/* ---------------- MLA: multi-head LATENT attention (absorbed form) over a latent KV cache, on the f16 matrix cores ----------------
+ * The attention of DeepSeek-V2 / V3 / R1 and Kimi K2 in the absorbed form, an EXTENSION like attention: device-resident entries only.  Every query head
+ * reads ONE shared cache row per position.
+ * THE CACHE ROW: D_k = 576 elements in the reference block format ggml_hip_kv_store_dev writes (F16: 1152 bytes; Q8_0: 18 blocks, 648 bytes), the row
+ *   of position j at base + j * nb_pos.  Elements 0 .. 511 are the compressed latent and ARE the value, elements 512 .. 575 are the rotated key part.
+ *   q is f32 [rows][n_head][576] in the same order, dst f32 [rows][n_head][512].  Only (D_k, D_v) = (576, 512) is served; 1 <= n_head <= 256.
+ *   There is ONE cache pointer: K and V are the same bytes.  No mask, window, soft-cap or sinks: they are not parameters at all.
+ * THE ROTATION of the key part stays the caller's.  The recipe for rows x f32 [n_tok][576] (row stride ld): call ggml_hip_rope_dev in place on the last 64
+ *   columns as a one-head view -- d_x = d_dst = x + 512, ldx_tok = ldd_tok = ld, ldx_head = ldd_head = 64, n_head = 1, D = 64 -- then store the rows:
+ *   ggml_hip_kv_store_dev with row_elems = 576 into a contiguous cache, ggml_hip_kv_store_latent_paged_dev into a paged one.
+ * A ROW of the problem is a pair (t, h), r = t * n_head + h; all rows share the cache.  vis(t) = causal ? clamp(n_kv - n_q + t + 1, 0, n_kv) : n_kv as
+ *   in ggml_hip_attn_dev.  n_kv is the host's, or *d_n_kv (an int32 on the device) clamped to [0, n_kv_max]; n_kv_max sizes every launch.
+ * THE ARITHMETIC (fixed): the operands are the PROMPT form's.  Q is rounded to f16 (RNE) once.  An F16 row is staged as it lies, a Q8_0 row is
+ *   dequantized while staged: f16((float)q * d).  Positions at or beyond n_kv are staged as ZEROS: what the cache holds there, NaN bytes included, does
+ *   not matter (below n_kv the cache must hold finite values: a masked weight is a zero operand).  The positions are walked in STEPS of `step` = 64, two
+ *   per chunk of 128, ascending; per step, all on v_mfma_f32_32x32x16_f16 with f32 accumulation:
+ *     S = Q K^T over all 576 elements;  s = scale * S in f32, an invisible j is -inf;  m' = max(m, max s);  alpha = expf(m - m') (0 while m = -inf);
+ *     P = f16(expf(s - m')), 0 where invisible;  l = l * alpha + sum of the ROUNDED P;  O = O * alpha + P V over the first 512 columns.
+ *   A step without a visible position of a row leaves the row's (m, l, O) as they are (alpha = 1, every P = 0).
+ * TWO FORMS, chosen from n_q alone -- never from the device, the grid, n_head, n_seq or n_kv_max:
+ *   WALK (n_q > 8): a workgroup owns a tile of 64 consecutive rows and walks the steps that hold a visible position of any of them; dst = O / l.  No work
+ *     buffer.
+ *   SPLIT (n_q <= 8): the positions are cut into SPANS of `span` chunks (one compile-time constant, reported in the plan).  A workgroup runs the same step
+ *     body over one span for its row tile and writes the unnormalised partial (m, l, O[512]) to the work buffer; a (row, span) with no visible position has no
+ *     partial.  A second launch merges a row's partials: M = max m_s; b_s = m_s == M ? 1 : expf(m_s - M); L and A[d] are fma chains over the spans in
+ *     ASCENDING order, the first term the product; dst = A / L.
+ *   A row with no visible position is +0.0f in both.  Work size: rows * ceil(n_kv_max / (128 * span)) * (512 + 4) floats, rounded up to 256 bytes plus 256
+ *   (the base is aligned by the entry); 0 for WALK; monotone in every argument.
+ * THE CONTRACTS, as bits:
+ *   1. One visible position: dst is the staged V row bit for bit -- deq(V_0) for F16, f16(deq(V_0)) for Q8_0 -- in both forms.
+ *   2. A row's bits depend on its own q row, the cache bytes below its vis, scale, the cache type and the form ONLY: not on n_head, the row's place in a
+ *      tile, the strides, n_kv_max, where n_kv comes from, or n_q within the form (row t of one call equals a row with the same vis of another call of
+ *      that form).
+ *   3. Paged equals contiguous per sequence, bit for bit: one step body, which does not know where a chunk lies.  Nothing depends on the page assignment,
+ *      n_pages, ld_pages, nb_page, n_seq or the slot.
+ * ggml_hip_attn_mla_dev: q, dst and d_cache 16-byte aligned; ldq_* / ldd_* multiples of 4 elements, ldq_head >= 576, ldd_head >= 512 (and the token strides
+ *   where there is more than one token); nb_pos a multiple of 16, at least a row's bytes; n_q <= 2^20, n_kv_max <= 2^24, n_q * n_head < 2^31.  d_work /
+ *   work_bytes: at least ggml_hip_attn_mla_work_size(..), else GGML_HIP_ERR_ARG.  A wrong kv_type is GGML_HIP_ERR_TYPE, a refused shape, stride or
+ *   alignment GGML_HIP_ERR_SHAPE, a null or short argument GGML_HIP_ERR_ARG; every refusal is decided before a device is touched.  n_q = 0 returns 0 after
+ *   the shape and stride checks.  Stream-ordered, no synchronize, no allocation, no atomics; capturable, and a captured call follows *d_n_kv.
+ * ggml_hip_attn_mla_paged_dev: n_seq sequences (1 .. 4096) of n_q rows EACH (uniform; a ragged twin is left out), q / dst [n_seq * n_q][n_head][..],
+ *   n_seq * n_q <= 2^20 and n_seq * n_q * n_head < 2^31.  The pool, nb_page, nb_pos, n_pages, d_pages, ld_pages, d_len and len_bias are the paged section's
+ *   with one row per position (nb_page >= 127 * nb_pos + a row's bytes): n_kv[b] = clamp(d_len[b] + len_bias, 0, n_kv_max); n_kv[b] = 0 gives zero rows; a
+ *   page id outside [0, n_pages) among a sequence's first ceil(n_kv[b] / 128) entries zeroes ALL its rows and never becomes an address.  NULL tables are
+ *   GGML_HIP_ERR_ARG.
+ * ggml_hip_kv_store_latent_paged_dev: rows src f32 [n_seq * n_q][576] (row stride ld, a multiple of 4) -> row (b, t) at position d_len[b] + t of
+ *   sequence b.  The bytes written are bit for bit ggml_hip_kv_store_dev(row_elems = 576) for that row (one thread per 32 (Q8_0) or 4 (F16) elements).  A
+ *   token whose position is outside [0, n_kv_max), or whose page id is outside [0, n_pages), writes nothing and no address is formed from it.
+ *   (ggml_hip_kv_store_paged_dev stops at D = 256, and a Q8_0 row of 648 bytes cannot be expressed as heads.)
+ * LEFT OUT: a ragged (d_q_start) twin; window, sinks, soft-cap and mask; other (D_k, D_v); a rope fused into the latent store. */
+enum { GGML_HIP_ATTN_MLA_SPLIT = 1, GGML_HIP_ATTN_MLA_WALK = 2 }; /* ggml_hip_attn_mla_plan_t.form */
+typedef struct ggml_hip_attn_mla_plan_t {
+    int32_t form, chunk;                     /* the form (0 for n_q = 0); positions per chunk (128) */
+    int32_t span, q_tile;                    /* chunks per span (MLA_SPAN, in both forms); rows (t, h) a workgroup owns */
+    int32_t step, launches;                  /* positions per online-softmax step; launches of one call (SPLIT 2, WALK 1) */
+    int64_t n_spans, workgroups;             /* ceil(n_kv_max / (chunk * span)); workgroups of the main launch */
+    int64_t merge_workgroups;                /* SPLIT: one per row; WALK 0 */
+    uint64_t work_bytes;                     /* ggml_hip_attn_mla_work_size / _paged_work_size */
+} ggml_hip_attn_mla_plan_t;
+int    ggml_hip_attn_mla_plan(int kv_type, int D_k, int D_v, int n_head, int64_t n_q, int64_t n_kv_max, ggml_hip_attn_mla_plan_t *out);
+size_t ggml_hip_attn_mla_work_size(int kv_type, int D_k, int D_v, int n_head, int64_t n_q, int64_t n_kv_max);
+int    ggml_hip_attn_mla_paged_plan(int kv_type, int D_k, int D_v, int n_head, int64_t n_seq, int64_t n_q, int64_t n_kv_max, ggml_hip_attn_mla_plan_t *out);
+size_t ggml_hip_attn_mla_paged_work_size(int kv_type, int D_k, int D_v, int n_head, int64_t n_seq, int64_t n_q, int64_t n_kv_max);
+int    ggml_hip_attn_mla_dev(int kv_type, const float *d_q, int64_t ldq_tok, int64_t ldq_head, const void *d_cache, int64_t nb_pos,
+                             int n_head, int D_k, int D_v, int64_t n_q, int64_t n_kv, const int32_t *d_n_kv, int64_t n_kv_max, int causal, float scale,
+                             float *d_dst, int64_t ldd_tok, int64_t ldd_head, void *d_work, size_t work_bytes, void *stream);
+int    ggml_hip_attn_mla_paged_dev(int kv_type, const float *d_q, int64_t ldq_tok, int64_t ldq_head, const void *d_pool, int64_t nb_page, int64_t nb_pos,
+                                   int n_pages, const int32_t *d_pages, int64_t ld_pages, const int32_t *d_len, int len_bias, int64_t n_seq,
+                                   int n_head, int D_k, int D_v, int64_t n_q, int64_t n_kv_max, int causal, float scale,
+                                   float *d_dst, int64_t ldd_tok, int64_t ldd_head, void *d_work, size_t work_bytes, void *stream);
+int    ggml_hip_kv_store_latent_paged_dev(int kv_type, const float *d_src, int64_t ld, int64_t n_seq, int64_t n_q, void *d_pool, int64_t nb_page,
+                                          int64_t nb_pos, int n_pages, const int32_t *d_pages, int64_t ld_pages, const int32_t *d_len, int64_t n_kv_max,
+                                          void *stream);
+
 #if defined(__GNUC__)
 #pragma GCC visibility pop
 #endif
