@@ -218,6 +218,8 @@ HIP_SYMBOLS = {
     "ggml_hip_mm_plan": (C.c_int, [C.c_int, C.c_int64, C.c_int64, C.c_int64, _P]),
     "ggml_hip_debug_force_gemm": (None, [C.c_int]),
     "ggml_hip_debug_q2k_min_pass_dev": (C.c_int, [_P, C.c_int64, _P, C.c_int64, _P, C.c_size_t, C.c_int, _P]),
+    "ggml_hip_mul_mat_init_fused": (C.c_int, [_P, C.c_int64]),
+    "ggml_hip_debug_fused_init_skip_panel": (None, [C.c_int]),
     "ggml_hip_quantize_act_dev": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p]),
     "ggml_hip_mul_mat_dev": (C.c_int, [_P, _P, C.c_int64, C.c_int64, _P, C.c_int64, _P, C.c_size_t, _P]),
     "ggml_hip_mul_mat_init_dev": (C.c_int, [_P, _P, C.c_int64, C.c_int64, _P, C.c_size_t, _P]),

@@ -589,9 +589,15 @@ int ggml_hip_debug_q2k_min_pass_dev(const ggml_hip_weight *w, int64_t N, float *
     return GGML_HIP_OK;
 }
 
+// does ggml_hip_mul_mat_dev quantize src1 inside the product launch for this weight and N?  (By weight, plan and N; src1 itself must suit K1's
+// lane-per-block kernel as well.)  ggml_hip_mul_mat_init_dev / _compute_dev never do: they are the two steps, and the fused route's reference.
+static bool fused_init_route(const ggml_hip_weight *w, const mm_plan &pl, int64_t N) {
+    return is_q(w->type) && !weight_row(w)->q8k && plan_act_image(pl) == 3 && !(pl.flags & MM_FLAG_MIN_PASS) && gemm_qmx_fused_serves(w, pl, N);
+}
+
 // the product under its one-call plan `pl` (w is not null, N > 0, M > 0)
 static int mul_mat_planned(const ggml_hip_weight *w, const mm_plan &pl, const float *d_src1, int64_t N, int64_t ld1, float *d_dst,
-                           int64_t ldd, void *d_work, size_t work_bytes, void *stream) {
+                           int64_t ldd, void *d_work, size_t work_bytes, void *stream, bool may_fuse_init = false) {
     if (!d_src1 || !d_dst) return fail(GGML_HIP_ERR_ARG, "null argument");
     if (ld1 < w->K || ldd < w->M) return fail(GGML_HIP_ERR_SHAPE, "ld1 < K or ldd < M");
     int rc = weight_device_current(w);
@@ -623,16 +629,27 @@ static int mul_mat_planned(const ggml_hip_weight *w, const mm_plan &pl, const fl
         HIP_TRY(launch_gemv_q_fused(w, d_src1, ld1, N, d_dst, ldd, (hipStream_t)stream));
         return GGML_HIP_OK;
     }
+    // the headline form quantizes src1 inside the product launch (gemm_qmx.hip mx_fuse): the arguments INIT and COMPUTE would refuse are refused
+    // the same way, and a src1 only the general INIT kernel reads goes through the two steps below
+    if (may_fuse_init && fused_init_route(w, pl, N) && quantize_act_bf6_serves(d_src1, N, w->K, ld1)) {
+        if (!d_work || work_bytes < ggml_hip_mul_mat_work_size(w->type, w->K, N))
+            return fail(GGML_HIP_ERR_ARG, "work buffer too small: need %zu", ggml_hip_mul_mat_work_size(w->type, w->K, N));
+        HIP_TRY(launch_gemm_qmx_fused(w, pl, d_src1, ld1, act_carve(d_work, w->K, pad_act(N)), N, d_dst, ldd, (hipStream_t)stream));
+        return GGML_HIP_OK;
+    }
     rc = mul_mat_init_step(w, pl, d_src1, N, ld1, d_work, work_bytes, stream);
     if (rc) return rc;
     return mul_mat_compute_step(w, pl, N, d_dst, ldd, d_work, work_bytes, stream);
 }
 
+int ggml_hip_mul_mat_init_fused(const ggml_hip_weight *w, int64_t N) { return w && N > 0 && w->M > 0 && fused_init_route(w, weight_plan(w, N, true), N) ? 1 : 0; }
+void ggml_hip_debug_fused_init_skip_panel(int panel) { gemm_qmx_fused_skip_panel(panel); }
+
 int ggml_hip_mul_mat_dev(const ggml_hip_weight *w, const float *d_src1, int64_t N, int64_t ld1, float *d_dst,
                          int64_t ldd, void *d_work, size_t work_bytes, void *stream) {
     if (!w) return fail(GGML_HIP_ERR_ARG, "null weight");
     if (N <= 0 || w->M <= 0) return GGML_HIP_OK;
-    return mul_mat_planned(w, weight_plan(w, N, true), d_src1, N, ld1, d_dst, ldd, d_work, work_bytes, stream);
+    return mul_mat_planned(w, weight_plan(w, N, true), d_src1, N, ld1, d_dst, ldd, d_work, work_bytes, stream, true);   // (this entry alone fuses INIT)
 }
 
 // does a kernel form with a fused store-phase epilogue serve this weight under its one-call plan?  The fused mat-vec (N <= 4), the MX

@@ -296,6 +296,10 @@ hipError_t launch_push_columns(const float *src, int64_t lds, int64_t N, int64_t
                                int64_t col0, hipStream_t st);
 // quantize.hip
 hipError_t launch_quantize_act(const float *x, int64_t N, int64_t K, int64_t ld1, act_planes p, int image, hipStream_t st, bool q8k = false);
+// the bf6 image (kind 3) by the lane-per-block kernel: does it serve this src1, and its first nb_head k-blocks alone (+ nclr words zeroed)
+bool quantize_act_bf6_serves(const float *x, int64_t N, int64_t K, int64_t ld1);
+hipError_t launch_quantize_act_bf6_head(const float *x, int64_t N, int64_t K, int64_t ld1, act_planes p, int64_t nb_head, uint32_t *clr, int nclr,
+                                        hipStream_t st);
 // ---- the weight types: ONE row per type id the library accepts anywhere -- the reference's thirteen and the extension ids of
 // include/ggml_hip_ext.h.  wtypes.cpp holds the table; everything that used to ask "is this a k-quant / IQ4_NL / BF16" reads a row.
 // DESIGN.md "Adding a weight type" says what a new type has to supply.
@@ -604,6 +608,13 @@ hipError_t launch_gemm_qmx_multi(const mm_plan &g, const ggml_hip_weight *const 
                                  hipStream_t st);
 hipError_t launch_gemm_qmx(const ggml_hip_weight *w, const mm_plan &pl, act_planes p, int64_t N, float *dst, int64_t ldd, hipStream_t st,
                            const mm_epilogue *ep);
+// The fused route of the Q4_0 256 x 128 form: K1's head launch for the first K quarter, then ONE launch that quantizes the other three quarters of src1
+// inside the K loop, a quarter ahead of it (gemm_qmx.hip mx_fuse).  The same image bytes and the same product bits as INIT + COMPUTE.  _serves: by
+// weight, plan and N alone; the launch also wants src1 as K1's lane-per-block kernel does (quantize_act_bf6_serves), else hipErrorNotSupported.
+bool gemm_qmx_fused_serves(const ggml_hip_weight *w, const mm_plan &pl, int64_t N);
+hipError_t launch_gemm_qmx_fused(const ggml_hip_weight *w, const mm_plan &pl, const float *x, int64_t ld1, act_planes p, int64_t N, float *dst, int64_t ldd,
+                                 hipStream_t st);
+void gemm_qmx_fused_skip_panel(int panel);                  // TEST HOOK: the producers of this column panel leave their shares to the help path (-1: none)
 // Q4_0, prompt-sized batches, K >= 2048 (gemm_qmp.hip K3p); hipErrorNotSupported where the form does not apply
 hipError_t launch_gemm_qmx_mid(const ggml_hip_weight *w, const mm_plan &pl, act_planes p, int64_t N, float *dst, int64_t ldd, hipStream_t st, const mm_epilogue *ep);
 // the same form on the int8 matrix cores: Q8_0, image 0 (gemm_qmp.hip)

@@ -28,6 +28,8 @@
 // raw buffer addressing; inline-asm scale-accumulate; K zero-padded to whole stages by the host side.
 #include "common.h"
 #include "plan.h"
+#include "act_bf6.h"
+#include <atomic>
 #include <cstdlib>
 #include <utility>
 
@@ -36,9 +38,16 @@
 #if !defined(GGML_HIP_DEV)      // the product build has no ablation paths: the switches exist only under -DGGML_HIP_DEV
 #undef GGML_MX_DBG
 #undef GGML_MX_XCD1D
+#undef GGML_MX_FUSE_DBG
 #endif
 #ifndef GGML_MX_DBG
 #define GGML_MX_DBG 0
+#endif
+// Developer cost split of the fused route (never in the product build; with any bit set the head launch writes the WHOLE image, so nothing depends
+// on the hand-off): -DGGML_MX_FUSE_DBG=<bits>  1 no quantize in the launch, 2 the plain 2 x 4 tile map, 4 image fetches without sc1, 8 every workgroup
+// writes its own shares (the same bytes again) and nothing is published or checked.  tools/experiments/ab_fused_cost.sh
+#ifndef GGML_MX_FUSE_DBG
+#define GGML_MX_FUSE_DBG 0
 #endif
 #ifndef GGML_MX_XCD1D
 #define GGML_MX_XCD1D 0        // 1: the former XCD order everywhere (A/B)
@@ -58,9 +67,42 @@ using rsrc_t = __amdgpu_buffer_rsrc_t;
 __device__ __forceinline__ rsrc_t make_rsrc(const void *p, uint32_t bytes) {
     return __builtin_amdgcn_make_buffer_rsrc(const_cast<void *>(p), 0, (int)bytes, 0x00020000);
 }
+template <int AUX = 0>      // cache policy bits of the instruction: 0 default, 16 = sc1 (served by L2, past the CU's L1)
 __device__ __forceinline__ void blds16(rsrc_t r, void *l, uint32_t voff, uint32_t soff) {
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(r, (lds_void *)l, 16, (int)voff, (int)soff, 0, 0);
+    __builtin_amdgcn_raw_ptr_buffer_load_lds(r, (lds_void *)l, 16, (int)voff, (int)soff, 0, AUX);
 }
+
+// ---- the fused route (launch_gemm_qmx_fused): K3m quantizes src1 itself, one K quarter ahead of its own loop ----
+// K1's head launch writes the image of K quarter 0 and zeroes the masks.  While a workgroup computes quarter q it writes its SHARE of its own
+// column panel of quarter q + 1 -- TN / tiles_m rows x the quarter's k-blocks, one block per thread and trip, the statements of act_bf6.h --
+// with plain stores, every wave waits for its stores, the workgroup passes a barrier, and one lane sets the workgroup's bit in the mask of
+// (panel, quarter) with an atomic OR.  One stage before quarter q + 1's first DMA the workgroup reads that mask ONCE and quantizes every share
+// whose bit is missing itself (the same bytes), then goes on: nothing waits for another workgroup, so neither the result nor termination
+// depends on which workgroups are resident or in what order they run.
+// Visibility: the tile map puts the tiles_m workgroups of a panel on one XCD (blocks b, b + 8, .. share one under round-robin dispatch), so
+// producer and consumer meet in one L2: the stores have left the producer's CU when its wait returns, the mask is read and the image is
+// fetched with sc1 (from L2, never from the reading CU's L1), and no write-back or invalidate is needed.  That placement is only OBSERVED,
+// so nothing rests on it: a mask is kept PER XCC id (read from the hardware register), a workgroup trusts only bits set by workgroups of its
+// own XCD, and shares written elsewhere are simply quantized again.
+// What the hand-off DEPENDS ON (no release / acquire fence is used; facts of gfx950 as the guide's hand-off tables and the emitted ISA give them,
+// to be re-checked when the compiler or the chip changes -- tools/isa_stats.sh, then look at the fused instantiation):
+//   * a vector store has reached the XCD's L2 when the issuing wave's `s_waitcnt vmcnt(0)` returns (the CU's L1 is write-through);
+//   * an agent-scope relaxed atomic OR / load executes in that L2 (`global_atomic_or`, `global_load_dword .. sc1`);
+//   * `sc1` on a load -- the mask read and every `buffer_load .. lds` piece of the fused instantiation -- is served past the CU's L1, so a line
+//     of the image another CU has just written is never taken from a stale L1 copy (all 14 DMA pieces of a stage must show `sc1 lds`);
+//   * both waits are inline asm (invisible to the compiler's waitcnt pass), and the bit is set behind a workgroup barrier behind EVERY wave's wait.
+// The head launch and the product launch are ordered by the stream: quarter 0 and the zeroed masks are visible at the launch boundary.
+// The route is taken only where a quarter has FUSED_MIN_QS .. FUSED_MAX_QS stages (launch side): with fewer there is no time between a workgroup's
+// produce and its neighbours' check, everyone helps, and the route loses against INIT + COMPUTE; with 16 it measured behind as well (docs/experiments/README.md).
+struct mx_fuse {
+    const float *x;                 // src1 rows, ld1_bytes apart; x_bytes in all (32-bit buffer offsets)
+    uint32_t *mask;                 // [16 XCC ids][tiles_n][4]: word q (1 .. 3) = the shares of that panel's quarter q written on that XCD;
+                                    // word 0 = how many shares the workgroups of that panel on that XCD took on the help path (tests read it)
+    uint32_t ld1_bytes, x_bytes;
+    int nbk;                        // k-blocks of K (those behind, up to the padded end, are written as zeros)
+    int qs;                         // stages per K quarter
+    int skip_panel;                 // TEST HOOK: the producers of this panel leave their shares to the help path (-1: none)
+};
 
 template <typename F, int... Is>
 __device__ __forceinline__ void static_for_impl(F &&f, std::integer_sequence<int, Is...>) {
@@ -110,15 +152,18 @@ struct Cfg {
 // VS = 1 | 2 | 4 "virtual" groups per wave group: the wave group runs the stage sets of VS groups one after the other, keeping each
 // set's sum apart, and the sums are added in group order -- the summation tree of a KSP * VS-way split, bit for bit, without
 // the extra waves.  What fixes an element's bits is KSP * VS (chosen from N and K); how it is spread over waves may follow M.
-template <int TYPE, int WMT, int WNT, int WGM, int WGN, int KB, int FB, int KSP, int VS>
+// FUSED: the instantiation of the fused route (mx_fuse above; Q4_0 256 x 128 without K split only); fx is unused otherwise
+template <int TYPE, int WMT, int WNT, int WGM, int WGN, int KB, int FB, int KSP, int VS, bool FUSED = false>
 __global__ __launch_bounds__(WGM * WGN * 64 * KSP, (VS > 1 && WGM * WGN * KSP == 4 && WMT * WNT == 2 ? 3 : 2))   // (three 4-wave workgroups per CU: 168 registers)
 void gemm_qmx_kernel(const uint8_t *__restrict__ w6a, const uint8_t *__restrict__ w6b, const float *__restrict__ wd,
                      const float *__restrict__ wm, const uint8_t *__restrict__ a6, const float *__restrict__ ad,
                      const float *__restrict__ asd, float *__restrict__ dst, int M, int N, int Mpad, int Npad, int nstages,
                      int ldd, int tiles_m, int tiles_n, uint32_t w6a_bytes, uint32_t wd_bytes, uint32_t a_bytes,
-                     uint32_t ad_bytes, uint32_t dst_bytes, const mm_epilogue ep) {
+                     uint32_t ad_bytes, uint32_t dst_bytes, const mm_epilogue ep, const mx_fuse fx) {
     using C = Cfg<TYPE, WMT, WNT, WGM, WGN, KB>;
     constexpr int NTILE = WMT * WNT, P = C::P;
+    static_assert(!FUSED || (TYPE == GGML_TYPE_Q4_0 && KSP == 1 && VS == 1 && C::TN == 128 && C::NT == 256), "the fused route is the Q4_0 256 x 128 form");
+    constexpr int DMA_AUX = FUSED && !(GGML_MX_FUSE_DBG & 4) ? 16 : 0;                 // fused: the image is fetched from L2 (another CU of the XCD may just have written it)
     constexpr int NF = (TYPE == GGML_TYPE_Q4_0 || TYPE == GGML_TYPE_Q4_1) ? 1 : 2;   // weight digits (fragments) per block
     static_assert(KB % 2 == 0, "fragment buffers alternate by k-block parity");
     static_assert(VS == 1 || (KSP == 1 && (VS == 2 || VS == 4)) || (KSP == 2 && VS == 2), "virtual split forms");
@@ -139,13 +184,14 @@ void gemm_qmx_kernel(const uint8_t *__restrict__ w6a, const uint8_t *__restrict_
     const int nwg = tiles_m * tiles_n;
     const int bid = blockIdx.x, xcd = bid & 7, q8 = nwg >> 3, r8 = nwg & 7;
     int tm_i, tn_i;
-    if ((tiles_m & 1) == 0 && (tiles_n & 3) == 0 && !GGML_MX_XCD1D) {
+    if ((!FUSED || (GGML_MX_FUSE_DBG & 2)) && (tiles_m & 1) == 0 && (tiles_n & 3) == 0 && !GGML_MX_XCD1D) {
         // 2 x 4 blocks of the tile grid per XCD: an XCD's 64 resident workgroups share half of the weight panels and a quarter of
         // the activation panels (4096^3: 14 MB through each L2 instead of 18 MB with a run of whole n-columns)
         const int hm = tiles_m >> 1, l = bid >> 3;
         tm_i = (xcd & 1) * hm + l % hm;
         tn_i = (xcd >> 1) * (tiles_n >> 2) + l / hm;
     } else {
+        // (the fused route: whole column panels per XCD -- the tiles_m workgroups that share a panel's image meet in one L2)
         const int t_lin = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (bid >> 3);
         tm_i = t_lin % tiles_m;
         tn_i = t_lin / tiles_m;
@@ -178,14 +224,14 @@ void gemm_qmx_kernel(const uint8_t *__restrict__ w6a, const uint8_t *__restrict_
         const uint32_t s0 = (uint32_t)s * KB * a_blk;
         if constexpr (i < C::A16_ROUNDS) {
             constexpr int u = P * i;
-            blds16(rA, sp + (size_t)(wave * 64 + C::NT * i) * 16, voff16, s0 + (u >> 1) * a_blk + (u & 1) * (uint32_t)(Npad * 16));
+            blds16<DMA_AUX>(rA, sp + (size_t)(wave * 64 + C::NT * i) * 16, voff16, s0 + (u >> 1) * a_blk + (u & 1) * (uint32_t)(Npad * 16));
         } else if constexpr (i < C::A16_ROUNDS + C::A8_ROUNDS) {
             constexpr int i8 = i - C::A16_ROUNDS, u = 2 * P * i8;
-            blds16(rA, sp + C::A16_BYTES + (size_t)(wave * 64 + C::NT * i8) * 16, voff8, s0 + (u >> 1) * a_blk);
+            blds16<DMA_AUX>(rA, sp + C::A16_BYTES + (size_t)(wave * 64 + C::NT * i8) * 16, voff8, s0 + (u >> 1) * a_blk);
         } else if (wave * 64 < C::SC_CHUNKS) {                           // uniform per wave
             const uint32_t sS0 = (uint32_t)s * KB * (uint32_t)(Npad * 4);
             if (C::SC_CHUNKS % 64 == 0 || lane < C::SC_CHUNKS % 64) {   // (32-column tiles: half a wave of 16-byte pieces; the DMA honours exec)
-                blds16(rAd, sp + C::A16_BYTES + C::A8_BYTES + (size_t)(wave * 64) * 16, voffS, sS0);
+                blds16<DMA_AUX>(rAd, sp + C::A16_BYTES + C::A8_BYTES + (size_t)(wave * 64) * 16, voffS, sS0);
                 if (TYPE == GGML_TYPE_Q4_1)
                     blds16(rAs, sp + C::A16_BYTES + C::A8_BYTES + C::SC_BYTES + (size_t)(wave * 64) * 16, voffS, sS0);
             }
@@ -357,6 +403,122 @@ void gemm_qmx_kernel(const uint8_t *__restrict__ w6a, const uint8_t *__restrict_
         });
     };
 
+    // ---- fused route: the shares `todo` (a bit per share) of K quarter q of this workgroup's column panel -> the image (mx_fuse above) ----
+    // share j = rows n0 + j * rows .. + rows - 1 (rows = TN / tiles_m, a power of two) x the quarter's qs * KB k-blocks.  ALL the shares asked for are
+    // taken in ONE pass over the threads (thread tid takes blocks tid, tid + NT, .. of the list "row fastest, then share, then k-block"), so a help
+    // trip costs as many rounds of loads as its blocks need, not one per share; a wave's 16-byte stores are runs of whole 128-byte lines.  K1b's arithmetic (quantize.hip): the block's 32
+    // floats come in ONE round of loads (every further round trip is time the whole workgroup stands still), then amax, the high digits, the low
+    // digits and the sum from registers -- 32 floats and 32 digits live, which the loop's dead registers (tacc, da, af and its temporaries) hold at a
+    // stage boundary without scratch (tools/isa_stats.sh).
+    const int rows_log = 31 - __builtin_clz((unsigned)(C::TN / (FUSED ? tiles_m : 1)));
+    auto quantize_shares = [&](int q, uint32_t todo) {
+        const rsrc_t rX = make_rsrc(fx.x, fx.x_bytes);
+        const int cnt = __builtin_popcount(todo), kbq = fx.qs * KB, total = (kbq * cnt) << rows_log;
+        for (int idx = tid; idx < total; idx += C::NT) {
+            const int su = idx >> rows_log, kb = su / cnt;
+            uint32_t m = todo;                              // the (su % cnt)-th share asked for
+            for (int o = su - kb * cnt; o > 0; --o) m &= m - 1;
+            const int j = __builtin_ctz(m);
+            const int n = n0 + (j << rows_log) + (idx & ((1 << rows_log) - 1));
+            const int b = q * kbq + kb;
+            if (n >= N) continue;                           // (K1b writes no row past N either)
+            bf6_u32x6 fh = {0, 0, 0, 0, 0, 0}, fl = fh;     // pad k-blocks: zero quants with zero scales
+            float dv = 0.0f, sv = 0.0f;
+            if (b < fx.nbk) {
+                const uint32_t xo = (uint32_t)n * fx.ld1_bytes + (uint32_t)b * 128u;
+                f32x4 v[8];
+#pragma unroll
+                for (int c = 0; c < 8; ++c) v[c] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rX, (int)(xo + 16u * c), 0, 0));
+                float amax = 0.0f;
+#pragma unroll
+                for (int c = 0; c < 8; ++c)
+#pragma unroll
+                    for (int k = 0; k < 4; ++k) amax = fmaxf(amax, fabsf(v[c][k]));
+                float d, id;
+                bf6_block_scale(amax, d, id);
+                bf6_f32x16 de, dd;                          // digits of the even / odd elements
+#pragma unroll
+                for (int c = 0; c < 8; ++c)
+#pragma unroll
+                    for (int k = 0; k < 4; ++k) {
+                        const float ah = bf6_digit_hi(bf6_quant(v[c][k], id));
+                        if (k & 1) dd[2 * c + (k >> 1)] = ah; else de[2 * c + (k >> 1)] = ah;
+                    }
+                fh = bf6_pack32(de, dd);
+                float sum = 0.0f;                           // exact: |sum| <= 32 * 127, in element order as K1b adds it
+#pragma unroll
+                for (int c = 0; c < 8; ++c)
+#pragma unroll
+                    for (int k = 0; k < 4; ++k) {
+                        const float qv = bf6_quant(v[c][k], id);
+                        sum += qv;
+                        const float al = bf6_digit_lo(qv, bf6_digit_hi(qv));
+                        if (k & 1) dd[2 * c + (k >> 1)] = al; else de[2 * c + (k >> 1)] = al;
+                    }
+                fl = bf6_pack32(de, dd);
+                dv = d; sv = d * sum;                       // the Q8_1 s0 + s1 of Ggml.cs:820-821 (intent D3)
+            }
+            // image per k-block: [half][Npad][16 B] then [half][Npad][8 B] (half 0 = ah, half 1 = al); range-checked by the descriptors
+            // (b differs from lane to lane: the block's offset rides in the per-lane offset, the plane's in the uniform one)
+            const uint32_t blk = (uint32_t)b * a_blk, sco = ((uint32_t)b * (uint32_t)Npad + (uint32_t)n) * 4u;
+            __builtin_amdgcn_raw_buffer_store_b128((u32x4){fh[0], fh[1], fh[2], fh[3]}, rA, (int)(blk + n * 16u), 0, 0);
+            __builtin_amdgcn_raw_buffer_store_b128((u32x4){fl[0], fl[1], fl[2], fl[3]}, rA, (int)(blk + n * 16u), (int)((uint32_t)Npad * 16u), 0);
+            __builtin_amdgcn_raw_buffer_store_b64((u32x2){fh[4], fh[5]}, rA, (int)(blk + n * 8u), (int)((uint32_t)Npad * 32u), 0);
+            __builtin_amdgcn_raw_buffer_store_b64((u32x2){fl[4], fl[5]}, rA, (int)(blk + n * 8u), (int)((uint32_t)Npad * 40u), 0);
+            __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(uint32_t, dv), rAd, (int)sco, 0, 0);
+            __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(uint32_t, sv), rAs, (int)sco, 0, 0);
+        }
+    };
+    // At the top of stage `it`:
+    //   produce  the own share of the NEXT quarter, behind the first stage of a quarter (it = 1, qs + 1, 2 qs + 1: quarters 1, 2, 3): loads, arithmetic,
+    //            stores -- and on into the stage, the stores in flight;
+    //   publish  one stage later: the stores are a stage old, so the wait for them is short; barrier; one lane sets the workgroup's bit;
+    //   check    quarter q + 1 in front of the stage whose compute() issues its first DMA (it = qs - 1, 2 qs - 1, 3 qs - 1): one look at the mask,
+    //            the missing shares quantized here, wait, barrier (so a pending publish is served by the same trip).
+    // With two stages per quarter produce and check fall on the same trips; with one there is no room to produce ahead and every workgroup
+    // quantizes its whole panel.  Which trips take the barrier depends on the trip number alone, never on what a wave read from the mask.
+    uint32_t *fmask = nullptr;
+    int fp_it = 0x7FFFFFFF, fc_it = 0x7FFFFFFF, fpub_q = 0;  // next produce / check trip; the quarter whose own share is stored but not yet published
+    if constexpr (FUSED) {
+        uint32_t xcc;
+        asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(xcc));
+        fmask = fx.mask + ((size_t)(xcc & 15u) * tiles_n + tn_i) * 4;
+        if (fx.qs >= 2 && tn_i != fx.skip_panel) fp_it = 1;
+        if (!(GGML_MX_FUSE_DBG & 8)) fc_it = fx.qs - 1;
+    }
+    auto fuse_top = [&](int it) {
+        if constexpr ((GGML_MX_FUSE_DBG & 1) != 0) return;  // (developer build: the cost of the map and the fetch policy alone)
+        const bool prod = it == fp_it, chk = it == fc_it, pub = fpub_q != 0;    // uniform
+        if (!(prod || chk || pub)) return;
+        uint32_t todo = 0;
+        int q = 0;
+        if (prod) {
+            q = (it - 1) / fx.qs + 1;
+            todo = 1u << tm_i;
+            fpub_q = (GGML_MX_FUSE_DBG & 8) ? 0 : q;        // (a publish of the trip before never meets a produce: they are qs - 1 >= 1 trips apart)
+            fp_it = q < 3 ? fp_it + fx.qs : 0x7FFFFFFF;
+        }
+        if (chk) {
+            q = (it + 1) / fx.qs;                           // (the quarter being produced, where both fall on one trip)
+            // ONE look at the mask (from L2: an agent-scope load); whatever is missing then is done here, nothing is waited for
+            uint32_t have = (uint32_t)__builtin_amdgcn_readfirstlane((int)__hip_atomic_load(fmask + q, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
+            if (fpub_q == q) have |= 1u << tm_i;           // (the own share is stored or about to be, its bit not yet set)
+            const uint32_t help = ~have & (uint32_t)((1ull << tiles_m) - 1);
+            todo |= help;
+            if (help != 0 && wave_all == 0 && lane == 0)    // (word 0 of the panel: what the help path did, for the tests)
+                (void)__hip_atomic_fetch_add(fmask, (uint32_t)__builtin_popcount(help), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            fc_it = q < 3 ? fc_it + fx.qs : 0x7FFFFFFF;
+        }
+        if (todo != 0) quantize_shares(q, todo);
+        if (!(chk || pub)) return;                          // produce alone: the stores ride into the stage
+        // every wave's stores have left the CU before the barrier; the bit is set behind it, and the DMA of a checked quarter is issued behind it
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        __builtin_amdgcn_s_barrier();
+        asm volatile("" ::: "memory");
+        if (fpub_q != 0 && wave_all == 0 && lane == 0) (void)__hip_atomic_fetch_or(fmask + fpub_q, 1u << tm_i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        fpub_q = 0;
+    };
+
     // ---- main loop: double-buffered LDS, one barrier per stage (vmcnt(0): see gemm_q16.hip).  Group grp takes stages
     //      grp, grp + KSP, ...; every wave passes the same number of barriers. ----
     static_assert(FB <= KB, "fragment look-ahead stays within two stages");
@@ -396,6 +558,7 @@ void gemm_qmx_kernel(const uint8_t *__restrict__ w6a, const uint8_t *__restrict_
         younger = (hwid & 1u) != 0 && nwg <= 512;            // WAVE_ID: the slot inside the SIMD
     }
     for (int it = 0; it < niter; ++it) {
+        if constexpr (FUSED) fuse_top(it);                   // (its vector-memory operations are all older than this stage's DMA pieces: the counted drain holds)
         if constexpr (WGM * WGN * KSP == 4 && GGML_MX_PRIO != 0) {
             // (priority on GGML_MX_PRIO_ON stages of every GGML_MX_PRIO.  With 2 of 3 the younger workgroup finished 6.5 us BEFORE the older one,
             // with 1 of 2 4.7 us behind it; 8 of 15: 138.1 | 139.2 us (tools/k3m_clock.hip, K loop median by wave slot).  What is left of
@@ -1135,7 +1298,52 @@ hipError_t launch_cfg(const ggml_hip_weight *w, act_planes p, int64_t N, float *
     return launch_lds(kfn<gemm_qmx_kernel<TYPE, WMT, WNT, WGM, WGN, KB, FB, KSP, VS>>, dim3((unsigned)(tiles_m * tiles_n)), C::NT * KSP, C::TOTAL * KSP,
                       C::TOTAL * KSP, st, w->q6a, w->q6b, w->d, w->m, (const uint8_t *)p.a8, p.ad, (const float *)p.as, dst, (int)w->M, (int)N, (int)w->Mpad,
                       (int)p.Npad, nstages, (int)ldd, tiles_m, tiles_n, (uint32_t)wq_bytes, (uint32_t)wd_bytes, (uint32_t)a_bytes, (uint32_t)ad_bytes,
-                      (uint32_t)dst_bytes, epilogue_or_none(ep));
+                      (uint32_t)dst_bytes, epilogue_or_none(ep), mx_fuse{});
+}
+
+// ---- the fused route: Q4_0 256 x 128 in one round of workgroups, K in whole stages that split into four quarters, a panel's tiles_m workgroups
+//      with equal power-of-two shares of its 128 rows (one mask bit each) ----
+std::atomic<int> g_fused_skip_panel{-1};                    // TEST HOOK (ggml_hip_debug_fused_init_skip_panel)
+using CfgFused = Cfg<GGML_TYPE_Q4_0, 2, 4, 4, 1, 4>;
+// Stages per K quarter from which the route is taken.  A workgroup produces at the top of a quarter's second stage, publishes a stage later and
+// checks at the top of the quarter's last stage: with qs stages that leaves its neighbours qs - 3 stages to publish in.  Measured against INIT +
+// COMPUTE in one process (docs/experiments/README.md, "the route by K"): it loses below this bound and wins from it on.
+// Above FUSED_MAX_QS the route is not taken either: K = 8192 (16 stages per quarter, two blocks per thread and produce) measured 2.4 us per step BEHIND
+// INIT + COMPUTE, and nothing between 4096 and 8192 has been measured.
+#ifndef FUSED_MIN_QS
+#define FUSED_MIN_QS 8
+#endif
+#ifndef FUSED_MAX_QS
+#define FUSED_MAX_QS 8
+#endif
+bool fused_serves(const ggml_hip_weight *w, const mm_plan &pl, int64_t N) {
+    if (w->type != GGML_TYPE_Q4_0 || w->ext_type != 0 || pl.family != MMF_MX || pl.form != MXF_256x128 || pl.wgs > 512 || !w->q6a || !w->q6b) return false;
+    const int64_t tiles_m = (w->M + CfgFused::TM - 1) / CfgFused::TM, nstages = (w->nbk + 3) / 4;
+    return N > 0 && nstages % 4 == 0 && nstages / 4 >= FUSED_MIN_QS && nstages / 4 <= FUSED_MAX_QS && tiles_m <= 32 && CfgFused::TN % tiles_m == 0;
+}
+hipError_t launch_fused(const ggml_hip_weight *w, const float *x, int64_t ld1, act_planes p, int64_t N, float *dst, int64_t ldd, hipStream_t st) {
+    using C = CfgFused;
+    constexpr int KB = 4;
+    if (w->Mpad % C::TM != 0 || p.Npad % C::TN != 0) return hipErrorInvalidValue;
+    const int tiles_m = (int)((w->M + C::TM - 1) / C::TM), tiles_n = (int)((N + C::TN - 1) / C::TN);
+    const int nstages = (int)((w->nbk + KB - 1) / KB);
+    const uint64_t nba = (uint64_t)pad_kblocks(w->nbk);
+    const uint64_t wq_bytes = (nba + K_LOOKAHEAD) * (uint64_t)w->Mpad * 16, wd_bytes = (nba + K_LOOKAHEAD) * (uint64_t)w->Mpad * 4;
+    const uint64_t a_bytes = nba * 48 * (uint64_t)p.Npad, ad_bytes = nba * (uint64_t)p.Npad * 4;
+    const uint64_t dst_bytes = ((uint64_t)(N - 1) * (uint64_t)ldd + (uint64_t)w->M) * 4, x_bytes = ((uint64_t)(N - 1) * (uint64_t)ld1 + (uint64_t)w->K) * 4;
+    constexpr uint64_t LIM = 0xFFFFFFFFull;
+    if (wq_bytes > LIM || a_bytes > LIM || x_bytes > LIM || (uint64_t)C::TN * (uint64_t)ldd * 4 > LIM) return hipErrorNotSupported;
+    // the masks live in the quarter of the image region the 48-byte bf6 image leaves free (the region is sized for the 64-byte f16 images)
+    const int nmask = 16 * tiles_n * 4;
+    if ((uint64_t)nmask * 4 > nba * 16 * (uint64_t)p.Npad) return hipErrorNotSupported;
+    uint32_t *mask = (uint32_t *)((uint8_t *)p.a8 + a_bytes);
+    const hipError_t e = launch_quantize_act_bf6_head(x, N, w->K, ld1, p, (int64_t)(GGML_MX_FUSE_DBG ? nstages : nstages / 4) * KB, mask, nmask, st);
+    if (e != hipSuccess) return e;
+    const mx_fuse fx = {x, mask, (uint32_t)(ld1 * 4), (uint32_t)x_bytes, (int)w->nbk, nstages / 4, g_fused_skip_panel.load(std::memory_order_relaxed)};
+    return launch_lds(kfn<gemm_qmx_kernel<GGML_TYPE_Q4_0, 2, 4, 4, 1, KB, 2, 1, 1, true>>, dim3((unsigned)(tiles_m * tiles_n)), C::NT, C::TOTAL, C::TOTAL, st, w->q6a,
+                      w->q6b, w->d, w->m, (const uint8_t *)p.a8, p.ad, (const float *)p.as, dst, (int)w->M, (int)N, (int)w->Mpad, (int)p.Npad, nstages, (int)ldd,
+                      tiles_m, tiles_n, (uint32_t)wq_bytes, (uint32_t)wd_bytes, (uint32_t)a_bytes, (uint32_t)ad_bytes, (uint32_t)dst_bytes, epilogue_or_none(nullptr),
+                      fx);
 }
 
 // K3s launch: KS = 8 waves per 32-row tile, each a contiguous eighth of K in pairs of blocks.  Chosen by N and K alone.
@@ -1305,6 +1513,14 @@ hipError_t launch_gemm_qmx_small_grouped(const mm_plan &g, int type, const moe_g
                                          int64_t M, int64_t Mpad, int64_t nbk, act_planes p, float *res, int64_t ldr, hipStream_t st) {
     if (g.family != MMF_K3S_MX || type != GGML_TYPE_Q4_0 || max_tiles <= 0 || M <= 0) return hipErrorInvalidValue;
     return launch_small_grouped(g, tab, tiles, n_tiles, max_tiles, M, Mpad, nbk, p, res, ldr, st);
+}
+
+bool gemm_qmx_fused_serves(const ggml_hip_weight *w, const mm_plan &pl, int64_t N) { return fused_serves(w, pl, N); }
+void gemm_qmx_fused_skip_panel(int panel) { g_fused_skip_panel.store(panel, std::memory_order_relaxed); }
+hipError_t launch_gemm_qmx_fused(const ggml_hip_weight *w, const mm_plan &pl, const float *x, int64_t ld1, act_planes p, int64_t N, float *dst, int64_t ldd,
+                                 hipStream_t st) {
+    if (!fused_serves(w, pl, N) || !quantize_act_bf6_serves(x, N, w->K, ld1)) return hipErrorNotSupported;
+    return launch_fused(w, x, ld1, p, N, dst, ldd, st);
 }
 
 hipError_t launch_gemm_qmx(const ggml_hip_weight *w, const mm_plan &pl, act_planes p, int64_t N, float *dst, int64_t ldd, hipStream_t st,

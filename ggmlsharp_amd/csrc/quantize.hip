@@ -12,6 +12,7 @@
 // All float arithmetic here must round exactly like the C# scalar code: one IEEE operation per C# operator,
 // no fused multiply-add, correctly rounded division.  Built with -ffp-contract=off.
 #include "common.h"
+#include "act_bf6.h"
 #include <cstdlib>
 
 namespace {
@@ -280,10 +281,13 @@ typedef __attribute__((address_space(3))) void lds_void_q;
 
 __global__ __launch_bounds__(256) void quantize_act_bf6_kernel(const float *__restrict__ x, int N, int nbk, uint32_t ld1_bytes,
                                                                uint32_t x_bytes, int8_t *__restrict__ a8, float *__restrict__ ad,
-                                                               int32_t *__restrict__ as, int Npad) {
+                                                               int32_t *__restrict__ as, int Npad, uint32_t *__restrict__ clr, int nclr) {
     __shared__ __attribute__((aligned(16))) uint8_t lds[4 * 8 * K1V_PIECE];
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    // the head launch of a fused product (launch_quantize_act_bf6_head): its first workgroup zeroes the hand-off masks of the launch behind it
+    if (clr != nullptr && blockIdx.x == 0 && blockIdx.y == 0)
+        for (int i = threadIdx.x; i < nclr; i += 256) clr[i] = 0u;
     const int b = blockIdx.x * 4 + wave;                     // this wave's k-block (< pad_kblocks(nbk) by the grid)
     const int n0 = blockIdx.y * 64;
     uint8_t *wl = lds + wave * (8 * K1V_PIECE);
@@ -324,29 +328,20 @@ __global__ __launch_bounds__(256) void quantize_act_bf6_kernel(const float *__re
     float amax = 0.0f;
 #pragma unroll
     for (int e = 0; e < 32; ++e) amax = fmaxf(amax, fabsf(v[e]));
-    const float d = amax / 127.0f;                          // Ggml.cs:751
-    const float id = d != 0.0f ? 1.0f / d : 0.0f;           // Ggml.cs:752
+    float d, id;                                            // (the statements of the arithmetic: act_bf6.h)
+    bf6_block_scale(amax, d, id);
     float sum = 0.0f;                                       // exact: |sum| <= 32 * 127
     f32x16q he, ho, le, lo;                                  // digits of the even / odd elements
 #pragma unroll
     for (int e = 0; e < 32; ++e) {
-        const float q = rintf(v[e] * id);                   // Ggml.cs:758-759 (D1, D2)
+        const float q = bf6_quant(v[e], id);
         sum += q;
-        const float ah = floorf(fmaf(q, 0.0625f, 0.5f));    // a = 16 ah + al, ah = floor((a + 8) / 16) in [-8, 8]
-        const float al = fmaf(ah, -16.0f, q);               // in [-8, 7]
+        const float ah = bf6_digit_hi(q);                   // a = 16 ah + al
+        const float al = bf6_digit_lo(q, ah);
         if (e & 1) { ho[e >> 1] = ah; lo[e >> 1] = al; } else { he[e >> 1] = ah; le[e >> 1] = al; }
     }
-    // Through asm with an early-clobber result: hipcc's builtin lets the 6-register result overlap the 32 source registers,
-    // and the instruction writes its result before it has read all of them (seen as garbage digits at elements 12..16).
-    // Both converts in ONE statement, so that no result shares a register with ANY of the 64 sources.  As two statements
-    // hipcc gave the second result the first convert's source registers and, in 22 of 100 launches, some rows came out with
-    // wrong quants 0..4 (tools/dbg_k1b.py; 8 wait states between the two did not help, distinct registers did: 0 of 250).
-    // The instruction evidently reads its sources for many cycles after issue with no interlock; the trailing nops keep
-    // whatever the compiler puts into the source registers next at a distance as well.
     u32x6q fh, fl;
-    asm volatile("v_cvt_scalef32_2xpk16_bf6_f32 %0, %2, %3, 1.0\n\ts_nop 7\n\tv_cvt_scalef32_2xpk16_bf6_f32 %1, %4, %5, 1.0\n\t"
-                 "s_nop 15\n\ts_nop 15"
-                 : "=&v"(fh), "=&v"(fl) : "v"(he), "v"(ho), "v"(le), "v"(lo));
+    bf6_pack32_pair(he, ho, le, lo, fh, fl);                // (one asm statement for both converts: act_bf6.h says why)
     float dv = d, sv = d * sum;                             // the Q8_1 s0 + s1 of Ggml.cs:820-821 (intent D3)
     if (pad) {                                              // uniform: pad k-blocks are zero quants with zero scales
         fh = (u32x6q){0, 0, 0, 0, 0, 0}; fl = fh; dv = 0.0f; sv = 0.0f;
@@ -749,16 +744,26 @@ hipError_t launch_quantize_act(const float *x, int64_t N, int64_t K, int64_t ld1
     else if (image == 3) {
         // lane-per-block form when the 32-bit buffer offsets reach (they do for every shape whose image does); rows must
         // be 16-byte aligned for the DMA (ld1 % 4, checked by the callers for every device entry)
-        const uint64_t xb = ((uint64_t)(N - 1) * (uint64_t)ld1 + (uint64_t)K) * 4;
-        if (xb <= 0xFFFFFFFFull && ld1 % 4 == 0 && ((uintptr_t)x & 15) == 0) {
-            dim3 g2((unsigned)(pad_kblocks(nbk) / 4), (unsigned)((N + 63) / 64));
-            quantize_act_bf6_kernel<<<g2, 256, 0, st>>>(x, (int)N, (int)nbk, (uint32_t)(ld1 * 4), (uint32_t)xb, p.a8, p.ad, p.as, (int)p.Npad);
-        } else {
-            quantize_act_kernel<3><<<grid, 256, 0, st>>>(x, N, nbk, ld1, p.a8, p.ad, p.as, p.Npad);
-        }
+        if (quantize_act_bf6_serves(x, N, K, ld1)) return launch_quantize_act_bf6_head(x, N, K, ld1, p, pad_kblocks(nbk), nullptr, 0, st);   // (the whole image)
+        quantize_act_kernel<3><<<grid, 256, 0, st>>>(x, N, nbk, ld1, p.a8, p.ad, p.as, p.Npad);
     }
     else
         quantize_act_kernel<0><<<grid, 256, 0, st>>>(x, N, nbk, ld1, p.a8, p.ad, p.as, p.Npad, sp3);
+    return hipGetLastError();
+}
+
+// The head of the bf6 image alone: k-blocks 0 .. nb_head - 1 (a multiple of 4) of every row, by the lane-per-block kernel.  For the fused
+// product launch (gemm_qmx.hip launch_gemm_qmx_fused), which quantizes the rest itself; the launch also zeroes that launch's nclr hand-off words.
+bool quantize_act_bf6_serves(const float *x, int64_t N, int64_t K, int64_t ld1) {
+    return N > 0 && ((uint64_t)(N - 1) * (uint64_t)ld1 + (uint64_t)K) * 4 <= 0xFFFFFFFFull && ld1 % 4 == 0 && ((uintptr_t)x & 15) == 0;
+}
+hipError_t launch_quantize_act_bf6_head(const float *x, int64_t N, int64_t K, int64_t ld1, act_planes p, int64_t nb_head, uint32_t *clr, int nclr,
+                                        hipStream_t st) {
+    const int64_t nbk = K / QK;
+    if (!quantize_act_bf6_serves(x, N, K, ld1) || nb_head <= 0 || nb_head % 4 != 0 || nb_head > pad_kblocks(nbk)) return hipErrorInvalidValue;
+    const uint64_t xb = ((uint64_t)(N - 1) * (uint64_t)ld1 + (uint64_t)K) * 4;
+    dim3 g2((unsigned)(nb_head / 4), (unsigned)((N + 63) / 64));
+    quantize_act_bf6_kernel<<<g2, 256, 0, st>>>(x, (int)N, (int)nbk, (uint32_t)(ld1 * 4), (uint32_t)xb, p.a8, p.ad, p.as, (int)p.Npad, clr, nclr);
     return hipGetLastError();
 }
 

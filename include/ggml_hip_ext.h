@@ -189,6 +189,16 @@ void   ggml_hip_debug_force_gemm(int which);
  * (the same bits whichever runs).  GGML_HIP_ERR_TYPE for any other weight type. */
 int    ggml_hip_debug_q2k_min_pass_dev(const ggml_hip_weight *w, int64_t N, float *d_dst, int64_t ldd, const void *d_work, size_t work_bytes,
                                        int form, void *stream);
+/* 1: ggml_hip_mul_mat_dev (that entry alone; mode 0 of ggml_hip_mul_mat_epilogue_dev is that entry) quantizes src1 INSIDE the product launch for this
+ * weight and N -- Q4_0 on 256 x 128 tiles in one round of workgroups, K four equal quarters of exactly eight 4-k-block stages each (3968 < K <= 4096:
+ * the headline's K; shorter K, and K = 8192, measured level with or behind the two steps and decline): a head launch writes the image of the first K quarter, the product launch writes the other three a
+ * quarter ahead of its own K loop.  The work buffer ends up holding the bytes ggml_hip_mul_mat_init_dev writes (image and scale planes) and dst the
+ * bits of ggml_hip_mul_mat_compute_dev; the part of the image region the bf6 image leaves free holds the launch's hand-off masks.  0: the two steps. */
+int    ggml_hip_mul_mat_init_fused(const ggml_hip_weight *w, int64_t N);
+/* TEST HOOK (process-wide): on the fused route, the workgroups of src1 column panel `panel` (128 rows each) do not write their shares of the image,
+ * so every workgroup of that panel takes the help path (it quantizes the missing shares itself).  -1: off.  Same bytes, same bits.  ONE value for the
+ * whole process, read when a product is launched -- a graph captured while it is set keeps it; not for use beside concurrent callers. */
+void   ggml_hip_debug_fused_init_skip_panel(int panel);
 /* Step 1 alone with an explicit layout: every src1 row -> Q8_0 (quantize_row_q8_0, Ggml.cs:733-762, the loop of
  * Ggml.cs:6641-6654) written as image `image_kind` (see above) into d_work.  image_kind + 16 (kinds 0..2, K % 256 == 0):
  * the Q8_K rule of the k-quant extension instead (one scale per 256 elements; see GGML_HIP_TYPE_Q5_K).  image_kind + 64 (kind 0 only,
