@@ -230,11 +230,14 @@ __device__ __forceinline__ void mla_body(uint8_t *lds, const float *__restrict__
         l = l * alpha + cs;
         m = mn;
         // ---- O^T = O^T alpha + V^T P^T: the P tile is the B operand as it stands -- element i of k-step ks is position 16 ks + (i & 3) + 8 (i >> 2) + 4 hh;
-        //      the A operand V^T[d][.] at the same positions is two transposed reads of the image, d = 256 dh + 32 dt + r ----
+        //      the A operand V^T[d][.] at the same positions is two transposed reads of the image, d = 256 dh + 32 dt + r.  The step's product is summed
+        //      from ZERO and added to O^T alpha in f32 (round to nearest): as the MFMA's C operand a residue of O^T alpha far below the product's last
+        //      bit is not rounded away but pulls the sum one ulp toward zero (a row whose weight sits on one position of a later step: V[j] minus an ulp) ----
 #pragma unroll
         for (int dt = 0; dt < NDT; ++dt) {
+            f32x16 pv;
 #pragma unroll
-            for (int i = 0; i < 16; ++i) o[dt][i] = o[dt][i] * alpha;
+            for (int i = 0; i < 16; ++i) pv[i] = 0.0f;
 #pragma unroll
             for (int ct = 0; ct < NCT; ++ct)
 #pragma unroll
@@ -243,8 +246,10 @@ __device__ __forceinline__ void mla_body(uint8_t *lds, const float *__restrict__
                     const f16x4 lo = tr_read(lds + tbase[0][dt & 3] + off), hi = tr_read(lds + tbase[1][dt & 3] + off);
                     f16x8 a;
                     a[0] = lo[0]; a[1] = lo[1]; a[2] = lo[2]; a[3] = lo[3]; a[4] = hi[0]; a[5] = hi[1]; a[6] = hi[2]; a[7] = hi[3];
-                    o[dt] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a, pf[ct][ks], o[dt], 0, 0, 0);
+                    pv = __builtin_amdgcn_mfma_f32_32x32x16_f16(a, pf[ct][ks], pv, 0, 0, 0);
                 }
+#pragma unroll
+            for (int i = 0; i < 16; ++i) o[dt][i] = o[dt][i] * alpha + pv[i];
         }
     }
 }

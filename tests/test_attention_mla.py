@@ -6,7 +6,8 @@ statistic over the CPU sweep, per form, is recorded there; the kernels are held 
 position returns the staged V row; a row's bits follow its own q row, the cache bytes below its vis, scale, the cache type and the form only; paged
 equals contiguous; the latent store equals ggml_hip_kv_store_dev at row_elems = 576.  The span is read from the plan, never from a literal.
 Shapes: n_head in {1, 16, 24, 128} (24: rows of different tokens and a partial last tile share a workgroup; 128 against the reference only), both cache
-types, n_q in {1, 3, 8} (SPLIT) and {9, 70} (WALK), n_kv in {1, 31, 128, 129, 379, 128 span + 1, 256 span + 37} (n_kv < n_q included), causal on and off."""
+types, n_q in {1, 3, 8} (SPLIT) and {9, 70} (WALK), n_kv in {1, 31, 128, 129, 379, 128 span + 1, 256 span + 37} (n_kv < n_q included), causal on and off.
+The step, chunk and span edges, the other n_q and head counts, explicit scales, steep scores and planted keys: tests/test_attention_mla_edges.py."""
 import ctypes as C
 import os
 import re
